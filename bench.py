@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- 96^3 patches/s, forward+backward, C-Swin-UNETR fs=48 / 6 classes (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line; `--full` adds everything else the harness measures or checks
+(replay / exchange checks, the roofline leg, the CPU baseline, the `secondary` configurations).  `--dump-outputs DIR` writes what the timed
+path computed in its last step as DIR/<name>.npy (float32 / float64, at most 64 MB; seeded inputs: two builds compare output for output).
 N > 1 runs one rank per GPU.  Under an external launcher (python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 every rank reads RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment; invoked bare, this process starts the N ranks itself as
 child processes through torch.distributed.run - before it has made any GPU call - and exits with the launcher's code (non-zero unless all
@@ -24,6 +27,8 @@ import torch  # noqa: E402
 
 import __graft_entry__ as ge  # noqa: E402
 
+DUMP_LIMIT = 64 << 20          # bytes of --dump-outputs in all
+DUMP_SAMPLE = 1 << 22          # elements of the fixed sample taken of an output too large to write whole
 
 WORKLOADS = {
     "c2": ("96^3 patches/sec fwd+bwd, C-Swin-UNETR fs=48 6-class", "patches/s",
@@ -126,6 +131,11 @@ def main():
                     help="bump the arena's device-side parameter version before every step, so that every replay re-casts and re-packs all weights as a "
                          "training loop's step does (the headline's timed steps have no optimiser step: their refresh launches find the copies current)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the short configs[2] / configs[4] / fp32 runs reported under `secondary` (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, run the checks and extra measurements: replay / exchange checks, roofline leg, CPU baseline and "
+                         "the `secondary` configurations (the --no-* switches above leave single parts out); default: the headline figure only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last step (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     a = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -135,6 +145,8 @@ def main():
         raise SystemExit("--gpus must be >= 1")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(a.gpus))
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if world != a.gpus:
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}: start one rank per GPU (or run `python bench.py --gpus {a.gpus}` bare)")
     if os.environ.get("MISEG_REHEARSE_ONE_GPU"):      # rehearsal of the N > 1 code path with every rank on the one card of a 1-GPU box
@@ -160,7 +172,7 @@ def main():
     hiplib.check_device(local)
     out = measure(a, rank, world, dist, dev)
     if rank == 0:
-        if world == 1 and dist is None and not a.no_secondary and a.workload == "c2" and a.dtype == "bf16":
+        if a.full and world == 1 and dist is None and not a.no_secondary and a.workload == "c2" and a.dtype == "bf16":
             # driver-timed figures of the other configurations ("builder-run only"): short runs of the same harness, AFTER the
             # headline measurement and outside its timed region; the headline line and its timed region are unchanged
             import copy
@@ -169,7 +181,7 @@ def main():
                                ("c2_fp32_parity_mode", dict(dtype="f32", steps=5, warmup=2)), ("c3_c_unetr_bf16", dict(workload="c3", steps=10, warmup=3)),
                                ("c5_sliding_window_bf16", dict(workload="c5", steps=2, warmup=2))):
                 b = copy.copy(a)
-                b.no_roofline, b.no_cpu_baseline = True, True
+                b.no_roofline, b.no_cpu_baseline, b.dump_outputs = True, True, None
                 for k, v in over.items():
                     setattr(b, k, v)
                 r = measure(b, rank, world, dist, dev)
@@ -286,6 +298,7 @@ def measure(a, rank, world, dist, dev):
     refresh = bool(getattr(a, "refresh_weights", False)) and arena is not None
 
     def step(i, eager=False, sample=None, comm=True):
+        """one step; returns the logits (the gradients are in p.grad, as a caller of the step receives them)"""
         k = order[i % len(order)] if sample is None else sample
         if refresh:
             arena.invalidate()          # one counter_add launch: the step's refresh kernels then re-lay-out every weight (as after an optimiser step)
@@ -293,32 +306,34 @@ def measure(a, rank, world, dist, dev):
             works, ub = [], []
             if graphed is not None and not eager and a.captured_collective:
                 # the collectives are nodes of the step's graph: exchange the bitmap (known up front), replay, settle the flags
-                graphed(pool[k:k + 1], [mods[k]], cot, publish=False)
+                y = graphed(pool[k:k + 1], [mods[k]], cot, publish=False)
                 arena.allreduce_finish(lambda: None, world, None)      # every exchange was a node of the graph; the global flags are in `used_dev`
-                return
+                return y
             if graphed is not None and not eager:
                 def between():          # the flags of a replayed graph are known up front: the bitmap exchange starts here as well
                     ub.append(arena.used_begin(host=not a.device_flags))
                     for lo, hi in early_ranges:
                         if hi > lo:
                             works.extend(arena.allreduce_begin(lo, hi))
-                graphed(pool[k:k + 1], [mods[k]], cot, between=between, publish=False)
+                y = graphed(pool[k:k + 1], [mods[k]], cot, between=between, publish=False)
             else:
                 arena.begin_step()
                 cut = []
-                model(pool[k:k + 1], [mods[k]], cut=cut).backward(cot)
+                y = model(pool[k:k + 1], [mods[k]], cut=cut)
+                y.backward(cot)
                 arena.flush()
                 for lo, hi in early_ranges:
                     if hi > lo:
                         works.extend(arena.allreduce_begin(lo, hi))
                 torch.autograd.backward([o for o, _ in cut], [l.grad for _, l in cut])
             arena.allreduce_end(works, world, rest=late_ranges, used_work=ub[0] if ub else None, host_flags=not a.device_flags)
-            return
+            return y.detach()
         if graphed is not None and not eager:
-            graphed(pool[k:k + 1], [mods[k]], cot)
+            y = graphed(pool[k:k + 1], [mods[k]], cot)
         elif arena is not None:
             arena.begin_step()
-            model(pool[k:k + 1], [mods[k]]).backward(cot)
+            y = model(pool[k:k + 1], [mods[k]])
+            y.backward(cot)
             arena.publish()
         else:
             ops.begin_step()
@@ -332,6 +347,7 @@ def measure(a, rank, world, dist, dev):
             else:
                 from mi_seg_amd.parallel.ddp import allreduce_gradients
                 allreduce_gradients(params, world)
+        return y.detach()
 
     # setup (untimed, not part of the W warm-up steps): touch both modalities once so that hipGraph capture / allocator growth of
     # either conditional-norm row set never lands inside the timed region
@@ -352,7 +368,7 @@ def measure(a, rank, world, dist, dev):
     per_step = []
     for i in range(a.steps):
         ts = time.perf_counter()
-        step(a.warmup + i)
+        y = step(a.warmup + i)
         if os.environ.get("MISEG_BENCH_VERBOSE"):
             torch.cuda.synchronize()
             per_step.append(round(1e3 * (time.perf_counter() - ts), 2))
@@ -367,6 +383,12 @@ def measure(a, rank, world, dist, dev):
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if a.dump_outputs and rank == 0:          # before anything else runs a step: the logits / gradients of the last timed step
+        named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+        grads = [p.grad.detach().float() if p.grad is not None else torch.zeros_like(p, dtype=torch.float32) for _, p in named]
+        write_outputs(a.dump_outputs, {"logits": y.float(), "grad_sample": seeded_sample(torch.cat([g.reshape(-1) for g in grads])),
+                                       "grad_norms": torch.stack([g.double().norm() for g in grads])})
+    del y
 
     if os.environ.get("MISEG_BENCH_EARLY_PRINT") and rank == 0:      # experiments whose replay check may abort: the timing first
         print(f"early: {world * a.steps / dt:.2f} {WORKLOADS[a.workload][1]}", file=sys.stderr)
@@ -474,7 +496,7 @@ def measure(a, rank, world, dist, dev):
     }
     if refresh:
         out["weight_refresh"] = "every step (device-side parameter version bumped before each replay: all casts and conv packs re-made)"
-    if graphed is not None:
+    if a.full and graphed is not None:
         check = replay_check()
         if not check["finite"] or check["logits_rel_err"] > 1e-2 or check["grad_rel_err"] > 5e-2:
             raise SystemExit(f"hipGraph replay does not reproduce the eager step: {check}")
@@ -484,14 +506,15 @@ def measure(a, rank, world, dist, dev):
         if awc and (awc["logits_rel_err_vs_eager"] > 1e-2 or awc["grad_rel_err_vs_eager"] > 5e-2 or awc["logits_moved_by"] < 1e-4):
             raise SystemExit(f"a replay after a weight change does not use the changed weights: {check}")
         out["replay_check"] = check
-    if dist is not None and arena is not None:
+    if a.full and dist is not None and arena is not None:
         out["exchange_check"] = exchange_check()
+    if dist is not None and arena is not None:
         out["collective"] = {"backend": dist.get_backend(), "ranks": dist.get_world_size(), "grad_dtype": a.grad_dtype,
                              "payload_bytes_per_step": int(arena.flat.numel() * (4 if a.grad_dtype == "f32" else 2)),
                              "used_flags": "device" if (a.device_flags and overlap) else "host read per step",
                              "launched_per_step": coll / a.steps, "captured_in_graph": bool(a.captured_collective and overlap and graphed is not None),
                              "captured_collectives_per_step": (fused.captured if (graphed is not None and fused is not None) else 0), "forced_on_one_rank": bool(arena.force_collective and world == 1)}
-    if rank == 0:
+    if rank == 0 and a.full:
         if not a.no_roofline:
             from mi_seg_amd.testing.roofline import profile_step, summarize
             prof = profile_step(lambda: step(a.warmup + a.steps, eager=True, comm=False))
@@ -535,10 +558,15 @@ def bench_train_step(a, model, dtype, dev, pool, mods, order, params):
         losses.append(gts(pool[k:k + 1], labels[k:k + 1], [mods[k]]).clone())
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:          # the last step's loss and the weights its optimiser step left
+        w = [p.detach().float() for p in arena.params]
+        write_outputs(a.dump_outputs, {"loss": losses[-1].double().reshape(1), "param_sample": seeded_sample(torch.cat([t.reshape(-1) for t in w])),
+                                       "param_norms": torch.stack([t.double().norm() for t in w])})
     losses = [float(l) for l in losses]
-    moved = float((arena.params[0].detach() - w0).abs().max())
-    if not all(l == l and abs(l) < 1e6 for l in losses) or moved == 0.0:
-        raise SystemExit(f"train step: losses {losses}, first parameter moved by {moved}")
+    if a.full:
+        moved = float((arena.params[0].detach() - w0).abs().max())
+        if not all(l == l and abs(l) < 1e6 for l in losses) or moved == 0.0:
+            raise SystemExit(f"train step: losses {losses}, first parameter moved by {moved}")
     out = {"metric": WORKLOADS[a.workload][0].replace("fwd+bwd", "full optimisation step (refresh + fwd + DiceFocal + bwd + AdamW)"), "value": a.steps / dt,
            "unit": WORKLOADS[a.workload][1], "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1000 * dt / a.steps, "higher_is_better": True,
            "scaling": "weak", "vs_baseline": None, "dtype": a.dtype, "data": "synthetic", "launch": "hipGraph",
@@ -576,26 +604,30 @@ def bench_sliding_window(a, model, dtype, dev, rank, world, dist):
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    # untimed: replays of the captured forward against the eager forward on window batches from the corners, the centre and the clamped
-    # last windows of the volume - `finite` alone let a replay bug through in round 2 (statistics pool recycled short: every replay after
-    # the first normalised with accumulated sums, logits 43 % off and perfectly finite)
-    grid = window_grid(size, (96, 96, 96), 0.5)
-    worst = 0.0
-    with torch.no_grad():
-        for i0 in (0, 348, nwin - sw, sw, 0):
-            xb = torch.cat([vol[:, :, d:d + 96, h:h + 96, w:w + 96] for (d, h, w) in grid[i0:i0 + sw]], 0).contiguous()
-            yg = pred(xb, [0] * sw).float().clone()
-            ye = model(xb, [0] * sw).float()
-            worst = max(worst, float((yg - ye).norm() / ye.norm()))
-    if not worst < 1e-2:
-        raise SystemExit(f"sliding window: the replayed forward is {worst:.3e} from the eager forward of the same window batch")
+    if a.dump_outputs and rank == 0:          # the last volume's stitched logits: a fixed sample of them and every class's mean
+        write_outputs(a.dump_outputs, {"logits_sample": seeded_sample(y), "class_means": y.mean(dim=(0, 2, 3, 4), dtype=torch.float64)})
     out = {"metric": WORKLOADS["c5"][0], "value": world * a.steps * nwin / dt, "unit": "windows/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
            "ms_per_step": 1000 * dt / a.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
            "launch": "hipGraph", "config": {"workload": WORKLOADS["c5"][2], "windows_per_volume": nwin, "sw_batch_size": sw,
                                             "replicas": "one volume per GPU, no collective (windows are independent)"},
-           "finite": bool(torch.isfinite(y).all()), "replay_check": {"window_batches": 5, "worst_rel_err_vs_eager": worst},
            "volumes_per_s": world * a.steps / dt}
-    if rank == 0:
+    if a.full:
+        # untimed: replays of the captured forward against the eager forward on window batches from the corners, the centre and the clamped
+        # last windows of the volume - `finite` alone let a replay bug through in round 2 (statistics pool recycled short: every replay after
+        # the first normalised with accumulated sums, logits 43 % off and perfectly finite)
+        grid = window_grid(size, (96, 96, 96), 0.5)
+        worst = 0.0
+        with torch.no_grad():
+            for i0 in (0, 348, nwin - sw, sw, 0):
+                xb = torch.cat([vol[:, :, d:d + 96, h:h + 96, w:w + 96] for (d, h, w) in grid[i0:i0 + sw]], 0).contiguous()
+                yg = pred(xb, [0] * sw).float().clone()
+                ye = model(xb, [0] * sw).float()
+                worst = max(worst, float((yg - ye).norm() / ye.norm()))
+        if not worst < 1e-2:
+            raise SystemExit(f"sliding window: the replayed forward is {worst:.3e} from the eager forward of the same window batch")
+        out["finite"] = bool(torch.isfinite(y).all())
+        out["replay_check"] = {"window_batches": 5, "worst_rel_err_vs_eager": worst}
+    if rank == 0 and a.full:
         if not a.no_roofline:
             from mi_seg_amd.testing.roofline import profile_step, summarize
             xw = vol[:, :, :96, :96, :96].expand(sw, -1, -1, -1, -1).contiguous()
@@ -606,6 +638,27 @@ def bench_sliding_window(a, model, dtype, dev, rank, world, dist):
             out["roofline"] = summarize(profile_step(one_batch), dtype, counters=False)
     arena.detach()
     return out
+
+
+def seeded_sample(t, n=DUMP_SAMPLE, seed=1234):
+    """t flattened, as float32: whole if it has at most n elements, else the same n positions every run (sorted, drawn by a seeded generator)"""
+    f = t.detach().reshape(-1)
+    if f.numel() <= n:
+        return f.float()
+    idx = torch.randint(0, f.numel(), (n,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return f[idx.to(f.device)].float()
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every tensor as path/<name>.npy (float32 stays float32, everything else becomes float64), at most DUMP_LIMIT bytes in all"""
+    import numpy as np
+    host = {k: v.detach().cpu().numpy().astype(np.float32 if v.dtype == torch.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in host.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {total} bytes, more than {DUMP_LIMIT}")
+    os.makedirs(path, exist_ok=True)
+    for k, v in host.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 if __name__ == "__main__":

@@ -1,11 +1,11 @@
 """Turn the rocprofv3 outputs of one round into the tracked files under profiles/.
 
-On the GPU box (three separate passes; counters never share a run with traces other than the kernel trace):
+On the GPU box (three separate passes; counters never share a run with traces other than the kernel trace), OUT = $PROFILE_OUT or <repo>/profile_out:
   cd /tmp && export TMPDIR=/tmp
-  rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_stats -o s -- python3 $R/bench.py
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $R/gpurun_out/prof_fetch -o f -- python3 $R/bench.py --no-graph --steps 3 --warmup 1 --no-cpu-baseline --no-roofline
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $R/gpurun_out/prof_write -o w -- python3 $R/bench.py --no-graph --steps 3 --warmup 1 --no-cpu-baseline --no-roofline
-Then here:  python scripts/make_profiles.py r01_e
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats -o s -- python3 $R/bench.py --full
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/prof_fetch -o f -- python3 $R/bench.py --no-graph --steps 3 --warmup 1 --full --no-cpu-baseline --no-roofline
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/prof_write -o w -- python3 $R/bench.py --no-graph --steps 3 --warmup 1 --full --no-cpu-baseline --no-roofline
+(scripts/profile_round.sh runs them and the bench lines.)  Then, with the same PROFILE_OUT:  python scripts/make_profiles.py r01_e
 """
 import csv, glob, json, os, re, shutil, sys
 from collections import defaultdict
@@ -13,10 +13,11 @@ from collections import defaultdict
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1]
 out = os.path.join(root, "profiles")
+src = os.environ.get("PROFILE_OUT") or os.path.join(root, "profile_out")
 
 
 def one(pattern):
-    files = glob.glob(os.path.join(root, "gpurun_out", pattern), recursive=True)
+    files = glob.glob(os.path.join(src, pattern), recursive=True)
     if not files:
         raise SystemExit(f"missing {pattern}")
     return max(files, key=os.path.getmtime)
@@ -60,7 +61,7 @@ json.dump({"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate pa
 # matrix-core utilisation per kernel (its own counter pass): mfma_util = SQ_VALU_MFMA_BUSY_CYCLES / (launch duration x 2.4 GHz x 256 CUs x 4 SIMDs) -
 # the gfx94x MfmaUtil formula rocprofv3 falls back to (MI355X_MICROARCH.md, "rocprofv3 PMC slots") with the launch's own start / end time stamps as the
 # cycle base: GRBM_GUI_ACTIVE of a counter-collection dispatch covers the profiler's start / stop around it (294 k cycles for a 2.7 us copy)
-mf = glob.glob(os.path.join(root, "gpurun_out", "prof_mfma/**/*counter_collection.csv"), recursive=True)
+mf = glob.glob(os.path.join(src, "prof_mfma/**/*counter_collection.csv"), recursive=True)
 if mf:
     path = max(mf, key=os.path.getmtime)
     acc = defaultdict(lambda: defaultdict(float))
@@ -91,12 +92,12 @@ if mf:
                          "CUs * 4 SIMDs), the share of the matrix pipes' cycles in which an MFMA was executing; kernels ordered by their share of the kernel time",
                "kernels": top}, open(os.path.join(out, f"{tag}_mfma.json"), "w"), indent=1)
 for name, log in (("bench_line", "bench_official.log"), ("bench_f32_line", "bench_f32.log"), ("bench_c3_line", "bench_c3.log"), ("bench_c5_line", "bench_c5.log")):
-    path = os.path.join(root, "gpurun_out", log)
+    path = os.path.join(src, log)
     if os.path.exists(path):
         lines = [l for l in open(path) if l.startswith("{")]
         if lines:
             open(os.path.join(out, f"{tag}_{name}.json"), "w").write(lines[-1])
-c3 = glob.glob(os.path.join(root, "gpurun_out", "prof_c3/**/*kernel_stats.csv"), recursive=True)
+c3 = glob.glob(os.path.join(src, "prof_c3/**/*kernel_stats.csv"), recursive=True)
 if c3:
     shutil.copy(max(c3, key=os.path.getmtime), os.path.join(out, f"{tag}_bench_c3_bf16_kernel_stats.csv"))
 print("wrote", tag, "kernels:", len(kernels))

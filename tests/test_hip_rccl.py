@@ -45,7 +45,7 @@ def test_two_rank_step_on_one_card(flags):
     env = dict(os.environ)
     env.update({"HSA_ENABLE_IPC_MODE_LEGACY": "0", "MISEG_REHEARSE_ONE_GPU": "1", "MISEG_DIST_BACKEND": "gloo"})
     env.pop("MISEG_HIP_LIB", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-roofline", "--no-secondary"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-roofline", "--no-secondary"]
     if flags == "host":
         cmd.append("--host-flags")
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=880)
