@@ -33,7 +33,7 @@ enum { MISEG_ACT_NONE = 0, MISEG_ACT_LEAKY = 1, MISEG_ACT_GELU = 2, MISEG_ACT_PR
 #define MISEG_MAX_STYLES 4
 
 /* bumped on EVERY change of a struct layout or prototype; bindings must refuse a library whose version differs from the header they mirror */
-#define MISEG_ABI_VERSION 9
+#define MISEG_ABI_VERSION 10
 int miseg_abi_version(void);
 const char* miseg_last_error(void);
 /* writes e.g. "gfx950" for the code objects embedded in the library */
@@ -621,6 +621,27 @@ typedef struct {
   uint64_t* counts; float* dice;   /* out fp32 [B][C] */
 } miseg_dice_metric_params;
 int miseg_dice_metric(const miseg_dice_metric_params* p, miseg_stream_t stream);
+
+/* SurfaceDistanceMetric(include_background, symmetric, distance_metric='euclidean') after AsDiscrete(argmax=True, to_onehot=C) (test.py:145-151;
+ * MONAI 1.1.0 metrics/surface_distance.py::compute_average_surface_distance, parity unpinned): per sample b and class c, with P = (pred == c)
+ * and G = (label == c), the masks are cropped to the tight box of P | G and squeezed (a box side of one voxel has no neighbours), edges are
+ * M ^ erode(M) (cross structure, zero border), and asd[b][c'] is the mean exact Euclidean distance (voxel units) of E_P to the nearest voxel
+ * of E_G, concatenated with E_G -> E_P when `symmetric`.  One side's edges empty => inf; both empty (or no foreground) => NaN.
+ * The prediction is either fp32 logits [B][C][D][H][W] (argmax, the FIRST maximum wins) or an int32 class map [B][D][H][W]: exactly one of
+ * the two.  Label values (and class-map values) outside [0, C) belong to no class.  include_background = 0 leaves out class 0: c' = c - 1.
+ * Every side of the volume 1..4096, C 1..64.  The call reads the (b, c) boxes back to the host to size the distance passes, so it synchronises
+ * the stream and cannot be captured into a graph.  Results are bit-reproducible (fixed-order double sums). */
+typedef struct {
+  uint32_t struct_size;
+  const float* logits; const int32_t* pred;
+  const void* label; int label_dtype;
+  int B, C, D, H, W;
+  int include_background, symmetric;
+  void* workspace;                 /* miseg_surface_distance_workspace_bytes(B, C, D, H, W) bytes, uninitialised */
+  double* asd;                     /* out fp64 [B][C - (include_background ? 0 : 1)] */
+} miseg_surface_distance_params;
+size_t miseg_surface_distance_workspace_bytes(int B, int C, int D, int H, int W);
+int miseg_surface_distance(const miseg_surface_distance_params* p, miseg_stream_t stream);
 
 /* One optimiser step for every parameter of a model in ONE launch (lightning_monai.py:255-278: AdamW / Adam / SGD-nesterov), over the flat
  * fp32 gradient arena the weight-gradient kernels accumulate into.  Descriptor i: parameter tensor `param` of n elements whose gradient, and

@@ -1660,6 +1660,40 @@ def dice_metric(logits, label):
     return dice
 
 
+def surface_distance(label, logits=None, pred=None, num_classes=None, include_background=True, symmetric=True):
+    """fp64 [B, C'] symmetric (or one-way) average surface distance per class after argmax of fp32 logits [B, C, D, H, W], or of an integer
+    class map pred [B, (1,) D, H, W] with num_classes classes (miseg_surface_distance; C' = C - (0 if include_background else 1)).
+    Synchronises the stream: the kernel reads the per-class boxes back to size its passes."""
+    if (logits is None) == (pred is None):
+        raise ValueError("surface_distance: exactly one of logits / pred")
+    if logits is not None:
+        if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.dim() != 5:
+            raise ValueError("surface_distance: logits must be contiguous float32 [B, C, D, H, W]")
+        B, Cc, D, H, W = logits.shape
+        dev = logits.device
+    else:
+        if num_classes is None:
+            raise ValueError("surface_distance: a class map needs num_classes")
+        B, Cc = pred.shape[0], int(num_classes)
+        if pred.dim() == 5 and pred.shape[1] == 1:
+            pred = pred[:, 0]
+        if pred.dim() != 4:
+            raise ValueError("surface_distance: pred must be a class map [B, (1,) D, H, W]")
+        D, H, W = pred.shape[1:]
+        pred = pred.to(torch.int32).contiguous()
+        dev = pred.device
+    if label.numel() != B * D * H * W:
+        raise ValueError("surface_distance: label does not match the prediction")
+    lab, ldt = _label(label.to(dev))
+    cp = Cc - (0 if include_background else 1)
+    asd = torch.empty(B, max(cp, 0), dtype=torch.float64, device=dev)
+    nbytes = L.load().miseg_surface_distance_workspace_bytes(B, Cc, D, H, W)
+    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    _call("miseg_surface_distance", L.SurfaceDistance(C.sizeof(L.SurfaceDistance), _ptr(logits), _ptr(pred), _ptr(lab), ldt, B, Cc, D, H, W,
+                                                      int(bool(include_background)), int(bool(symmetric)), _ptr(ws), _ptr(asd)))
+    return asd
+
+
 def stitch_windows(win, out, starts, roi, count=None, slab=None):
     """win fp32 [nd*nh*nw, C, rd, rh, rw] (the windows of the nd depth layers `starts[0]`, all resident), out fp32 [C, D, H, W];
     starts = (list_d, list_h, list_w).  slab = (d_begin, d_count): write only these depths of `out` from the resident layers (which then

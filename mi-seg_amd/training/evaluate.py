@@ -1,0 +1,119 @@
+"""Test-set evaluation: Dice and average surface distance per class, per modality and over the whole set (reference test.py:17-123).
+
+With float32 logits on a HIP device, this module's AsDiscrete post-transforms, DiceMetric and SurfaceDistanceMetric, the batch takes the fused
+path (dice_from_logits + surface_distance_from_logits: no one-hot volume is built); anything else runs the reference's decollate / post-transform
+/ metric chain.  The checkpoint loading and MONAI's get_loaders of the reference's main() stay with the caller."""
+import torch
+import torch.nn.functional as F
+
+from .metrics import Cumulative, DiceMetric, SurfaceDistanceMetric, dice_from_logits, surface_distance_from_logits
+
+
+class AsDiscrete:
+    """monai.transforms.AsDiscrete(argmax, to_onehot) on one channel-first sample [C, ...] (a label: [1, ...])"""
+
+    def __init__(self, argmax=False, to_onehot=None):
+        self.argmax, self.to_onehot = argmax, to_onehot
+
+    def __call__(self, x):
+        if self.argmax:
+            x = x.argmax(dim=0, keepdim=True)
+        if self.to_onehot is not None:
+            x = F.one_hot(x[0].long(), self.to_onehot).movedim(-1, 0)
+        return x.to(torch.float32)
+
+
+def decollate_batch(t):
+    return list(t.unbind(0))
+
+
+def _fused(output, post_label, post_pred, acc_func, surface_distance):
+    """the batch can skip the one-hot volumes: the post-transforms and metrics are the ones this module knows the semantics of"""
+    C = output.shape[1]
+    return (output.is_cuda and output.dtype == torch.float32 and output.dim() == 5 and C <= 64
+            and isinstance(post_pred, AsDiscrete) and post_pred.argmax and post_pred.to_onehot == C
+            and isinstance(post_label, AsDiscrete) and not post_label.argmax and post_label.to_onehot == C
+            and type(acc_func) is DiceMetric and (surface_distance is None or type(surface_distance) is SurfaceDistanceMetric))
+
+
+def compute_metric_modality(metric_func, include_background=0):
+    """per-modality batch average of every class (NaNs left out, as do_metric_reduction's mean_batch) and their mean over the classes that
+    have a value (reference test.py:17-43); prints and returns {key: value}"""
+    metric, mod_metric = metric_func.get_buffer()
+    metric = metric.cpu()
+    mod_metric = mod_metric.cpu()
+    out = {}
+    for m in torch.unique(mod_metric):
+        metric_m = metric[mod_metric == m]
+        nans = torch.isnan(metric_m)
+        not_nans = (~nans).float()
+        t_zero = torch.zeros(1, device=metric_m.device, dtype=metric_m.dtype)
+        not_nans = not_nans.sum(dim=0)
+        metric_m[nans] = 0
+        metric_m = torch.where(not_nans > 0, metric_m.sum(dim=0) / not_nans, t_zero)
+        per_class = {f"val_modality{m}/class{c + include_background}": v for c, v in enumerate(metric_m.tolist())}
+        print(per_class)
+        avg = {f"val_modality{m}/avg": torch.nanmean(metric_m[not_nans > 0]).item()}
+        print(avg)
+        out.update(per_class)
+        out.update(avg)
+    return out
+
+
+def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=None, amp=True, surface_distance=None, results=None):
+    """the reference's evaluation loop (test.py:46-123): returns the mean total Dice over the classes with a value (and the mean total surface
+    distance when `surface_distance` is given).  `results`, a dict, receives the printed values: "dice_modality", "dice_total" and, with
+    `surface_distance`, "surface_distance_modality", "surface_distance_total", each {printed key: value}."""
+    model.eval()
+    acc_mod_cumulative = Cumulative()
+    surface_mod_cumulative = Cumulative() if surface_distance is not None else None
+    dev_type = torch.device(device).type
+    with torch.no_grad():
+        for batch in loader:
+            data, target = batch["image"].to(device), batch["label"].to(device)
+            modality = batch["modality"].to(device) if "modality" in batch.keys() else None
+            with torch.autocast(device_type=dev_type, enabled=amp and dev_type == "cuda"):
+                output = model_inferer(data, modalities=modality) if model_inferer is not None else model(data, modality)
+            fused = _fused(output, post_label, post_pred, acc_func, surface_distance)
+            if fused:
+                C = output.shape[1]
+                dice = dice_from_logits(output, target, C)
+                batch_acc = dice if acc_func.include_background else dice[:, 1:]
+                acc_func.extend(batch_acc)
+            else:
+                val_output_convert = torch.stack([post_pred(t) for t in decollate_batch(output)])
+                val_labels_convert = torch.stack([post_label(t) for t in decollate_batch(target)])
+                batch_acc = acc_func(y_pred=val_output_convert, y=val_labels_convert)
+            acc_mod_cumulative.extend(batch_acc, modality)
+            if surface_distance is not None:
+                if fused:
+                    batch_surface = surface_distance_from_logits(output, target, output.shape[1], include_background=surface_distance.include_background,
+                                                                 symmetric=surface_distance.symmetric)
+                    surface_distance.extend(batch_surface)
+                else:
+                    batch_surface = surface_distance(y_pred=val_output_convert, y=val_labels_convert)
+                surface_mod_cumulative.extend(batch_surface, modality)
+    results = {} if results is None else results
+    print("Dice per modality")
+    include_background_acc = int(not acc_func.include_background)
+    results["dice_modality"] = compute_metric_modality(acc_mod_cumulative, include_background_acc)
+    print("Surface Distance per modality")
+    if surface_distance is not None:
+        include_background_surf = int(not surface_distance.include_background)
+        results["surface_distance_modality"] = compute_metric_modality(surface_mod_cumulative, include_background_surf)
+    accuracy, not_nans = acc_func.aggregate()
+    dict_acc_class = {f"val_total_dice/class{c + include_background_acc}": v for c, v in enumerate(accuracy.tolist())}
+    print(dict_acc_class)
+    results["dice_total"] = dict_acc_class
+    if surface_distance is not None:
+        surface, not_nans_surface = surface_distance.aggregate()
+        dict_surf_class = {f"val_total_surface_distance/class{c + include_background_surf}": v for c, v in enumerate(surface.tolist())}
+        print(dict_surf_class)
+        results["surface_distance_total"] = dict_surf_class
+        surface_distance.reset()
+        surface_mod_cumulative.reset()
+    acc_func.reset()
+    acc_mod_cumulative.reset()
+    if surface_distance is not None:
+        return torch.nanmean(accuracy[not_nans > 0]).item(), torch.nanmean(surface[not_nans_surface > 0]).item()
+    return torch.nanmean(accuracy[not_nans > 0]).item()

@@ -1,4 +1,6 @@
-"""Dice metric / AsDiscrete with MONAI 1.1.0 semantics (reference lightning_monai.py:68-79,190-195).  Parity unpinned (Appendix B)."""
+"""Dice metric / AsDiscrete with MONAI 1.1.0 semantics (reference lightning_monai.py:68-79,190-195).  Parity unpinned (Appendix B).
+Average surface distance and the cumulative metric objects of the reference's evaluation script (test.py:17-171)."""
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -32,3 +34,226 @@ def dice_from_logits(logits, label, num_classes):
         from ..hip import ops
         return ops.dice_metric(logits.contiguous(), label.to(logits.device))
     return dice_metric(as_discrete_argmax_onehot(logits, num_classes), as_discrete_onehot(label, num_classes))
+
+
+# ------------------------------------------------------------------------------------------ surface distance (reference test.py:145-151)
+# MONAI 1.1.0 metrics/surface_distance.py + metrics/utils.py restated (parity unpinned).  The CPU restatement below is
+# MONAI's own recipe (scipy.ndimage when it imports, an exact numpy EDT otherwise); on a HIP device csrc/surface.hip computes the same numbers.
+
+def _erode(m):
+    """scipy.ndimage.binary_erosion(m) with its defaults: cross structure, border_value 0 (a 0-d array erodes to itself)"""
+    if m.ndim == 0:
+        return m.copy()
+    p = np.pad(m, 1, constant_values=False)
+    out = m.copy()
+    for ax in range(m.ndim):
+        for lo in (0, 2):
+            out &= p[tuple(slice(lo, lo + n) if a == ax else slice(1, 1 + n) for a, n in enumerate(m.shape))]
+    return out
+
+
+def _edt(nonseed):
+    """distance_transform_edt(nonseed): exact Euclidean distance of every voxel to the nearest False voxel (at least one exists), float64.
+    Separable: the squared distance along axis 0 first, then min_k f(x + k) + k^2 along every further axis."""
+    inf = np.int64(1) << 40
+    f = np.where(nonseed, inf, 0).astype(np.int64)
+    for ax in range(f.ndim):
+        f = np.moveaxis(f, ax, 0)
+        g = f.copy()
+        for k in range(1, f.shape[0]):
+            np.minimum(g[k:], f[:-k] + k * k, out=g[k:])
+            np.minimum(g[:-k], f[k:] + k * k, out=g[:-k])
+        f = np.moveaxis(g, 0, ax)
+    return np.sqrt(f.astype(np.float64))
+
+
+def _ndimage():
+    try:
+        from scipy import ndimage
+        return ndimage
+    except ImportError:
+        return None
+
+
+def _mask_edges(p, g, nd):
+    """get_mask_edges: crop to the box of p | g, squeeze, edges = erode(m) ^ m"""
+    u = p | g
+    if not u.any():
+        return np.zeros_like(p), np.zeros_like(g)
+    box = tuple(slice(int(i.min()), int(i.max()) + 1) for i in np.nonzero(u))
+    p, g = np.squeeze(p[box]), np.squeeze(g[box])
+    erode = nd.binary_erosion if nd is not None else _erode
+    return erode(p) ^ p, erode(g) ^ g
+
+
+def _surface_distance(ea, eb, nd):
+    """get_surface_distance(ea, eb, 'euclidean'): distance of every voxel of ea to the nearest voxel of eb"""
+    if not eb.any():
+        dis = np.full(eb.shape, np.inf)
+    else:
+        if not ea.any():
+            return np.full(eb.shape, np.inf)[eb]
+        dis = nd.distance_transform_edt(~eb) if nd is not None else _edt(~eb)
+    return np.asarray(dis[ea])
+
+
+def average_surface_distance_numpy(pred, gt, symmetric, use_scipy=True):
+    """pred, gt: bool [B, C, *spatial] -> float64 [B, C] (compute_average_surface_distance after ignore_background).  use_scipy=False takes
+    the numpy erosion / EDT even where scipy imports."""
+    nd = _ndimage() if use_scipy else None
+    B, Cc = pred.shape[:2]
+    asd = np.empty((B, Cc))
+    for b, c in np.ndindex(B, Cc):
+        ep, eg = _mask_edges(pred[b, c], gt[b, c], nd)
+        sd = _surface_distance(ep, eg, nd)
+        if symmetric:
+            sd = np.concatenate([sd, _surface_distance(eg, ep, nd)])
+        asd[b, c] = np.nan if sd.shape == (0,) else sd.mean()
+    return asd
+
+
+def _check_metric(distance_metric):
+    if distance_metric != "euclidean":
+        raise NotImplementedError(f"distance_metric '{distance_metric}' is not implemented (supported: 'euclidean')")
+
+
+def _exclusive_onehot(t):
+    """every voxel has exactly one channel at 1 and the others at 0"""
+    return bool((((t == 0) | (t == 1)).all() & (t.sum(dim=1) == 1).all()).item())
+
+
+def compute_average_surface_distance(y_pred, y, include_background=False, symmetric=False, distance_metric="euclidean"):
+    """MONAI's compute_average_surface_distance on one-hot [B, C, *spatial] inputs -> float64 [B, C'] (C' = C - 1 without background), on the
+    device of y_pred.  On a HIP device with exclusive one-hot 3-D inputs: class maps into csrc/surface.hip; otherwise the CPU restatement."""
+    _check_metric(distance_metric)
+    if y_pred.shape != y.shape:
+        raise ValueError(f"y_pred and y should have same shapes, got {tuple(y_pred.shape)} and {tuple(y.shape)}.")
+    Cc = y_pred.shape[1]
+    if (y_pred.is_cuda and y_pred.dim() == 5 and Cc <= 64 and max(y_pred.shape[2:]) <= 4096 and
+            _exclusive_onehot(y_pred) and _exclusive_onehot(y.to(y_pred.device))):
+        from ..hip import ops
+        return ops.surface_distance(y.to(y_pred.device).argmax(dim=1).to(torch.uint8), pred=y_pred.argmax(dim=1), num_classes=Cc,
+                                    include_background=include_background, symmetric=symmetric)
+    if not include_background:
+        y_pred, y = y_pred[:, 1:], y[:, 1:]
+    asd = average_surface_distance_numpy(y_pred.detach().cpu().numpy().astype(bool), y.detach().cpu().numpy().astype(bool), symmetric)
+    return torch.from_numpy(asd).to(y_pred.device)
+
+
+def surface_distance_from_logits(logits, label, num_classes, include_background=True, symmetric=True):
+    """AsDiscrete(argmax, to_onehot) on the logits + AsDiscrete(to_onehot) on the label + SurfaceDistanceMetric, fused: fp64 [B, C'].  On a HIP
+    device (fp32 [B, C, D, H, W] logits): one launch set over logits + labels, no one-hot volume (csrc/surface.hip); on CPU tensors
+    (--infer_cpu) the restatement above.  Label values outside [0, C) belong to no class, as in dice_from_logits."""
+    if (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 5 and logits.shape[1] == num_classes and num_classes <= 64
+            and max(logits.shape[2:]) <= 4096):
+        from ..hip import ops
+        return ops.surface_distance(label.to(logits.device), logits=logits.contiguous(), include_background=include_background, symmetric=symmetric)
+    classes = torch.arange(num_classes, device=logits.device).view(1, -1, *([1] * (logits.dim() - 2)))
+    pred = logits.argmax(dim=1, keepdim=True) == classes
+    lab = label.to(logits.device).reshape(logits.shape[0], 1, *logits.shape[2:]).long() == classes
+    c0 = 0 if include_background else 1
+    asd = average_surface_distance_numpy(pred[:, c0:].cpu().numpy(), lab[:, c0:].cpu().numpy(), symmetric)
+    return torch.from_numpy(asd).to(logits.device)
+
+
+# ------------------------------------------------------------------------------------------ cumulative metrics (MONAI 1.1.0 metrics/metric.py)
+_REDUCTIONS = ("none", "mean", "sum", "mean_batch", "sum_batch", "mean_channel", "sum_channel")
+
+
+def do_metric_reduction(f, reduction="mean"):
+    """monai.metrics.utils.do_metric_reduction on a [B, C] tensor -> (reduced, not_nans): NaNs are left out and counted, inf is not"""
+    if reduction not in _REDUCTIONS:
+        raise ValueError(f"Unsupported reduction: {reduction}, available options are {list(_REDUCTIONS)}.")
+    nans = torch.isnan(f)
+    not_nans = (~nans).float()
+    t_zero = torch.zeros(1, device=f.device, dtype=f.dtype)
+    if reduction == "none":
+        return f, not_nans
+    f = f.clone()
+    f[nans] = 0
+    if reduction == "mean":
+        not_nans = not_nans.sum(dim=1)
+        f = torch.where(not_nans > 0, f.sum(dim=1) / not_nans, t_zero)
+        not_nans = (not_nans > 0).float().sum(dim=0)
+        f = torch.where(not_nans > 0, f.sum(dim=0) / not_nans, t_zero)
+    elif reduction == "sum":
+        not_nans = not_nans.sum(dim=[0, 1])
+        f = torch.sum(f, dim=[0, 1])
+    elif reduction == "mean_batch":
+        not_nans = not_nans.sum(dim=0)
+        f = torch.where(not_nans > 0, f.sum(dim=0) / not_nans, t_zero)
+    elif reduction == "sum_batch":
+        not_nans = not_nans.sum(dim=0)
+        f = f.sum(dim=0)
+    elif reduction == "mean_channel":
+        not_nans = not_nans.sum(dim=1)
+        f = torch.where(not_nans > 0, f.sum(dim=1) / not_nans, t_zero)
+    else:
+        not_nans = not_nans.sum(dim=1)
+        f = f.sum(dim=1)
+    return f, not_nans
+
+
+class Cumulative:
+    """monai.metrics.Cumulative: extend(*batch_first_tensors) appends to one buffer per argument; get_buffer() concatenates them along the
+    batch (one tensor for one buffer, else a list)"""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self._buffers = None
+
+    def extend(self, *data):
+        if self._buffers is None:
+            self._buffers = [[] for _ in data]
+        for buf, d in zip(self._buffers, data):
+            d = torch.as_tensor(d)
+            buf.append(d.reshape(1) if d.dim() == 0 else d.detach())
+
+    def get_buffer(self):
+        if self._buffers is None:
+            return None
+        out = [torch.cat(b, dim=0) if b else None for b in self._buffers]
+        return out[0] if len(out) == 1 else out
+
+
+class _CumulativeMetric(Cumulative):
+    """CumulativeIterationMetric: __call__(y_pred=, y=) computes the per-batch [B, C'] values, appends them and returns them"""
+
+    def __init__(self, include_background=True, reduction="mean", get_not_nans=False):
+        super().__init__()
+        self.include_background, self.reduction, self.get_not_nans = include_background, reduction, get_not_nans
+
+    def __call__(self, y_pred, y):
+        ret = self._compute(y_pred, y)
+        self.extend(ret)
+        return ret
+
+    def aggregate(self, reduction=None):
+        data = self.get_buffer()
+        if not isinstance(data, torch.Tensor):
+            raise ValueError("the data to aggregate must be PyTorch Tensor.")
+        f, not_nans = do_metric_reduction(data, reduction or self.reduction)
+        return (f, not_nans) if self.get_not_nans else f
+
+
+class DiceMetric(_CumulativeMetric):
+    """monai.metrics.DiceMetric (ignore_empty=True) on one-hot [B, C, ...] inputs: dice_metric above, channel 0 dropped without background"""
+
+    def _compute(self, y_pred, y):
+        d = dice_metric(y_pred.float(), y.float().to(y_pred.device))
+        return d if self.include_background else d[:, 1:]
+
+
+class SurfaceDistanceMetric(_CumulativeMetric):
+    """monai.metrics.SurfaceDistanceMetric on one-hot [B, C, ...] inputs (compute_average_surface_distance above), float64 [B, C']"""
+
+    def __init__(self, include_background=False, symmetric=False, distance_metric="euclidean", reduction="mean", get_not_nans=False):
+        _check_metric(distance_metric)
+        super().__init__(include_background, reduction, get_not_nans)
+        self.symmetric, self.distance_metric = symmetric, distance_metric
+
+    def _compute(self, y_pred, y):
+        return compute_average_surface_distance(y_pred, y, include_background=self.include_background, symmetric=self.symmetric,
+                                                distance_metric=self.distance_metric)

@@ -1,0 +1,100 @@
+"""the fused average surface distance (csrc/surface.hip, miseg_surface_distance) at the bench.py --workload c5 volume size: a seeded synthetic
+512 x 512 x 363 label of 6 classes (nested and overlapping ellipsoids, some cut by the volume border), the prediction a perturbed copy, fp32
+logits.  Times the metric from logits with device events after warm-up (include_background True / False, symmetric), prints the bytes the
+passes move (from the shapes and the class boxes), the share of HBM peak, and the CPU restatement's time on a cropped volume."""
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+import numpy as np
+import torch
+import __graft_entry__ as ge
+
+ge.load_package()
+from mi_seg_amd.training import metrics as M
+
+D, H, W, C = 363, 512, 512, 6
+HBM_PEAK = 8.0e12            # MI355X HBM3E spec (6.29 TB/s measured with a float4 copy)
+
+
+def ellipsoids(shape, specs, device):
+    zz, yy, xx = (torch.arange(n, device=device, dtype=torch.float32) for n in shape)
+    lab = torch.zeros(shape, dtype=torch.uint8, device=device)
+    for c, ctr, r in specs:          # later ones paint over earlier ones: nested and overlapping structures
+        e = ((zz.view(-1, 1, 1) - ctr[0]) / r[0]) ** 2 + ((yy.view(1, -1, 1) - ctr[1]) / r[1]) ** 2 + ((xx.view(1, 1, -1) - ctr[2]) / r[2]) ** 2 <= 1
+        lab[e] = c
+    return lab
+
+
+def volume(device="cuda"):
+    g = torch.Generator().manual_seed(0)
+    specs = [(1, (180, 256, 256), (150, 220, 230)),        # the body: almost the whole volume
+             (2, (120, 200, 180), (60, 80, 70)), (3, (250, 300, 330), (70, 90, 60)),
+             (4, (190, 260, 250), (25, 30, 35)),           # nested inside 1, overlapping nothing else
+             (5, (20, 480, 40), (60, 70, 80)),             # cut by three faces of the volume
+             (2, (340, 60, 500), (40, 50, 30))]            # a second piece of class 2, on the border
+    lab = ellipsoids((D, H, W), specs, device)
+    jit = [(c, tuple(x + float(torch.randint(-4, 5, (1,), generator=g)) for x in ctr), tuple(x * (1 + 0.05 * float(torch.randn(1, generator=g))) for x in r))
+           for c, ctr, r in specs]
+    pred = ellipsoids((D, H, W), jit, device)
+    flip = torch.rand((D, H, W), generator=g).to(device) < 0.002
+    pred[flip] = torch.randint(0, C, (int(flip.sum()),), generator=g).to(device=device, dtype=torch.uint8)
+    return pred, lab
+
+
+def traffic(pred, lab, include_background):
+    """bytes of one call: the classify pass over logits + label, then per (c, box) the W / H / D passes (both directions: int32 distances,
+    packed stacks, edge bytes, class maps)"""
+    S = D * H * W
+    total = S * (C * 4 + 1 + 2)
+    for c in range(0 if include_background else 1, C):
+        u = (pred == c) | (lab == c)
+        if not bool(u.any()):
+            continue
+        ext = []
+        for ax in range(3):
+            i = u.any(dim=tuple(d for d in range(3) if d != ax)).nonzero()
+            ext.append(int(i.max() - i.min() + 1))
+        vol = ext[0] * ext[1] * ext[2]
+        total += vol * (2 + 1 + 2 * 4 * 3)        # W: class maps, edges, the two distance rows written twice and read once
+        total += vol * 2 * 4 * 4                  # H: read, write, stack write + read
+        total += vol * (2 * 4 * 3 + 2)            # D + gather: read, stack write + read, edge bytes
+    return total
+
+
+def main():
+    pred, lab = volume()
+    logits = torch.nn.functional.one_hot(pred.long(), C).permute(3, 0, 1, 2).float()[None].contiguous()
+    logits += 0.1 * torch.rand_like(logits)
+    label = lab[None, None]
+    for inc in (True, False):
+        for _ in range(2):
+            out = M.surface_distance_from_logits(logits, label, C, include_background=inc, symmetric=True)
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = M.surface_distance_from_logits(logits, label, C, include_background=inc, symmetric=True)
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        ms = sorted(ts)[len(ts) // 2]
+        nb = traffic(pred, lab, inc)
+        print(f"include_background={inc!s:5}  {ms:8.2f} ms (median of 5)  {nb / 1e9:6.2f} GB  {nb / ms / 1e9:6.3f} TB/s = {100 * nb / ms / 1e9 / (HBM_PEAK / 1e12):5.1f} % "
+              f"of HBM peak  asd {[round(v, 3) for v in out[0].tolist()]}")
+    # the CPU restatement (scipy.ndimage when it imports: MONAI's recipe) on a crop, one thread
+    crop = (slice(100, 228), slice(140, 268), slice(150, 246))
+    p, g = pred[crop].cpu().numpy().astype(np.int64), lab[crop].cpu().numpy().astype(np.int64)
+    cls = np.arange(C).reshape(1, C, 1, 1, 1)
+    t0 = time.perf_counter()
+    M.average_surface_distance_numpy(p[None, None] == cls, g[None, None] == cls, True)
+    cpu = time.perf_counter() - t0
+    n = p.size
+    print(f"CPU restatement ({'scipy' if M._ndimage() is not None else 'numpy'}), include_background=True, crop {p.shape}: {cpu:.2f} s "
+          f"({cpu / n * 1e9:.1f} ns per voxel; x{D * H * W / n:.0f} voxels for the whole volume)")
+
+
+if __name__ == "__main__":
+    main()
