@@ -33,7 +33,7 @@ enum { MISEG_ACT_NONE = 0, MISEG_ACT_LEAKY = 1, MISEG_ACT_GELU = 2, MISEG_ACT_PR
 #define MISEG_MAX_STYLES 4
 
 /* bumped on EVERY change of a struct layout or prototype; bindings must refuse a library whose version differs from the header they mirror */
-#define MISEG_ABI_VERSION 10
+#define MISEG_ABI_VERSION 11
 int miseg_abi_version(void);
 const char* miseg_last_error(void);
 /* writes e.g. "gfx950" for the code objects embedded in the library */
@@ -752,6 +752,30 @@ typedef struct {
   int C, Di, Hi, Wi, Do, Ho, Wo, mode, elem_bytes;
 } miseg_resample3d_params;
 int miseg_resample3d(const miseg_resample3d_params* p, miseg_stream_t stream);
+
+/* The prediction export (predict_whs.py:92-114: AsDiscrete(argmax=True), the inverse of SpatialPadd / Spacingd / Orientationd through the
+ * label key in nearest mode, the class remap): out[z][y][x] = lut[argmax_c logits[c][i_D][i_H][i_W]], where the logits index along axis_a
+ * (0 = D, 1 = H, 2 = W) is table_a[coordinate a] for each output axis a of X, Y, Z.  The tables fold the flips, the pad crop and the nearest
+ * resampling rule into one lookup per axis (the host builds them), so the kernel is a pure gather.  Argmax takes the FIRST maximum with a
+ * strict `>` (dice_count / surface_classify): a NaN in channel 0 gives class 0, a NaN in a later channel never wins.  Two launches: the argmax of
+ * the box [box_*0, box_*0 + box_n*) the tables index into a uint8 class map in the workspace, then the gather + LUT through LDS tiles.  Table
+ * values are clamped into the box (the host wrapper refuses values outside it).  out is C-contiguous [nz][ny][nx] (the NIfTI file's own
+ * Fortran order) of out_bytes = 1, 2 or 4-byte unsigned elements (lut values truncated to that width).  C 1..64, every side 1..65535, the box
+ * below 2^31 voxels.  The call only enqueues and reads nothing back: it can be captured into a graph. */
+typedef struct {
+  uint32_t struct_size;
+  const float* logits;             /* fp32 [C][D][H][W] */
+  int C, D, H, W;
+  int box_d0, box_h0, box_w0, box_nd, box_nh, box_nw;
+  int nx, ny, nz;
+  int axis_x, axis_y, axis_z;      /* logits axis indexed by output axis X / Y / Z: a permutation of 0, 1, 2 */
+  const int32_t* table_x; const int32_t* table_y; const int32_t* table_z;   /* device int32 [nx] / [ny] / [nz]: logits index along that axis */
+  const int32_t* lut;              /* device int32 [C]: the value written for each class */
+  void* workspace;                 /* miseg_label_export_workspace_bytes(box_nd, box_nh, box_nw) bytes, uninitialised */
+  void* out; int out_bytes;
+} miseg_label_export_params;
+size_t miseg_label_export_workspace_bytes(int box_nd, int box_nh, int box_nw);
+int miseg_label_export(const miseg_label_export_params* p, miseg_stream_t stream);
 
 /* sizeof() of a params struct as this library was compiled ("miseg_gemm_params", ...), 0 for an unknown name: bindings compare it with
  * their own mirror at load time (together with miseg_abi_version) so that header and binding cannot drift silently. */

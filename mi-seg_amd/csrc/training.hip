@@ -3,6 +3,7 @@
 //   * Dice metric after argmax / one-hot                                                                     (lightning_monai.py:68-79,190-195)
 //   * AdamW / Adam / SGD-nesterov step of EVERY parameter in one launch over the gradient arena              (lightning_monai.py:255-278)
 //   * sliding-window stitching as one gather over resident window logits                                     (lightning_monai.py:86-93,187)
+//   * the prediction export: argmax + inverse pad / spacing / orientation + class remap as one gather           (predict_whs.py:92-114)
 // MONAI 1.1.0 arithmetic restated from its public API (parity unpinned by any reference test).
 #include "common.h"
 #include "opt_math.h"
@@ -519,6 +520,62 @@ __global__ void __launch_bounds__(256) resample_nearest_kernel(const E* __restri
   }
 }
 
+// ------------------------------------------------------------------------------------------------ prediction export
+// Pass 1: first-maximum argmax of the logits box into a uint8 class map [bd][bh][bw] (lanes along w: every channel row is read coalesced).
+static __global__ void __launch_bounds__(256) export_argmax_kernel(const float* __restrict__ logits, uint8_t* __restrict__ cls, int C, int H, int W,
+                                                                   int64_t vox, int d0, int h0, int w0, int bh, int bw, int nbox) {
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < nbox; e += gridDim.x * 256) {
+    const int w = e % bw, h = (e / bw) % bh, d = e / (bw * bh);
+    const float* x = logits + ((int64_t)(d0 + d) * H + (h0 + h)) * W + (w0 + w);
+    int arg = 0;
+    float mx = x[0];
+    for (int c = 1; c < C; ++c) {
+      const float v = x[(int64_t)c * vox];
+      if (v > mx) { mx = v; arg = c; }            // strict: the FIRST maximum wins; a NaN after channel 0 never does
+    }
+    cls[e] = (uint8_t)arg;
+  }
+}
+
+// Pass 2: one workgroup = a 64 (X) x 64 (axis f) output tile at one coordinate of axis g.  The class-map bytes under the tile are read with the
+// lanes along whichever of X / f indexes the map's fast axis, staged in LDS, then written out with the lanes along X (whole 128-B lines of
+// uint16), through the LUT.
+constexpr int EXPORT_TILE = 64, EXPORT_LD = EXPORT_TILE + 1;
+struct ExportArgs {
+  const int32_t* tab[3];           // output axis X, Y, Z -> table
+  int n[3], lo[3], bn[3], st[3];   // per output axis: size, box origin / extent of its logits axis, class-map stride
+  int f, g, fast_x, C;
+};
+
+template <class O>
+__global__ void __launch_bounds__(256) export_gather_kernel(const uint8_t* __restrict__ cls, const int32_t* __restrict__ lut, O* __restrict__ out, ExportArgs a) {
+  __shared__ int offs[2][EXPORT_TILE];
+  __shared__ uint8_t tile[EXPORT_TILE * EXPORT_LD];         // [j along f][i along X]
+  __shared__ O lut_s[64];
+  const int tid = threadIdx.x, x0 = blockIdx.x * EXPORT_TILE, j0 = blockIdx.y * EXPORT_TILE, cg = blockIdx.z;
+  const int nx = a.n[0], nf = a.n[a.f];
+  if (tid < 2 * EXPORT_TILE) {
+    const int ax = tid < EXPORT_TILE ? 0 : a.f, i = tid & (EXPORT_TILE - 1), c = (ax == 0 ? x0 : j0) + i;
+    offs[tid >> 6][i] = c < a.n[ax] ? min(max(a.tab[ax][c] - a.lo[ax], 0), a.bn[ax] - 1) * a.st[ax] : 0;
+  } else if (tid < 2 * EXPORT_TILE + a.C) lut_s[tid - 2 * EXPORT_TILE] = (O)lut[tid - 2 * EXPORT_TILE];
+  __syncthreads();
+  const int og = min(max(a.tab[a.g][cg] - a.lo[a.g], 0), a.bn[a.g] - 1) * a.st[a.g];
+#pragma unroll 4
+  for (int k = 0; k < EXPORT_TILE * EXPORT_TILE / 256; ++k) {
+    const int e = tid + 256 * k;
+    const int i = a.fast_x ? (e & 63) : (e >> 6), j = a.fast_x ? (e >> 6) : (e & 63);
+    if (x0 + i < nx && j0 + j < nf) tile[j * EXPORT_LD + i] = cls[(int64_t)offs[0][i] + offs[1][j] + og];
+  }
+  __syncthreads();
+  const int64_t ost[3] = {1, (int64_t)nx, (int64_t)nx * a.n[1]};
+  O* ob = out + x0 + (int64_t)j0 * ost[a.f] + (int64_t)cg * ost[a.g];
+#pragma unroll 4
+  for (int k = 0; k < EXPORT_TILE * EXPORT_TILE / 256; ++k) {
+    const int e = tid + 256 * k, i = e & 63, j = e >> 6;
+    if (x0 + i < nx && j0 + j < nf) ob[i + (int64_t)j * ost[a.f]] = lut_s[tile[j * EXPORT_LD + i]];
+  }
+}
+
 template <class F> static int dispatch_label(int dt, F&& f) {
   switch (dt) {
     case MISEG_LABEL_F32: return f((const float*)nullptr);
@@ -729,6 +786,53 @@ extern "C" int miseg_resample3d(const miseg_resample3d_params* p, miseg_stream_t
     else return set_error(MISEG_E_UNSUPPORTED, "resample3d: element of %d bytes", p->elem_bytes);
   } else return set_error(MISEG_E_BADARG, "resample3d: mode %d", p->mode);
   MISEG_LAUNCH_CHECK("resample3d");
+  return MISEG_OK;
+}
+
+extern "C" size_t miseg_label_export_workspace_bytes(int box_nd, int box_nh, int box_nw) {
+  if (box_nd <= 0 || box_nh <= 0 || box_nw <= 0) return 0;
+  return (((size_t)box_nd * box_nh * box_nw) + 255) & ~(size_t)255;
+}
+
+extern "C" int miseg_label_export(const miseg_label_export_params* p, miseg_stream_t s_) {
+  hipStream_t s = (hipStream_t)s_;
+  MISEG_REQUIRE(p && p->struct_size == sizeof(miseg_label_export_params), MISEG_E_BADARG, "label_export: struct_size %u != %zu", p ? p->struct_size : 0u,
+                sizeof(miseg_label_export_params));
+  MISEG_REQUIRE(p->logits && p->table_x && p->table_y && p->table_z && p->lut && p->workspace && p->out, MISEG_E_BADARG, "label_export: null pointer");
+  MISEG_REQUIRE(p->C >= 1 && p->C <= 64, MISEG_E_BADARG, "label_export: C %d (1..64)", p->C);
+  MISEG_REQUIRE(p->out_bytes == 1 || p->out_bytes == 2 || p->out_bytes == 4, MISEG_E_BADARG, "label_export: out_bytes %d (1, 2 or 4)", p->out_bytes);
+  const int dims[3] = {p->D, p->H, p->W}, lo[3] = {p->box_d0, p->box_h0, p->box_w0}, bn[3] = {p->box_nd, p->box_nh, p->box_nw};
+  const int n[3] = {p->nx, p->ny, p->nz}, axis[3] = {p->axis_x, p->axis_y, p->axis_z};
+  for (int k = 0; k < 3; ++k) {
+    MISEG_REQUIRE(dims[k] > 0 && dims[k] <= 65535 && n[k] > 0 && n[k] <= 65535, MISEG_E_BADARG, "label_export: logits %dx%dx%d, out %dx%dx%d (sides 1..65535)",
+                  p->D, p->H, p->W, p->nx, p->ny, p->nz);
+    MISEG_REQUIRE(lo[k] >= 0 && bn[k] > 0 && lo[k] + bn[k] <= dims[k], MISEG_E_BADARG, "label_export: box axis %d [%d, %d + %d) leaves the side %d", k, lo[k],
+                  lo[k], bn[k], dims[k]);
+    MISEG_REQUIRE(axis[k] >= 0 && axis[k] < 3 && axis[k] != axis[(k + 1) % 3] && axis[k] != axis[(k + 2) % 3], MISEG_E_BADARG,
+                  "label_export: axes (%d, %d, %d) are not a permutation of (0, 1, 2)", axis[0], axis[1], axis[2]);
+  }
+  const int64_t nbox = (int64_t)bn[0] * bn[1] * bn[2];
+  MISEG_REQUIRE(nbox < ((int64_t)1 << 31), MISEG_E_UNSUPPORTED, "label_export: box of %lld voxels (below 2^31)", (long long)nbox);
+  uint8_t* cls = (uint8_t*)p->workspace;
+  int g1 = cdiv(nbox, 256 * 4);
+  if (g1 > 8192) g1 = 8192;
+  export_argmax_kernel<<<g1, 256, 0, s>>>(p->logits, cls, p->C, p->H, p->W, (int64_t)p->D * p->H * p->W, lo[0], lo[1], lo[2], bn[1], bn[2], (int)nbox);
+  MISEG_LAUNCH_CHECK("label_export argmax");
+  ExportArgs a;
+  const int st[3] = {bn[1] * bn[2], bn[2], 1};
+  const int32_t* tab[3] = {p->table_x, p->table_y, p->table_z};
+  for (int k = 0; k < 3; ++k) { a.tab[k] = tab[k]; a.n[k] = n[k]; a.lo[k] = lo[axis[k]]; a.bn[k] = bn[axis[k]]; a.st[k] = st[axis[k]]; }
+  // the tile's second axis: the one that indexes the class map's fast axis W, unless X does (then Y)
+  a.fast_x = axis[0] == 2;
+  a.f = a.fast_x ? 1 : (axis[1] == 2 ? 1 : 2);
+  a.g = 3 - a.f;
+  a.C = p->C;
+  const dim3 grid(cdiv(n[0], EXPORT_TILE), cdiv(n[a.f], EXPORT_TILE), n[a.g]);
+  const void* lut = p->lut;
+  if (p->out_bytes == 1) export_gather_kernel<uint8_t><<<grid, 256, 0, s>>>(cls, (const int32_t*)lut, (uint8_t*)p->out, a);
+  else if (p->out_bytes == 2) export_gather_kernel<uint16_t><<<grid, 256, 0, s>>>(cls, (const int32_t*)lut, (uint16_t*)p->out, a);
+  else export_gather_kernel<uint32_t><<<grid, 256, 0, s>>>(cls, (const int32_t*)lut, (uint32_t*)p->out, a);
+  MISEG_LAUNCH_CHECK("label_export gather");
   return MISEG_OK;
 }
 

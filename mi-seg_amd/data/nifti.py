@@ -65,8 +65,9 @@ def read_nifti(path):
     return np.ascontiguousarray(arr.astype(dt.newbyteorder("=")) if arr.dtype.byteorder not in ("=", "|") else arr), A
 
 
-def write_nifti(path, array, affine=None):
-    """single-file NIfTI-1 with an sform (used by tests and by the prediction export)"""
+def write_nifti(path, array, affine=None, compresslevel=9, mtime=None):
+    """single-file NIfTI-1 with an sform (used by tests and by the prediction export).  A .gz path is compressed at `compresslevel`; `mtime`
+    is the time stamp of the gzip header (None: now; 0 makes the file's bytes a function of its content alone)."""
     array = np.asarray(array)
     if array.dtype.name not in CODES:
         raise ValueError(f"dtype {array.dtype} has no NIfTI code")
@@ -83,15 +84,16 @@ def write_nifti(path, array, affine=None):
     struct.pack_into("<2h", hdr, 252, 0, 1)
     struct.pack_into("<12f", hdr, 280, *[float(v) for v in affine[:3].reshape(-1)])
     hdr[344:348] = b"n+1\0"
-    with _open(path, "wb") as f:
+    f = gzip.GzipFile(path, "wb", compresslevel=compresslevel, mtime=mtime) if str(path).endswith(".gz") else open(path, "wb")
+    with f:
         f.write(bytes(hdr))
         f.write(np.asfortranarray(array).tobytes(order="F"))
 
 
-def reorient_to_ras(array, affine):
-    """axis permutation + flips that make the voxel axes point Right / Anterior / Superior (closest-axis rule, like nibabel's
-    io_orientation / MONAI Orientationd): returns (array, new affine)"""
-    R = affine[:3, :3]
+def ras_orientation(affine):
+    """the closest-axis rule of nibabel's io_orientation / MONAI Orientationd: (order, flips) such that RAS axis k is the file's voxel axis
+    order[k], reversed when flips[k]"""
+    R = np.asarray(affine)[:3, :3]
     vox = np.sqrt((R ** 2).sum(0))
     vox[vox == 0] = 1.0
     cos = R / vox
@@ -101,7 +103,13 @@ def reorient_to_ras(array, affine):
         a = max(cand)[1]
         used.add(a)
         order.append(a)
-        flips.append(cos[world, a] < 0)
+        flips.append(bool(cos[world, a] < 0))
+    return order, flips
+
+
+def reorient_to_ras(array, affine):
+    """axis permutation + flips that make the voxel axes point Right / Anterior / Superior (ras_orientation): returns (array, new affine)"""
+    order, flips = ras_orientation(affine)
     out = np.transpose(array, order + list(range(3, array.ndim)))
     A = affine[:, order + [3]].copy()
     for ax, fl in enumerate(flips):

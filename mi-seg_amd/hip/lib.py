@@ -20,7 +20,7 @@ class _S(C.Structure):
     pass
 
 
-ABI_VERSION = 10         # == MISEG_ABI_VERSION of include/miseg_hip.h; load() refuses a library that reports another
+ABI_VERSION = 11         # == MISEG_ABI_VERSION of include/miseg_hip.h; load() refuses a library that reports another
 C_NAMES = {}             # ctypes mirror -> name of the C struct it mirrors (tests/test_abi.py checks sizeof / offsetof of every field)
 
 
@@ -143,6 +143,10 @@ Augment = _struct("Augment", cname="miseg_augment_params", fields=[
 Resample3d = _struct("Resample3d", cname="miseg_resample3d_params", fields=[
     ("struct_size", u32), ("in", vp), ("out", vp), ("C", i32), ("Di", i32), ("Hi", i32), ("Wi", i32), ("Do", i32), ("Ho", i32), ("Wo", i32),
     ("mode", i32), ("elem_bytes", i32)])
+LabelExport = _struct("LabelExport", cname="miseg_label_export_params", fields=[
+    ("struct_size", u32), ("logits", vp), ("C", i32), ("D", i32), ("H", i32), ("W", i32), ("box_d0", i32), ("box_h0", i32), ("box_w0", i32),
+    ("box_nd", i32), ("box_nh", i32), ("box_nw", i32), ("nx", i32), ("ny", i32), ("nz", i32), ("axis_x", i32), ("axis_y", i32), ("axis_z", i32),
+    ("table_x", vp), ("table_y", vp), ("table_z", vp), ("lut", vp), ("workspace", vp), ("out", vp), ("out_bytes", i32)])
 Dropout = _struct("Dropout", cname="miseg_dropout_params", fields=[
     ("struct_size", u32), ("x", vp), ("ldx", i64), ("y", vp), ("ldy", i64), ("rows", i64), ("C", i32), ("dtype", i32), ("rows_per_sample", i64),
     ("p", f32), ("seed", C.c_uint64), ("stream_id", C.c_uint64), ("step_dev", vp)])
@@ -246,6 +250,8 @@ PROTOS = {
     "miseg_stitch_windows": (i32, [C.POINTER(Stitch), vp]),
     "miseg_augment_crop": (i32, [C.POINTER(Augment), vp]),
     "miseg_resample3d": (i32, [C.POINTER(Resample3d), vp]),
+    "miseg_label_export_workspace_bytes": (C.c_size_t, [i32, i32, i32]),
+    "miseg_label_export": (i32, [C.POINTER(LabelExport), vp]),
     "miseg_dropout": (i32, [C.POINTER(Dropout), vp]),
     "miseg_counter_add": (i32, [vp, C.c_uint64, vp]),
     "miseg_conv3_wgrad_tiny": (i32, [i32, i32, i32, i32, i32, i32, i32]),

@@ -1694,6 +1694,71 @@ def surface_distance(label, logits=None, pred=None, num_classes=None, include_ba
     return asd
 
 
+_EXPORT_DTYPES = {torch.uint8: 1, torch.uint16: 2, torch.uint32: 4}
+
+
+def first_max_argmax(x):
+    """argmax over dim 0 under the kernels' rule: a strict `>` scan, so the FIRST maximum wins and a NaN after channel 0 never does (a NaN in
+    channel 0 gives class 0).  torch.argmax differs only where NaNs are present."""
+    arg = torch.zeros(x.shape[1:], dtype=torch.int64, device=x.device)
+    mx = x[0]
+    for c in range(1, x.shape[0]):
+        up = x[c] > mx
+        mx = torch.where(up, x[c], mx)
+        arg = torch.where(up, torch.full_like(arg, c), arg)
+    return arg
+
+
+def label_export(logits, tables, axes, lut, dtype=torch.uint16):
+    """[nz, ny, nx] label map (C-contiguous: a NIfTI file's Fortran order) of out[z][y][x] = lut[argmax_c logits[c][i_D][i_H][i_W]], the
+    logits index along axes[a] being tables[a][coordinate a] for the output axes a = X, Y, Z (miseg_label_export).  logits fp32 [(1,) C, D, H,
+    W]; tables three int32 vectors; axes a permutation of (0, 1, 2); lut int [C]; dtype uint8 / uint16 / uint32 (lut values truncated to it).
+    First-maximum argmax (first_max_argmax).  CPU logits take the same arithmetic in torch."""
+    if logits.dim() == 5 and logits.shape[0] == 1:
+        logits = logits[0]
+    if logits.dim() != 4 or logits.dtype != torch.float32:
+        raise ValueError("label_export: logits must be float32 [C, D, H, W]")
+    if dtype not in _EXPORT_DTYPES:
+        raise ValueError(f"label_export: dtype {dtype} (uint8 / uint16 / uint32)")
+    if sorted(int(a) for a in axes) != [0, 1, 2] or len(tables) != 3:
+        raise ValueError(f"label_export: axes {tuple(axes)} are not a permutation of (0, 1, 2)")
+    Cc, dims, dev = logits.shape[0], logits.shape[1:], logits.device
+    if not 1 <= Cc <= 64:
+        raise ValueError(f"label_export: {Cc} channels (1..64)")
+    lut = torch.as_tensor(lut).to(device=dev, dtype=torch.int64)
+    if lut.shape != (Cc,):
+        raise ValueError(f"label_export: lut of shape {tuple(lut.shape)} for {Cc} classes")
+    tabs, box = [], [None] * 3
+    for a in range(3):
+        t = torch.as_tensor(tables[a]).to(device=dev, dtype=torch.int32).contiguous()
+        if t.dim() != 1 or t.numel() == 0:
+            raise ValueError(f"label_export: table {'XYZ'[a]} must be a non-empty vector")
+        lo, hi = (int(v) for v in t.aminmax())
+        k = int(axes[a])
+        if lo < 0 or hi >= dims[k]:
+            raise ValueError(f"label_export: table {'XYZ'[a]} spans [{lo}, {hi}], outside the logits side {dims[k]}")
+        tabs.append(t)
+        box[k] = (lo, hi - lo + 1)
+    n = [t.numel() for t in tabs]
+    mask = (1 << (8 * _EXPORT_DTYPES[dtype])) - 1
+    if not logits.is_cuda:
+        cls = first_max_argmax(logits)
+        for k in range(3):
+            a = [int(v) for v in axes].index(k)
+            cls = cls.index_select(k, tabs[a].long())
+        cls = cls.permute(int(axes[2]), int(axes[1]), int(axes[0]))
+        return (lut & mask)[cls].to(dtype).contiguous()
+    logits = logits.contiguous()
+    out = torch.empty(n[2], n[1], n[0], dtype=dtype, device=dev)
+    lut32 = (lut & mask).to(torch.int32)             # the kernel truncates lut[c] to the element width
+    nbytes = L.load().miseg_label_export_workspace_bytes(box[0][1], box[1][1], box[2][1])
+    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    _call("miseg_label_export", L.LabelExport(C.sizeof(L.LabelExport), _ptr(logits), Cc, *dims, box[0][0], box[1][0], box[2][0], box[0][1], box[1][1],
+                                              box[2][1], *n, *(int(a) for a in axes), *(_ptr(t) for t in tabs), _ptr(lut32), _ptr(ws), _ptr(out),
+                                              _EXPORT_DTYPES[dtype]))
+    return out
+
+
 def stitch_windows(win, out, starts, roi, count=None, slab=None):
     """win fp32 [nd*nh*nw, C, rd, rh, rw] (the windows of the nd depth layers `starts[0]`, all resident), out fp32 [C, D, H, W];
     starts = (list_d, list_h, list_w).  slab = (d_begin, d_count): write only these depths of `out` from the resident layers (which then

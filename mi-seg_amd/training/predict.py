@@ -1,0 +1,131 @@
+"""Prediction export: the reference's predict_whs.py (35-114).  Each image of a data list's "test" entries goes through the prediction transforms
+(data/preprocess.py::load_image_for_prediction), the sliding-window inference with its modality, and then the way back - argmax, the inverse
+of the pad, the spacing and the orientation, the MM-WHS label codes - as one miseg_label_export call on the device, into a uint16 NIfTI
+label map in the image's own grid and affine."""
+import os
+import time
+from argparse import ArgumentParser
+
+import torch
+
+from ..data.checkpoint import load_model_state
+from ..data.decathlon import load_decathlon_datalist_with_modality, modality_id
+from ..data.nifti import write_nifti
+from ..data.preprocess import load_image_for_prediction
+from ..hip import ops
+from ..networks.utils.utils import model_from_argparse_args
+from ..utils.parser import add_model_argparse_args
+from .inferer import sliding_window_inference
+
+LABEL_MAP = {1: 500, 2: 600, 3: 420, 4: 550, 5: 205, 6: 820, 7: 850}      # predict_whs.py:18-26 (_MAP): class -> MM-WHS label code
+NO_GPU_MESSAGE = "predict_whs: the model and the label export run on the HIP device only (--no_gpu given, or no device visible)"
+COMPRESSLEVEL = 1        # gzip level of a .nii.gz label map (level 9 of a 190 MB volume costs seconds on one core for a few % of size)
+
+
+def label_lut(C, mapping=LABEL_MAP):
+    """int32 [C]: the class code each class index is written as, the reference's remap_tensor (one masked assignment per key, in order)
+    restated per class; a class without a key keeps its index"""
+    lut = []
+    for c in range(C):
+        v = c
+        for key, value in mapping.items():
+            if v == key:
+                v = value
+        lut.append(v)
+    return torch.tensor(lut, dtype=torch.int32)
+
+
+def invert_prediction(logits, geometry, lut, dtype=torch.uint16):
+    """logits [(1,) C, D, H, W] on the padded, resampled RAS grid -> label map in the file's grid: an [X, Y, Z] view of a C-contiguous [Z, Y, X]
+    buffer (the file's Fortran order), lut[first-maximum argmax] per voxel.  Device logits take miseg_label_export, CPU logits the same
+    arithmetic in torch (hip/ops.py::label_export)."""
+    shape = tuple(logits.shape[-3:])
+    if shape != geometry.padded_shape:
+        raise ValueError(f"invert_prediction: logits grid {shape} is not the geometry's padded grid {geometry.padded_shape}")
+    tables, axes = geometry.index_tables(logits.device if logits.is_cuda else None)
+    return ops.label_export(logits, tables, axes, lut, dtype).permute(2, 1, 0)
+
+
+def to_host(label_xyz):
+    """device [X, Y, Z] view of a [Z, Y, X] buffer -> numpy [X, Y, Z] in Fortran order, copied as it lies (no transpose on either side)"""
+    buf = label_xyz.permute(2, 1, 0)
+    if not buf.is_contiguous():
+        raise ValueError("to_host: not a view of a C-contiguous [Z, Y, X] buffer")
+    host = torch.empty(buf.shape, dtype=buf.dtype, pin_memory=buf.is_cuda)
+    host.copy_(buf)
+    return host.numpy().transpose(2, 1, 0)
+
+
+def output_path(image_path, result_dir):
+    """the reference's file name: the image's basename with "image" replaced by "label", under result_dir"""
+    return os.path.join(result_dir, os.path.basename(image_path).replace("image", "label"))
+
+
+def _sync(device):
+    if torch.device(device).type == "cuda":
+        torch.cuda.synchronize(device)
+    return time.perf_counter()
+
+
+def predict_volume(model, item, args):
+    """one data-list item ({"image", "modality"}) -> path of the written label map; prints the time of each stage"""
+    device = args.device
+    roi = (args.roi_x, args.roi_y, args.roi_z)
+    t0 = time.perf_counter()
+    image, geom = load_image_for_prediction(item["image"], (args.space_x, args.space_y, args.space_z), roi, device)
+    t1 = _sync(device)
+    modality = torch.tensor([modality_id(item.get("modality", 0))], device=device)
+    logits = sliding_window_inference(image, roi, args.sw_batch_size, model, overlap=args.infer_overlap, modalities=modality)
+    del image
+    t2 = _sync(device)
+    label = invert_prediction(logits, geom, label_lut(logits.shape[1]))
+    del logits                                    # the next volume's inference starts without this one's logits
+    t3 = _sync(device)
+    host = to_host(label)
+    del label
+    t4 = time.perf_counter()
+    path = output_path(item["image"], args.result_dir)
+    write_nifti(path, host, geom.affine, compresslevel=COMPRESSLEVEL, mtime=0)
+    t5 = time.perf_counter()
+    print(f"{os.path.basename(path)}: {'x'.join(str(s) for s in host.shape)} read+preprocess {t1 - t0:.3f} s, inference {t2 - t1:.3f} s, "
+          f"inverse {1e3 * (t3 - t2):.2f} ms, device-to-host {1e3 * (t4 - t3):.2f} ms, write {t5 - t4:.3f} s", flush=True)
+    return path
+
+
+def predict(model, datalist, args):
+    """predict_volume over the data list into args.result_dir (created); returns the written paths"""
+    os.makedirs(args.result_dir, exist_ok=True)
+    model.eval()
+    with torch.no_grad():
+        return [predict_volume(model, item, args) for item in datalist]
+
+
+def build_parser():
+    """the reference's command line (predict_whs.py:117-127): the model options plus its own, with its defaults"""
+    parser = add_model_argparse_args(ArgumentParser())
+    parser.add_argument("--checkpoint", default="", type=str, help="Checkpoint")
+    parser.add_argument("--sample", default="", type=str, help="accepted for compatibility, unused")
+    parser.add_argument("--space_x", default=1.0, type=float, help="spacing in x direction")
+    parser.add_argument("--space_y", default=1.0, type=float, help="spacing in y direction")
+    parser.add_argument("--space_z", default=1.0, type=float, help="spacing in z direction")
+    parser.add_argument("--no_gpu", action="store_true", help="refused: prediction runs on the HIP device only")
+    parser.add_argument("--data_dir", default="dataset/MM-WHS", type=str, help="dataset directory(ies)")
+    parser.add_argument("--json_list", default="CT_test.json", help="Json list(s) of input dataset(s)", type=str)
+    parser.add_argument("--result_dir", default="dataset/MM_WHS/MM_WHS_test/CT/", help="Directory for results", type=str)
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.no_gpu or not torch.cuda.is_available():
+        raise SystemExit(NO_GPU_MESSAGE)
+    if len(args.feature_size) == 1:
+        args.feature_size = args.feature_size[0]
+    args.device = "cuda:0"
+    args.distributed = False
+    torch.cuda.set_device(args.device)
+    model = model_from_argparse_args(args)
+    load_model_state(model, args.checkpoint)
+    model = model.to(args.device).eval()
+    datalist = load_decathlon_datalist_with_modality(os.path.join(args.data_dir, args.json_list), True, "test", base_dir=args.data_dir)
+    return predict(model, datalist, args)
