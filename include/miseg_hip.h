@@ -33,7 +33,7 @@ enum { MISEG_ACT_NONE = 0, MISEG_ACT_LEAKY = 1, MISEG_ACT_GELU = 2, MISEG_ACT_PR
 #define MISEG_MAX_STYLES 4
 
 /* bumped on EVERY change of a struct layout or prototype; bindings must refuse a library whose version differs from the header they mirror */
-#define MISEG_ABI_VERSION 11
+#define MISEG_ABI_VERSION 12
 int miseg_abi_version(void);
 const char* miseg_last_error(void);
 /* writes e.g. "gfx950" for the code objects embedded in the library */
@@ -535,6 +535,18 @@ int miseg_ncdhw_to_rows(const float* x, void* y, int B, int Cin, int64_t S, int 
  * other's adjoint, so the backward passes are the same two kernels.  D, H, W are the FINE grid; the coarse grid is ceil(./2). */
 typedef struct { const void* x; int64_t ldx; void* y; int64_t ldy; int B, D, H, W, C, dtype, dir; } miseg_resample2_params;
 int miseg_resample2(const miseg_resample2_params* p, miseg_stream_t stream);
+/* ---- decoder step of the conditional UNet (networks/nets/unet_vanilla.py:101-117 nn.Upsample(scale_factor=f) nearest, :162-169
+ * torch.concat((skip, up), dim=1)) ----
+ * out[b,z,y,x][0:Cs] = skip[b,z,y,x][:], out[b,z,y,x][Cs:Cs+Cu] = x[b, z/f, y/f, x/f][:] in one launch; f = 1 or 2, the FINE grid D, H, W exactly
+ * f x x's grid.  Channels-last rows with their own leading dimensions.  The skip's gradient is the left half of the concat's gradient (a view,
+ * no kernel); x's gradient is miseg_upsample_cat_bwd below.  Both only enqueue and can be captured. */
+typedef struct { const void* skip; int64_t ldskip; const void* x; int64_t ldx; void* out; int64_t ldout; int B, D, H, W, Cs, Cu, factor, dtype; } miseg_upsample_cat_params;
+int miseg_upsample_cat(const miseg_upsample_cat_params* p, miseg_stream_t stream);
+/* dx[b,z',y',x'][c] = sum over the f^3 fine children, in (dz, dy, dx) order, of dcat[child][c] -- dcat is the right half of the concat's
+ * gradient as a row view (its first channel, its leading dimension), D, H, W the fine grid; fp32 accumulation rounded once to dtype, no
+ * atomics (bit-reproducible). */
+typedef struct { const void* dcat; int64_t lddcat; void* dx; int64_t lddx; int B, D, H, W, C, factor, dtype; } miseg_upsample_cat_bwd_params;
+int miseg_upsample_cat_bwd(const miseg_upsample_cat_bwd_params* p, miseg_stream_t stream);
 /* y[r][c] = x[r][c] + bias[c]  (Conv3d / ConvTranspose3d bias, convolutions.py:115-139; the gradient is miseg_colsum) */
 typedef struct { const void* x; int64_t ldx; const float* bias; void* y; int64_t ldy; int64_t rows; int C, dtype; } miseg_rowbias_params;
 int miseg_rowbias_add(const miseg_rowbias_params* p, miseg_stream_t stream);

@@ -1998,6 +1998,119 @@ extern "C" int miseg_resample2(const miseg_resample2_params* p, miseg_stream_t s
   });
 }
 
+namespace miseg {
+// nearest upsample by f (1 or 2) of x into the right half of a channel concat: out[fine row] = [skip[fine row] | x[fine row / f]].  One
+// workgroup per fine (b, z, y) line; its lanes walk the line's W * (cvs + cvu) 16-byte vectors (or elements when VEC == 1) in order, so every
+// wave-instruction touches consecutive bytes of out and, per half, of one input row run.  The line's coarse row is scalar arithmetic.
+template <class T, int VEC>
+__global__ void __launch_bounds__(256) upsample_cat_kernel(const T* __restrict__ skip, int64_t ldskip, const T* __restrict__ x, int64_t ldx, T* __restrict__ out,
+                                                           int64_t ldout, int D, int H, int W, int cvs, int cvu, int f) {
+  const int line = blockIdx.x;                       // (b * D + z) * H + y
+  const int y = line % H, bz = line / H;
+  const int z = bz % D, b = bz / D;
+  const int Dc = D / f, Hc = H / f, Wc = W / f;
+  const int64_t row0 = (int64_t)line * W;
+  const int64_t crow0 = (((int64_t)b * Dc + z / f) * Hc + y / f) * Wc;
+  const int cvt = cvs + cvu;
+  const int n = W * cvt;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int w = i / cvt;
+    const int c = i - w * cvt;
+    const int64_t r = row0 + w;
+    V<T, VEC> v;
+    if (c < cvs) v.load(skip + r * ldskip + c * VEC);
+    else v.load(x + (crow0 + w / f) * ldx + (c - cvs) * VEC);
+    v.store(out + r * ldout + c * VEC);
+  }
+}
+
+// adjoint of the right half: dx[coarse row] = sum over the f^3 children (dz, dy, dx in that order) of dcat[child row], fp32, rounded once.
+// One workgroup per `lpb` consecutive coarse (b, z', y') lines (the host picks lpb so that the lanes divide the work evenly: a 48-voxel line of
+// 8 vectors is 384 items, two lines are three full rounds of 256 lanes).  No atomics, so the result does not depend on scheduling.
+template <class T, int VEC>
+__global__ void __launch_bounds__(256) upsample_cat_bwd_kernel(const T* __restrict__ dcat, int64_t lddcat, T* __restrict__ dx, int64_t lddx, int D, int H, int W,
+                                                               int cv, int f, int lines, int lpb) {
+  const int Dc = D / f, Hc = H / f, Wc = W / f;
+  const int n1 = Wc * cv;
+  const int n = lpb * n1;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int l = i / n1;
+    const int line = blockIdx.x * lpb + l;           // (b * Dc + z') * Hc + y'
+    if (line >= lines) break;
+    const int y = line % Hc, bz = line / Hc;
+    const int z = bz % Dc, b = bz / Dc;
+    const int j = i - l * n1;
+    const int w = j / cv;
+    const int c = (j - w * cv) * VEC;
+    float acc[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+    for (int dz = 0; dz < f; ++dz)
+      for (int dy = 0; dy < f; ++dy) {
+        const int64_t frow = (((int64_t)b * D + z * f + dz) * H + y * f + dy) * W + (int64_t)w * f;
+        for (int dw = 0; dw < f; ++dw) {
+          V<T, VEC> g;
+          g.load(dcat + (frow + dw) * lddcat + c);
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) acc[k] += g.v[k];
+        }
+      }
+    V<T, VEC> o;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) o.v[k] = acc[k];
+    o.store(dx + ((int64_t)line * Wc + w) * lddx + c);
+  }
+}
+}  // namespace miseg
+
+extern "C" int miseg_upsample_cat(const miseg_upsample_cat_params* p, miseg_stream_t s_) {
+  hipStream_t s = (hipStream_t)s_;
+  MISEG_REQUIRE(p && p->skip && p->x && p->out && p->B > 0 && p->D > 0 && p->H > 0 && p->W > 0 && p->Cs > 0 && p->Cu > 0, MISEG_E_BADARG,
+                "upsample_cat: bad args");
+  MISEG_REQUIRE(p->factor == 1 || p->factor == 2, MISEG_E_BADARG, "upsample_cat: factor %d (1 or 2)", p->factor);
+  MISEG_REQUIRE(p->D % p->factor == 0 && p->H % p->factor == 0 && p->W % p->factor == 0, MISEG_E_BADARG,
+                "upsample_cat: fine grid %dx%dx%d is not %d x a coarse grid", p->D, p->H, p->W, p->factor);
+  MISEG_REQUIRE(p->ldskip >= p->Cs && p->ldx >= p->Cu && p->ldout >= p->Cs + p->Cu, MISEG_E_BADARG, "upsample_cat: a leading dimension is below its channel count");
+  const int64_t lines = (int64_t)p->B * p->D * p->H;
+  MISEG_REQUIRE(lines < (1ll << 31) && (int64_t)p->W * (p->Cs + p->Cu) < (1ll << 31), MISEG_E_BADARG, "upsample_cat: grid too large");
+  DT(p, {
+    constexpr int N = Vec16<T>::N;
+    const bool vec = p->Cs % N == 0 && p->Cu % N == 0 && p->ldskip % N == 0 && p->ldx % N == 0 && p->ldout % N == 0 && al16(p->skip) && al16(p->x) && al16(p->out);
+    if (vec) miseg::upsample_cat_kernel<T, N><<<(unsigned)lines, 256, 0, s>>>((const T*)p->skip, p->ldskip, (const T*)p->x, p->ldx, (T*)p->out, p->ldout, p->D, p->H, p->W,
+                                                                             p->Cs / N, p->Cu / N, p->factor);
+    else miseg::upsample_cat_kernel<T, 1><<<(unsigned)lines, 256, 0, s>>>((const T*)p->skip, p->ldskip, (const T*)p->x, p->ldx, (T*)p->out, p->ldout, p->D, p->H, p->W,
+                                                                          p->Cs, p->Cu, p->factor);
+    MISEG_LAUNCH_CHECK("upsample_cat");
+  });
+}
+
+extern "C" int miseg_upsample_cat_bwd(const miseg_upsample_cat_bwd_params* p, miseg_stream_t s_) {
+  hipStream_t s = (hipStream_t)s_;
+  MISEG_REQUIRE(p && p->dcat && p->dx && p->B > 0 && p->D > 0 && p->H > 0 && p->W > 0 && p->C > 0, MISEG_E_BADARG, "upsample_cat_bwd: bad args");
+  MISEG_REQUIRE(p->factor == 1 || p->factor == 2, MISEG_E_BADARG, "upsample_cat_bwd: factor %d (1 or 2)", p->factor);
+  MISEG_REQUIRE(p->D % p->factor == 0 && p->H % p->factor == 0 && p->W % p->factor == 0, MISEG_E_BADARG,
+                "upsample_cat_bwd: fine grid %dx%dx%d is not %d x a coarse grid", p->D, p->H, p->W, p->factor);
+  MISEG_REQUIRE(p->lddcat >= p->C && p->lddx >= p->C, MISEG_E_BADARG, "upsample_cat_bwd: a leading dimension is below the channel count");
+  const int64_t lines = (int64_t)p->B * (p->D / p->factor) * (p->H / p->factor);
+  MISEG_REQUIRE(lines < (1ll << 31) && 4ll * p->W * p->C < (1ll << 31), MISEG_E_BADARG, "upsample_cat_bwd: grid too large");
+  DT(p, {
+    constexpr int N = Vec16<T>::N;
+    const bool vec = p->C % N == 0 && p->lddcat % N == 0 && p->lddx % N == 0 && al16(p->dcat) && al16(p->dx);
+    const int cv = vec ? p->C / N : p->C;
+    const int64_t n1 = (int64_t)(p->W / p->factor) * cv;
+    int lpb = 1;                                     // lines per workgroup: the best lane utilisation over 1..4 lines, the fewer lines on a tie
+    double best = 0.0;
+    for (int k = 1; k <= 4 && k * n1 < (1ll << 31); ++k) {
+      const double u = (double)(k * n1) / (256.0 * (double)((k * n1 + 255) / 256));
+      if (u > best + 1e-9) { best = u; lpb = k; }
+    }
+    const unsigned grid = (unsigned)((lines + lpb - 1) / lpb);
+    if (vec) miseg::upsample_cat_bwd_kernel<T, N><<<grid, 256, 0, s>>>((const T*)p->dcat, p->lddcat, (T*)p->dx, p->lddx, p->D, p->H, p->W, cv, p->factor, (int)lines, lpb);
+    else miseg::upsample_cat_bwd_kernel<T, 1><<<grid, 256, 0, s>>>((const T*)p->dcat, p->lddcat, (T*)p->dx, p->lddx, p->D, p->H, p->W, cv, p->factor, (int)lines, lpb);
+    MISEG_LAUNCH_CHECK("upsample_cat_bwd");
+  });
+}
+
 extern "C" int miseg_rowbias_add(const miseg_rowbias_params* p, miseg_stream_t s_) {
   hipStream_t s = (hipStream_t)s_;
   MISEG_REQUIRE(p && p->x && p->y && p->bias && p->rows > 0 && p->C > 0, MISEG_E_BADARG, "rowbias_add: bad args");

@@ -1135,6 +1135,27 @@ def cat_channels(a, b):
     return _Cat2.apply(a, b)
 
 
+class _UpsampleCat(Function):
+    """cat([skip, nearest_upsample(x, f)], channel) in one kernel; the backward hands the skip the left half of the gradient as a view and x
+    the f^3-child sums of the right half (a copy-free view when f == 1)."""
+
+    @staticmethod
+    def forward(ctx, skip, x, factor):
+        ctx.cs, ctx.f = skip.shape[-1], int(factor)
+        return ops.upsample_cat(skip, x, factor)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = _rv(g)
+        right = g[..., ctx.cs:]
+        return g[..., :ctx.cs], (right if ctx.f == 1 else ops.upsample_cat_bwd(right, ctx.f)), None
+
+
+def upsample_cat(skip, x, factor):
+    """torch.concat((skip, nn.Upsample(scale_factor=factor)(x)), dim=1) on channels-last rows (reference unet_vanilla.py:162-169)"""
+    return _UpsampleCat.apply(skip, x, int(factor))
+
+
 def image_rows(x_ncdhw, dtype):
     """the NCDHW fp32 network input as channels-last rows [B, D, H, W, C] in the compute dtype (no gradient: the image is data) - the entry
     of multi-channel images (--in_channels > 1, utils/parser.py:11) into the ordinary convolution kernels"""

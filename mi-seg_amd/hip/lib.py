@@ -20,7 +20,7 @@ class _S(C.Structure):
     pass
 
 
-ABI_VERSION = 11         # == MISEG_ABI_VERSION of include/miseg_hip.h; load() refuses a library that reports another
+ABI_VERSION = 12         # == MISEG_ABI_VERSION of include/miseg_hip.h; load() refuses a library that reports another
 C_NAMES = {}             # ctypes mirror -> name of the C struct it mirrors (tests/test_abi.py checks sizeof / offsetof of every field)
 
 
@@ -89,6 +89,10 @@ Copy2d = _struct("Copy2d", cname="miseg_copy2d_params", fields=[("src", vp), ("l
 CastDesc = _struct("CastDesc", cname="miseg_cast_desc", fields=[("src", vp), ("dst", vp), ("R", i32), ("C", i32), ("transpose", i32), ("inner", i32), ("outer", i32), ("tile0", i32)])
 Resample2 = _struct("Resample2", cname="miseg_resample2_params", fields=[("x", vp), ("ldx", i64), ("y", vp), ("ldy", i64), ("B", i32), ("D", i32), ("H", i32), ("W", i32), ("C", i32),
                                   ("dtype", i32), ("dir", i32)])
+UpsampleCat = _struct("UpsampleCat", cname="miseg_upsample_cat_params", fields=[("skip", vp), ("ldskip", i64), ("x", vp), ("ldx", i64), ("out", vp), ("ldout", i64),
+                                      ("B", i32), ("D", i32), ("H", i32), ("W", i32), ("Cs", i32), ("Cu", i32), ("factor", i32), ("dtype", i32)])
+UpsampleCatBwd = _struct("UpsampleCatBwd", cname="miseg_upsample_cat_bwd_params", fields=[("dcat", vp), ("lddcat", i64), ("dx", vp), ("lddx", i64), ("B", i32), ("D", i32),
+                                            ("H", i32), ("W", i32), ("C", i32), ("factor", i32), ("dtype", i32)])
 Rowbias = _struct("Rowbias", cname="miseg_rowbias_params", fields=[("x", vp), ("ldx", i64), ("bias", vp), ("y", vp), ("ldy", i64), ("rows", i64), ("C", i32), ("dtype", i32)])
 PreluFwd = _struct("PreluFwd", cname="miseg_prelu_fwd_params", fields=[("x", vp), ("ldx", i64), ("slope", vp), ("y", vp), ("ldy", i64), ("rows", i64), ("C", i32), ("dtype", i32)])
 PreluBwd = _struct("PreluBwd", cname="miseg_prelu_bwd_params", fields=[("dy", vp), ("lddy", i64), ("x", vp), ("ldx", i64), ("slope", vp), ("dx", vp), ("lddx", i64), ("dslope", vp),
@@ -234,6 +238,8 @@ PROTOS = {
     "miseg_fill32_ranges": (i32, [vp, C.c_uint32, vp, i32, vp]),
     "miseg_param_cast_batch": (i32, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "miseg_resample2": (i32, [C.POINTER(Resample2), vp]),
+    "miseg_upsample_cat": (i32, [C.POINTER(UpsampleCat), vp]),
+    "miseg_upsample_cat_bwd": (i32, [C.POINTER(UpsampleCatBwd), vp]),
     "miseg_rowbias_add": (i32, [C.POINTER(Rowbias), vp]),
     "miseg_prelu_fwd": (i32, [C.POINTER(PreluFwd), vp]),
     "miseg_prelu_bwd": (i32, [C.POINTER(PreluBwd), vp]),

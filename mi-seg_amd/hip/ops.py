@@ -1374,6 +1374,41 @@ def resample2(x, up, fine_shape=None):
     return out
 
 
+def upsample_cat(skip, x, factor):
+    """cat([skip, nearest_upsample(x, factor)], channel) in one launch (reference unet_vanilla.py:162-169): skip [B,D,H,W,Cs] and x
+    [B,D/f,H/f,W/f,Cu] row views of one dtype, factor 1 or 2 -> a new [B,D,H,W,Cs+Cu]."""
+    factor = int(factor)
+    if factor not in (1, 2):
+        raise NotImplementedError(f"upsample_cat: scale factor {factor} (1 or 2)")
+    B, D, H, W = _vol(skip)
+    if x.dim() != 5 or x.shape[0] != B or tuple(factor * v for v in x.shape[1:4]) != (D, H, W):
+        raise ValueError(f"upsample_cat: x {tuple(x.shape)} upsampled by {factor} does not match the skip {tuple(skip.shape)}")
+    if x.dtype != skip.dtype:
+        raise ValueError(f"upsample_cat: dtypes {skip.dtype} / {x.dtype}")
+    lds, _, Cs = rows(skip)
+    ldx, _, Cu = rows(x)
+    out = torch.empty(B, D, H, W, Cs + Cu, dtype=x.dtype, device=x.device)
+    _call("miseg_upsample_cat", L.UpsampleCat(_ptr(skip), lds, _ptr(x), ldx, _ptr(out), Cs + Cu, B, D, H, W, Cs, Cu, factor, _dt(x)),
+          prof=("upsample_cat", 0.0, _nb(skip, x, out)))
+    return out
+
+
+def upsample_cat_bwd(dcat_right, factor):
+    """gradient of x in upsample_cat: dcat_right is the right half of the concat's gradient ([B,D,H,W,Cu] row view, its own leading dimension);
+    returns [B,D/f,H/f,W/f,Cu], each entry the fp32 sum of its f^3 fine children in a fixed order, rounded once"""
+    factor = int(factor)
+    if factor not in (1, 2):
+        raise NotImplementedError(f"upsample_cat_bwd: scale factor {factor} (1 or 2)")
+    B, D, H, W = _vol(dcat_right)
+    if D % factor or H % factor or W % factor:
+        raise ValueError(f"upsample_cat_bwd: grid {(D, H, W)} is not {factor} x a coarse grid")
+    ld, _, Cu = rows(dcat_right)
+    dx = torch.empty(B, D // factor, H // factor, W // factor, Cu, dtype=dcat_right.dtype, device=dcat_right.device)
+    _call("miseg_upsample_cat_bwd", L.UpsampleCatBwd(_ptr(dcat_right), ld, _ptr(dx), Cu, B, D, H, W, Cu, factor, _dt(dx)),
+          prof=("upsample_cat", 0.0, _nb(dcat_right, dx)))
+    return dx
+
+
 def rowbias_add(x, bias):
     ld, n, Cc = rows(x)
     y = torch.empty(x.shape, dtype=x.dtype, device=x.device)

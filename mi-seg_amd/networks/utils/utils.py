@@ -5,6 +5,7 @@ import torch
 
 from ..nets.swin_unetr import SwinUNETR
 from ..nets.unet import UNet
+from ..nets.unet_vanilla import UNetVanilla
 from ..nets.unetr import UNETR
 
 __all__ = ["model_from_argparse_args"]
@@ -16,6 +17,8 @@ def model_from_argparse_args(args):
         model = UNETR.from_argparse_args(args)
     elif name == "unet":
         model = UNet.from_argparse_args(args)
+    elif name == "unet_vanilla":
+        model = UNetVanilla.from_argparse_args(args)
     elif name in ("swin_unetr", "pre_swin_unetr"):
         model = SwinUNETR.from_argparse_args(args)
         if name == "pre_swin_unetr":

@@ -7,7 +7,7 @@ MODEL_ARGS = {
     "monai.net": [
         ("--pretrained", dict(type=str, help="path to pre-trained model checkpoint")),
         ("--ckpt_path", dict(type=str, help="path to a training checkpoint to resume")),
-        ("--model_name", dict(default="unetr", type=str, help="unet | unetr | swin_unetr | pre_swin_unetr")),
+        ("--model_name", dict(default="unetr", type=str, help="unet | unet_vanilla | unetr | swin_unetr | pre_swin_unetr")),
         ("--in_channels", dict(default=1, type=int)), ("--out_channels", dict(default=14, type=int)),
         ("--roi_x", dict(default=96, type=int)), ("--roi_y", dict(default=96, type=int)), ("--roi_z", dict(default=96, type=int)),
         ("--feature_size", dict(default=[16], type=int, nargs="+")),
