@@ -33,7 +33,7 @@ enum { MISEG_ACT_NONE = 0, MISEG_ACT_LEAKY = 1, MISEG_ACT_GELU = 2, MISEG_ACT_PR
 #define MISEG_MAX_STYLES 4
 
 /* bumped on EVERY change of a struct layout or prototype; bindings must refuse a library whose version differs from the header they mirror */
-#define MISEG_ABI_VERSION 12
+#define MISEG_ABI_VERSION 13
 int miseg_abi_version(void);
 const char* miseg_last_error(void);
 /* writes e.g. "gfx950" for the code objects embedded in the library */
@@ -309,7 +309,7 @@ int miseg_colsum_batch(const miseg_colsum_desc* descs_host, int n, int dtype, mi
 typedef struct {
   const void* x; int64_t ldx; void* y; int64_t ldy; const void* wpk;
   int B, D, H, W, Cin, Cout, dtype;
-  void* workspace;                 /* miseg_conv3_fwd_workspace_bytes (0 bytes for most shapes: may be NULL then) */
+  void* workspace;                 /* miseg_conv3_plan_info.workspace_bytes (0 bytes for most shapes: may be NULL then) */
   /* optional epilogue pieces, only on the 96-byte-chunk path (channel rows of `dtype` a multiple of 96 bytes; else MISEG_E_UNSUPPORTED):
    * res (ldres): added to the result before rounding (the other gradient of a forked input when this is the data-gradient pass);
    * stat: fp64 [16][B][Cout][2] (miseg_instnorm_stat_bytes, zero on entry) - per-channel sum / sum of squares of the ROUNDED
@@ -320,48 +320,43 @@ typedef struct {
   /* ABI 4: 1 = background launch (96-byte-chunk path): one workgroup per CU instead of two, so that the kernels of another stream find
    * registers, LDS and wave slots on every CU while this one runs (a branch of the step running beside its latency-bound chain) */
   int32_t background;
-  /* ABI 5: 1 = when the launch splits its reduction (miseg_conv3_fwd_splits > 1) it stops after the partial slabs in `workspace`
+  /* ABI 5: 1 = when the launch splits its reduction (miseg_conv3_plan_info.splits > 1) it stops after the partial slabs in `workspace`
    * ([splits][B*D*H*W][Cout] fp32): the caller's next launch sums them (miseg_instnorm_fwd_slabs) - y and stat are NOT written.  No `res`. */
   int32_t defer_slabs;
-  /* ABI 9, only where miseg_conv3_fuses_shortcut(...) says so (bf16, 96-byte chunks, unsplit launch): y += sc_x * sc_w^T, a 1x1x1 term -
+  /* ABI 9, only where miseg_conv3_plan_info.sc says so (bf16, 96-byte chunks, unsplit launch, 16-byte aligned operands): y += sc_x * sc_w^T, a 1x1x1 term -
    * the data-gradient pass of a residual block's first convolution takes the gradient of the block's 1x1x1 shortcut convolution
    * along (dynunet_block.py:87-97,100-126: dx = dgrad3x3(g1) + g3 W3) instead of reading a [voxels][Cout] tensor that a GEMM wrote.
    * sc_x: [B][D][H][W][sc_C] rows (ld_sc_x), sc_C a multiple of 48; sc_w: [Cout][sc_C] in `dtype` (W3 transposed), contiguous. */
   const void* sc_x; int64_t ld_sc_x; const void* sc_w; int32_t sc_C;
-  /* ABI 9, only where miseg_conv3_fuses_s2c(...) says so (96-byte chunks, unsplit launch, even D / H / W): output channels [0, s2c_C) are NOT
+  /* ABI 9, only where miseg_conv3_plan_info.s2c says so (96-byte chunks, unsplit launch, even D / H / W): output channels [0, s2c_C) are NOT
    * written to y but to s2c_out [B][D/2][H/2][W/2][8][s2c_C] - voxel (d, h, w) at block j = 4 (d&1) + 2 (h&1) + (w&1) of its coarse voxel: the
    * layout in which the ConvTranspose3d(k2, s2) in front of a decoder block reads the gradient of its output (unetr_block.py:80-85; the
    * data-gradient pass of that block's first convolution produces it, left half of the concat buffer).  Channels >= s2c_C go to y as usual. */
   void* s2c_out; int32_t s2c_C;
-  /* ABI 9, only where miseg_conv3_fuses_fwd_shortcut(...) says so: fs_y = x * fs_w^T as a SECOND output of the launch - the 1x1x1 shortcut
+  /* ABI 9, only where miseg_conv3_plan_info.fs says so: fs_y = x * fs_w^T as a SECOND output of the launch - the 1x1x1 shortcut
    * convolution of a residual block beside its first 3x3x3 convolution (dynunet_block.py:87-97: both read the block's input).  fs_w: [Cout][Cin]
    * in `dtype`, contiguous; fs_y: [B][D][H][W][Cout] rows (ld_fs_y); fs_stat (optional): instance-norm statistics of fs_y, as `stat` for y. */
   const void* fs_w; void* fs_y; int64_t ld_fs_y; void* fs_stat;
 } miseg_conv3_params;
-/* small grids split the reduction over workgroups and need an fp32 staging buffer of the output */
-size_t miseg_conv3_fwd_workspace_bytes(int B, int D, int H, int W, int Cin, int Cout, int dtype);
-/* number of partial slabs the launch leaves in `workspace` (1 = no split: y is written directly) */
-int miseg_conv3_fwd_splits(int B, int D, int H, int W, int Cin, int Cout, int dtype);
-/* 1 when miseg_conv3_fwd serves these shapes with its tiny-volume weight-streaming kernel (ABI 9: 3^3 / 6^3 voxels, hundreds of channels, bf16, aligned
- * operands) - information for a host that names / times launches; the call and its results are the same either way */
-int miseg_conv3_fwd_tiny(int B, int D, int H, int W, int Cin, int Cout, int dtype);
-/* 1 when miseg_conv3_fwd with these shapes can take a 1x1x1 shortcut term of sc_C channels along (miseg_conv3_params.sc_x) */
-int miseg_conv3_fuses_shortcut(int B, int D, int H, int W, int Cin, int Cout, int sc_C, int dtype);
-/* 1 when miseg_conv3_fwd with these shapes can produce a 1x1x1 convolution of its input as a second output (miseg_conv3_params.fs_w) */
-int miseg_conv3_fuses_fwd_shortcut(int B, int D, int H, int W, int Cin, int Cout, int dtype);
-/* 1 when miseg_conv3_fwd with these shapes can store its first s2c_C output channels in space-to-channel order (miseg_conv3_params.s2c_out) */
-int miseg_conv3_fuses_s2c(int B, int D, int H, int W, int Cin, int Cout, int s2c_C, int dtype);
+/* ABI 13: what miseg_conv3_fwd(p) does with these params - the launch dispatches on exactly this plan.  A requested piece that the
+ * launch cannot serve comes back 0 (the launch refuses it with MISEG_E_UNSUPPORTED); pointers are only tested for NULL and alignment,
+ * so a host may ask with stand-ins for buffers it has not allocated yet.  Host only: touches no device. */
+#define MISEG_CONV3_GENERIC 0      /* row-major kernel: no optional piece */
+#define MISEG_CONV3_FWD96 1        /* 96-byte channel chunks */
+#define MISEG_CONV3_FWD_TINY 2     /* 3^3 / 6^3 volumes, weight streaming, always split */
+typedef struct {
+  int32_t kernel;                  /* MISEG_CONV3_* */
+  int32_t splits;                  /* partial slabs [splits][B*D*H*W][Cout] fp32 in `workspace` (1: y is written directly) */
+  size_t workspace_bytes;          /* 0: `workspace` may be NULL */
+  int32_t res, stat, sc, s2c, fs, defer_slabs;      /* 1: requested and served (stat: not with defer_slabs served) */
+} miseg_conv3_plan_info;
+int miseg_conv3_fwd_plan(const miseg_conv3_params* p, miseg_conv3_plan_info* plan);
 int miseg_conv3_fwd(const miseg_conv3_params* p, miseg_stream_t stream);
 
 /* w: fp32 torch layout [Cout][Cin][3][3][3].  fwd_pack feeds miseg_conv3_fwd on x, bwd_pack (taps mirrored, channels swapped) feeds it
  * on dy; either may be NULL.  The layout is internal (row-major [Cout][27][CinP] or planar [27][CinP/k][CoutP16][k], by channel count);
  * buffers hold miseg_pack_conv3_elems(Cin, Cout, dtype, which) elements of `dtype` (which: 0 = fwd, 1 = bwd). */
 size_t miseg_pack_conv3_elems(int Cin, int Cout, int dtype, int which);
-/* K extent (elements; a whole number of 96-byte chunks) of the fast path for C channels on the K side of miseg_conv3_fwd, or 0 where the
- * generic row-major kernel runs.  Rows of >= 64 bytes that are neither a multiple of 96 bytes nor of a narrow chunk (64 / 32 bytes, bf16)
- * bytes are padded with zero weights to the next chunk (32 -> 48, 64 -> 96, 128 -> 144, 256 -> 288 bf16 channels; C-UNETR: 146.2 / 155.2 / 161.0 / 165.7 / 163.4 patches/s at 0 / 256 / 128 / 64 / 32).  Fused residual / statistics
- * (miseg_conv3_params.res / .stat) need a non-zero value. */
-int miseg_conv3_k96(int C, int dtype);
 /* 16x16 tiles miseg_pack_conv3_batch walks for one layer (the padded K groups of a fast-path pack get tiles of their own) */
 int miseg_pack_conv3_tiles(int Cin, int Cout, int dtype);
 typedef struct { const float* w; void* fwd_pack; void* bwd_pack; int Cin, Cout, dtype; } miseg_pack_conv3_params;
@@ -384,15 +379,21 @@ typedef struct {
   const void* x; int64_t ldx; const void* dy; int64_t lddy; float* dw;
   int B, D, H, W, Cin, Cout, dtype;
   int accumulate;                  /* 0: dw = result; 1: dw += result; 2: dw is known to be zero on entry (no fill, no read-back) */
-  void* workspace;                 /* miseg_conv3_wgrad_workspace_bytes */
+  void* workspace;                 /* miseg_conv3_wgrad_plan_info.workspace_bytes (0: may be NULL) */
   int32_t max_workgroups;          /* ABI 4: 0 = fill the chip (256); else a cap on the workgroups of the launch (a workgroup owns its CU's registers:
                                     * a background launch leaves the other CUs to the kernels of another stream).  miseg_conv3_wgrad only */
 } miseg_conv3_wgrad_params;
-size_t miseg_conv3_wgrad_workspace_bytes(int B, int D, int H, int W, int Cin, int Cout);
+/* ABI 13: the kernel miseg_conv3_wgrad(p) takes for these params and the workspace it needs (host only, as miseg_conv3_fwd_plan):
+ * fp32 / bf16 slab kernels, NARROW (bf16, 16 / 32 channels on both sides), TINY (bf16, 3^3 / 6^3 voxels, Cin % 16 == 0, Cout % 48 == 0,
+ * aligned; no workspace).  Only TINY stores the whole of dw when accumulate is 2, and it is a write-bound launch of its own that a host
+ * should not queue for miseg_conv3_wgrad_group */
+#define MISEG_CONV3_WGRAD_F32 0
+#define MISEG_CONV3_WGRAD_NARROW 1
+#define MISEG_CONV3_WGRAD_TINY 2
+#define MISEG_CONV3_WGRAD_BF16 3
+typedef struct { int32_t kernel; int32_t pad_; size_t workspace_bytes; } miseg_conv3_wgrad_plan_info;
+int miseg_conv3_wgrad_plan(const miseg_conv3_wgrad_params* p, miseg_conv3_wgrad_plan_info* plan);
 int miseg_conv3_wgrad(const miseg_conv3_wgrad_params* p, miseg_stream_t stream);
-/* 1 when miseg_conv3_wgrad takes a layer of this shape with the tiny-volume kernel (ABI 6: bf16, 3^3 / 6^3 voxels, Cin % 16 == 0,
- * Cout % 48 == 0): a write-bound launch of its own that a host should not queue for miseg_conv3_wgrad_group */
-int miseg_conv3_wgrad_tiny(int B, int D, int H, int W, int Cin, int Cout, int dtype);
 /* Up to 24 layers of one dtype in one launch (+ one for the partial sums): the small-grid weight gradients of a backward pass
  * (dynunet_block.py:100-126 at 48^3 and below) fill the chip together instead of one after the other.  `workspace` of the
  * params is ignored; one shared buffer of miseg_conv3_wgrad_group_workspace_bytes is passed instead (may be NULL when that is 0). */

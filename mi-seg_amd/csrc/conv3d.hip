@@ -1780,12 +1780,9 @@ __global__ void __launch_bounds__(256) conv3_wgrad_tiny_kernel(const bf16* __res
   }
 }
 
-static bool wgrad_tiny_shape(int B, int D, int H, int W, int Cin, int Cout, int dtype) {
-  return dtype == MISEG_BF16 && D == H && H == W && (D == 3 || D == 6) && B >= 1 && B <= 64 && Cin % 16 == 0 && Cout % 48 == 0;
-}
 static bool wgrad_tiny(const miseg_conv3_wgrad_params* p) {
-  return wgrad_tiny_shape(p->B, p->D, p->H, p->W, p->Cin, p->Cout, p->dtype) && ((uintptr_t)p->x % 16 == 0) && ((uintptr_t)p->dy % 16 == 0) && p->ldx % 8 == 0 &&
-         p->lddy % 8 == 0;
+  return p->dtype == MISEG_BF16 && p->D == p->H && p->H == p->W && (p->D == 3 || p->D == 6) && p->B >= 1 && p->B <= 64 && p->Cin % 16 == 0 &&
+         p->Cout % 48 == 0 && ((uintptr_t)p->x % 16 == 0) && ((uintptr_t)p->dy % 16 == 0) && p->ldx % 8 == 0 && p->lddy % 8 == 0;
 }
 static int conv3_wgrad_tiny_launch(const miseg_conv3_wgrad_params* p, hipStream_t s) {
   const dim3 grid(p->Cin / 16, p->Cout / 48);
@@ -1927,112 +1924,91 @@ static void fwd96_plan(int nbricks, int Cout, int nchunks, int* nt, int* ksplit)
   *ksplit = ks;
 }
 
-extern "C" size_t miseg_conv3_fwd_workspace_bytes(int B, int D, int H, int W, int Cin, int Cout, int dtype) {
-  const int esz = dtype == MISEG_F32 ? 4 : 2;
-  const int rowbytes = conv3_k96(Cin, esz, conv3_pad_min_bytes()) * esz;
-  if (!rowbytes) return 0;
-  int nt, ks;
-  fwd96_plan(B * cdiv(D, FBD) * cdiv(H, FBH) * cdiv(W, FBW), Cout, rowbytes / (16 * conv3_gpt(Cin, esz, conv3_pad_min_bytes())), &nt, &ks);
-  return ks > 1 ? (size_t)ks * B * D * H * W * Cout * sizeof(float) : 0;
+// THE plan of a forward launch: conv3_fwd_launch dispatches on it and miseg_conv3_fwd_plan returns its public part (host only)
+struct Conv3FwdPlan {
+  miseg_conv3_plan_info pub;
+  int k96, gpt, nchunks, nt, cps;      // fast path: K extent, groups per chunk, chunks, 16-channel tiles per block, chunks per split
+};
+static void conv3_fwd_plan(const miseg_conv3_params* p, Conv3FwdPlan* q) {
+  const int esz = p->dtype == MISEG_F32 ? 4 : 2, kpc = 16 / esz;
+  const bool bf16 = p->dtype == MISEG_BF16;
+  *q = Conv3FwdPlan{};
+  q->pub.splits = 1;
+  q->k96 = conv3_k96(p->Cin, esz, conv3_pad_min_bytes());
+  if (!q->k96) { q->pub.kernel = MISEG_CONV3_GENERIC; return; }      // (weights come from the row-major pack: same predicate in the pack)
+  q->gpt = conv3_gpt(p->Cin, esz, conv3_pad_min_bytes());
+  q->nchunks = q->k96 * esz / (16 * q->gpt);
+  int ks;
+  fwd96_plan(p->B * cdiv(p->D, FBD) * cdiv(p->H, FBH) * cdiv(p->W, FBW), p->Cout, q->nchunks, &q->nt, &ks);
+  q->cps = cdiv(q->nchunks, ks);
+  const int splits = q->pub.splits = cdiv(q->nchunks, q->cps);
+  q->pub.workspace_bytes = splits > 1 ? (size_t)splits * p->B * p->D * p->H * p->W * p->Cout * sizeof(float) : 0;
+  const bool vec_x = ((uintptr_t)p->x % 16 == 0) && (p->ldx % kpc == 0);
+  // tiny volumes whose every chunk is a split of its own: the weight-streaming kernel (same pack, same slabs)
+  const int nvox = p->D * p->H * p->W;
+  const bool tiny = bf16 && splits > 1 && q->gpt == 6 && splits == q->nchunks && nvox <= 256 && vec_x && !p->background && p->Cin % 8 == 0 &&
+                    (size_t)(p->D + 2) * (p->H + 2) * (p->W + 2) * TINY_ROWB <= 64 * 1024;
+  q->pub.kernel = tiny ? MISEG_CONV3_FWD_TINY : MISEG_CONV3_FWD96;
+  q->pub.defer_slabs = p->defer_slabs && splits > 1 && !p->res;
+  q->pub.res = p->res != nullptr;
+  q->pub.stat = p->stat && !q->pub.defer_slabs;
+  // the three folds of round 5 ride in the unsplit fast-path launch only
+  q->pub.sc = p->sc_x && bf16 && q->gpt == 6 && splits == 1 && p->sc_w && p->sc_C > 0 && p->sc_C % (6 * kpc) == 0 && (uintptr_t)p->sc_x % 16 == 0 &&
+              p->ld_sc_x % kpc == 0 && (uintptr_t)p->sc_w % 16 == 0;
+  q->pub.fs = p->fs_w && bf16 && q->gpt == 6 && splits == 1 && p->fs_y && p->Cin % (6 * kpc) == 0 && vec_x && (uintptr_t)p->fs_w % 16 == 0;
+  q->pub.s2c = p->s2c_out && splits == 1 && p->s2c_C > 0 && p->s2c_C < p->Cout && p->s2c_C % (16 * q->nt) == 0 && p->s2c_C % kpc == 0 &&
+               p->D % 2 == 0 && p->H % 2 == 0 && p->W % 2 == 0 && (uintptr_t)p->s2c_out % 16 == 0;
 }
 
-extern "C" int miseg_conv3_fuses_shortcut(int B, int D, int H, int W, int Cin, int Cout, int Csc, int dtype) {
-  if (dtype != MISEG_BF16) return 0;
-  const int k96 = conv3_k96(Cin, 2, conv3_pad_min_bytes());
-  if (!k96 || conv3_gpt(Cin, 2, conv3_pad_min_bytes()) != 6 || Csc <= 0 || Csc % 48 != 0) return 0;
-  int nt, ks;
-  fwd96_plan(B * cdiv(D, FBD) * cdiv(H, FBH) * cdiv(W, FBW), Cout, k96 * 2 / 96, &nt, &ks);
-  return ks == 1 ? 1 : 0;
+static int conv3_fwd_check(const miseg_conv3_params* p) {
+  MISEG_REQUIRE(p->B > 0 && p->D > 0 && p->H > 0 && p->W > 0 && p->Cin > 0 && p->Cout > 0, MISEG_E_BADARG, "conv3_fwd: bad shape");
+  MISEG_REQUIRE(p->ldx >= p->Cin && p->ldy >= p->Cout, MISEG_E_BADARG, "conv3_fwd: row stride smaller than channel count");
+  MISEG_REQUIRE(p->dtype == MISEG_F32 || p->dtype == MISEG_BF16, MISEG_E_BADARG, "conv3_fwd: dtype %d", p->dtype);
+  return MISEG_OK;
 }
 
-// 1 when miseg_conv3_fwd serves this problem with the tiny-volume weight-streaming kernel (conv3_fwd_tiny_kernel): the same predicate as its launch
-extern "C" int miseg_conv3_fwd_tiny(int B, int D, int H, int W, int Cin, int Cout, int dtype) {
-  if (dtype != MISEG_BF16 || Cin % 8 != 0) return 0;
-  const int k96 = conv3_k96(Cin, 2, conv3_pad_min_bytes());
-  if (!k96 || conv3_gpt(Cin, 2, conv3_pad_min_bytes()) != 6) return 0;
-  const int nchunks = k96 * 2 / 96, nvox = D * H * W;
-  int nt, ks;
-  fwd96_plan(B * cdiv(D, FBD) * cdiv(H, FBH) * cdiv(W, FBW), Cout, nchunks, &nt, &ks);
-  return (ks > 1 && ks == nchunks && nvox <= 256 && (size_t)(D + 2) * (H + 2) * (W + 2) * TINY_ROWB <= 64 * 1024) ? 1 : 0;
-}
-
-extern "C" int miseg_conv3_fuses_fwd_shortcut(int B, int D, int H, int W, int Cin, int Cout, int dtype) {
-  return miseg_conv3_fuses_shortcut(B, D, H, W, Cin, Cout, Cin, dtype);      // (the same launch conditions; the 1x1x1 term's K side is Cin itself)
-}
-
-extern "C" int miseg_conv3_fuses_s2c(int B, int D, int H, int W, int Cin, int Cout, int s2c_C, int dtype) {
-  const int esz = dtype == MISEG_F32 ? 4 : 2;
-  const int k96 = conv3_k96(Cin, esz, conv3_pad_min_bytes());
-  if (!k96 || (D | H | W) & 1 || s2c_C <= 0 || s2c_C >= Cout || s2c_C % (16 / esz) != 0) return 0;
-  int nt, ks;
-  fwd96_plan(B * cdiv(D, FBD) * cdiv(H, FBH) * cdiv(W, FBW), Cout, k96 * esz / (16 * conv3_gpt(Cin, esz, conv3_pad_min_bytes())), &nt, &ks);
-  return (ks == 1 && s2c_C % (16 * nt) == 0) ? 1 : 0;
-}
-
-extern "C" int miseg_conv3_fwd_splits(int B, int D, int H, int W, int Cin, int Cout, int dtype) {
-  const int esz = dtype == MISEG_F32 ? 4 : 2;
-  const int rowbytes = conv3_k96(Cin, esz, conv3_pad_min_bytes()) * esz;
-  if (!rowbytes) return 1;
-  int nt, ks;
-  const int nchunks = rowbytes / (16 * conv3_gpt(Cin, esz, conv3_pad_min_bytes()));
-  fwd96_plan(B * cdiv(D, FBD) * cdiv(H, FBH) * cdiv(W, FBW), Cout, nchunks, &nt, &ks);
-  const int cps = cdiv(nchunks, ks);
-  return cdiv(nchunks, cps);
+extern "C" int miseg_conv3_fwd_plan(const miseg_conv3_params* p, miseg_conv3_plan_info* plan) {
+  MISEG_REQUIRE(p && plan, MISEG_E_BADARG, "conv3_fwd_plan: null pointer");
+  if (const int rc = conv3_fwd_check(p)) return rc;
+  Conv3FwdPlan q;
+  conv3_fwd_plan(p, &q);
+  *plan = q.pub;
+  return MISEG_OK;
 }
 
 template <class T>
 static int conv3_fwd_launch(const miseg_conv3_params* p, hipStream_t s) {
   constexpr int KPC = Vec16<T>::N;
-  const int k96 = conv3_k96(p->Cin, (int)sizeof(T), conv3_pad_min_bytes());
-  const int CinP = k96 ? k96 : round_up(p->Cin, KPC);
+  Conv3FwdPlan q;
+  conv3_fwd_plan(p, &q);
+  const miseg_conv3_plan_info& pl = q.pub;
+  const int CinP = q.k96 ? q.k96 : round_up(p->Cin, KPC);
   const int rowbytes = CinP * (int)sizeof(T);
   ConvGeom g{p->B, p->D, p->H, p->W, cdiv(p->D, BD), cdiv(p->H, BH), cdiv(p->W, BW)};
   const int nbricks = g.B * g.nbd * g.nbh * g.nbw;
   const bool vec_x = ((uintptr_t)p->x % 16 == 0) && (p->ldx % KPC == 0);
+  MISEG_REQUIRE(!p->res || pl.res, MISEG_E_UNSUPPORTED, "conv3_fwd: fused residual needs 96-byte channel chunks");
+  MISEG_REQUIRE(!p->stat || pl.stat || pl.defer_slabs, MISEG_E_UNSUPPORTED, "conv3_fwd: fused statistics need 96-byte channel chunks");
+  MISEG_REQUIRE(!p->sc_x || pl.sc, MISEG_E_UNSUPPORTED, "conv3_fwd: fused shortcut on these operands (ask miseg_conv3_fwd_plan first)");
+  MISEG_REQUIRE(!p->fs_w || pl.fs, MISEG_E_UNSUPPORTED, "conv3_fwd: second (1x1x1) output on these operands (ask miseg_conv3_fwd_plan first)");
+  MISEG_REQUIRE(!p->s2c_out || pl.s2c, MISEG_E_UNSUPPORTED, "conv3_fwd: space-to-channel store on these operands (ask miseg_conv3_fwd_plan first)");
+  MISEG_REQUIRE(!pl.workspace_bytes || p->workspace, MISEG_E_BADARG, "conv3_fwd: workspace required (miseg_conv3_plan_info.workspace_bytes)");
   // ---- fast path: 96-byte channel chunks, planar LDS images (weights must come from the planar pack: same predicate
   // in miseg_pack_conv3_weight: conv3_k96)
-  if (k96) {
+  if (pl.kernel != MISEG_CONV3_GENERIC) {
     ConvGeom gf{p->B, p->D, p->H, p->W, cdiv(p->D, FBD), cdiv(p->H, FBH), cdiv(p->W, FBW)};
     const int nbr = gf.B * gf.nbd * gf.nbh * gf.nbw;
-    int nt, ksplit;
-    const int gpt = conv3_gpt(p->Cin, (int)sizeof(T), conv3_pad_min_bytes());
-    const int nchunks = rowbytes / (16 * gpt);
-    fwd96_plan(nbr, p->Cout, nchunks, &nt, &ksplit);
-    const int cps = cdiv(nchunks, ksplit);
-    ksplit = cdiv(nchunks, cps);
-    float* scratch = nullptr;
-    if (ksplit > 1) {
-      MISEG_REQUIRE(p->workspace, MISEG_E_BADARG, "conv3_fwd: workspace required (miseg_conv3_fwd_workspace_bytes)");
-      scratch = (float*)p->workspace;
-    }
+    const int nt = q.nt, gpt = q.gpt, nchunks = q.nchunks, cps = q.cps, ksplit = pl.splits;
+    float* scratch = ksplit > 1 ? (float*)p->workspace : nullptr;
     const bool vec_y = ((uintptr_t)p->y % 16 == 0) && (p->ldy % KPC == 0);
     const int CoP = round_up(p->Cout, 16);
-    if (p->sc_x) {      // the fused 1x1x1 shortcut term (miseg_conv3_fuses_shortcut)
-      constexpr bool is_bf16 = std::is_same<T, bf16>::value;
-      MISEG_REQUIRE(is_bf16 && gpt == 6 && ksplit == 1 && p->sc_w && p->sc_C > 0 && p->sc_C % (6 * KPC) == 0,
-                    MISEG_E_UNSUPPORTED, "conv3_fwd: fused shortcut on this shape / dtype (ask miseg_conv3_fuses_shortcut first)");
-      MISEG_REQUIRE((uintptr_t)p->sc_x % 16 == 0 && p->ld_sc_x % KPC == 0 && (uintptr_t)p->sc_w % 16 == 0, MISEG_E_BADARG, "conv3_fwd: shortcut operands must be 16-byte aligned");
-    }
-    if (p->fs_w) {      // the block's 1x1x1 shortcut convolution as a second output (miseg_conv3_fuses_fwd_shortcut)
-      constexpr bool is_bf16_ = std::is_same<T, bf16>::value;
-      MISEG_REQUIRE(is_bf16_ && gpt == 6 && ksplit == 1 && p->fs_y && p->Cin % (6 * KPC) == 0 && vec_x, MISEG_E_UNSUPPORTED,
-                    "conv3_fwd: second (1x1x1) output on this shape / dtype (ask miseg_conv3_fuses_fwd_shortcut first)");
-      MISEG_REQUIRE((uintptr_t)p->fs_w % 16 == 0, MISEG_E_BADARG, "conv3_fwd: fs_w must be 16-byte aligned");
-    }
-    if (p->s2c_out) {   // the left channels stored in space-to-channel order (miseg_conv3_fuses_s2c)
-      MISEG_REQUIRE(ksplit == 1 && p->s2c_C > 0 && p->s2c_C < p->Cout && p->s2c_C % (16 * nt) == 0 && p->D % 2 == 0 && p->H % 2 == 0 && p->W % 2 == 0,
-                    MISEG_E_UNSUPPORTED, "conv3_fwd: space-to-channel store on this shape (ask miseg_conv3_fuses_s2c first)");
-      MISEG_REQUIRE((uintptr_t)p->s2c_out % 16 == 0 && p->s2c_C % KPC == 0, MISEG_E_BADARG, "conv3_fwd: s2c_out must be 16-byte aligned");
-    }
     size_t lds = (size_t)gpt * FPS * 16 + (size_t)2 * 12 * 16 * nt * 16;
     if (p->background && lds < 83 * 1024) lds = 83 * 1024;      // more than half of the 160 KB: one workgroup per CU
     MISEG_REQUIRE((int64_t)p->B * p->D * p->H * p->W < (1LL << 31), MISEG_E_UNSUPPORTED, "conv3_fwd: more than 2^31 voxels");
     const int ny = cdiv(p->Cout, 16 * nt);
     if constexpr (std::is_same<T, bf16>::value) {
-      // tiny volumes whose every chunk is a split of its own: the weight-streaming kernel (same pack, same slabs)
       const int nvox = p->D * p->H * p->W;
-      if (scratch && gpt == 6 && ksplit == nchunks && nvox <= 256 && vec_x && !p->background && p->Cin % 8 == 0 &&
-          (size_t)(p->D + 2) * (p->H + 2) * (p->W + 2) * TINY_ROWB <= 64 * 1024) {
+      if (pl.kernel == MISEG_CONV3_FWD_TINY) {
         const size_t lds_t = (size_t)(p->D + 2) * (p->H + 2) * (p->W + 2) * TINY_ROWB;
         if (nvox <= 32) {
           dim3 gt(cdiv(CoP / 16, 4), nchunks, p->B);
@@ -2044,10 +2020,7 @@ static int conv3_fwd_launch(const miseg_conv3_params* p, hipStream_t s) {
           conv3_fwd_tiny_kernel<4, 4><<<gt, 256, lds_t, s>>>((const bf16*)p->x, p->ldx, (const bf16*)p->wpk, p->D, p->H, p->W, p->Cin, p->Cout, CoP, scratch, p->B * nvox);
         }
         MISEG_LAUNCH_CHECK("conv3_fwd_tiny");
-        if (p->defer_slabs) {
-          MISEG_REQUIRE(!p->res, MISEG_E_UNSUPPORTED, "conv3_fwd: defer_slabs with a fused residual");
-          return MISEG_OK;
-        }
+        if (pl.defer_slabs) return MISEG_OK;
         return slabs_to_out_stats(scratch, ksplit, p->y, p->ldy, p->res, p->ldres, p->B, nvox, p->Cout, p->dtype, (double*)p->stat, s);
       }
     }
@@ -2060,7 +2033,7 @@ static int conv3_fwd_launch(const miseg_conv3_params* p, hipStream_t s) {
                                                                  (T*)p->s2c_out, p->s2c_C, (const T*)p->fs_w, (T*)p->fs_y, p->ld_fs_y, (double*)p->fs_stat)
 #define F96_CASE(n, wd, gp)                                                                                                                  \
   case n:                                                                                                                                   \
-    if (!scratch && (p->res || p->stat || p->sc_x || p->s2c_out || p->fs_w)) { F96_LAUNCH(n, wd, true, gp); } else { F96_LAUNCH(n, wd, false, gp); }   \
+    if (!scratch && (pl.res || pl.stat || pl.sc || pl.s2c || pl.fs)) { F96_LAUNCH(n, wd, true, gp); } else { F96_LAUNCH(n, wd, false, gp); }   \
     break;
     if (gpt == 6) { switch (nt) { F96_CASE(1, 3, 6) F96_CASE(2, 2, 6) F96_CASE(3, 3, 6) } }
     else if (gpt == 4) { switch (nt) { F96_CASE(1, 3, 4) F96_CASE(2, 2, 4) F96_CASE(3, 3, 4) } }
@@ -2068,15 +2041,11 @@ static int conv3_fwd_launch(const miseg_conv3_params* p, hipStream_t s) {
 #undef F96_CASE
 #undef F96_LAUNCH
     MISEG_LAUNCH_CHECK("conv3_fwd96");
-    if (scratch && p->defer_slabs) {      // the caller's next launch sums the slabs itself (miseg_instnorm_fwd_slabs)
-      MISEG_REQUIRE(!p->res, MISEG_E_UNSUPPORTED, "conv3_fwd: defer_slabs with a fused residual");
-      return MISEG_OK;
-    }
+    if (pl.defer_slabs) return MISEG_OK;      // the caller's next launch sums the slabs itself (miseg_instnorm_fwd_slabs)
     if (scratch)      // sum of the slabs + residual -> y, with the statistics of y when asked for (one launch)
       return slabs_to_out_stats(scratch, ksplit, p->y, p->ldy, p->res, p->ldres, p->B, p->D * p->H * p->W, p->Cout, p->dtype, (double*)p->stat, s);
     return MISEG_OK;
   }
-  MISEG_REQUIRE(!p->res && !p->stat, MISEG_E_UNSUPPORTED, "conv3_fwd: fused residual / statistics need 96-byte channel chunks");
   int chunk_bytes;
   if (rowbytes <= 128) chunk_bytes = rowbytes;
   else if (rowbytes % 128 == 0) chunk_bytes = 128;
@@ -2100,11 +2069,8 @@ static int conv3_fwd_launch(const miseg_conv3_params* p, hipStream_t s) {
 
 extern "C" int miseg_conv3_fwd(const miseg_conv3_params* p, miseg_stream_t s_) {
   MISEG_REQUIRE(p && p->x && p->y && p->wpk, MISEG_E_BADARG, "conv3_fwd: null pointer");
-  MISEG_REQUIRE(p->B > 0 && p->D > 0 && p->H > 0 && p->W > 0 && p->Cin > 0 && p->Cout > 0, MISEG_E_BADARG, "conv3_fwd: bad shape");
-  MISEG_REQUIRE(p->ldx >= p->Cin && p->ldy >= p->Cout, MISEG_E_BADARG, "conv3_fwd: row stride smaller than channel count");
-  if (p->dtype == MISEG_F32) return conv3_fwd_launch<float>(p, (hipStream_t)s_);
-  if (p->dtype == MISEG_BF16) return conv3_fwd_launch<bf16>(p, (hipStream_t)s_);
-  return set_error(MISEG_E_BADARG, "conv3_fwd: dtype %d", p->dtype);
+  if (const int rc = conv3_fwd_check(p)) return rc;
+  return p->dtype == MISEG_F32 ? conv3_fwd_launch<float>(p, (hipStream_t)s_) : conv3_fwd_launch<bf16>(p, (hipStream_t)s_);
 }
 
 extern "C" size_t miseg_pack_conv3_elems(int Cin, int Cout, int dtype, int which) {
@@ -2114,10 +2080,9 @@ extern "C" size_t miseg_pack_conv3_elems(int Cin, int Cout, int dtype, int which
   return which == 0 ? (size_t)28 * CinP * round_up(Cout, 16) : (size_t)28 * CoutP * round_up(Cin, 16);
 }
 
-extern "C" int miseg_conv3_k96(int C, int dtype) { return conv3_k96(C, dtype == MISEG_F32 ? 4 : 2, conv3_pad_min_bytes()); }
-
 extern "C" int miseg_pack_conv3_tiles(int Cin, int Cout, int dtype) {
-  const int kf = miseg_conv3_k96(Cin, dtype), kb = miseg_conv3_k96(Cout, dtype);
+  const int esz = dtype == MISEG_F32 ? 4 : 2;
+  const int kf = conv3_k96(Cin, esz, conv3_pad_min_bytes()), kb = conv3_k96(Cout, esz, conv3_pad_min_bytes());
   return cdiv(kf > Cin ? kf : Cin, PK_T) * cdiv(kb > Cout ? kb : Cout, PK_T);
 }
 
@@ -2189,17 +2154,28 @@ static void wgrad_plan(int B, int D, int H, int W, int Cin, int Cout, int wbd, i
   *nsplit = ns;
 }
 
-extern "C" size_t miseg_conv3_wgrad_workspace_bytes(int B, int D, int H, int W, int Cin, int Cout) {
-  int ncob, ncib, ns2, ns4;
-  wgrad_plan(B, D, H, W, Cin, Cout, 2, &ncob, &ncib, &ns2);
-  wgrad_plan(B, D, H, W, Cin, Cout, 4, &ncob, &ncib, &ns4);
-  const int ns = ns2 > ns4 ? ns2 : ns4;
-  size_t need = (size_t)ncob * ncib * ns * 27 * WG_CB * WG_CB * sizeof(float);
-  if ((Cin == 16 || Cin == 32) && (Cout == 16 || Cout == 32)) {      // the narrow-layer kernel: one slab per workgroup
-    const size_t nar = (size_t)WG_NARROW_MAX_WG * 27 * Cin * Cout * sizeof(float);
-    if (nar > need) need = nar;
+// THE plan of a weight-gradient launch: miseg_conv3_wgrad dispatches on it, miseg_conv3_wgrad_plan returns it (host only)
+static int conv3_wgrad_plan(const miseg_conv3_wgrad_params* p, miseg_conv3_wgrad_plan_info* pl) {
+  MISEG_REQUIRE(p->B > 0 && p->D > 0 && p->H > 0 && p->W > 0 && p->Cin > 0 && p->Cout > 0, MISEG_E_BADARG, "conv3_wgrad: bad shape");
+  MISEG_REQUIRE(p->dtype == MISEG_F32 || p->dtype == MISEG_BF16, MISEG_E_BADARG, "conv3_wgrad: dtype %d", p->dtype);
+  *pl = miseg_conv3_wgrad_plan_info{};
+  if (p->dtype == MISEG_F32) pl->kernel = MISEG_CONV3_WGRAD_F32;
+  else if (wgrad_narrow(p)) pl->kernel = MISEG_CONV3_WGRAD_NARROW;
+  else if (wgrad_tiny(p)) pl->kernel = MISEG_CONV3_WGRAD_TINY;
+  else pl->kernel = MISEG_CONV3_WGRAD_BF16;
+  if (pl->kernel == MISEG_CONV3_WGRAD_NARROW) {      // one slab per workgroup
+    pl->workspace_bytes = (size_t)wgrad_narrow_workgroups(p) * 27 * p->Cin * p->Cout * sizeof(float);
+  } else if (pl->kernel != MISEG_CONV3_WGRAD_TINY) {      // the slab kernels (conv3_wgrad_launch: fp32 bricks of depth 2, bf16 of depth 4)
+    int ncob, ncib, ns;
+    wgrad_plan(p->B, p->D, p->H, p->W, p->Cin, p->Cout, p->dtype == MISEG_F32 ? 2 : 4, &ncob, &ncib, &ns, p->max_workgroups);
+    pl->workspace_bytes = (size_t)ncob * ncib * ns * 27 * WG_CB * WG_CB * sizeof(float);
   }
-  return need;
+  return MISEG_OK;
+}
+
+extern "C" int miseg_conv3_wgrad_plan(const miseg_conv3_wgrad_params* p, miseg_conv3_wgrad_plan_info* plan) {
+  MISEG_REQUIRE(p && plan, MISEG_E_BADARG, "conv3_wgrad_plan: null pointer");
+  return conv3_wgrad_plan(p, plan);
 }
 
 template <class T, int WBD>
@@ -2385,8 +2361,6 @@ extern "C" int miseg_debug_wgrad_stamps(unsigned long long* out) {   // read and
 }
 #endif
 
-extern "C" int miseg_conv3_wgrad_tiny(int B, int D, int H, int W, int Cin, int Cout, int dtype) { return wgrad_tiny_shape(B, D, H, W, Cin, Cout, dtype) ? 1 : 0; }
-
 extern "C" int miseg_conv3_wgrad_group(const miseg_conv3_wgrad_params* descs, int n, void* workspace, miseg_stream_t s_) {
   MISEG_REQUIRE(descs && n > 0 && n <= WG_GROUP_MAX, MISEG_E_BADARG, "conv3_wgrad_group: 1..%d layers per launch", WG_GROUP_MAX);
   for (int i = 0; i < n; ++i) {
@@ -2402,11 +2376,14 @@ extern "C" int miseg_conv3_wgrad_group(const miseg_conv3_wgrad_params* descs, in
 }
 
 extern "C" int miseg_conv3_wgrad(const miseg_conv3_wgrad_params* p, miseg_stream_t s_) {
-  MISEG_REQUIRE(p && p->x && p->dy && p->dw && p->workspace, MISEG_E_BADARG, "conv3_wgrad: null pointer");
-  MISEG_REQUIRE(p->B > 0 && p->D > 0 && p->H > 0 && p->W > 0 && p->Cin > 0 && p->Cout > 0, MISEG_E_BADARG, "conv3_wgrad: bad shape");
-  if (p->dtype == MISEG_F32) return conv3_wgrad_launch<float, 2>(p, (hipStream_t)s_);
-  if (p->dtype == MISEG_BF16 && wgrad_narrow(p)) return conv3_wgrad_narrow_launch(p, (hipStream_t)s_);
-  if (wgrad_tiny(p)) return conv3_wgrad_tiny_launch(p, (hipStream_t)s_);
-  if (p->dtype == MISEG_BF16) return conv3_wgrad_launch<bf16, 4>(p, (hipStream_t)s_);
-  return set_error(MISEG_E_BADARG, "conv3_wgrad: dtype %d", p->dtype);
+  MISEG_REQUIRE(p && p->x && p->dy && p->dw, MISEG_E_BADARG, "conv3_wgrad: null pointer");
+  miseg_conv3_wgrad_plan_info pl;
+  if (const int rc = conv3_wgrad_plan(p, &pl)) return rc;
+  MISEG_REQUIRE(!pl.workspace_bytes || p->workspace, MISEG_E_BADARG, "conv3_wgrad: workspace required (miseg_conv3_wgrad_plan_info.workspace_bytes)");
+  switch (pl.kernel) {
+    case MISEG_CONV3_WGRAD_F32: return conv3_wgrad_launch<float, 2>(p, (hipStream_t)s_);
+    case MISEG_CONV3_WGRAD_NARROW: return conv3_wgrad_narrow_launch(p, (hipStream_t)s_);
+    case MISEG_CONV3_WGRAD_TINY: return conv3_wgrad_tiny_launch(p, (hipStream_t)s_);
+    default: return conv3_wgrad_launch<bf16, 4>(p, (hipStream_t)s_);
+  }
 }

@@ -851,7 +851,7 @@ class _Conv3(Function):
         if sc is not None:
             assert isinstance(sc, tuple) and sc[0] == "sc", "the gradient of a forked conv input arrived as partial slabs"
             sc, gskip = sc[1:], None
-        if sc is not None and not (ctx.needs_input_grad[0] and ops.conv3_fuses_shortcut(dy, ctx.wshape[1], sc[0].shape[-1])):
+        if sc is not None and not (ctx.needs_input_grad[0] and ops.conv3_fuses_shortcut(dy, ctx.wshape[1], sc[0], sc[1])):
             gskip, sc = ops.gemm_nt(sc[0], sc[1]), None          # (the promise cannot be kept by this launch after all: the plain product)
         if ctx.needs_input_grad[0]:
             if ctx.dx_to_norm and gskip is None and sc is None:
@@ -896,7 +896,7 @@ class _Conv3Shortcut(Function):
         fwdp, bwdp = ops.pack_conv3(w1, x.dtype, True, need_dx)
         Cout = w1.shape[0]
         w3c = ops.cast_matrix(w3, x.dtype).view(w3.shape[0], -1)
-        if ops.conv3_fuses_fwd_shortcut(x, Cout) and w3c.is_contiguous():
+        if ops.conv3_fuses_fwd_shortcut(x, Cout, w3c):
             y, stat, y3, stat3 = ops.conv3_fwd(x, fwdp, Cout, want_stat=want_stat, fs=(w3c, True))
         else:
             y, stat = ops.conv3_fwd(x, fwdp, Cout, want_stat=want_stat) if want_stat else (ops.conv3_fwd(x, fwdp, Cout), None)
@@ -920,8 +920,7 @@ class _Conv3Shortcut(Function):
         dx = None
         if ctx.needs_input_grad[0]:
             w3t = ops.cast_matrix(w3, dy.dtype, transpose=True)      # [Cin][Cout3]
-            fold = (dy3.dtype == torch.bfloat16 and dy3.data_ptr() % 16 == 0 and ops.rows(dy3)[0] % 8 == 0 and w3t.is_contiguous()
-                    and ops.conv3_fuses_shortcut(dy, Cin, dy3.shape[-1]))
+            fold = ops.conv3_fuses_shortcut(dy, Cin, dy3, w3t)
             gskip = None if fold else ops.gemm_nt(dy3, w3t)
             dy8 = None
             if ctx.s2c_left and ops.conv3_fuses_s2c(dy, Cin, ctx.s2c_left):
@@ -965,9 +964,8 @@ def conv3(x, weight, want_stat=False, fork=False, dx_to_norm=False):
     r = _Conv3.apply(x, weight, want_stat, fork, dx_to_norm, getattr(x, "_miseg_upcat", 0) if x.requires_grad else 0)
     if fork and x.dtype == torch.bfloat16 and x.requires_grad and x.dim() == 5:
         # may a 1x1x1 convolution on the forked input leave its data gradient to this convolution's data-gradient launch? (conv1(fold_dx))
-        B, D, H, W, Cin = x.shape
-        Cout = weight.shape[0]
-        if ops.FOLD_SHORTCUT and ops.L.load().miseg_conv3_fuses_shortcut(B, D, H, W, Cout, Cin, Cout, ops.L.BF16):
+        Cin, Cout = x.shape[-1], weight.shape[0]
+        if ops.conv3_fuses_shortcut((x, Cout), Cin, Cout):      # (the data-gradient launch reads fresh [.., Cout] gradients)
             r[-1]._miseg_sc_fold = Cout
     return r
 
@@ -1241,8 +1239,7 @@ class _Conv1(Function):
         dx = None
         if ctx.needs_input_grad[0]:
             wt = ops.cast_matrix(weight, dy.dtype, transpose=True)      # [Cin][Cout]
-            if (ctx.fold_dx and dy.dtype == torch.bfloat16 and dy.data_ptr() % 16 == 0 and ops.rows(dy)[0] % 8 == 0 and wt.is_contiguous()
-                    and wt.data_ptr() % 16 == 0):
+            if ctx.fold_dx and dy.dtype == wt.dtype == torch.bfloat16 and wt.is_contiguous():      # (conv3_fwd(sc=) asks the plan with these operands)
                 dx = torch.empty_like(x)
                 ops.pending_dx_put(dx, ("sc", dy, wt))
             else:

@@ -20,7 +20,7 @@ class _S(C.Structure):
     pass
 
 
-ABI_VERSION = 12         # == MISEG_ABI_VERSION of include/miseg_hip.h; load() refuses a library that reports another
+ABI_VERSION = 13         # == MISEG_ABI_VERSION of include/miseg_hip.h; load() refuses a library that reports another
 C_NAMES = {}             # ctypes mirror -> name of the C struct it mirrors (tests/test_abi.py checks sizeof / offsetof of every field)
 
 
@@ -74,6 +74,11 @@ PackConv3 = _struct("PackConv3", cname="miseg_pack_conv3_params", fields=[("w", 
 Conv3Wgrad = _struct("Conv3Wgrad", cname="miseg_conv3_wgrad_params", fields=[("x", vp), ("ldx", i64), ("dy", vp), ("lddy", i64), ("dw", vp), ("B", i32), ("D", i32),
                                     ("H", i32), ("W", i32), ("Cin", i32), ("Cout", i32), ("dtype", i32), ("accumulate", i32),
                                     ("workspace", vp), ("max_workgroups", i32)])
+CONV3_GENERIC, CONV3_FWD96, CONV3_FWD_TINY = 0, 1, 2      # miseg_conv3_plan_info.kernel
+Conv3Plan = _struct("Conv3Plan", cname="miseg_conv3_plan_info", fields=[("kernel", i32), ("splits", i32), ("workspace_bytes", C.c_size_t), ("res", i32), ("stat", i32),
+                                  ("sc", i32), ("s2c", i32), ("fs", i32), ("defer_slabs", i32)])
+CONV3_WGRAD_F32, CONV3_WGRAD_NARROW, CONV3_WGRAD_TINY, CONV3_WGRAD_BF16 = 0, 1, 2, 3      # miseg_conv3_wgrad_plan_info.kernel
+Conv3WgradPlan = _struct("Conv3WgradPlan", cname="miseg_conv3_wgrad_plan_info", fields=[("kernel", i32), ("pad_", i32), ("workspace_bytes", C.c_size_t)])
 Winattn = _struct("Winattn", cname="miseg_winattn_params", fields=[("qkv", vp), ("ldq", i64), ("out", vp), ("ldo", i64), ("qkv_bias", vp), ("bias_table", vp),
                               ("lse", vp), ("B", i32), ("D", i32), ("H", i32), ("W", i32), ("C", i32), ("heads", i32),
                               ("dtype", i32), ("wd", i32), ("wh", i32), ("ww", i32), ("sd", i32), ("sh", i32), ("sw", i32),
@@ -173,11 +178,6 @@ PROTOS = {
     "miseg_instnorm_bwd_slabs": (i32, [C.POINTER(InstnormBwd), vp, i32, i64, vp]),
     "miseg_instnorm_fwd_slabs": (i32, [C.POINTER(InstnormApply), vp, i32, i64, vp]),
     "miseg_instnorm_fused_max_rows": (i32, []),
-    "miseg_conv3_fwd_splits": (i32, [i32, i32, i32, i32, i32, i32, i32]),
-    "miseg_conv3_fuses_shortcut": (i32, [i32, i32, i32, i32, i32, i32, i32, i32]),
-    "miseg_conv3_fwd_tiny": (i32, [i32, i32, i32, i32, i32, i32, i32]),
-    "miseg_conv3_fuses_s2c": (i32, [i32, i32, i32, i32, i32, i32, i32, i32]),
-    "miseg_conv3_fuses_fwd_shortcut": (i32, [i32, i32, i32, i32, i32, i32, i32]),
     "miseg_instnorm_fwd": (i32, [C.POINTER(InstnormApply), vp]),
     "miseg_instnorm_bwd": (i32, [C.POINTER(InstnormBwd), vp]),
     "miseg_instnorm_pair_bwd": (i32, [C.POINTER(InstnormPairBwd), vp]),
@@ -201,14 +201,13 @@ PROTOS = {
     "miseg_gemm_tn_reduce_batch": (i32, [vp, i32, vp]),
     "miseg_gemm_tn_group": (i32, [vp, i32, i32, vp]),
     "miseg_colsum_batch": (i32, [vp, i32, i32, vp]),
-    "miseg_conv3_fwd_workspace_bytes": (C.c_size_t, [i32, i32, i32, i32, i32, i32, i32]),
+    "miseg_conv3_fwd_plan": (i32, [C.POINTER(Conv3), C.POINTER(Conv3Plan)]),
     "miseg_conv3_fwd": (i32, [C.POINTER(Conv3), vp]),
     "miseg_pack_conv3_elems": (C.c_size_t, [i32, i32, i32, i32]),
-    "miseg_conv3_k96": (i32, [i32, i32]),
     "miseg_pack_conv3_tiles": (i32, [i32, i32, i32]),
     "miseg_pack_conv3_weight": (i32, [C.POINTER(PackConv3), vp]),
     "miseg_pack_conv3_batch": (i32, [vp, i32, i32, i32, vp, vp, vp]),
-    "miseg_conv3_wgrad_workspace_bytes": (C.c_size_t, [i32, i32, i32, i32, i32, i32]),
+    "miseg_conv3_wgrad_plan": (i32, [C.POINTER(Conv3Wgrad), C.POINTER(Conv3WgradPlan)]),
     "miseg_conv3_wgrad": (i32, [C.POINTER(Conv3Wgrad), vp]),
     "miseg_conv3_wgrad_group_workspace_bytes": (C.c_size_t, [C.POINTER(Conv3Wgrad), i32]),
     "miseg_conv3_wgrad_group": (i32, [C.POINTER(Conv3Wgrad), i32, vp, vp]),
@@ -260,7 +259,6 @@ PROTOS = {
     "miseg_label_export": (i32, [C.POINTER(LabelExport), vp]),
     "miseg_dropout": (i32, [C.POINTER(Dropout), vp]),
     "miseg_counter_add": (i32, [vp, C.c_uint64, vp]),
-    "miseg_conv3_wgrad_tiny": (i32, [i32, i32, i32, i32, i32, i32, i32]),
     "miseg_counter_copy": (i32, [vp, vp, vp]),
     "miseg_abi_struct_size": (C.c_size_t, [C.c_char_p]),
     "miseg_device_check": (i32, [i32]),

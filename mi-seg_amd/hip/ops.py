@@ -624,10 +624,9 @@ def gemm_tn_regroups(a, b, out):
         return False
     lda, K, M = rows(a)
     N = rows(b)[2]
-    if not (M % 48 == 0 and N % 48 == 0 and K >= 2048 and a.dtype == torch.bfloat16):
-        return True                      # grouped launch
     p = L.Gemm(_ptr(a), lda, _ptr(b), rows(b)[0], _ptr(out), N, M, N, K, 1, 1, _dt(a), L.F32, None, L.ACT_NONE, 1, 0, None, None, 0, None, 0, 0, 0)
-    return L.load().miseg_gemm_tn_splits(C.byref(p)) > 1      # streaming kernel with partial tiles: their deferred sum regroups
+    splits = L.load().miseg_gemm_tn_splits(C.byref(p))
+    return splits == 0 or splits > 1      # grouped launch (no streaming kernel), or streaming kernel with partial tiles: their deferred sum regroups
 
 
 FOLD_COLSUM = os.environ.get("MISEG_NO_COLSUM_FOLD") is None      # A/B switch of round 5 (gemm_tn(colsum_out=))
@@ -650,15 +649,15 @@ def gemm_tn(a, b, out=None, accumulate=False, split_k=0, regroup=0, colsum_out=N
     assert not regroup or (q is not None and split_k <= 0 and N % regroup == 0)
     if q is not None:
         q.writes[out.data_ptr()] = q.writes.get(out.data_ptr(), 0) + 1      # step-wide writer count of the slot (direct and queued, main and side)
-    if q is not None and split_k <= 0 and not (M % 48 == 0 and N % 48 == 0 and K >= 2048 and a.dtype == torch.bfloat16):
-        q.lists().gemm_tn.append((a, b, out, int(accumulate) == 2, int(regroup)))      # small problem: grouped launch at the end of the backward pass
+    split_k = max(0, split_k)          # 0: the library picks the kernel and the split over the reduction rows
+    # (the direct kernels always add: "known zero" only saves the grouped launch its read of the slot)
+    p = L.Gemm(_ptr(a), lda, _ptr(b), ldb, _ptr(out), N, M, N, K, 1, 1, _dt(a), L.F32, None, L.ACT_NONE, int(bool(accumulate)), split_k, None, None, 0, None, 0, 0, 0)
+    lib = L.load()
+    if q is not None and split_k == 0 and lib.miseg_gemm_tn_splits(C.byref(p)) == 0:
+        q.lists().gemm_tn.append((a, b, out, int(accumulate) == 2, int(regroup)))      # no streaming kernel: grouped launch at the end of the backward pass
         if colsum_out is not None:
             colsum(a, colsum_out, accumulate=True)
         return out
-    accumulate = bool(accumulate)      # (the direct kernels always add: "known zero" only saves the grouped launch its read of the slot)
-    split_k = max(0, split_k)          # 0: the library picks the kernel and the split over the reduction rows
-    p = L.Gemm(_ptr(a), lda, _ptr(b), ldb, _ptr(out), N, M, N, K, 1, 1, _dt(a), L.F32, None, L.ACT_NONE, int(accumulate), split_k, None, None, 0, None, 0, 0, 0)
-    lib = L.load()
     if colsum_out is not None:
         if FOLD_COLSUM and split_k == 0 and colsum_out.dtype == torch.float32 and lib.miseg_gemm_tn_fuses_colsum(C.byref(p)):
             p.tn_colsum = colsum_out.data_ptr()
@@ -1074,10 +1073,6 @@ def cast_matrix(w, dtype, transpose=False, regroup=None):
 
 
 # ------------------------------------------------------------------------------------------ conv 3x3x3
-def _round_up(a, b):
-    return (a + b - 1) // b * b
-
-
 def pack_conv3(w, dtype, want_fwd=True, want_bwd=True):
     """packs of a 3x3x3 weight for the forward (x side) and data-gradient (dy side) kernels; with a training arena the
     packs refreshed by the step's batched kernel (runtime/arena.py)."""
@@ -1130,38 +1125,56 @@ def check_no_pending():
         raise RuntimeError(f"{n} deferred data-gradient slab sum(s) were never consumed (conv3(..., dx_to_norm=True) in front of something that is no instance norm)")
 
 
+FRESH = 256      # stand-in pointer of a buffer that is not allocated yet (fresh allocations are 256-byte aligned): the plans test pointers for NULL / alignment only
+
+
+def _rows_ptr(t):
+    """(pointer, ld, C, dtype) of a rows view; (like, C) stands for a fresh contiguous [B, D, H, W, C] tensor over like's volume"""
+    return (FRESH, t[1], t[1], _dt(t[0])) if isinstance(t, tuple) else (_ptr(t), rows(t)[0], t.shape[-1], _dt(t))
+
+
+def _plan(fn, p, plan):
+    """the library's plan of a 3x3x3 launch (miseg_conv3_fwd_plan / miseg_conv3_wgrad_plan) from the launch's own params"""
+    L.check(getattr(L.load(), fn)(C.byref(p), C.byref(plan)), fn)
+    return plan
+
+
+def conv3_fwd_plan(x, Cout, **pieces):
+    """the plan (L.Conv3Plan) of conv3_fwd(x, ..., Cout) with these fields of miseg_conv3_params set (x: a tensor or a (like, C) stand-in)"""
+    ptr, ld, Cin, dt = _rows_ptr(x)
+    p = L.Conv3(ptr, ld, FRESH, Cout, FRESH, *_vol(x[0] if isinstance(x, tuple) else x), Cin, Cout, dt, **pieces)
+    return _plan("miseg_conv3_fwd_plan", p, L.Conv3Plan())
+
+
 FOLD_SHORTCUT = os.environ.get("MISEG_NO_SC_FOLD") is None      # A/B switch of round 5 (conv3_fwd(sc=))
 
 
-def conv3_fuses_shortcut(x, Cout, Csc):
-    """can conv3_fwd(x, ..., Cout, sc=(g [.., Csc], w [Cout, Csc])) take the 1x1x1 term along (miseg_conv3_params.sc_x)?"""
-    if not FOLD_SHORTCUT or x.dtype != torch.bfloat16:
+def conv3_fuses_shortcut(x, Cout, g, w=None):
+    """can conv3_fwd(x, ..., Cout, sc=(g, w)) take the 1x1x1 term along (miseg_conv3_params.sc_x)?  x: a tensor or a (like, C) stand-in;
+    g: the [.., Csc] rows, or Csc for fresh ones; w: the [Cout, Csc] matrix, None for a fresh one"""
+    gp, ldg, Csc, gdt = _rows_ptr((x[0] if isinstance(x, tuple) else x, g) if isinstance(g, int) else g)
+    if not FOLD_SHORTCUT or gdt != _rows_ptr(x)[3] or (w is not None and not (w.is_contiguous() and _dt(w) == gdt)):
         return False
-    B, D, H, W = _vol(x)
-    return bool(L.load().miseg_conv3_fuses_shortcut(B, D, H, W, rows(x)[2], Cout, Csc, _dt(x)))
+    return bool(conv3_fwd_plan(x, Cout, sc_x=gp, ld_sc_x=ldg, sc_w=_ptr(w) if w is not None else FRESH, sc_C=Csc).sc)
 
 
 FOLD_S2C = os.environ.get("MISEG_NO_S2C_FOLD") is None      # A/B switch of round 5 (conv3_fwd(s2c=))
 
 
 def conv3_fuses_s2c(x, Cout, C_left):
-    """can conv3_fwd(x, ..., Cout, s2c=...) store its first C_left output channels in space-to-channel order (miseg_conv3_params.s2c_out)?"""
-    if not FOLD_S2C:
-        return False
-    B, D, H, W = _vol(x)
-    return bool(L.load().miseg_conv3_fuses_s2c(B, D, H, W, rows(x)[2], Cout, C_left, _dt(x)))
+    """can conv3_fwd(x, ..., Cout, s2c=<a fresh tensor>) store its first C_left output channels in space-to-channel order (miseg_conv3_params.s2c_out)?"""
+    return FOLD_S2C and bool(conv3_fwd_plan(x, Cout, s2c_out=FRESH, s2c_C=C_left).s2c)
 
 
 FOLD_FWD_SHORTCUT = os.environ.get("MISEG_NO_FS_FOLD") is None      # A/B switch of round 5 (conv3_fwd(fs=))
 
 
-def conv3_fuses_fwd_shortcut(x, Cout):
-    """can conv3_fwd(x, ..., Cout, fs=...) produce the 1x1x1 convolution of x as a second output (miseg_conv3_params.fs_w)?"""
-    if not FOLD_FWD_SHORTCUT or x.dtype != torch.bfloat16:
+def conv3_fuses_fwd_shortcut(x, Cout, w=None):
+    """can conv3_fwd(x, ..., Cout, fs=(w, ..)) produce the 1x1x1 convolution of x as a second output (miseg_conv3_params.fs_w)?  w: the
+    [Cout, Cin] matrix, None for a fresh one"""
+    if not FOLD_FWD_SHORTCUT or (w is not None and not (w.is_contiguous() and w.dtype == x.dtype)):
         return False
-    B, D, H, W = _vol(x)
-    ld, _, Cin = rows(x)
-    return bool(L.load().miseg_conv3_fuses_fwd_shortcut(B, D, H, W, Cin, Cout, _dt(x))) and x.data_ptr() % 16 == 0 and ld % 8 == 0
+    return bool(conv3_fwd_plan(x, Cout, fs_w=_ptr(w) if w is not None else FRESH, fs_y=FRESH, ld_fs_y=Cout).fs)
 
 
 def conv3_fwd(x, wpk, Cout, out=None, res=None, want_stat=False, defer=False, sc=None, s2c=None, fs=None):
@@ -1178,54 +1191,60 @@ def conv3_fwd(x, wpk, Cout, out=None, res=None, want_stat=False, defer=False, sc
     ld, n, Cin = rows(x)
     if out is None:
         out = torch.empty(B, D, H, W, Cout, dtype=x.dtype, device=x.device)
+    ldy = rows(out)[0]
     lib = L.load()
-    wsb = lib.miseg_conv3_fwd_workspace_bytes(B, D, H, W, Cin, Cout, _dt(x))
-    ws = torch.empty(wsb // 4, dtype=torch.float32, device=x.device) if wsb else None
-    flops = 2.0 * B * D * H * W * 27 * Cin * Cout
-    fast = lib.miseg_conv3_k96(Cin, _dt(x)) != 0      # 96-byte chunks (padded where the rows are wide enough to pay for it)
-    bg = 1 if (fast and _background()) else 0
-    tiny_k = fast and not bg and x.data_ptr() % 16 == 0 and ld % 8 == 0 and bool(lib.miseg_conv3_fwd_tiny(B, D, H, W, Cin, Cout, _dt(x)))
-    name = (f"conv3_fwd{'_tiny' if tiny_k else '96' if fast else ''}_kernel<{'bf16' if x.dtype == torch.bfloat16 else 'f32'}>"
-            + (" (background)" if bg else ""))
-    fuse_res = res is not None and fast and res.dtype == x.dtype       # (the roofline leg times the launches exactly as the step issues them)
-    # algorithmic bytes: x read once, y written once, the weight pack, the fused residual read once
-    nbytes = float(x.element_size()) * (B * D * H * W * (Cin + Cout + (Cout if fuse_res else 0)) + wpk.numel())
-    stat = None
     # want_stat == "defer" (the caller's next op is an instance norm that can take the partial slabs: instnorm_fwd_slabs): a split launch
     # over <= 2048 rows per sample stops after its slabs and the norm's ONE launch sums them, writes `out`, and normalises
     defer_req = bool(defer) or want_stat == "defer"      # (defer without want_stat: the data-gradient direction, returns (out, PendingSlabs | None))
-    nsplit = lib.miseg_conv3_fwd_splits(B, D, H, W, Cin, Cout, _dt(x)) if (defer_req and fast and res is None and ws is not None) else 1
-    defer = nsplit > 1 and D * H * W <= lib.miseg_instnorm_fused_max_rows() and rows(out)[0] == Cout
-    if want_stat and fast and not defer:      # (a split reduction computes them in its second launch)
-        stat = STAT_POOL.take(lib.miseg_instnorm_stat_bytes(B, Cout) // 8, x.device).view(-1, B, Cout, 2)
     scx, scw, ldsc, Csc = None, None, 0, 0
     if sc is not None:
         scx, scw = sc
         ldsc, nsc, Csc = rows(scx)
-        assert fast and nsc == n and scw.is_contiguous() and tuple(scw.shape) == (Cout, Csc) and scw.dtype == x.dtype == scx.dtype
-        flops += 2.0 * n * Csc * Cout
-        nbytes += float(x.element_size()) * (n * Csc + scw.numel())
-    fsw = y2 = stat2 = None
+        assert nsc == n and scw.is_contiguous() and tuple(scw.shape) == (Cout, Csc) and scw.dtype == x.dtype == scx.dtype
+    fsw = None
     if fs is not None:
         fsw, want2 = fs
-        assert fast and not defer_req and fsw.is_contiguous() and tuple(fsw.shape) == (Cout, Cin) and fsw.dtype == x.dtype
+        assert not defer_req and fsw.is_contiguous() and tuple(fsw.shape) == (Cout, Cin) and fsw.dtype == x.dtype
+    # the launch's own params, asked first: FRESH stands in for the statistics and the second output until the plan serves them
+    p = L.Conv3(_ptr(x), ld, _ptr(out), ldy, _ptr(wpk), B, D, H, W, Cin, Cout, _dt(x), None, _ptr(res) if res is not None and res.dtype == x.dtype else None,
+                rows(res)[0] if res is not None else 0, FRESH if want_stat else None, 0,
+                int(defer_req and D * H * W <= lib.miseg_instnorm_fused_max_rows() and ldy == Cout),
+                _ptr(scx), ldsc, _ptr(scw), Csc, _ptr(s2c), (s2c.shape[-1] // 8) if s2c is not None else 0,
+                _ptr(fsw), FRESH if fs is not None else None, Cout if fs is not None else 0, None)
+    plan = _plan("miseg_conv3_fwd_plan", p, L.Conv3Plan())
+    if plan.kernel != L.CONV3_GENERIC and _background():
+        p.background = 1
+        plan = _plan("miseg_conv3_fwd_plan", p, L.Conv3Plan())
+    fuse_res, defer = bool(plan.res), bool(plan.defer_slabs)      # (the roofline leg times the launches exactly as the step issues them)
+    if not fuse_res:
+        p.res, p.ldres = None, 0
+    ws = torch.empty(plan.workspace_bytes // 4, dtype=torch.float32, device=x.device) if plan.workspace_bytes else None
+    stat = STAT_POOL.take(lib.miseg_instnorm_stat_bytes(B, Cout) // 8, x.device).view(-1, B, Cout, 2) if plan.stat else None
+    p.workspace, p.stat = _ptr(ws), _ptr(stat)
+    name = (f"conv3_fwd{('', '96', '_tiny')[plan.kernel]}_kernel<{'bf16' if x.dtype == torch.bfloat16 else 'f32'}>"
+            + (" (background)" if p.background else ""))
+    flops = 2.0 * B * D * H * W * 27 * Cin * Cout
+    # algorithmic bytes: x read once, y written once, the weight pack, the fused residual read once
+    nbytes = float(x.element_size()) * (B * D * H * W * (Cin + Cout + (Cout if fuse_res else 0)) + wpk.numel())
+    if sc is not None:
+        flops += 2.0 * n * Csc * Cout
+        nbytes += float(x.element_size()) * (n * Csc + scw.numel())
+    y2 = stat2 = None
+    if fs is not None:
         y2 = torch.empty(B, D, H, W, Cout, dtype=x.dtype, device=x.device)
         if want2:
             stat2 = STAT_POOL.take(lib.miseg_instnorm_stat_bytes(B, Cout) // 8, x.device).view(-1, B, Cout, 2)
+        p.fs_y, p.fs_stat = _ptr(y2), _ptr(stat2)
         flops += 2.0 * n * Cin * Cout
         nbytes += float(x.element_size()) * (n * Cout + fsw.numel())
-    mk = lambda st: L.Conv3(_ptr(x), ld, _ptr(out), rows(out)[0], _ptr(wpk), B, D, H, W, Cin, Cout, _dt(x), _ptr(ws),
-                            _ptr(res) if fuse_res else None, rows(res)[0] if fuse_res else 0, _ptr(st), bg, 1 if defer else 0,
-                            _ptr(scx), ldsc, _ptr(scw), Csc, _ptr(s2c), (s2c.shape[-1] // 8) if s2c is not None else 0,
-                            _ptr(fsw), _ptr(y2), Cout if y2 is not None else 0, _ptr(stat2))
-    _call("miseg_conv3_fwd", mk(stat), prof=(name, flops, nbytes))
+    _call("miseg_conv3_fwd", p, prof=(name, flops, nbytes))
     if fs is not None:
         assert res is None or fuse_res
         return out, stat, y2, stat2
     if res is not None and not fuse_res:
         out = add(out, res)
     if defer:
-        return out, PendingSlabs(ws, nsplit, B * D * H * W * Cout)
+        return out, PendingSlabs(ws, plan.splits, B * D * H * W * Cout)
     if defer_req and not want_stat:
         return out, None
     return (out, stat) if want_stat else out
@@ -1278,36 +1297,42 @@ def _flush_conv_wgrads(q, background=0, keep=False):
     q.clear()
 
 
+def _conv3_wgrad_params(x, dy, dw, accumulate):
+    (ldx, n, Cin), (lddy, n2, Cout) = rows(x), rows(dy)
+    assert n == n2
+    return L.Conv3Wgrad(_ptr(x), ldx, _ptr(dy), lddy, _ptr(dw), *_vol(x), Cin, Cout, _dt(x), int(accumulate), None, 0)
+
+
+def conv3_wgrad_plan(x, dy):
+    """the plan (L.Conv3WgradPlan) of conv3_wgrad(x, dy): the kernel and its workspace"""
+    return _plan("miseg_conv3_wgrad_plan", _conv3_wgrad_params(x, dy, None, 0), L.Conv3WgradPlan())
+
+
+def _conv3_wgrad_launch(p, device, name):
+    wsb = _plan("miseg_conv3_wgrad_plan", p, L.Conv3WgradPlan()).workspace_bytes
+    ws = torch.empty(wsb // 4, dtype=torch.float32, device=device) if wsb else None
+    p.workspace = _ptr(ws)
+    _call("miseg_conv3_wgrad", p, prof=(name, 2.0 * p.B * p.D * p.H * p.W * 27 * p.Cin * p.Cout))
+
+
 def _conv3_wgrad_now(x, dy, dw, accumulate):
-    """a queued single-layer weight gradient, launched now.  The tiny-volume kernel stores straight into dw; the workspace is still sized
-    by the library, so that a layer it sends to the slab kernels after all (operands it finds misaligned) has its slabs"""
-    B, D, H, W = _vol(x)
-    ldx, _, Cin = rows(x)
-    lddy, _, Cout = rows(dy)
-    ws = torch.empty(max(L.load().miseg_conv3_wgrad_workspace_bytes(B, D, H, W, Cin, Cout) // 4, 1), dtype=torch.float32, device=x.device)
-    _call("miseg_conv3_wgrad", L.Conv3Wgrad(_ptr(x), ldx, _ptr(dy), lddy, _ptr(dw), B, D, H, W, Cin, Cout, _dt(x), int(accumulate), _ptr(ws), 0),
-          prof=("conv3_wgrad_tiny_kernel", 2.0 * B * D * H * W * 27 * Cin * Cout))
+    """a queued single-layer weight gradient (the tiny-volume kernel, TINY_WGRAD_AT = "flush"), launched now"""
+    _conv3_wgrad_launch(_conv3_wgrad_params(x, dy, dw, accumulate), x.device, "conv3_wgrad_tiny_kernel")
 
 
 def conv3_wgrad(x, dy, dw=None, accumulate=False):
     """accumulate: False / True, or 2 = `dw` is known to hold zeros (a fresh arena slot): single-producer layers then store instead
     of read-modify-write and the others skip their zero fill."""
-    B, D, H, W = _vol(x)
-    ldx, n, Cin = rows(x)
-    lddy, n2, Cout = rows(dy)
-    assert n == n2
     if dw is None:
-        dw = torch.empty(Cout, Cin, 3, 3, 3, dtype=torch.float32, device=x.device)
+        dw = torch.empty(rows(dy)[2], rows(x)[2], 3, 3, 3, dtype=torch.float32, device=x.device)
         accumulate = False
+    p = _conv3_wgrad_params(x, dy, dw, accumulate)
+    kernel = _plan("miseg_conv3_wgrad_plan", p, L.Conv3WgradPlan()).kernel
     q = _queues(dw) if accumulate else None
     # (narrow bf16 layers - 16 / 32 channels on both sides - have a kernel of their own that finishes a 48^3 layer in ~10 us: never queued)
-    narrow = x.dtype == torch.bfloat16 and Cin in (16, 32) and Cout in (16, 32)
-    lib = L.load()
     # tiny volumes (3^3 / 6^3, hundreds of channels: encoder10 / decoder5): the write-bound kernel of their own, launched where the backward
     # pass reaches them (TINY_WGRAD_AT = "inline") or with the queued launches at its end ("flush": in front of the grouped launch)
-    # (the library's own test also wants 16-byte aligned operands and row strides that are multiples of 8 elements: the same test here)
-    tiny = (bool(lib.miseg_conv3_wgrad_tiny(B, D, H, W, Cin, Cout, _dt(x))) and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0
-            and ldx % 8 == 0 and lddy % 8 == 0)
+    tiny = kernel == L.CONV3_WGRAD_TINY
     if q is not None and q.unzeroed and dw.data_ptr() in q.unzeroed:
         q.unzeroed.discard(dw.data_ptr())
         if not (tiny and int(accumulate) == 2):      # anything but the overwriting launch reads (or only adds to) the slot: it gets its zeros now
@@ -1315,15 +1340,13 @@ def conv3_wgrad(x, dy, dw=None, accumulate=False):
     if tiny and q is not None and TINY_WGRAD_AT != "inline":
         q.lists().tiny_wgrad.append((x, dy, dw, int(accumulate)))
         return dw
-    if q is not None and B * D * H * W <= CONV_WGRAD_GROUP_VOXELS and not narrow and not tiny:
+    if q is not None and p.B * p.D * p.H * p.W <= CONV_WGRAD_GROUP_VOXELS and kernel not in (L.CONV3_WGRAD_NARROW, L.CONV3_WGRAD_TINY):
         q.lists().conv_wgrad.append((x, dy, dw, int(accumulate)))      # keeps x and dy alive until the flush
         return dw
     if tiny and q is not None and int(accumulate) == 2:
         q.inline_final.append(dw)      # written here, once, by plain stores: nothing queued will touch the slot again
-    ws = torch.empty(lib.miseg_conv3_wgrad_workspace_bytes(B, D, H, W, Cin, Cout) // 4, dtype=torch.float32, device=x.device)
-    bg = _background()
-    _call("miseg_conv3_wgrad", L.Conv3Wgrad(_ptr(x), ldx, _ptr(dy), lddy, _ptr(dw), B, D, H, W, Cin, Cout, _dt(x), int(accumulate), _ptr(ws), bg),
-          prof=(f"conv3_wgrad_kernel<{'bf16' if x.dtype == torch.bfloat16 else 'f32'}>" + (" (background)" if bg else ""), 2.0 * B * D * H * W * 27 * Cin * Cout))
+    p.max_workgroups = bg = _background()
+    _conv3_wgrad_launch(p, x.device, f"conv3_wgrad_kernel<{'bf16' if x.dtype == torch.bfloat16 else 'f32'}>" + (" (background)" if bg else ""))
     return dw
 
 

@@ -523,7 +523,7 @@ def _conv_case(dtype, B, D, H, W, Cin, Cout, seed=0):
 @pytest.mark.parametrize("B,D,H,W,Cin,Cout", [(1, 8, 8, 8, 48, 48), (2, 5, 9, 11, 12, 24), (1, 12, 16, 8, 96, 48), (1, 3, 3, 3, 192, 96),
                                              (1, 6, 6, 6, 8, 12), (1, 4, 8, 16, 48, 96), (1, 7, 7, 7, 16, 16), (2, 9, 10, 13, 32, 16), (1, 24, 24, 24, 16, 32),
                                              (1, 5, 8, 8, 32, 32),       # (the 16 / 32-channel bf16 cases take the narrow-layer weight-gradient kernel)
-                                             # rows >= 256 bytes that are no multiple of 96: K side padded to the next chunk (miseg_conv3_k96),
+                                             # rows >= 256 bytes that are no multiple of 96: K side padded to the next chunk (conv3_k96),
                                              # forward on Cin, data gradient on Cout; ragged channel counts and a generic-path partner
                                              (1, 12, 12, 12, 128, 256), (1, 6, 7, 5, 256, 128), (2, 5, 6, 7, 130, 64), (1, 4, 4, 4, 200, 40),
                                              # whole 48-channel blocks on volumes that are no whole number of 4 x 8 x 8 bricks: the pipelined weight-gradient
@@ -597,6 +597,7 @@ def test_conv3_takes_a_1x1x1_shortcut_term_along(B, D, H, W, Cin, Cout, Csc, wit
     res = rnd(B, D, H, W, Cout, dtype=dtype, seed=24) if with_res else None
     assert ops.conv3_fuses_shortcut(x, Cout, Csc)
     assert not ops.conv3_fuses_shortcut(x.float(), Cout, Csc) and not ops.conv3_fuses_shortcut(x, Cout, 40)
+    assert ops.conv3_fuses_shortcut(x, Cout, g, ws)      # (asked with the operands themselves)
     y = ops.conv3_fwd(x, fwdp, Cout, res=res, sc=(g, ws))
     ref = F.conv3d(x.float().permute(0, 4, 1, 2, 3), w.to(dtype).float(), padding=1).permute(0, 2, 3, 4, 1) + g.float() @ ws.float().t()
     if with_res:
@@ -665,7 +666,7 @@ def test_conv3_tiny_volume_weight_streaming_kernel(B, S, Cin, Cout):
     ops = _ops()
     dtype = torch.bfloat16
     x, w = _conv_case(dtype, B, S, S, S, Cin, Cout, seed=61)
-    assert ops.L.load().miseg_conv3_fwd_tiny(B, S, S, S, Cin, Cout, ops.L.BF16) == 1
+    assert ops.conv3_fwd_plan(x, Cout).kernel == ops.L.CONV3_FWD_TINY
     fwdp, bwdp = ops.pack_conv3(w, dtype)
     y = ops.conv3_fwd(x, fwdp, Cout)
     wq = w.to(dtype).float()
@@ -772,9 +773,9 @@ def test_conv3_wgrad_tiny_volumes(B, S, Cin, Cout):
     operands: plain, accumulate, and "slot holds zeros" modes; batches > 1 (the k dimension continues over the samples)."""
     ops = _ops()
     dtype = torch.bfloat16
-    assert ops.L.load().miseg_conv3_wgrad_tiny(B, S, S, S, Cin, Cout, ops.L.BF16) == 1
     x = rnd(B, S, S, S, Cin, dtype=dtype, seed=301)
     dy = rnd(B, S, S, S, Cout, dtype=dtype, seed=302)
+    assert ops.conv3_wgrad_plan(x, dy).kernel == ops.L.CONV3_WGRAD_TINY
     ref = torch.nn.grad.conv3d_weight(x.float().permute(0, 4, 1, 2, 3), (Cout, Cin, 3, 3, 3), dy.float().permute(0, 4, 1, 2, 3), padding=1)
     dw = ops.conv3_wgrad(x, dy)
     assert rel_err(dw, ref) < 1e-5          # exact products of bf16 operands, fp32 sums: only the summation order differs
@@ -865,7 +866,7 @@ def test_conv3_wgrad_grouped(dtype):
             assert ops.conv3_wgrad(x, dy, dw=dw, accumulate=True) is dw
             outs.append(dw)
         # (tiny volumes with whole channel blocks - bf16 (1, 3, 3, 3, 96, 96) and (1, 6, 6, 6, 48, 96) - take the write-bound kernel of their own right away)
-        tiny = [bool(ops.L.load().miseg_conv3_wgrad_tiny(*x.shape[:4], x.shape[-1], dy.shape[-1], ops._dt(x))) for x, dy, _ in cases]
+        tiny = [ops.conv3_wgrad_plan(x, dy).kernel == ops.L.CONV3_WGRAD_TINY for x, dy, _ in cases]
         assert len(ops.DEFAULT_QUEUES.conv_wgrad) == len(cases) - sum(tiny) and sum(tiny) == (2 if dtype == torch.bfloat16 else 0)
         assert all(torch.equal(o, c[2]) for o, c, t in zip(outs, cases, tiny) if not t), "queued launches must not have run yet"
         ops.DEFAULT_QUEUES.flush()

@@ -758,6 +758,47 @@ def test_arena_fill_leaves_out_the_slots_a_kernel_overwrites():
         arena.detach()
 
 
+def test_arena_fill_of_a_slot_whose_layer_leaves_the_overwriting_kernel():
+    """the fill leaves a slot out because the previous step's launch was the tiny-volume kernel that stores all of it; this step the same
+    slot's operands are a view whose rows are no multiple of 8 elements, so the library plans the slab kernel, which adds into the slot:
+    conv3_wgrad must zero it first (it asks the library's plan, not a copy of its predicate).  Poisoned with NaN, the slot must equal the
+    gradient of a fully filled one."""
+    from mi_seg_amd.hip import functional as HF
+    from mi_seg_amd.hip import ops
+    from mi_seg_amd.runtime import arena as A
+    B, S, Cin, Cout = 2, 3, 48, 96
+    w = torch.nn.Parameter(torch.randn(Cout, Cin, 3, 3, 3, device=DEV))
+    arena = A.ParamArena([w], torch.bfloat16)
+    g = torch.Generator(device="cpu").manual_seed(5)
+    x = torch.randn(B, S, S, S, Cin, generator=g).to(DEV, torch.bfloat16)
+    xw = torch.randn(B, S, S, S, Cin + 4, generator=g).to(DEV, torch.bfloat16)
+    x2 = xw[..., :Cin]                               # ld = Cin + 4: not a multiple of 8 elements
+    dy = torch.randn(B, S, S, S, Cout, generator=g).to(DEV, torch.bfloat16)
+    assert ops.conv3_wgrad_plan(x, dy).kernel == ops.L.CONV3_WGRAD_TINY
+    assert ops.conv3_wgrad_plan(x2, dy).kernel == ops.L.CONV3_WGRAD_BF16
+
+    def step(xs, poison):
+        if poison:
+            arena.flat.fill_(float("nan"))
+        arena.begin_step()
+        slot, mode = HF._slot_first(w)
+        assert mode == 2
+        ops.conv3_wgrad(xs, dy, dw=slot, accumulate=mode)
+        arena.end_backward()
+        return arena.views[0].clone()
+    try:
+        assert A.SKIP_OVERWRITTEN_FILL
+        step(x, False)
+        assert arena._overwritten == [0]             # the tiny kernel stored the whole slot: the next fill leaves it out
+        got = step(x2, True)
+        assert bool(torch.isfinite(got).all())
+        ref = ops.conv3_wgrad(x2, dy)
+        assert rel_err(got, ref) < 1e-5
+        assert arena._overwritten == []             # the slab kernel added into the slot: the next fill is whole again
+    finally:
+        arena.detach()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", ["swin_unetr", "unetr", "unetr_conv", "unet"])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
