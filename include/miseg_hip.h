@@ -33,7 +33,7 @@ enum { MISEG_ACT_NONE = 0, MISEG_ACT_LEAKY = 1, MISEG_ACT_GELU = 2, MISEG_ACT_PR
 #define MISEG_MAX_STYLES 4
 
 /* bumped on EVERY change of a struct layout or prototype; bindings must refuse a library whose version differs from the header they mirror */
-#define MISEG_ABI_VERSION 13
+#define MISEG_ABI_VERSION 14
 int miseg_abi_version(void);
 const char* miseg_last_error(void);
 /* writes e.g. "gfx950" for the code objects embedded in the library */
@@ -598,13 +598,18 @@ int miseg_fill32(void* dst, uint32_t value, size_t n, miseg_stream_t stream);
  * pinned dependency that is not vendored: PARITY UNPINNED by any reference test).
  * ---------------------------------------------------------------------------------------------- */
 enum { MISEG_LABEL_F32 = 0, MISEG_LABEL_I32 = 1, MISEG_LABEL_I64 = 2, MISEG_LABEL_U8 = 3 };
-enum { MISEG_LOSS_DICE_FOCAL = 0, MISEG_LOSS_DICE_CE = 1 };
+enum { MISEG_LOSS_DICE_FOCAL = 0, MISEG_LOSS_DICE_CE = 1, MISEG_LOSS_GDICE_FOCAL = 2 };
+enum { MISEG_GDICE_W_SQUARE = 0, MISEG_GDICE_W_SIMPLE = 1, MISEG_GDICE_W_UNIFORM = 2 };
 /* DiceFocalLoss / DiceCELoss(to_onehot_y=True, softmax=True) on fp32 NCDHW logits [B][C][S] and class-id labels [B][1][S]
  * (lightning_monai.py:48-65, training_step :149-166).
  *   dice_focal, include_background = 0: channel 0 is stripped from logits AND target first, the softmax of the Dice term runs over the C-1
  *     foreground logits, the focal term (sigmoid form on raw logits, gamma) over the same channels;  = 1: all C channels.
  *   dice_ce: softmax over all C channels, Dice over channels >= (include_background ? 0 : 1), cross-entropy over all channels.
  *   Dice per (b, c): 1 - (2 sum(p t) + smooth_nr) / (sum(t) + sum(p^2 or p) + smooth_dr), mean over (b, c); focal: mean over (b, c, s); CE: mean over (b, s).
+ *   gdice_focal (ABI 14): GeneralizedDiceFocalLoss(to_onehot_y=True, softmax=True) (utils/training_utils.py:26-33).  Softmax over
+ *     ALL C channels, then channel 0 dropped from the Dice and focal terms when include_background = 0.  Per sample b, over the kept classes:
+ *     1 - (2 sum_c w I + smooth_nr) / (sum_c w (G + P) + smooth_dr), I = sum(p t), G = sum(t), P = sum(p) (never squared: squared_pred is ignored),
+ *     w = 1/G^2 | 1/G | 1 by weight_type, an infinite w replaced by the sample's largest finite one (all infinite: all 0); mean over b.  Focal as dice_focal.
  * miseg_seg_loss_fwd: one pass over logits + labels -> per-workgroup fp64 partial sums in `workspace`, summed in a FIXED order by a
  *   one-workgroup launch (bit-reproducible) into sums[B][C][3] (sum p t, sum p^2|p, sum t) + sums[3 B C] (focal / CE total) and the scalar loss.
  * miseg_seg_loss_bwd: second pass -> dlogits [B][C][S] fp32 = gscale * d(loss)/d(logits) (gscale: device scalar or NULL = 1), from the saved sums. */
@@ -619,6 +624,7 @@ typedef struct {
   double* sums;                    /* out (fwd) / in (bwd): 3 B C + 1 doubles */
   float* loss;                     /* out (fwd): scalar */
   const float* gscale; float* dlogits;   /* bwd only */
+  int weight_type;                 /* MISEG_GDICE_W_*: gdice_focal only, ignored by the other kinds */
 } miseg_seg_loss_params;
 size_t miseg_seg_loss_workspace_bytes(int B, int C, int64_t S);
 int miseg_seg_loss_fwd(const miseg_seg_loss_params* p, miseg_stream_t stream);
@@ -626,12 +632,17 @@ int miseg_seg_loss_bwd(const miseg_seg_loss_params* p, miseg_stream_t stream);
 
 /* DiceMetric(include_background=True, get_not_nans=True) after AsDiscrete(argmax=True, to_onehot=C) (lightning_monai.py:68-79,190-195):
  * dice[b][c] = 2 |pred == c & label == c| / (|pred == c| + |label == c|), NaN where |label == c| == 0; argmax takes the FIRST maximum.
- * counts: uint64 [B][C][3] scratch (zeroed by the call; integer atomics: bit-reproducible). */
+ * counts: uint64 [B][C][3] scratch (zeroed by the call; integer atomics: bit-reproducible).
+ * gdice (ABI 14, optional): GeneralizedDiceScore(include_background, weight_type) from the SAME counts (tune.py:124-129,208-213; MONAI 1.1.0
+ *   compute_generalized_dice, parity unpinned): per sample over the kept classes 2 sum_c w I / sum_c w (G + P) with the weights of
+ *   gdice_focal above; where that denominator is 0: 1 if the prediction has no kept-class voxel, else 0.  NULL: Dice alone, as before. */
 typedef struct {
   uint32_t struct_size;
   const float* logits; const void* label; int label_dtype;
   int B, C; int64_t S;
   uint64_t* counts; float* dice;   /* out fp32 [B][C] */
+  float* gdice;                    /* out fp32 [B] or NULL */
+  int include_background, weight_type;   /* of gdice: MISEG_GDICE_W_* */
 } miseg_dice_metric_params;
 int miseg_dice_metric(const miseg_dice_metric_params* p, miseg_stream_t stream);
 

@@ -1,5 +1,6 @@
 // What runs right after the hot path every training / validation step, all HBM-bound:
-//   * DiceFocal / DiceCE loss: one pass for the per-(b,c) sums + loss, one pass for d(loss)/d(logits)      (lightning_monai.py:46-67)
+//   * DiceFocal / DiceCE / GeneralizedDiceFocal loss: one pass for the per-(b,c) sums + loss, one for d(loss)/d(logits)    (lightning_monai.py:46-67,
+//                                                                                                               utils/training_utils.py:26-33)
 //   * Dice metric after argmax / one-hot                                                                     (lightning_monai.py:68-79,190-195)
 //   * AdamW / Adam / SGD-nesterov step of EVERY parameter in one launch over the gradient arena              (lightning_monai.py:255-278)
 //   * sliding-window stitching as one gather over resident window logits                                     (lightning_monai.py:86-93,187)
@@ -23,7 +24,7 @@ constexpr int LOSS_VPB = 256 * LOSS_VEC;         // voxels per workgroup (256 th
 template <class L> __device__ __forceinline__ int label_at(const L* lab, int64_t i) { return (int)lab[i]; }
 
 struct LossGeom {
-  int B, C, kind, c0, sq;
+  int B, C, kind, c0, sq, wt;
   int64_t S;
   float gamma;
 };
@@ -69,11 +70,30 @@ template <int MAXC> __device__ __forceinline__ float softmax_from(const float (&
   return mx + logf(sum);
 }
 
+// GeneralizedDiceLoss / compute_generalized_dice class weights (MONAI 1.1.0; utils/training_utils.py:26-33, tune.py:124-129):
+// 1/G^2 | 1/G | 1 of the label count G; an infinite weight (class absent from the sample) becomes the largest finite one of the sample's kept
+// classes, 0 when there is none.  q: the sample's [C][3] sums or counts with G at q[3 c + 2].
+__device__ __forceinline__ double gdice_raw_weight(double G, int wt) {
+  return wt == MISEG_GDICE_W_UNIFORM ? 1.0 : wt == MISEG_GDICE_W_SIMPLE ? 1.0 / G : 1.0 / (G * G);
+}
+template <class T> __device__ __forceinline__ double gdice_max_weight(const T* q, int c0, int C, int wt) {
+  double m = 0.0;
+  for (int c = c0; c < C; ++c) {
+    const double w = gdice_raw_weight((double)q[3 * c + 2], wt);
+    if (w <= 1.7976931348623157e308 && w > m) m = w;
+  }
+  return m;
+}
+__device__ __forceinline__ double gdice_weight(double G, int wt, double wmax) {
+  const double w = gdice_raw_weight(G, wt);
+  return w <= 1.7976931348623157e308 ? w : wmax;
+}
+
 // grid (blocks per sample, B).  part: double [B][nblk][3 C + 1]
 template <class L, int MAXC, int VEC>
 __global__ void __launch_bounds__(256) seg_loss_fwd_kernel(const float* __restrict__ logits, const L* __restrict__ label, LossGeom g, double* __restrict__ part) {
   const int b = blockIdx.y, tid = threadIdx.x;
-  const int c0d = g.c0, c0s = g.kind == MISEG_LOSS_DICE_CE ? 0 : g.c0;
+  const int c0d = g.c0, c0s = g.kind == MISEG_LOSS_DICE_FOCAL ? g.c0 : 0;   // dice_ce / gdice_focal: softmax over all channels, channel 0 dropped after
   const float* xb = logits + (int64_t)b * g.C * g.S;
   const L* lb = label + (int64_t)b * g.S;
   float aI[MAXC], aP[MAXC], aT[MAXC], aO = 0.f;
@@ -115,7 +135,7 @@ __global__ void __launch_bounds__(256) seg_loss_fwd_kernel(const float* __restri
           aI[c] += p[c] * t;
           aP[c] += g.sq ? p[c] * p[c] : p[c];
           aT[c] += t;
-          if (g.kind == MISEG_LOSS_DICE_FOCAL) {
+          if (g.kind != MISEG_LOSS_DICE_CE) {
             float f, df;
             focal_term<false>(x[c], t, g.gamma, f, df);
             aO += f;
@@ -181,31 +201,77 @@ static __global__ void __launch_bounds__(1024) seg_loss_finalize_kernel(const do
     }
     const int cn = g.C - g.c0;
     sums[(int64_t)3 * g.B * g.C] = tot_o;
-    const double o_mean = g.kind == MISEG_LOSS_DICE_FOCAL ? tot_o / ((double)g.B * cn * g.S) : tot_o / ((double)g.B * g.S);
+    const double o_mean = g.kind != MISEG_LOSS_DICE_CE ? tot_o / ((double)g.B * cn * g.S) : tot_o / ((double)g.B * g.S);
+    if (g.kind == MISEG_LOSS_GDICE_FOCAL) {      // one term per SAMPLE: the classes meet in the weighted numerator / denominator
+      double gd = 0.0;
+      for (int b = 0; b < g.B; ++b) {
+        const double* q = sums + (int64_t)b * g.C * 3;
+        const double wmax = gdice_max_weight(q, g.c0, g.C, g.wt);
+        double num = 0.0, den = 0.0;
+        for (int c = g.c0; c < g.C; ++c) {
+          const double w = gdice_weight(q[3 * c + 2], g.wt, wmax);
+          num += w * q[3 * c];
+          den += w * (q[3 * c + 2] + q[3 * c + 1]);
+        }
+        gd += 1.0 - (2.0 * num + nr) / (den + dr);
+      }
+      *loss = (float)(ld * gd / (double)g.B + lo * o_mean);
+      return;
+    }
     *loss = (float)(ld * dice / ((double)g.B * cn) + lo * o_mean);
   }
 }
 
-template <class L, int MAXC, int VEC>
+// GD: the gdice_focal kind.  A template parameter, not a run-time test: the fp64 coefficient prologue below cost the MAXC = 16 instantiation of
+// the other kinds 117 VGPRs and two thirds of its occupancy when it sat behind `g.kind`.
+template <class L, int MAXC, int VEC, bool GD>
 __global__ void __launch_bounds__(256) seg_loss_bwd_kernel(const float* __restrict__ logits, const L* __restrict__ label, LossGeom g, float nr, float dr, float ld, float lo,
                                                            const double* __restrict__ sums, const float* __restrict__ gscale, float* __restrict__ dlogits) {
   const int b = blockIdx.y, tid = threadIdx.x;
-  const int c0d = g.c0, c0s = g.kind == MISEG_LOSS_DICE_CE ? 0 : g.c0;
+  const int c0d = g.c0, c0s = (GD || g.kind == MISEG_LOSS_DICE_CE) ? 0 : g.c0;
   const int cn = g.C - g.c0;
   const float gs = gscale ? *gscale : 1.f;
   // per-channel Dice coefficients: dD/dp = ca t + cb p (squared) | ca t + cb (plain)
   float ca[MAXC], cb[MAXC];
+  if constexpr (GD) {
+    // dL/dp = ca t + cb with ca = -2 k w / den_b, cb = k num_b w / den_b^2, k = lambda gscale / B; num_b, den_b couple the classes of the
+    // sample.  w reaches 1e-12 (1 / G^2, G up to 96^3), so thread c forms the quotients of class c in fp64 and rounds them once; the
+    // others pick them up from LDS.
+    __shared__ float coef[2 * MAXC];
+    if (tid < MAXC) {
+      float a = 0.f, bb = 0.f;
+      if (tid >= c0d && tid < g.C) {
+        const double* q = sums + (int64_t)b * g.C * 3;
+        const double wmax = gdice_max_weight(q, c0d, g.C, g.wt);
+        double num = 0.0, den = 0.0;
+        for (int c = c0d; c < g.C; ++c) {
+          const double w = gdice_weight(q[3 * c + 2], g.wt, wmax);
+          num += w * q[3 * c];
+          den += w * (q[3 * c + 2] + q[3 * c + 1]);
+        }
+        const double numb = 2.0 * num + nr, denb = den + dr, k = (double)ld * gs / (double)g.B;
+        const double w = gdice_weight(q[3 * tid + 2], g.wt, wmax);
+        a = (float)(-2.0 * k * w / denb);
+        bb = (float)(k * numb * w / (denb * denb));
+      }
+      coef[2 * tid] = a; coef[2 * tid + 1] = bb;
+    }
+    __syncthreads();
 #pragma unroll
-  for (int c = 0; c < MAXC; ++c) {
-    ca[c] = cb[c] = 0.f;
-    if (c >= c0d && c < g.C) {
-      const double* q = sums + ((int64_t)b * g.C + c) * 3;
-      const double den = q[2] + q[1] + dr, num = 2.0 * q[0] + nr, k = (double)ld * gs / ((double)g.B * cn);
-      ca[c] = (float)(-2.0 * k / den);
-      cb[c] = (float)((g.sq ? 2.0 : 1.0) * k * num / (den * den));
+    for (int c = 0; c < MAXC; ++c) { ca[c] = coef[2 * c]; cb[c] = coef[2 * c + 1]; }
+  } else {
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+      ca[c] = cb[c] = 0.f;
+      if (c >= c0d && c < g.C) {
+        const double* q = sums + ((int64_t)b * g.C + c) * 3;
+        const double den = q[2] + q[1] + dr, num = 2.0 * q[0] + nr, k = (double)ld * gs / ((double)g.B * cn);
+        ca[c] = (float)(-2.0 * k / den);
+        cb[c] = (float)((g.sq ? 2.0 : 1.0) * k * num / (den * den));
+      }
     }
   }
-  const float ko = g.kind == MISEG_LOSS_DICE_FOCAL ? lo * gs / ((float)g.B * cn * (float)g.S) : lo * gs / ((float)g.B * (float)g.S);
+  const float ko = (GD || g.kind == MISEG_LOSS_DICE_FOCAL) ? lo * gs / ((float)g.B * cn * (float)g.S) : lo * gs / ((float)g.B * (float)g.S);
   const float* xb = logits + (int64_t)b * g.C * g.S;
   float* db = dlogits + (int64_t)b * g.C * g.S;
   const L* lb = label + (int64_t)b * g.S;
@@ -241,14 +307,14 @@ __global__ void __launch_bounds__(256) seg_loss_bwd_kernel(const float* __restri
 #pragma unroll
       for (int c = 0; c < MAXC; ++c) {
         const float t = (lab == c) ? 1.f : 0.f;
-        G[c] = ca[c] * t + (g.sq ? cb[c] * p[c] : cb[c]);       // zero outside the Dice channels (ca = cb = 0)
+        G[c] = ca[c] * t + (!GD && g.sq ? cb[c] * p[c] : cb[c]);       // zero outside the Dice channels (ca = cb = 0)
         dot += G[c] * p[c];
       }
 #pragma unroll
       for (int c = 0; c < MAXC; ++c) {
         const float t = (lab == c) ? 1.f : 0.f;
         float d = p[c] * (G[c] - dot);                            // softmax Jacobian; p = 0 outside the softmax support
-        if (g.kind == MISEG_LOSS_DICE_FOCAL) {
+        if (GD || g.kind == MISEG_LOSS_DICE_FOCAL) {
           if (c >= c0d && c < g.C) {
             float f, df;
             focal_term<true>(x[c], t, g.gamma, f, df);
@@ -301,11 +367,25 @@ __global__ void __launch_bounds__(256) dice_count_kernel(const float* __restrict
   if (tid < 3 * C && cnt[tid]) atomicAdd(&counts[(int64_t)b * 3 * C + tid], (unsigned long long)cnt[tid]);
 }
 
-static __global__ void dice_finalize_kernel(const unsigned long long* __restrict__ counts, int n, float* __restrict__ dice) {
+// gdice (optional): GeneralizedDiceScore from the same counts, by the thread of each sample's class 0, in double (DESIGN.md section 7.4 rules 6-7)
+static __global__ void dice_finalize_kernel(const unsigned long long* __restrict__ counts, int n, float* __restrict__ dice, int C, int c0, int wt,
+                                            float* __restrict__ gdice) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const double inter = (double)counts[3 * i], np = (double)counts[3 * i + 1], nl = (double)counts[3 * i + 2];
   dice[i] = nl > 0 ? (float)(2.0 * inter / (np + nl)) : __int_as_float(0x7fc00000);
+  if (!gdice || i % C) return;
+  const unsigned long long* q = counts + (int64_t)3 * i;      // the sample's [C][3]
+  const double wmax = gdice_max_weight(q, c0, C, wt);
+  double num = 0.0, den = 0.0;
+  unsigned long long npred = 0;
+  for (int c = c0; c < C; ++c) {
+    const double w = gdice_weight((double)q[3 * c + 2], wt, wmax);
+    num += w * (double)q[3 * c];
+    den += w * ((double)q[3 * c + 2] + (double)q[3 * c + 1]);
+    npred += q[3 * c + 1];
+  }
+  gdice[i / C] = den == 0.0 ? (npred == 0 ? 1.f : 0.f) : (float)(2.0 * num / den);
 }
 
 // ------------------------------------------------------------------------------------------------ optimiser
@@ -591,13 +671,17 @@ static int loss_check(const miseg_seg_loss_params* p, const char* what) {
                 p ? p->struct_size : 0u, sizeof(miseg_seg_loss_params));
   MISEG_REQUIRE(p->logits && p->label && p->sums && p->workspace, MISEG_E_BADARG, "%s: null pointer", what);
   MISEG_REQUIRE(p->B > 0 && p->B <= 64 && p->C >= 2 && p->C <= LOSS_MAXC && p->S > 0, MISEG_E_UNSUPPORTED, "%s: B %d (<= 64), C %d (2..%d)", what, p->B, p->C, LOSS_MAXC);
-  MISEG_REQUIRE(p->kind == MISEG_LOSS_DICE_FOCAL || p->kind == MISEG_LOSS_DICE_CE, MISEG_E_BADARG, "%s: kind %d", what, p->kind);
+  MISEG_REQUIRE(p->kind == MISEG_LOSS_DICE_FOCAL || p->kind == MISEG_LOSS_DICE_CE || p->kind == MISEG_LOSS_GDICE_FOCAL, MISEG_E_BADARG, "%s: kind %d", what, p->kind);
+  MISEG_REQUIRE(p->kind != MISEG_LOSS_GDICE_FOCAL || (p->weight_type >= MISEG_GDICE_W_SQUARE && p->weight_type <= MISEG_GDICE_W_UNIFORM), MISEG_E_BADARG,
+                "%s: weight_type %d", what, p->weight_type);
   return MISEG_OK;
 }
 
 static LossGeom loss_geom(const miseg_seg_loss_params* p) {
   LossGeom g;
   g.B = p->B; g.C = p->C; g.kind = p->kind; g.c0 = p->include_background ? 0 : 1; g.sq = p->squared_pred ? 1 : 0; g.S = p->S; g.gamma = p->gamma;
+  g.wt = p->weight_type;
+  if (p->kind == MISEG_LOSS_GDICE_FOCAL) g.sq = 0;      // the generalized Dice never squares the prediction
   return g;
 }
 
@@ -642,11 +726,15 @@ extern "C" int miseg_seg_loss_bwd(const miseg_seg_loss_params* p, miseg_stream_t
   return dispatch_label(p->label_dtype, [&](auto* tag) -> int {
     typedef typename std::remove_const<typename std::remove_pointer<decltype(tag)>::type>::type L;
     dim3 grid(nblk, p->B);
-#define MISEG_LB(MAXC, VEC) seg_loss_bwd_kernel<L, MAXC, VEC><<<grid, 256, 0, s>>>(p->logits, (const L*)p->label, g, p->smooth_nr, p->smooth_dr, p->lambda_dice, \
-                                                                                    p->lambda_other, p->sums, p->gscale, p->dlogits)
-    if (p->C <= 8) {
-      if (vec) MISEG_LB(8, LOSS_VEC); else MISEG_LB(8, 1);
-    } else MISEG_LB(LOSS_MAXC, 1);
+#define MISEG_LB(MAXC, VEC, GD) seg_loss_bwd_kernel<L, MAXC, VEC, GD><<<grid, 256, 0, s>>>(p->logits, (const L*)p->label, g, p->smooth_nr, p->smooth_dr, p->lambda_dice, \
+                                                                                            p->lambda_other, p->sums, p->gscale, p->dlogits)
+    if (p->kind == MISEG_LOSS_GDICE_FOCAL) {
+      if (p->C <= 8) {
+        if (vec) MISEG_LB(8, LOSS_VEC, true); else MISEG_LB(8, 1, true);
+      } else MISEG_LB(LOSS_MAXC, 1, true);
+    } else if (p->C <= 8) {
+      if (vec) MISEG_LB(8, LOSS_VEC, false); else MISEG_LB(8, 1, false);
+    } else MISEG_LB(LOSS_MAXC, 1, false);
 #undef MISEG_LB
     MISEG_LAUNCH_CHECK("seg_loss_bwd");
     return MISEG_OK;
@@ -659,6 +747,8 @@ extern "C" int miseg_dice_metric(const miseg_dice_metric_params* p, miseg_stream
                 sizeof(miseg_dice_metric_params));
   MISEG_REQUIRE(p->logits && p->label && p->counts && p->dice, MISEG_E_BADARG, "dice_metric: null pointer");
   MISEG_REQUIRE(p->B > 0 && p->C >= 1 && p->C <= 64 && p->S > 0, MISEG_E_UNSUPPORTED, "dice_metric: C %d (1..64)", p->C);
+  MISEG_REQUIRE(!p->gdice || (p->weight_type >= MISEG_GDICE_W_SQUARE && p->weight_type <= MISEG_GDICE_W_UNIFORM), MISEG_E_BADARG, "dice_metric: weight_type %d",
+                p->weight_type);
   if (fill_words_async(p->counts, 0, (size_t)p->B * p->C * 3 * 2, s) != hipSuccess) return set_error(MISEG_E_LAUNCH, "dice_metric: fill");
   return dispatch_label(p->label_dtype, [&](auto* tag) -> int {
     typedef typename std::remove_const<typename std::remove_pointer<decltype(tag)>::type>::type L;
@@ -666,7 +756,8 @@ extern "C" int miseg_dice_metric(const miseg_dice_metric_params* p, miseg_stream
     if (gx > 2048) gx = 2048;
     dice_count_kernel<L, 64><<<dim3(gx, p->B), 256, 0, s>>>(p->logits, (const L*)p->label, p->C, p->S, (unsigned long long*)p->counts);
     MISEG_LAUNCH_CHECK("dice_count");
-    dice_finalize_kernel<<<cdiv(p->B * p->C, 64), 64, 0, s>>>((const unsigned long long*)p->counts, p->B * p->C, p->dice);
+    dice_finalize_kernel<<<cdiv(p->B * p->C, 64), 64, 0, s>>>((const unsigned long long*)p->counts, p->B * p->C, p->dice, p->C,
+                                                              p->include_background || p->C == 1 ? 0 : 1, p->weight_type, p->gdice);
     MISEG_LAUNCH_CHECK("dice_finalize");
     return MISEG_OK;
   });

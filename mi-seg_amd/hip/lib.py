@@ -20,7 +20,7 @@ class _S(C.Structure):
     pass
 
 
-ABI_VERSION = 13         # == MISEG_ABI_VERSION of include/miseg_hip.h; load() refuses a library that reports another
+ABI_VERSION = 14         # == MISEG_ABI_VERSION of include/miseg_hip.h; load() refuses a library that reports another
 C_NAMES = {}             # ctypes mirror -> name of the C struct it mirrors (tests/test_abi.py checks sizeof / offsetof of every field)
 
 
@@ -130,9 +130,10 @@ Mlp = _struct("Mlp", cname="miseg_mlp_params", fields=[("struct_size", u32), ("M
 SegLoss = _struct("SegLoss", cname="miseg_seg_loss_params", fields=[
     ("struct_size", u32), ("kind", i32), ("logits", vp), ("label", vp), ("label_dtype", i32), ("B", i32), ("C", i32), ("S", i64),
     ("include_background", i32), ("squared_pred", i32), ("smooth_nr", f32), ("smooth_dr", f32), ("gamma", f32), ("lambda_dice", f32),
-    ("lambda_other", f32), ("workspace", vp), ("sums", vp), ("loss", vp), ("gscale", vp), ("dlogits", vp)])
+    ("lambda_other", f32), ("workspace", vp), ("sums", vp), ("loss", vp), ("gscale", vp), ("dlogits", vp), ("weight_type", i32)])
 DiceMetric = _struct("DiceMetric", cname="miseg_dice_metric_params", fields=[
-    ("struct_size", u32), ("logits", vp), ("label", vp), ("label_dtype", i32), ("B", i32), ("C", i32), ("S", i64), ("counts", vp), ("dice", vp)])
+    ("struct_size", u32), ("logits", vp), ("label", vp), ("label_dtype", i32), ("B", i32), ("C", i32), ("S", i64), ("counts", vp), ("dice", vp),
+    ("gdice", vp), ("include_background", i32), ("weight_type", i32)])
 SurfaceDistance = _struct("SurfaceDistance", cname="miseg_surface_distance_params", fields=[
     ("struct_size", u32), ("logits", vp), ("pred", vp), ("label", vp), ("label_dtype", i32), ("B", i32), ("C", i32), ("D", i32), ("H", i32), ("W", i32),
     ("include_background", i32), ("symmetric", i32), ("workspace", vp), ("asd", vp)])
@@ -161,7 +162,8 @@ Dropout = _struct("Dropout", cname="miseg_dropout_params", fields=[
     ("p", f32), ("seed", C.c_uint64), ("stream_id", C.c_uint64), ("step_dev", vp)])
 AUG_MAX_SAMPLES = 16
 LABEL_F32, LABEL_I32, LABEL_I64, LABEL_U8 = 0, 1, 2, 3
-LOSS_DICE_FOCAL, LOSS_DICE_CE = 0, 1
+LOSS_DICE_FOCAL, LOSS_DICE_CE, LOSS_GDICE_FOCAL = 0, 1, 2
+GDICE_W_SQUARE, GDICE_W_SIMPLE, GDICE_W_UNIFORM = 0, 1, 2      # MISEG_GDICE_W_* (MONAI w_type / weight_type "square", "simple", "uniform")
 OPT_ADAMW, OPT_ADAM, OPT_SGD_NESTEROV = 0, 1, 2
 OPT_BLOCK = 4096
 STITCH_MAX_WINDOWS = 64

@@ -1653,11 +1653,23 @@ def _label(label):
     return label.contiguous(), kinds[label.dtype]
 
 
-class SegLossCfg:
-    """DiceFocalLoss / DiceCELoss hyper-parameters as LitMonai builds them (reference lightning_monai.py:48-65)"""
+GDICE_WEIGHT_TYPES = {"square": L.GDICE_W_SQUARE, "simple": L.GDICE_W_SIMPLE, "uniform": L.GDICE_W_UNIFORM}
 
-    def __init__(self, kind, include_background, squared_pred, smooth_nr, smooth_dr, gamma=2.0, lambda_dice=1.0, lambda_other=1.0):
+
+def gdice_weight_type(name):
+    """MONAI's w_type / weight_type name -> MISEG_GDICE_W_*"""
+    if name not in GDICE_WEIGHT_TYPES:
+        raise ValueError(f"Unsupported weight type: {name}, available options are {list(GDICE_WEIGHT_TYPES)}.")
+    return GDICE_WEIGHT_TYPES[name]
+
+
+class SegLossCfg:
+    """DiceFocalLoss / DiceCELoss hyper-parameters as LitMonai builds them (reference lightning_monai.py:48-65); weight_type (a MISEG_GDICE_W_*)
+    belongs to GeneralizedDiceFocalLoss (reference utils/training_utils.py:26-33), whose lambda_dice is its lambda_gdl"""
+
+    def __init__(self, kind, include_background, squared_pred, smooth_nr, smooth_dr, gamma=2.0, lambda_dice=1.0, lambda_other=1.0, weight_type=L.GDICE_W_SQUARE):
         self.kind, self.include_background, self.squared_pred = kind, bool(include_background), bool(squared_pred)
+        self.weight_type = int(weight_type)
         self.smooth_nr, self.smooth_dr, self.gamma, self.lambda_dice, self.lambda_other = float(smooth_nr), float(smooth_dr), float(gamma), float(lambda_dice), float(lambda_other)
 
 
@@ -1672,7 +1684,7 @@ def _seg_loss_params(logits, label, cfg, sums, ws):
         raise ValueError(f"seg_loss: label {tuple(label.shape)} does not match logits {tuple(logits.shape)} ([B, 1, ...] class ids)")
     lab, ldt = _label(label)
     p = L.SegLoss(C.sizeof(L.SegLoss), cfg.kind, _ptr(logits), _ptr(lab), ldt, B, Cc, S, int(cfg.include_background), int(cfg.squared_pred), cfg.smooth_nr,
-                  cfg.smooth_dr, cfg.gamma, cfg.lambda_dice, cfg.lambda_other, _ptr(ws), _ptr(sums), None, None, None)
+                  cfg.smooth_dr, cfg.gamma, cfg.lambda_dice, cfg.lambda_other, _ptr(ws), _ptr(sums), None, None, None, cfg.weight_type)
     return p, lab, (B, Cc, S)
 
 
@@ -1703,8 +1715,9 @@ def seg_loss_bwd(logits, label, cfg, sums, gscale=None):
     return dlogits
 
 
-def dice_metric(logits, label):
-    """[B, C] Dice per class after argmax (NaN where the class is absent from the label)"""
+def dice_metric(logits, label, gdice=None):
+    """[B, C] Dice per class after argmax (NaN where the class is absent from the label).  gdice = (include_background, weight_type name): also the
+    generalized Dice score [B] from the same counts (one pass over the volume) -> (dice, score)"""
     if logits.dtype != torch.float32 or not logits.is_contiguous():
         raise ValueError("dice_metric: logits must be contiguous float32 [B, C, ...]")
     B, Cc = logits.shape[0], logits.shape[1]
@@ -1714,8 +1727,13 @@ def dice_metric(logits, label):
     lab, ldt = _label(label)
     counts = torch.empty(B * Cc * 3, dtype=torch.int64, device=logits.device)
     dice = torch.empty(B, Cc, dtype=torch.float32, device=logits.device)
-    _call("miseg_dice_metric", L.DiceMetric(C.sizeof(L.DiceMetric), _ptr(logits), _ptr(lab), ldt, B, Cc, S, _ptr(counts), _ptr(dice)))
-    return dice
+    if gdice is None:
+        _call("miseg_dice_metric", L.DiceMetric(C.sizeof(L.DiceMetric), _ptr(logits), _ptr(lab), ldt, B, Cc, S, _ptr(counts), _ptr(dice), None, 1, 0))
+        return dice
+    score = torch.empty(B, dtype=torch.float32, device=logits.device)
+    _call("miseg_dice_metric", L.DiceMetric(C.sizeof(L.DiceMetric), _ptr(logits), _ptr(lab), ldt, B, Cc, S, _ptr(counts), _ptr(dice), _ptr(score), int(bool(gdice[0])),
+                                            gdice_weight_type(gdice[1])))
+    return dice, score
 
 
 def surface_distance(label, logits=None, pred=None, num_classes=None, include_background=True, symmetric=True):

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from ..training.inferer import sliding_window_inference
-from ..training.losses import DiceCELoss, DiceFocalLoss
+from ..training.losses import DiceCELoss, DiceFocalLoss, GeneralizedDiceFocalLoss
 from ..training.metrics import dice_from_logits
 from ..training.schedulers import WarmupCosineSchedule
 from .utils.utils import model_from_argparse_args
@@ -39,6 +39,9 @@ class LitMonai(_Base):
         elif criterion == "dice_ce":
             self.criterion = DiceCELoss(include_background=include_background, to_onehot_y=True, softmax=True, squared_pred=squared_pred,
                                         smooth_nr=smooth_nr, smooth_dr=smooth_dr)
+        elif criterion == "generalized_dice_focal":      # not a branch of the reference's LitMonai: its tune.py builds this loss (utils/training_utils.py:26-33)
+            self.criterion = GeneralizedDiceFocalLoss(include_background=include_background, to_onehot_y=True, softmax=True, smooth_nr=smooth_nr,
+                                                      smooth_dr=smooth_dr)
         else:
             raise ValueError("Criterion {} not implemented, please chose another optimizer.".format(criterion))
         self.out_channels = out_channels

@@ -2,11 +2,14 @@
 
 With float32 logits on a HIP device, this module's AsDiscrete post-transforms, DiceMetric and SurfaceDistanceMetric, the batch takes the fused
 path (dice_from_logits + surface_distance_from_logits: no one-hot volume is built); anything else runs the reference's decollate / post-transform
-/ metric chain.  The checkpoint loading and MONAI's get_loaders of the reference's main() stay with the caller."""
+/ metric chain.  `additional_metrics` (reference utils/trainer.py:145-149,246-250): a GeneralizedDiceScore rides on the fused path, fed from the
+same miseg_dice_metric call as the Dice; any other metric object sends the batch down the unfused chain.  The checkpoint loading and MONAI's
+get_loaders of the reference's main() stay with the caller."""
 import torch
 import torch.nn.functional as F
 
-from .metrics import Cumulative, DiceMetric, SurfaceDistanceMetric, dice_from_logits, surface_distance_from_logits
+from .metrics import (Cumulative, DiceMetric, GeneralizedDiceScore, SurfaceDistanceMetric, dice_from_logits, generalized_dice_from_logits,
+                      surface_distance_from_logits)
 
 
 class AsDiscrete:
@@ -27,13 +30,14 @@ def decollate_batch(t):
     return list(t.unbind(0))
 
 
-def _fused(output, post_label, post_pred, acc_func, surface_distance):
+def _fused(output, post_label, post_pred, acc_func, surface_distance, additional_metrics=None):
     """the batch can skip the one-hot volumes: the post-transforms and metrics are the ones this module knows the semantics of"""
     C = output.shape[1]
     return (output.is_cuda and output.dtype == torch.float32 and output.dim() == 5 and C <= 64
             and isinstance(post_pred, AsDiscrete) and post_pred.argmax and post_pred.to_onehot == C
             and isinstance(post_label, AsDiscrete) and not post_label.argmax and post_label.to_onehot == C
-            and type(acc_func) is DiceMetric and (surface_distance is None or type(surface_distance) is SurfaceDistanceMetric))
+            and type(acc_func) is DiceMetric and (surface_distance is None or type(surface_distance) is SurfaceDistanceMetric)
+            and all(type(m) is GeneralizedDiceScore for m in additional_metrics or ()))
 
 
 def compute_metric_modality(metric_func, include_background=0):
@@ -60,10 +64,13 @@ def compute_metric_modality(metric_func, include_background=0):
     return out
 
 
-def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=None, amp=True, surface_distance=None, results=None):
+def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=None, amp=True, surface_distance=None, results=None,
+         additional_metrics=None):
     """the reference's evaluation loop (test.py:46-123): returns the mean total Dice over the classes with a value (and the mean total surface
     distance when `surface_distance` is given).  `results`, a dict, receives the printed values: "dice_modality", "dice_total" and, with
-    `surface_distance`, "surface_distance_modality", "surface_distance_total", each {printed key: value}."""
+    `surface_distance`, "surface_distance_modality", "surface_distance_total", each {printed key: value}.  `additional_metrics`: a list of
+    cumulative metric objects updated with every batch and aggregated (`metric.aggregate().item()`) and reset at the end, as the reference's
+    validation loop does (utils/trainer.py:145-149,246-250); their values are printed and stored in results["additional_metrics"]."""
     model.eval()
     acc_mod_cumulative = Cumulative()
     surface_mod_cumulative = Cumulative() if surface_distance is not None else None
@@ -74,16 +81,25 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
             modality = batch["modality"].to(device) if "modality" in batch.keys() else None
             with torch.autocast(device_type=dev_type, enabled=amp and dev_type == "cuda"):
                 output = model_inferer(data, modalities=modality) if model_inferer is not None else model(data, modality)
-            fused = _fused(output, post_label, post_pred, acc_func, surface_distance)
+            fused = _fused(output, post_label, post_pred, acc_func, surface_distance, additional_metrics)
             if fused:
                 C = output.shape[1]
-                dice = dice_from_logits(output, target, C)
+                if additional_metrics:      # the first score comes out of the Dice's own pass; a further one (other settings) re-reads the volume
+                    m0 = additional_metrics[0]
+                    dice, score = generalized_dice_from_logits(output, target, C, m0.include_background, m0.weight_type, with_dice=True)
+                    m0.extend(score)
+                    for m in additional_metrics[1:]:
+                        m.extend(generalized_dice_from_logits(output, target, C, m.include_background, m.weight_type))
+                else:
+                    dice = dice_from_logits(output, target, C)
                 batch_acc = dice if acc_func.include_background else dice[:, 1:]
                 acc_func.extend(batch_acc)
             else:
                 val_output_convert = torch.stack([post_pred(t) for t in decollate_batch(output)])
                 val_labels_convert = torch.stack([post_label(t) for t in decollate_batch(target)])
                 batch_acc = acc_func(y_pred=val_output_convert, y=val_labels_convert)
+                for m in additional_metrics or ():
+                    m(y_pred=val_output_convert, y=val_labels_convert)
             acc_mod_cumulative.extend(batch_acc, modality)
             if surface_distance is not None:
                 if fused:
@@ -114,6 +130,13 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
         surface_mod_cumulative.reset()
     acc_func.reset()
     acc_mod_cumulative.reset()
+    if additional_metrics:
+        metrics = []
+        for m in additional_metrics:
+            metrics.append(m.aggregate().item())
+            m.reset()
+        print({"additional_metrics": metrics})
+        results["additional_metrics"] = metrics
     if surface_distance is not None:
         return torch.nanmean(accuracy[not_nans > 0]).item(), torch.nanmean(surface[not_nans_surface > 0]).item()
     return torch.nanmean(accuracy[not_nans > 0]).item()

@@ -1,5 +1,6 @@
 """Dice metric / AsDiscrete with MONAI 1.1.0 semantics (reference lightning_monai.py:68-79,190-195).  Parity unpinned (Appendix B).
-Average surface distance and the cumulative metric objects of the reference's evaluation script (test.py:17-171)."""
+Average surface distance and the cumulative metric objects of the reference's evaluation script (test.py:17-171).
+Generalized Dice score of the reference's validation (tune.py:124-129,208-213)."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -34,6 +35,56 @@ def dice_from_logits(logits, label, num_classes):
         from ..hip import ops
         return ops.dice_metric(logits.contiguous(), label.to(logits.device))
     return dice_metric(as_discrete_argmax_onehot(logits, num_classes), as_discrete_onehot(label, num_classes))
+
+
+# ------------------------------------------------------------------------------------------ generalized Dice score (reference tune.py:124-129)
+_WEIGHT_TYPES = ("square", "simple", "uniform")
+
+
+def _check_weight_type(weight_type):
+    if weight_type not in _WEIGHT_TYPES:
+        raise ValueError(f"Unsupported weight type: {weight_type}, available options are {list(_WEIGHT_TYPES)}.")
+
+
+def compute_generalized_dice(y_pred, y, include_background=True, weight_type="square"):
+    """MONAI 1.1.0 compute_generalized_dice on one-hot [B, C, ...] inputs -> fp32 [B] (DESIGN.md section 7.4 rules 6-7, parity unpinned):
+    2 sum_c w I / sum_c w (G + P) over the kept classes with w = 1/G^2 | 1/G | 1 of the label count, an infinite w replaced by the sample's
+    largest finite one; where the denominator is 0 the score is 1 if the prediction has no kept-class voxel and 0 otherwise.  The sums are
+    voxel counts, formed in float64 (MONAI forms the weights in float32: the same numbers to fp32 rounding)."""
+    _check_weight_type(weight_type)
+    if y_pred.shape != y.shape:
+        raise ValueError(f"y_pred - {tuple(y_pred.shape)} - and y - {tuple(y.shape)} - should have the same shapes.")
+    if y_pred.dim() < 3:
+        raise ValueError(f"y_pred should have at least 3 dimensions (batch, channel, spatial), got {y_pred.dim()}.")
+    y = y.to(y_pred.device)
+    if not include_background and y_pred.shape[1] > 1:
+        y_pred, y = y_pred[:, 1:], y[:, 1:]
+    from .losses import generalized_dice_weights
+    dims = tuple(range(2, y_pred.dim()))
+    yp, yt = y_pred.double(), y.double()
+    inter = (yp * yt).sum(dims)
+    y_o, y_pred_o = yt.sum(dims), yp.sum(dims)
+    w = generalized_dice_weights(y_o, weight_type)
+    numer = 2.0 * (inter * w).sum(1)
+    denom = ((y_o + y_pred_o) * w).sum(1)
+    score = numer / denom.clamp(min=1e-300)
+    empty = torch.where(y_pred_o.sum(1) == 0, torch.ones_like(score), torch.zeros_like(score))
+    return torch.where(denom == 0, empty, score).float()
+
+
+def generalized_dice_from_logits(logits, label, num_classes, include_background=True, weight_type="square", with_dice=False):
+    """AsDiscrete(argmax, to_onehot) on the logits + AsDiscrete(to_onehot) on the label + compute_generalized_dice: fp32 [B].  On a HIP device:
+    the one pass of dice_from_logits, the score taken from the same integer counts (miseg_dice_metric with its `gdice` output,
+    bit-reproducible); on CPU tensors the torch arithmetic above.  with_dice=True returns (dice [B, C], score [B]) from that one pass."""
+    _check_weight_type(weight_type)
+    if logits.is_cuda and logits.dtype == torch.float32 and logits.shape[1] == num_classes and num_classes <= 64:
+        from ..hip import ops
+        dice, score = ops.dice_metric(logits.contiguous(), label.to(logits.device), gdice=(include_background, weight_type))
+    else:
+        pred, lab = as_discrete_argmax_onehot(logits, num_classes), as_discrete_onehot(label, num_classes)
+        score = compute_generalized_dice(pred, lab, include_background, weight_type)
+        dice = dice_metric(pred, lab) if with_dice else None
+    return (dice, score) if with_dice else score
 
 
 # ------------------------------------------------------------------------------------------ surface distance (reference test.py:145-151)
@@ -257,3 +308,31 @@ class SurfaceDistanceMetric(_CumulativeMetric):
     def _compute(self, y_pred, y):
         return compute_average_surface_distance(y_pred, y, include_background=self.include_background, symmetric=self.symmetric,
                                                 distance_metric=self.distance_metric)
+
+
+class GeneralizedDiceScore(_CumulativeMetric):
+    """monai.metrics.GeneralizedDiceScore (1.1.0) on one-hot [B, C, ...] inputs: compute_generalized_dice above, one value per sample.
+    aggregate() returns the reduced value alone (`metric.aggregate().item()`, reference utils/trainer.py:249)."""
+    _AGGREGATE = ("none", "mean", "sum", "mean_batch", "sum_batch")
+
+    def __init__(self, include_background=True, reduction="mean_batch", weight_type="square"):
+        if reduction not in self._AGGREGATE:
+            raise ValueError(f"reduction must be one of {list(self._AGGREGATE)}.")
+        _check_weight_type(weight_type)
+        super().__init__(include_background, reduction, False)
+        self.weight_type = weight_type
+
+    def _compute(self, y_pred, y):
+        return compute_generalized_dice(y_pred, y, include_background=self.include_background, weight_type=self.weight_type)
+
+    def aggregate(self, reduction=None):
+        data = self.get_buffer()
+        if not isinstance(data, torch.Tensor):
+            raise ValueError("The data to aggregate must be a PyTorch Tensor.")
+        reduction = reduction or self.reduction
+        if reduction not in self._AGGREGATE:
+            raise KeyError(f"reduction must be one of {list(self._AGGREGATE)}.")
+        if reduction in ("mean", "sum"):         # the [B] buffer as one channel: do_metric_reduction reduces the channel axis first
+            data = data.reshape(-1, 1)
+        f, _ = do_metric_reduction(data, reduction)
+        return f
