@@ -649,9 +649,6 @@ __global__ void __launch_bounds__(NW * 64, 2) winattn_bwd_mfma_kernel(const bf16
   att_unit(g.heads, win, head);
   const int tid = threadIdx.x;
   const int n = g.n, C = g.C, nt16 = (n + 15) / 16;
-#if defined(ATT_EXP_STOP) && ATT_EXP_STOP == 0
-  return;
-#endif
   if (tid < 52) padb[tid] = 0.f;
   __syncthreads();
   float mg2 = 0.f, mv2 = 0.f, mda = 0.f;
@@ -707,9 +704,6 @@ __global__ void __launch_bounds__(NW * 64, 2) winattn_bwd_mfma_kernel(const bf16
   // LDS float atomics cost ~190 cycles per wave-instruction on gfx950 (integer ones 4-8): the rel-pos bias gradient is
   // binned in fixed point.  |dS_qk| <= p_qk (|dO_q||V_k| + |delta_q|) and a bin receives at most one key per query, so
   // |bin| <= n * bmax; the scale keeps two bits of headroom for the bf16 rounding of the operands.
-#if defined(ATT_EXP_STOP) && ATT_EXP_STOP == 1
-  if (tsize != -1) return;
-#endif
   const float bmax = sqrtf(__uint_as_float(bound[0]) * __uint_as_float(bound[1])) + __uint_as_float(bound[2]);
   // (a contribution stays below 2^21 so that fma(x, fscale, 1.5 * 2^23) rounds it to an integer in the low mantissa bits: one fma + one
   // integer subtract where mul + rndne + cvt were three instructions)
@@ -756,9 +750,6 @@ __global__ void __launch_bounds__(NW * 64, 2) winattn_bwd_mfma_kernel(const bf16
       if (kt == nt16 - 1 && (n & 15)) { itail = i; kval = ki < n; }
     }
   }
-#if defined(ATT_EXP_STOP) && ATT_EXP_STOP == 2
-  if (tsize != -1) return;
-#endif
   const uint64_t dk0 = DROP ? dropout_step_key(dr.key, dr.step_dev) : 0ull;
   const int dcg = (n + 3) / 4;
   const int64_t dbase = ((int64_t)win * g.heads + head) * n;
@@ -767,11 +758,7 @@ __global__ void __launch_bounds__(NW * 64, 2) winattn_bwd_mfma_kernel(const bf16
   const char* const ds_r = mytile + (4 * kg + (fi >> 2)) * ATT_DS_LD + (fi & 3) * 8;   // transposed read: lane (query fi, keys 4kg..)
 
   f32x4 padq = f32x4{0.f, 0.f, 0.f, 0.f};      // dQ of zero-padded queries (lane: dims 4 (lane & 3) ..), summed over this wave's query tiles
-#ifdef ATT_EXP_QDIV
-  for (int qt = 0; qt < nt16 / ATT_EXP_QDIV; ++qt) {
-#else
   for (int qt = 0; qt < nt16; ++qt) {
-#endif
     const int q0 = qt * 16;
     const int4 qc4 = *reinterpret_cast<const int4*>(qcode + q0 + 4 * kg);
     const int qc[4] = {qc4.x, qc4.y, qc4.z, qc4.w};
@@ -797,11 +784,7 @@ __global__ void __launch_bounds__(NW * 64, 2) winattn_bwd_mfma_kernel(const bf16
 #pragma unroll
         for (int e = 0; e < 4; ++e) {      // all four bias gathers first: an LDS read issued behind one of the bin atomics would wait for it
           bidx[e] = qc[e] - ck[i];
-#ifdef ATT_EXP_NOBIAS
-          tbv[e] = 0.f;
-#else
           tbv[e] = *reinterpret_cast<const float*>(tkb[i] + qc[e]);      // = table + bidx: the key's share of the address is formed once per wave
-#endif
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -841,11 +824,7 @@ __global__ void __launch_bounds__(NW * 64, 2) winattn_bwd_mfma_kernel(const bf16
         const s16x4 dsT = att_tr4(ds_r);                                                 // [k = key 4kg..][col = query fi]
         dq = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(kA[i], dsT, dq, 0, 0, 0);        // dQ^T[dim][query] += K^T dS^T
         __builtin_amdgcn_wave_barrier();
-#ifdef ATT_EXP_NOATOM
-        if (false) {
-#else
         if (DT) {
-#endif
 #pragma unroll
           for (int e = 0; e < 4; ++e)
             atomicAdd(reinterpret_cast<int*>(reinterpret_cast<char*>(dtable) + bidx[e]), __float_as_int(fmaf(dsv[e], fscale, 12582912.f)) - 0x4B400000);
@@ -872,9 +851,6 @@ __global__ void __launch_bounds__(NW * 64, 2) winattn_bwd_mfma_kernel(const bf16
       }
     }
   }
-#if defined(ATT_EXP_STOP) && ATT_EXP_STOP == 3
-  if (tsize != -1) return;
-#endif
   // bias gradient of the zero-padded tokens (their q / k / v rows are the bias itself): per-lane sums, folded over the lanes that hold the same
   // dims, one LDS atomic per (dim, wave).  Round 5: as one LDS float atomic per padded token and dim - 16 lanes of a wave on ONE address, ~190
   // cycles each - they were 30 of the 86 us of the 24^3 stage (37 % of its padded 28^3 grid is padding) and 5 us per query tile of a border window.
@@ -920,15 +896,8 @@ __global__ void __launch_bounds__(NW * 64, 2) winattn_bwd_mfma_kernel(const bf16
       }
     }
   }
-#if defined(ATT_EXP_STOP) && ATT_EXP_STOP == 4
-  if (tsize != -1) return;
-#endif
   __syncthreads();
-#ifdef ATT_EXP_NOFLUSH
-  if (false)
-#else
   if (dbias_table)
-#endif
     for (int i = tid; i < tsize; i += NTHR) {
       const int v = dtable[i];
       if (v != 0) atomicAdd(dbias_table + (int64_t)i * g.heads + head, (float)v / fscale);

@@ -335,23 +335,6 @@ extern "C" int miseg_graph_split_create(void* graph_, miseg_stream_t launch_stre
     info->main_lane_nodes = (int)lanes[0].size();
     info->streams_concurrent = plan->concurrent ? 1 : 0;
   }
-  if (false) {      // (debug listing of the pieces; was MISEG_DEBUG_GRAPH_SPLIT: the library reads no environment)
-    fprintf(stderr, "[graph_split] %d nodes, %zu edges, %d lanes, %d crossing edges, %zu segments, %zu side stream(s)%s\n", (int)n, ne, nl, plan->cross,
-            plan->segs.size(), plan->side.size(), plan->concurrent ? "" : " (NOT seen to run concurrently)");
-    for (size_t s = 0; s < plan->segs.size(); ++s) {
-      const Segment& g = plan->segs[s];
-      int nk = 0, nc = 0, nm = 0, no = 0;      // kernel / memcpy / memset / other nodes
-      for (int v : g.nodes) {
-        hipGraphNodeType ty = hipGraphNodeTypeEmpty;
-        (void)hipGraphNodeGetType(nodes[v], &ty);
-        if (ty == hipGraphNodeTypeKernel) ++nk; else if (ty == hipGraphNodeTypeMemcpy) ++nc; else if (ty == hipGraphNodeTypeMemset) ++nm; else ++no;
-      }
-      fprintf(stderr, "  seg %zu: lane %d stream %d, %zu nodes (%d kernels, %d copies, %d memsets, %d other; topo %d..%d)%s, waits:", s, g.lane, g.stream, g.nodes.size(), nk, nc, nm, no,
-              pos[g.nodes.front()], pos[g.nodes.back()], g.record ? ", records" : "");
-      for (int w : g.waits) fprintf(stderr, " %d", w);
-      fprintf(stderr, "\n");
-    }
-  }
   *out = (miseg_graph_split_t)plan;
   return MISEG_OK;
 }

@@ -4,7 +4,6 @@ from csrc/ (see hip/ops.py); torch supplies tensors, the caching allocator, stre
 Layout contract: activations are channels-last ([B, D, H, W, C] or [B, L, C]) in the compute dtype (float32 for the
 parity mode, bfloat16 for throughput); parameters and their gradients are float32.
 """
-import os
 
 import torch
 from torch.autograd import Function
@@ -189,7 +188,6 @@ def drop_path(x, p, training=True):
 # ----------------------------------------------------------------------------------------------------------------
 _PENDING_OUT = None      # see _InstNorm.forward
 _LAST_STAT = None          # statistics buffer of the _InstNorm.forward that has just run (instance_norm(fork=True))
-FORK_KEEPS_STAT = os.environ.get("MISEG_NO_FORK_STAT") is None      # A/B switch of round 5
 
 
 class _InstNorm(Function):
@@ -377,7 +375,7 @@ def instance_norm(x, params=None, styles_dev=None, styles_host=None, res=None, a
         # the skip branch is x itself: its statistics - left on it by its producer, or summed by this norm's own statistics pass (round 5: the
         # affine-less norm of a Swin stage's returned feature map and norm1 of the stage's first block read the SAME tensor; the second
         # statistics launch, 4.7 us of the un-overlapped forward chain per stage, is gone) - stay valid for the next norm of x
-        st = stat if isinstance(stat, torch.Tensor) else (_LAST_STAT if FORK_KEEPS_STAT else None)
+        st = stat if isinstance(stat, torch.Tensor) else _LAST_STAT
         if st is not None:
             r[1]._miseg_stat = st
     _LAST_STAT = None
@@ -558,8 +556,7 @@ def _wgrad_into(p, g, act):
     """dW = g^T act of a linear layer: into the parameter's arena slot (returns None) or as a fresh tensor"""
     slot, mode = _slot_first(p)
     if slot is not None:
-        with ops.wgrad_side(g, act):
-            ops.gemm_tn(g, act, out=slot, accumulate=mode)      # (2: the slot still holds the step's zeros - a store, not a read-modify-write)
+        ops.gemm_tn(g, act, out=slot, accumulate=mode)      # (2: the slot still holds the step's zeros - a store, not a read-modify-write)
         return None
     return ops.gemm_tn(g, act).view(p.shape)
 
@@ -571,8 +568,7 @@ def _wb_grads_into(pw, pb, g, act, need_w=True, need_b=True):
     need_b = need_b and pb is not None
     if need_w and need_b and getattr(pw, "_miseg_grad", None) is not None and getattr(pb, "_miseg_grad", None) is not None:
         slot, mode = _slot_first(pw)
-        with ops.wgrad_side(g, act):
-            ops.gemm_tn(g, act, out=slot, accumulate=mode, colsum_out=_slot(pb))
+        ops.gemm_tn(g, act, out=slot, accumulate=mode, colsum_out=_slot(pb))
         return None, None
     return (_wgrad_into(pw, g, act) if need_w else None), (_bgrad_into(pb, g) if need_b else None)
 
@@ -876,8 +872,7 @@ class _Conv3(Function):
                 if q is not None and q.branch_deferred and ops.in_branch_backward():
                     ops.stamp("branch_bwd_head", fine=True)
                     ops.flush_branch_deferred(q)
-                with ops.wgrad_side(x, dy, kind="conv"):
-                    ops.conv3_wgrad(x, dy, dw=slot, accumulate=mode)
+                ops.conv3_wgrad(x, dy, dw=slot, accumulate=mode)
             else:
                 dw = ops.conv3_wgrad(x, dy)
         return dx, dw, None, None, None, None
@@ -935,15 +930,13 @@ class _Conv3Shortcut(Function):
             if slot is not None and ops.defer_to_branch(x, dy, slot, mode):
                 pass
             elif slot is not None:
-                with ops.wgrad_side(x, dy, kind="conv"):
-                    ops.conv3_wgrad(x, dy, dw=slot, accumulate=mode)
+                ops.conv3_wgrad(x, dy, dw=slot, accumulate=mode)
             else:
                 dw1 = ops.conv3_wgrad(x, dy)
         if ctx.needs_input_grad[2]:
             slot, mode = _slot_first(ctx.params[1])
             if slot is not None:
-                with ops.wgrad_side(dy3, x):
-                    ops.gemm_tn(dy3, x, out=slot, accumulate=mode)
+                ops.gemm_tn(dy3, x, out=slot, accumulate=mode)
             else:
                 dw3 = ops.gemm_tn(dy3, x).view(w3.shape)
         return dx, dw1, dw3, None, None
@@ -991,8 +984,7 @@ class _Conv3T(Function):
         if ctx.needs_input_grad[1]:
             slot = _slot(ctx.params[0])
             if slot is not None:
-                with ops.wgrad_side(x, dy, kind="conv"):
-                    ops.conv3_wgrad(dy, x, dw=slot, accumulate=True)
+                ops.conv3_wgrad(dy, x, dw=slot, accumulate=True)
             else:
                 dw = ops.conv3_wgrad(dy, x)          # roles swapped: dw[Cin_t][Cout_t][27]
         return dx, dw
@@ -1201,15 +1193,13 @@ class _Conv3Thin(Function):
             dy = _rv(dy)
             if slot is not None:
                 ops.conv3_thin_wgrad(xr, dy, slot)
-                ops.early_group_flush(ops._queues(slot))      # the stem's weight gradient is the last node of a side branch's backward pass
                 return None, None, None
             return None, ops.conv3_thin_wgrad(xr, dy, ops.zeros_f32(ctx.wshape, dy.device)), None
         if slot is not None:
             dy = _rv(dy)
-            with ops.wgrad_side(xr, dy, kind="conv"):
-                dwp = ops.conv3_wgrad(xr, dy)                    # [Cout, CP, 3, 3, 3], channels >= Cin are zero
-                slot.add_(dwp[:, : ctx.wshape[1]])
-                ops._WGRAD_KEEP.append(dwp)
+            dwp = ops.conv3_wgrad(xr, dy)                    # [Cout, CP, 3, 3, 3], channels >= Cin are zero
+            slot.add_(dwp[:, : ctx.wshape[1]])
+            ops._WGRAD_KEEP.append(dwp)
             return None, None, None
         dwp = ops.conv3_wgrad(xr, _rv(dy))
         return None, dwp[:, : ctx.wshape[1]].contiguous(), None
@@ -1248,8 +1238,7 @@ class _Conv1(Function):
         if ctx.needs_input_grad[1]:
             slot, mode = _slot_first(ctx.params[0])
             if slot is not None:
-                with ops.wgrad_side(dy, x):
-                    ops.gemm_tn(dy, x, out=slot, accumulate=mode)
+                ops.gemm_tn(dy, x, out=slot, accumulate=mode)
             else:
                 dw = ops.gemm_tn(dy, x).view(weight.shape)
         return dx, dw, None, None
@@ -1310,13 +1299,11 @@ class _UpCat(Function):
             if slot is not None and ops.gemm_tn_regroups(x, dy8, slot):
                 # dW[ci][co][j] = sum over voxels of x[v][ci] dy8[v][(j, co)]: the grouped launch / the batched partial-tile sum stores the product's
                 # column (j, co) at (co, j) - the torch layout of the arena slot, no [(j, co)][ci] intermediate, no permute pass (round 5)
-                with ops.wgrad_side(x, dy8):
-                    ops.gemm_tn(x, dy8, out=slot.view(Cin, 8 * Cout), accumulate=mode, regroup=Cout)
+                ops.gemm_tn(x, dy8, out=slot.view(Cin, 8 * Cout), accumulate=mode, regroup=Cout)
             elif slot is not None:
-                with ops.wgrad_side(dy8, x):
-                    dwf = ops.gemm_tn(dy8, x)                                             # [(j,co)][ci]
-                    ops.permute3(dwf, slot, (Cin, Cout, 8), (1, Cin, Cout * Cin), accumulate=True)
-                    ops._WGRAD_KEEP.append(dwf)
+                dwf = ops.gemm_tn(dy8, x)                                             # [(j,co)][ci]
+                ops.permute3(dwf, slot, (Cin, Cout, 8), (1, Cin, Cout * Cin), accumulate=True)
+                ops._WGRAD_KEEP.append(dwf)
             else:
                 dwf = ops.gemm_tn(dy8, x)                                                 # [(j,co)][ci]
                 dw = torch.empty(weight.shape, dtype=torch.float32, device=x.device)

@@ -111,7 +111,7 @@ class _ProfRegion:
         return False
 
 
-def _call(fn_name, params, prof=None, prof_params=None, extra=()):
+def _call(fn_name, params, prof=None, extra=()):
     lib = L.load()
     if PROFILE_HOOK is not None and prof is not None:
         with _ProfRegion(prof[0], prof[1], prof[2] if len(prof) > 2 else 0.0):
@@ -125,12 +125,6 @@ def _call(fn_name, params, prof=None, prof_params=None, extra=()):
 def _nb(*tensors):
     """bytes of the given tensors (None skipped): the algorithmic traffic of a launch that touches each of them once"""
     return float(sum(t.numel() * t.element_size() for t in tensors if t is not None))
-
-
-def _prof_scratch(t):
-    """(round 3's roofline leg repeated every launch five times and sent the accumulating outputs of the repeats here; since round 4 a launch
-    is timed once, in place: no scratch)"""
-    return None
 
 
 # ------------------------------------------------------------------------------------------ instance norm
@@ -262,9 +256,7 @@ def instnorm_stats(x, B, S):
     ld, n, Cc = rows(x)
     assert n == B * S, (n, B, S)
     stat = STAT_POOL.take(L.load().miseg_instnorm_stat_bytes(B, Cc) // 8, x.device).view(-1, B, Cc, 2)
-    sc = _prof_scratch(stat)
-    _call("miseg_instnorm_stats", L.InstnormStats(_ptr(x), ld, B, S, Cc, _dt(x), _ptr(stat)), prof=("instnorm", 0.0, _nb(x)),
-          prof_params=L.InstnormStats(_ptr(x), ld, B, S, Cc, _dt(x), _ptr(sc)) if sc is not None else None)
+    _call("miseg_instnorm_stats", L.InstnormStats(_ptr(x), ld, B, S, Cc, _dt(x), _ptr(stat)), prof=("instnorm", 0.0, _nb(x)))
     return stat
 
 
@@ -343,18 +335,15 @@ def instnorm_bwd(dy, y, x, B, S, stat, styles, gammas, dgammas, dbetas, act=L.AC
     dres = torch.empty(x.shape, dtype=x.dtype, device=x.device) if want_dres else None
     dstat = STAT_POOL.take(L.load().miseg_instnorm_stat_bytes(B, Cc) // 8, x.device)
     ns = len(gammas) if gammas is not None else 1
-    mk = lambda ds, dg, db: L.InstnormBwd(_ptr(dy), rows(dy)[0], _ptr(y), rows(y)[0] if y is not None else 0, _ptr(x), ld, _ptr(dx), rows(dx)[0],
-                                          _ptr(dres), rows(dres)[0] if dres is not None else 0, B, S, Cc, _dt(x), _ptr(stat), eps, _ptr(ds), _ptr(styles), ns,
-                                          _style_arrays(gammas, ns), _style_arrays(dg, ns), _style_arrays(db, ns), act, slope,
-                                          _ptr(gadd), rows(gadd)[0] if gadd is not None else 0, _style_arrays(betas, ns))
-    # (roofline leg: the repeated launches accumulate their reduction into scratch and leave the affine gradients alone)
-    sc = _prof_scratch(dstat)
+    p = L.InstnormBwd(_ptr(dy), rows(dy)[0], _ptr(y), rows(y)[0] if y is not None else 0, _ptr(x), ld, _ptr(dx), rows(dx)[0],
+                      _ptr(dres), rows(dres)[0] if dres is not None else 0, B, S, Cc, _dt(x), _ptr(stat), eps, _ptr(dstat), _ptr(styles), ns,
+                      _style_arrays(gammas, ns), _style_arrays(dgammas, ns), _style_arrays(dbetas, ns), act, slope,
+                      _ptr(gadd), rows(gadd)[0] if gadd is not None else 0, _style_arrays(betas, ns))
     if pending is not None:
-        _call("miseg_instnorm_bwd_slabs", mk(dstat, dgammas, dbetas), prof=("instnorm", 0.0, _nb(y, x, dx, dres, gadd) + 4.0 * pending.n * pending.stride),
-              prof_params=mk(sc, None, None) if sc is not None else None, extra=(_ptr(pending.ws), pending.n, pending.stride))
+        _call("miseg_instnorm_bwd_slabs", p, prof=("instnorm", 0.0, _nb(y, x, dx, dres, gadd) + 4.0 * pending.n * pending.stride),
+              extra=(_ptr(pending.ws), pending.n, pending.stride))
         return dx, dres
-    _call("miseg_instnorm_bwd", mk(dstat, dgammas, dbetas), prof=("instnorm", 0.0, _nb(dy, y, x, dx, dres, gadd)),
-          prof_params=mk(sc, None, None) if sc is not None else None)
+    _call("miseg_instnorm_bwd", p, prof=("instnorm", 0.0, _nb(dy, y, x, dx, dres, gadd)))
     return dx, dres
 
 
@@ -404,20 +393,14 @@ def instnorm_pair_bwd(dy, y, xa, xb, B, S, stat_a, stat_b, styles, gammas_a, gam
     ns = len(gammas_a) if gammas_a is not None else 1
     if r1 is not None:
         assert xb is None and y is None and rows(r1[0])[1] == n and r1[1].numel() == Cc and r1[2].numel() == Cc and r1[2].dtype == torch.float32
-
-    def mk(da, db_, ga, ba, gb, bb, dw):
-        p = L.InstnormPairBwd(_ptr(dy), rows(dy)[0], _ptr(y), rows(y)[0] if y is not None else 0, _ptr(xa), ld, _ptr(xb), rows(xb)[0] if xb is not None else 0,
-                              _ptr(dxa), rows(dxa)[0], _ptr(dxb), rows(dxb)[0] if dxb is not None else 0,
-                              B, S, Cc, _dt(xa), _ptr(stat_a), _ptr(stat_b), eps, _ptr(da), _ptr(db_), _ptr(styles), ns,
-                              _style_arrays(gammas_a, ns), _style_arrays(gammas_b, ns), _style_arrays(ga, ns), _style_arrays(ba, ns),
-                              _style_arrays(gb, ns), _style_arrays(bb, ns), slope, _style_arrays(betas_a, ns), _style_arrays(betas_b, ns))
-        if r1 is not None:
-            p.r1x, p.ldr1x, p.r1w, p.r1dw = _ptr(r1[0]), rows(r1[0])[0], _ptr(r1[1]), _ptr(dw)
-        return p
-    sa, sb = _prof_scratch(dsa), _prof_scratch(dsb)
-    _call("miseg_instnorm_pair_bwd", mk(dsa, dsb, dgammas_a, dbetas_a, dgammas_b, dbetas_b, r1[2] if r1 is not None else None),
-          prof=("instnorm", 0.0, _nb(dy, y, xa, xb, dxa, dxb, r1[0] if r1 is not None else None)),
-          prof_params=mk(sa, sb, None, None, None, None, _prof_scratch(r1[2]) if r1 is not None else None) if sa is not None else None)
+    p = L.InstnormPairBwd(_ptr(dy), rows(dy)[0], _ptr(y), rows(y)[0] if y is not None else 0, _ptr(xa), ld, _ptr(xb), rows(xb)[0] if xb is not None else 0,
+                          _ptr(dxa), rows(dxa)[0], _ptr(dxb), rows(dxb)[0] if dxb is not None else 0,
+                          B, S, Cc, _dt(xa), _ptr(stat_a), _ptr(stat_b), eps, _ptr(dsa), _ptr(dsb), _ptr(styles), ns,
+                          _style_arrays(gammas_a, ns), _style_arrays(gammas_b, ns), _style_arrays(dgammas_a, ns), _style_arrays(dbetas_a, ns),
+                          _style_arrays(dgammas_b, ns), _style_arrays(dbetas_b, ns), slope, _style_arrays(betas_a, ns), _style_arrays(betas_b, ns))
+    if r1 is not None:
+        p.r1x, p.ldr1x, p.r1w, p.r1dw = _ptr(r1[0]), rows(r1[0])[0], _ptr(r1[1]), _ptr(r1[2])
+    _call("miseg_instnorm_pair_bwd", p, prof=("instnorm", 0.0, _nb(dy, y, xa, xb, dxa, dxb, r1[0] if r1 is not None else None)))
     return dxa, dxb
 
 
@@ -473,11 +456,11 @@ class NormRef:
         ref.gamma, ref.beta = _style_arrays(self.gammas, ns), _style_arrays(self.betas, ns)
 
 
-FOLD_NORMS = not os.environ.get("MISEG_NO_NORM_FOLD")      # A/B switch of round 5: the Swin block's norm apply / norm-backward reduce as launches of their own
+FOLD_NORMS = True      # False: the Swin block's norm apply / norm-backward reduce as launches of their own (the tests' reference path)
 # the norm-backward sums in the epilogue of the SMALL-M data-gradient GEMM (<= 2048 rows: the deep Swin stages): the kernels have it (tested),
 # the step does not use it - there the norm backward is ONE register-resident launch already, the fold would trade it for an apply launch
 # (same launch count; measured 153.0 / 153.4 with it against 152.9 / 153.2 without: nothing); the forward folds stay on at every stage
-SMALL_BSTAT = bool(os.environ.get("MISEG_SMALL_BSTAT"))
+SMALL_BSTAT = False
 
 
 def gemm_nt_folds(a, w, anorm=None, bstat_x=None, act=L.ACT_NONE, res=None):
@@ -538,7 +521,7 @@ def gemm_nt(a, w, bias=None, act=L.ACT_NONE, out=None, out_dtype=None, split_k=1
         dstat = STAT_POOL.take(L.load().miseg_instnorm_stat_bytes(1, N) // 8, a.device)
         p.stat, p.stat_mode, p.bs_x, p.ld_bs_x, p.bs_stat, p.bs_eps = dstat.data_ptr(), 2, _ptr(bx), rows(bx)[0], _ptr(bst), float(beps)
         _set_gemm_stat(out, dstat)
-    if want_stat and not os.environ.get("MISEG_NO_GEMM_STAT") and L.load().miseg_gemm_fuses_stat(C.byref(p)):
+    if want_stat and L.load().miseg_gemm_fuses_stat(C.byref(p)):
         # all M rows are one sample (the caller checked): the kernel leaves the norm statistics of the output in `stat`
         stat = STAT_POOL.take(L.load().miseg_instnorm_stat_bytes(1, N) // 8, a.device).view(-1, 1, N, 2)
         p.stat = stat.data_ptr()
@@ -549,8 +532,6 @@ def gemm_nt(a, w, bias=None, act=L.ACT_NONE, out=None, out_dtype=None, split_k=1
 
 def mlp_fused(x, hid):
     """the fused MLP kernels take this problem (bf16, 48 -> 192 -> 48 channels, >= 4096 tokens)"""
-    if os.environ.get("MISEG_NO_FUSED_MLP"):
-        return False
     _, M, Cc = rows(x)
     return x.dtype == torch.bfloat16 and bool(L.load().miseg_mlp_fused(M, Cc, hid, _dt(x)))
 
@@ -620,16 +601,13 @@ def gemm_nt_scatter(a, w, dst, grid):
 def gemm_tn_regroups(a, b, out):
     """can gemm_tn(a, b, out, accumulate=..., regroup=...) run for these operands?  (needs a step queue: the regrouped store lives in the
     grouped launch / the batched partial-tile sum at the end of the backward pass)"""
-    if _queues(out) is None or os.environ.get("MISEG_NO_TN_REGROUP"):      # (the A/B switch of round 5: gemm_tn + permute3)
+    if _queues(out) is None:
         return False
     lda, K, M = rows(a)
     N = rows(b)[2]
     p = L.Gemm(_ptr(a), lda, _ptr(b), rows(b)[0], _ptr(out), N, M, N, K, 1, 1, _dt(a), L.F32, None, L.ACT_NONE, 1, 0, None, None, 0, None, 0, 0, 0)
     splits = L.load().miseg_gemm_tn_splits(C.byref(p))
     return splits == 0 or splits > 1      # grouped launch (no streaming kernel), or streaming kernel with partial tiles: their deferred sum regroups
-
-
-FOLD_COLSUM = os.environ.get("MISEG_NO_COLSUM_FOLD") is None      # A/B switch of round 5 (gemm_tn(colsum_out=))
 
 
 def gemm_tn(a, b, out=None, accumulate=False, split_k=0, regroup=0, colsum_out=None):
@@ -659,7 +637,7 @@ def gemm_tn(a, b, out=None, accumulate=False, split_k=0, regroup=0, colsum_out=N
             colsum(a, colsum_out, accumulate=True)
         return out
     if colsum_out is not None:
-        if FOLD_COLSUM and split_k == 0 and colsum_out.dtype == torch.float32 and lib.miseg_gemm_tn_fuses_colsum(C.byref(p)):
+        if split_k == 0 and colsum_out.dtype == torch.float32 and lib.miseg_gemm_tn_fuses_colsum(C.byref(p)):
             p.tn_colsum = colsum_out.data_ptr()
         else:
             colsum(a, colsum_out, accumulate=True)
@@ -681,50 +659,14 @@ def permute3(src, dst, n, strides, accumulate=False):
     return dst
 
 
-WGRAD_STREAM = None   # side HIP stream for the weight-gradient kernels (set by runtime/arena.py); None: launch in line
-WGRAD_KINDS = ("gemm", "conv")
-_WGRAD_KEEP = []      # operands of side-stream launches, kept alive until the join
-
-
-class _Side:
-    """`with ops.wgrad_side(x, dy): <launch a weight-gradient kernel>`: the launch goes to the side stream behind everything
-    already queued on the current one.  Weight gradients only feed the gradient arena, so they are off the critical dX chain
-    of the backward pass and fill the CUs its many small-grid kernels leave idle."""
-
-    def __init__(self, keep, kind):
-        self.side = WGRAD_STREAM if kind in WGRAD_KINDS else None
-        if self.side is not None:
-            _WGRAD_KEEP.extend(keep)
-
-    def __enter__(self):
-        if self.side is not None:
-            self.side.wait_stream(torch.cuda.current_stream())
-            self.ctx = torch.cuda.stream(self.side)
-            self.ctx.__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        if self.side is not None:
-            self.ctx.__exit__(*exc)
-        return False
-
-
-def wgrad_side(*keep, kind="gemm"):
-    return _Side(keep, kind)
-
-
+_WGRAD_KEEP = []      # operands of branch-stream launches, kept alive until the join (join_wgrad)
 _BRANCH_STREAM = None
-_MAIN_STREAM = None            # the stream a model's forward forked its side branch from (swin_unetr.py sets it)
 BACKGROUND_LAUNCHES = 0        # running count of launches issued in background form (bench.py reports the per-step figure)
 BACKGROUND_WORKGROUPS = 32     # cap of the branch's own background weight-gradient launch (each workgroup owns a CU).  Step against no branch,
                                # two boxes, before the deferral below: 256 (no cap) -0.4 %, 128 +1.0, 64 +1.4, 32 +2.0 / +2.4, 16 +2.0, 8 -3.8
 DEFERRED_WORKGROUPS = 64       # cap of the main stream's deferred weight gradients (defer_to_branch).  (own cap, this cap) on one box, no branch =
                                # 132.6, branch alone 134.5: (24, 48) 136.9, (24, 64) 140.8, (24, 96) 139.8, (48, 64) 140.6, (64, 64) 140.7, (32, 32) 128.9
 DEFERRED_WORKGROUPS_SPLIT = 96      # the same launches inside the first half of a split step (flush_deferred_on_branch)
-GROUP_EARLY_WORKGROUPS = 0      # cap of the early (branch-stream) grouped weight-gradient launch; 0 = off
-FLUSH_SMALL_ON_BRANCH = True      # (rounds 3 - 4 measured the alternatives; re-swept in round 5 after the grouped conv launch halved: 160.7 against 159.7 / 158.7 / 158.0
-FLUSH_SIDE_ON_BRANCH = True       #  with this one / the next / the third off - module constants again)
-FLUSH_MAIN_BEFORE_JOIN = True   # arena.end_backward: the main stream's grouped launches do not wait for the branch
 DEFER_MIN_ROWS = 400000        # 96^3 layers only (the smaller ones are grouped into one launch at the end of the backward pass)
 # (round 3: the queue of deferred launches itself lives on the training arena's StepQueues - `branch_deferred` - and is found through the
 # gradient slot a launch accumulates into, like the other per-step queues: two models in one process no longer share it)
@@ -807,31 +749,16 @@ def flush_deferred_on_branch(params):
         flush_branch_deferred(q, cap=DEFERRED_WORKGROUPS_SPLIT)
 
 
-def early_group_flush(q):
-    """at the TAIL of the side branch's backward pass (its last node calls this): the small layers' weight gradients queued so far go out on
-    the branch stream as one grouped launch in background form, beside what the main stream has left of its small-grid chain - instead of
-    after it, at the very end of the step.  (At the HEAD of the branch the same launch made the branch the critical path: 145.4 -> 134.7
-    patches/s with 64 workgroups, 141.1 with 128.)  GROUP_EARLY_WORKGROUPS = 0 switches it off.
-    Round 3, with the wait on the main stream this launch needs for its operands: 146.5 -> 114.0 patches/s uncapped, 111.1 with 128 - the
-    device-clock stamps show the WHOLE branch starting 2.3 ms later (its head at 5.9 ms instead of 3.6): a second edge main -> branch inside
-    the captured step makes the hipGraph executor run the branch's segment behind the main stream's.  The same happened to a third stream
-    forked for this launch at the point where the main stream enters the Swin stages' backward pass (147 -> 118: branch and third stream
-    shared one queue, GPU_MAX_HW_QUEUES=8 changed nothing).  One fork and one join per side stream is what replays concurrently."""
-    if q is None or not q.conv_wgrad or not GROUP_EARLY_WORKGROUPS or not in_branch_backward() or _MAIN_STREAM is None:
-        return
-    # the queued layers' operands were produced on the MAIN stream: everything the host has issued there so far (autograd issues the nodes of
-    # both streams in one order) is what the launch needs.  -1: no cap (the branch's chain is over, the launch is alone on its stream)
-    torch.cuda.current_stream().wait_stream(_MAIN_STREAM)
-    stamp("early_group_begin")
-    _flush_conv_wgrads(q.conv_wgrad, background=max(GROUP_EARLY_WORKGROUPS, 0), keep=True)
-    stamp("early_group_end")
-
-
 def join_branch(flush_deferred=True, queues=None, flush_main=False):
     """the current stream waits for the branch stream: before anything that consumes what the branch's backward produced (the side queue's
     launches of arena.end_backward, the optimiser, the end of a hipGraph capture).  queues: the arena's StepQueues whose
     deferred launches are issued here when the branch's backward never ran (nothing in it needed a gradient).
-    flush_main: the main stream's own queued launches go out BEFORE the wait (they read nothing of the branch's)."""
+    flush_main: the main stream's own queued launches go out BEFORE the wait (they read nothing of the branch's).
+    The branch stream is forked once (the model's forward) and joined once (here), and the end-of-pass launches below ride behind its last
+    kernel: one fork and one join per side stream is what a captured step replays concurrently.  A second edge main -> branch inside the
+    step (round 3: the grouped conv weight gradients issued early, at the tail of the branch's backward pass, behind a wait for the main
+    stream) made the hipGraph executor run the WHOLE branch behind the main stream's segment, 146.5 -> 114.0 patches/s, and so did a third
+    stream forked for that launch (147 -> 118)."""
     global _FLUSHING
     if flush_deferred:
         for q in ([queues] if queues is not None else list(QUEUES.values())):
@@ -841,23 +768,18 @@ def join_branch(flush_deferred=True, queues=None, flush_main=False):
     _FLUSHING = True
     if flush_main and queues is not None:
         cur = torch.cuda.current_stream() if _BRANCH_STREAM is not None else None      # (no side stream: the CPU ranks of the gloo tests)
-        if queues.side is not None and _BRANCH_STREAM is not None and FLUSH_SIDE_ON_BRANCH and cur != _BRANCH_STREAM:
+        if queues.side is not None and _BRANCH_STREAM is not None and cur != _BRANCH_STREAM:
             # what the branch's backward queued goes out on the BRANCH stream, behind its last kernel: the branch ends ~0.3 ms before the main
             # chain (step stamps), so these launches run beside the main stream's last kernels instead of behind the join.  The main stream's
             # grouped GEMM weight gradients, partial-tile sums and column sums follow them there (after a wait for the main chain), beside
             # the main stream's grouped conv weight gradients: that launch holds one 96 KB workgroup per CU and leaves the rest of the CU idle
             with torch.cuda.stream(_BRANCH_STREAM):
                 queues.side.flush()
-            if FLUSH_SMALL_ON_BRANCH and (queues.gemm_tn or queues.tn_reduce or queues.colsum or queues.tiny_wgrad):
-                for lst in (queues.gemm_tn, queues.tn_reduce, queues.colsum, queues.tiny_wgrad):      # operands of the main stream, read on the branch: alive until join_wgrad
+            if queues.gemm_tn or queues.tn_reduce or queues.colsum:
+                for lst in (queues.gemm_tn, queues.tn_reduce, queues.colsum):      # operands of the main stream, read on the branch: alive until join_wgrad
                     _WGRAD_KEEP.extend(t for it in lst for t in it if isinstance(t, torch.Tensor))
                 _BRANCH_STREAM.wait_stream(cur)
                 with torch.cuda.stream(_BRANCH_STREAM):
-                    # (MISEG_TINY_WGRAD_AT=flush: the tiny-volume conv weight gradients of encoder10 / decoder5 - write-bound, 176 MB in four ~20 us
-                    # launches - go out here, beside the main stream's grouped conv weight gradients; measured slower than inline, see TINY_WGRAD_AT)
-                    for x_, dy_, dw_, acc_ in queues.tiny_wgrad:
-                        _conv3_wgrad_now(x_, dy_, dw_, acc_)
-                    queues.tiny_wgrad.clear()
                     _flush_gemm_tn(queues.gemm_tn, queues.writes)
                     _flush_tn_reduces(queues.tn_reduce)
                     _flush_colsums(queues.colsum)
@@ -894,10 +816,8 @@ def _background():
 
 
 def join_wgrad():
-    """the current stream waits for the side streams; call once after the backward pass (arena.end_backward)."""
+    """the current stream waits for the branch stream; call once after the backward pass (arena.end_backward)."""
     join_branch()
-    if WGRAD_STREAM is not None:
-        torch.cuda.current_stream().wait_stream(WGRAD_STREAM)
     _WGRAD_KEEP.clear()
 
 
@@ -908,7 +828,7 @@ class StepQueues:
     storage of the gradient slot a kernel accumulates into - two models (two arenas) in one process do not share anything."""
 
     def __init__(self, side=True, writes=None):
-        self.colsum, self.gemm_tn, self.tn_reduce, self.conv_wgrad, self.tiny_wgrad = [], [], [], [], []
+        self.colsum, self.gemm_tn, self.tn_reduce, self.conv_wgrad = [], [], [], []
         self.unzeroed = set()        # data_ptr of arena slots the step's fill left out (their weight-gradient kernel overwrites them whole: arena.begin_step);
                                      # conv3_wgrad zero-fills one first if the launch it is about to issue would read or only add to it
         self.inline_final = []       # arena slots whose ONLY write of the step happened inline, as a plain store (the tiny-volume conv weight gradients):
@@ -930,19 +850,12 @@ class StepQueues:
 
     def flush_small(self):
         """the queued GEMM weight gradients, partial-tile sums and column sums only (the grouped conv weight gradients keep waiting): what
-        completes the small parameters of a range whose conv weights were written inline (tiny-volume layers), cheaply, mid-chain.  With
-        MISEG_TINY_WGRAD_AT=flush those conv weights are queued too: they go out here, or the range would be reduced without them"""
-        for x, dy, dw, acc in self.tiny_wgrad:
-            _conv3_wgrad_now(x, dy, dw, acc)
-        self.tiny_wgrad.clear()
+        completes the small parameters of a range whose conv weights were written inline (tiny-volume layers), cheaply, mid-chain"""
         _flush_gemm_tn(self.gemm_tn, self.writes)
         _flush_tn_reduces(self.tn_reduce)
         _flush_colsums(self.colsum)
 
     def flush(self, side=True):
-        for x, dy, dw, acc in self.tiny_wgrad:
-            _conv3_wgrad_now(x, dy, dw, acc)
-        self.tiny_wgrad.clear()
         _flush_conv_wgrads(self.conv_wgrad)
         _flush_gemm_tn(self.gemm_tn, self.writes)
         _flush_tn_reduces(self.tn_reduce)
@@ -969,9 +882,6 @@ def _flush_tn_reduces(q):
     if not q:
         return
     lib = L.load()
-    if os.environ.get("MISEG_DEBUG_QUEUES"):
-        import sys
-        print("tn_reduce queue:", [(it[3], it[4], it[5]) for it in q], file=sys.stderr)
     for i in range(0, len(q), 32):
         chunk = q[i:i + 32]
         descs = (L.TnReduceDesc * len(chunk))()
@@ -986,9 +896,6 @@ def _flush_gemm_tn(q, writes=None):
     if not q:
         return
     lib = L.load()
-    if os.environ.get("MISEG_DEBUG_QUEUES"):      # measurement aid: what the grouped launch holds (M, N, K, zeroed)
-        import sys
-        print("gemm_tn queue:", [(rows(it[0])[2], rows(it[1])[2], rows(it[0])[1], int(it[3]), it[4]) for it in q], file=sys.stderr)
     once = writes
     if once is None:      # (no step-wide count: at least the problems of this launch)
         once = {}
@@ -1013,9 +920,6 @@ def _flush_colsums(q):
     if not q:
         return
     lib = L.load()
-    if os.environ.get("MISEG_DEBUG_QUEUES"):
-        import sys
-        print("colsum queue:", [(rows(t)[1], rows(t)[2]) for t, _ in q], file=sys.stderr)
     for dt in {t.dtype for t, _ in q}:
         items = [(t, o) for t, o in q if t.dtype == dt]
         for i in range(0, len(items), 32):
@@ -1146,33 +1050,24 @@ def conv3_fwd_plan(x, Cout, **pieces):
     return _plan("miseg_conv3_fwd_plan", p, L.Conv3Plan())
 
 
-FOLD_SHORTCUT = os.environ.get("MISEG_NO_SC_FOLD") is None      # A/B switch of round 5 (conv3_fwd(sc=))
-
-
 def conv3_fuses_shortcut(x, Cout, g, w=None):
     """can conv3_fwd(x, ..., Cout, sc=(g, w)) take the 1x1x1 term along (miseg_conv3_params.sc_x)?  x: a tensor or a (like, C) stand-in;
     g: the [.., Csc] rows, or Csc for fresh ones; w: the [Cout, Csc] matrix, None for a fresh one"""
     gp, ldg, Csc, gdt = _rows_ptr((x[0] if isinstance(x, tuple) else x, g) if isinstance(g, int) else g)
-    if not FOLD_SHORTCUT or gdt != _rows_ptr(x)[3] or (w is not None and not (w.is_contiguous() and _dt(w) == gdt)):
+    if gdt != _rows_ptr(x)[3] or (w is not None and not (w.is_contiguous() and _dt(w) == gdt)):
         return False
     return bool(conv3_fwd_plan(x, Cout, sc_x=gp, ld_sc_x=ldg, sc_w=_ptr(w) if w is not None else FRESH, sc_C=Csc).sc)
 
 
-FOLD_S2C = os.environ.get("MISEG_NO_S2C_FOLD") is None      # A/B switch of round 5 (conv3_fwd(s2c=))
-
-
 def conv3_fuses_s2c(x, Cout, C_left):
     """can conv3_fwd(x, ..., Cout, s2c=<a fresh tensor>) store its first C_left output channels in space-to-channel order (miseg_conv3_params.s2c_out)?"""
-    return FOLD_S2C and bool(conv3_fwd_plan(x, Cout, s2c_out=FRESH, s2c_C=C_left).s2c)
-
-
-FOLD_FWD_SHORTCUT = os.environ.get("MISEG_NO_FS_FOLD") is None      # A/B switch of round 5 (conv3_fwd(fs=))
+    return bool(conv3_fwd_plan(x, Cout, s2c_out=FRESH, s2c_C=C_left).s2c)
 
 
 def conv3_fuses_fwd_shortcut(x, Cout, w=None):
     """can conv3_fwd(x, ..., Cout, fs=(w, ..)) produce the 1x1x1 convolution of x as a second output (miseg_conv3_params.fs_w)?  w: the
     [Cout, Cin] matrix, None for a fresh one"""
-    if not FOLD_FWD_SHORTCUT or (w is not None and not (w.is_contiguous() and w.dtype == x.dtype)):
+    if w is not None and not (w.is_contiguous() and w.dtype == x.dtype):
         return False
     return bool(conv3_fwd_plan(x, Cout, fs_w=_ptr(w) if w is not None else FRESH, fs_y=FRESH, ld_fs_y=Cout).fs)
 
@@ -1259,19 +1154,10 @@ class PendingSlabs:
         self.ws, self.n, self.stride = ws, n, stride
 
 
-# where the tiny-volume weight gradients are launched (conv3_wgrad): "inline" (default) = where the backward pass reaches the layer; "flush" =
-# queued for the end of the backward pass - with a side branch they then run on the BRANCH stream beside the main stream's grouped launch
-# (join_branch), without one (and in the two-graph data-parallel step, whose first half must finish these layers) in front of it.
-# Round 5, same box: inline 155.2 / 154.5 patches/s, on the branch at the end 154.2 / 154.2 - four write-bound launches (176 MB) beside the
-# grouped conv weight gradients lengthen the tail by more than the 80 us they take off the chain
-TINY_WGRAD_AT = os.environ.get("MISEG_TINY_WGRAD_AT", "inline")
 CONV_WGRAD_GROUP_VOXELS = 48 ** 3   # layers up to this many voxels are queued: alone they fill a fraction of the chip for 40-85 us each
 
 
-def _flush_conv_wgrads(q, background=0, keep=False):
-    """background > 0: the grouped launch walks its units with that many workgroups (miseg_conv3_wgrad_params.max_workgroups of the first
-    descriptor) - issued on the side-branch stream beside the main stream's small-grid launches; operands and workspace stay alive until
-    join_wgrad (the queue that held them is cleared here, and the allocator knows nothing about the branch stream's reads)"""
+def _flush_conv_wgrads(q):
     if not q:
         return
     lib = L.load()
@@ -1284,16 +1170,13 @@ def _flush_conv_wgrads(q, background=0, keep=False):
                 B, D, H, W = _vol(x)
                 ldx, _, Cin = rows(x)
                 lddy, _, Cout = rows(dy)
-                descs[j] = L.Conv3Wgrad(_ptr(x), ldx, _ptr(dy), lddy, _ptr(dw), B, D, H, W, Cin, Cout, _dt(x), acc, None, int(background) if j == 0 else 0)
+                descs[j] = L.Conv3Wgrad(_ptr(x), ldx, _ptr(dy), lddy, _ptr(dw), B, D, H, W, Cin, Cout, _dt(x), acc, None, 0)
             wsb = lib.miseg_conv3_wgrad_group_workspace_bytes(descs, len(chunk))
             ws = torch.empty(max(wsb // 4, 1), dtype=torch.float32, device=chunk[0][0].device)
             fl = sum(2.0 * 27 * it[0].shape[-1] * it[1].shape[-1] * (it[0].numel() // it[0].shape[-1]) for it in chunk)
-            with _ProfRegion("conv3_wgrad_group_kernel" + (" (background)" if background else ""), fl):
+            with _ProfRegion("conv3_wgrad_group_kernel", fl):
                 L.check(lib.miseg_conv3_wgrad_group(descs, len(chunk), _ptr(ws), _stream()), "conv3_wgrad_group")
             _stamp_launch("conv3_wgrad_group")
-            if background or keep:
-                _WGRAD_KEEP.append(ws)
-                _WGRAD_KEEP.extend(t for it in chunk for t in it[:2])
     q.clear()
 
 
@@ -1315,11 +1198,6 @@ def _conv3_wgrad_launch(p, device, name):
     _call("miseg_conv3_wgrad", p, prof=(name, 2.0 * p.B * p.D * p.H * p.W * 27 * p.Cin * p.Cout))
 
 
-def _conv3_wgrad_now(x, dy, dw, accumulate):
-    """a queued single-layer weight gradient (the tiny-volume kernel, TINY_WGRAD_AT = "flush"), launched now"""
-    _conv3_wgrad_launch(_conv3_wgrad_params(x, dy, dw, accumulate), x.device, "conv3_wgrad_tiny_kernel")
-
-
 def conv3_wgrad(x, dy, dw=None, accumulate=False):
     """accumulate: False / True, or 2 = `dw` is known to hold zeros (a fresh arena slot): single-producer layers then store instead
     of read-modify-write and the others skip their zero fill."""
@@ -1331,15 +1209,13 @@ def conv3_wgrad(x, dy, dw=None, accumulate=False):
     q = _queues(dw) if accumulate else None
     # (narrow bf16 layers - 16 / 32 channels on both sides - have a kernel of their own that finishes a 48^3 layer in ~10 us: never queued)
     # tiny volumes (3^3 / 6^3, hundreds of channels: encoder10 / decoder5): the write-bound kernel of their own, launched where the backward
-    # pass reaches them (TINY_WGRAD_AT = "inline") or with the queued launches at its end ("flush": in front of the grouped launch)
+    # pass reaches them (round 5: queued for the end of the pass, on the branch stream beside the grouped launch, 154.2 / 154.2 patches/s
+    # against 155.2 / 154.5 - four write-bound launches, 176 MB, lengthen the tail by more than the 80 us they take off the chain)
     tiny = kernel == L.CONV3_WGRAD_TINY
     if q is not None and q.unzeroed and dw.data_ptr() in q.unzeroed:
         q.unzeroed.discard(dw.data_ptr())
         if not (tiny and int(accumulate) == 2):      # anything but the overwriting launch reads (or only adds to) the slot: it gets its zeros now
             fill32(dw)
-    if tiny and q is not None and TINY_WGRAD_AT != "inline":
-        q.lists().tiny_wgrad.append((x, dy, dw, int(accumulate)))
-        return dw
     if q is not None and p.B * p.D * p.H * p.W <= CONV_WGRAD_GROUP_VOXELS and kernel not in (L.CONV3_WGRAD_NARROW, L.CONV3_WGRAD_TINY):
         q.lists().conv_wgrad.append((x, dy, dw, int(accumulate)))      # keeps x and dy alive until the flush
         return dw
@@ -1514,13 +1390,11 @@ def winattn_fwd(qkv, qkv_bias, table, heads, window, shift, tw, scale, drop=None
 def winattn_bwd(qkv, out, lse, dout, qkv_bias, table, heads, window, shift, tw, scale, dqkv_bias, dtable, drop=None):
     dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
     f = winattn_params(qkv, out, qkv_bias, table, lse, heads, window, shift, tw, scale, drop)
-    mk = lambda dqb, dtb: L.WinattnBwd(f, _ptr(dout), rows(dout)[0], _ptr(dqkv), rows(dqkv)[0], _ptr(dqb), _ptr(dtb))
+    p = L.WinattnBwd(f, _ptr(dout), rows(dout)[0], _ptr(dqkv), rows(dqkv)[0], _ptr(dqkv_bias), _ptr(dtable))
     B, D, H, W = _vol(qkv)
     n = window[0] * window[1] * window[2]
     nw = B * -(-D // window[0]) * -(-H // window[1]) * -(-W // window[2])
-    sq, st_ = _prof_scratch(dqkv_bias), _prof_scratch(dtable)      # (roofline leg: the repeats accumulate the bias / table gradients into scratch)
-    _call("miseg_winattn_bwd", mk(dqkv_bias, dtable), prof=("winattn", 10.0 * nw * heads * n * n * (qkv.shape[-1] // 3 // heads), _nb(qkv, out, lse, dout, dqkv)),
-          prof_params=mk(sq, st_) if (sq is not None or st_ is not None) else None)
+    _call("miseg_winattn_bwd", p, prof=("winattn", 10.0 * nw * heads * n * n * (qkv.shape[-1] // 3 // heads), _nb(qkv, out, lse, dout, dqkv)))
     return dqkv
 
 

@@ -152,7 +152,7 @@ class SwinUNETR(nn.Module):
     # Where the training forward forks that branch: "e10" = where it is taped (in front of encoder10, beside encoder10 / decoder5..3);
     # "s0" / "s1" / "s2" = as soon as Swin feature map 0 / 1 / 2 is queued, i.e. beside the Swin stages behind it, on a tape of its own that
     # joins the outer tape in front of encoder10 (HF.inner_tape_join): the backward pass is issued where it always was
-    fork_at = os.environ.get("MISEG_FORK_AT", "e10")
+    fork_at = "e10"
 
     @staticmethod
     def _skip_block(block, inp, styles, shape, channels, dt, **kw):
@@ -196,8 +196,7 @@ class SwinUNETR(nn.Module):
         branch = self.side_branch and dt == torch.bfloat16 and torch.is_grad_enabled() and not x_in.requires_grad
         # inference (no tape, so no ordering constraint from the backward pass): the two blocks are forked right behind `layers1` and run
         # beside the deep Swin stages, encoder3 / 4 / 10 and decoder5..3
-        infer_branch = (self.side_branch and dt == torch.bfloat16 and not torch.is_grad_enabled()
-                        and os.environ.get("MISEG_NO_INFER_BRANCH") is None)
+        infer_branch = self.side_branch and dt == torch.bfloat16 and not torch.is_grad_enabled()
         enc0 = enc1 = None
 
         def fork_inference(hs0):
@@ -218,7 +217,6 @@ class SwinUNETR(nn.Module):
             if i != {"s0": 0, "s1": 1, "s2": 2}[self.fork_at] or not feats[0].requires_grad:
                 return
             side, cur = ops.branch_stream(x_in.device), torch.cuda.current_stream()
-            ops._MAIN_STREAM = cur
             side.wait_stream(cur)
             for t in (feats[0], x_in, styles[0] if styles is not None else None):
                 if t is not None:
@@ -261,7 +259,6 @@ class SwinUNETR(nn.Module):
             # Swin stages (in front of decoder2, i.e. no forward overlap but a longer backward window, measured 138.7; here 143.4; right
             # behind the Swin transformer 143.3)
             side, cur = ops.branch_stream(x_in.device), torch.cuda.current_stream()
-            ops._MAIN_STREAM = cur
             if inner:      # forked earlier, on a tape of its own: the backward pass is taped here (nothing is launched)
                 with torch.cuda.stream(side):
                     enc0, enc1 = HF.inner_tape_join(inner["outs"], inner["outer"], inner["leaves"])

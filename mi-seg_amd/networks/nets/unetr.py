@@ -113,8 +113,7 @@ class UNETR(nn.Module):
             # decoder2's two 96^3 weight gradients wait for the branch's backward pass (hip/ops.py::defer_to_branch), as decoder1's do in
             # SwinUNETR.  Round 3 left them inline (0.29 ms launches then: throttled they became the critical path, 133.2 -> 123 .. 132.9); with
             # the narrow-layer weight-gradient kernel they are 45 + 60 us and deferring pays: 204.8 / 207.6 -> 209.2 / 211.5 patches/s
-            # (MISEG_UNETR_DEFER=0 keeps them inline)
-            (ops.close_branch_deferral if os.environ.get("MISEG_UNETR_DEFER") == "0" else ops.open_branch_deferral)(self.parameters())
+            ops.open_branch_deferral(self.parameters())
         else:
             enc1 = self.encoder1(None, styles, image=x_in, dtype=dt)
         enc2 = self.encoder2(self.proj_feat(hidden[3]), styles)

@@ -10,7 +10,6 @@ when the device-side parameter version moved since they last ran.  It moves when
     `refresh_weights()`, `GraphedStep` / `GraphedForward` / `GraphedTrainStep` before every replay, notices both and bumps it;
   * the caller says so: `arena.invalidate()` - REQUIRED after any other write: in-place ops on the `p.data` / `p.detach()` alias (it has a
     version counter of its own: an EMA swap-in or a weight clamp written that way is invisible), raw-pointer writes of custom kernels.
-`MISEG_REFRESH_ALWAYS=1` in the environment makes every refresh unconditional (the round-2 behaviour, ~0.2 ms per C-Swin-UNETR step).
 
 Without an arena the autograd Functions in hip/functional.py allocate and return each gradient (torch semantics,
 ``grad is None`` for parameters that were not used); with one they add into ``p._miseg_grad`` and return None, and
@@ -28,11 +27,11 @@ from ..hip import lib as L
 from ..hip import ops
 
 
-SKIP_OVERWRITTEN_FILL = not os.environ.get("MISEG_FULL_ARENA_FILL")      # A/B switch of round 5 (read once)
+SKIP_OVERWRITTEN_FILL = True      # False: the step's fill covers the whole arena (the tests' reference for the ranged fill)
 
 
 class ParamArena:
-    def __init__(self, params, dtype=torch.bfloat16, n_buckets=4, overlap_wgrad=False, grad_dtype=torch.float32, force_collective=None):
+    def __init__(self, params, dtype=torch.bfloat16, n_buckets=4, grad_dtype=torch.float32, force_collective=None):
         """force_collective (default: the environment's MISEG_FORCE_COLLECTIVE=1): a one-rank process group normally skips every collective (the
         local sums ARE the mean); with this set the exchanges are launched anyway - the RCCL leg then runs, and is testable, on a one-GPU box
         (tests/test_hip_rccl.py, `bench.py --force-dist`).  `collectives_launched` counts every collective this arena has issued.
@@ -54,7 +53,6 @@ class ParamArena:
         for p, v in zip(self.params, self.views):
             p._miseg_grad, p._miseg_arena, p._miseg_used = v, self, False
         self.dtype = dtype
-        self.wgrad_stream = torch.cuda.Stream(device=dev) if (overlap_wgrad and dev.type == "cuda") else None
         self.epoch = 0
         self._req = {}          # (id(p), transpose, inner, outer) -> [param, shadow, filled_epoch]
         self._table = None      # (device descriptor bytes, ndesc, total tiles)
@@ -88,7 +86,6 @@ class ParamArena:
         self._bm = None         # (stream, pinned result, event) of the bitmap exchange on a card
         self.used_on_device = False     # True after an exchange that left the global "used" flags in `used_dev` only (allreduce_end(host_flags=False))
         self._offs, self._size = offs, off
-        import os
         self.force_collective = bool(int(os.environ.get("MISEG_FORCE_COLLECTIVE", "0") or 0)) if force_collective is None else bool(force_collective)
         self.collectives_launched = 0
         self._qkey = self.flat.untyped_storage().data_ptr()
@@ -124,8 +121,6 @@ class ParamArena:
         # the conv weight gradients of the 48^3-and-smaller layers) are queued per arena and issued by end_backward()
         self.queues = ops.QUEUES[self._qkey] = ops.StepQueues()
         self.queues.on_branch_end = getattr(self, "branch_end_hook", None)
-        ops.WGRAD_STREAM = self.wgrad_stream      # None unless overlap_wgrad: measured SLOWER on one MI355X (93.3 -> 90 patches/s: the
-                                                  # cross-stream edges of the hipGraph cost more than the idle CUs they fill)
         self.epoch += 1
         if getattr(self, "_accumulating", False):     # the previous micro-batch ran under no_sync(): keep summing into the arena
             zero = False
@@ -190,10 +185,7 @@ class ParamArena:
                     ent[3] = self.epoch
 
     def _ver(self, slot):
-        """(params_version, state) device pointers of the versioned refresh launches; (None, None) = unconditional (MISEG_REFRESH_ALWAYS=1)"""
-        import os
-        if os.environ.get("MISEG_REFRESH_ALWAYS"):
-            return None, None
+        """(params_version, state) device pointers of the versioned refresh launches"""
         base = self.versions.data_ptr()
         return C.c_void_p(base), C.c_void_p(base + 8 * slot)
 
@@ -307,7 +299,7 @@ class ParamArena:
         """issue the queued bias-gradient column sums (one launch per 32); call after loss.backward(), inside the captured
         region when the step is a hipGraph.  publish() / allreduce() call it too."""
         # the main stream's grouped launches first (beside the branch's last kernels), the wait, then what the branch's backward queued
-        ops.join_branch(queues=self.queues, flush_main=ops.FLUSH_MAIN_BEFORE_JOIN)
+        ops.join_branch(queues=self.queues, flush_main=True)
         if self.queues is not None:
             self.queues.flush()
             # parameters whose gradient was complete when the main chain of the pass ended (see StepQueues.inline_final)
@@ -324,7 +316,6 @@ class ParamArena:
         ops.stamp("queues_flushed")
         ops.check_no_pending()
         ops.join_wgrad()
-        ops.WGRAD_STREAM = None
 
     def flush_small(self):
         """between the two halves of a split backward pass when the range that goes out early holds only layers whose conv weight gradients were
@@ -339,7 +330,7 @@ class ParamArena:
         # (weight gradients deferred to the branch's backward pass wait for the second half unless the model already issued them:
         # SwinUNETR.split_defers = "early").  As in end_backward: the grouped GEMM gradients / column sums go out on the branch stream beside
         # the main stream's grouped conv weight gradients
-        ops.join_branch(flush_deferred=False, queues=self.queues, flush_main=ops.FLUSH_MAIN_BEFORE_JOIN)
+        ops.join_branch(flush_deferred=False, queues=self.queues, flush_main=True)
         if self.queues is not None:
             self.queues.flush()
 
@@ -547,7 +538,6 @@ class ParamArena:
         self.queues = None
         ops.QUEUES.pop(self._qkey, None)
         ops.join_wgrad()
-        ops.WGRAD_STREAM = None
         for p in self.params:
             for a in ("_miseg_grad", "_miseg_arena", "_miseg_used"):
                 if hasattr(p, a):

@@ -392,7 +392,7 @@ class GraphedTrainStep:
         self.graphs = {}
         # opt-in (MISEG_EARLY_OPT=1): measured SLOWER on the headline net - 138.1 / 137.3 patches/s against 140.1 / 139.1 with the one-launch
         # step behind the pass (same box): 1.2 GB of optimiser traffic beside the end-of-pass grouped launches lengthens the tail by more than
-        # the 0.28 ms it takes off the chain (the same finding as the tiny-volume weight gradients on the branch, hip/ops.py::TINY_WGRAD_AT)
+        # the 0.28 ms it takes off the chain (the same finding as the tiny-volume weight gradients on the branch, hip/ops.py::conv3_wgrad)
         self.early_optimizer = bool(os.environ.get("MISEG_EARLY_OPT"))
         if optimizer.lr_dev is None:
             optimizer.lr_dev = torch.tensor([optimizer.lr], dtype=torch.float32, device=dev)

@@ -7,7 +7,6 @@ runtime/arena.py::ParamArena (set by the weight-gradient kernels' autograd nodes
 device and the kernel leaves unused tensors alone, with a per-parameter step count for Adam's bias correction.  The moments live in two
 flat fp32 buffers laid out like the arena."""
 import ctypes as C
-import os
 
 import torch
 
@@ -15,7 +14,6 @@ from ..hip import lib as L
 from ..hip import ops
 
 KINDS = {"adamw": L.OPT_ADAMW, "adam": L.OPT_ADAM, "sgd": L.OPT_SGD_NESTEROV}
-FUSE_CONV_PACKS = os.environ.get("MISEG_NO_OPT_PACK") is None      # A/B switch of round 5 (ArenaOptimizer._fused_tables)
 
 
 class ArenaOptimizer:
@@ -62,7 +60,7 @@ class ArenaOptimizer:
         (miseg_opt_step_pack_conv3), everything else by the element-wise launch in front of it.  Returns (rest table | None, map, pack table) once
         the arena holds a current conv-pack table whose weights are all trainable arena parameters, else None (the plain one-launch step)."""
         a = self.arena
-        if not FUSE_CONV_PACKS or self._early is not None or not a.flat.is_cuda or a._ptable is None or a._pdirty or a.dtype not in (torch.float32, torch.bfloat16):
+        if self._early is not None or not a.flat.is_cuda or a._ptable is None or a._pdirty or a.dtype not in (torch.float32, torch.bfloat16):
             return None
         key = a._ptable[0].data_ptr()
         cur = self.__dict__.get("_fused")

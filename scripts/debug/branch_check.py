@@ -14,10 +14,10 @@ m.set_compute_dtype(torch.bfloat16)
 arena = ParamArena([p for p in m.parameters() if p.requires_grad], torch.bfloat16)
 log = []
 orig = ops._call
-def call(fn_name, params, prof=None, prof_params=None):
+def call(fn_name, params, prof=None, extra=()):
     main = torch.cuda.current_stream() != ops._BRANCH_STREAM if ops._BRANCH_STREAM is not None else True
     log.append((fn_name, "M" if main else "B", getattr(params, "background", None), getattr(params, "max_workgroups", None), torch._C._current_graph_task_id()))
-    return orig(fn_name, params, prof, prof_params)
+    return orig(fn_name, params, prof, extra)
 ops._call = call
 x = torch.randn(1, 1, 96, 96, 96, device="cuda")
 for it in range(2):

@@ -21,7 +21,7 @@ from mi_seg_amd.networks.norms.utils import parse_normalization  # noqa: E402
 from mi_seg_amd.utils.detfill import det_input, fill_module_  # noqa: E402
 
 LOG = []
-SKIP = {"rows", "begin_step", "wgrad_side", "join_wgrad", "pop_gemm_stat", "winattn_params", "flush_tn_reduces", "flush_gemm_tn", "flush_colsums",
+SKIP = {"rows", "begin_step", "join_wgrad", "pop_gemm_stat", "winattn_params", "flush_tn_reduces", "flush_gemm_tn", "flush_colsums",
         "flush_conv_wgrads"}
 
 

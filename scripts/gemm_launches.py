@@ -21,10 +21,10 @@ for _ in range(3): step()
 torch.cuda.synchronize()
 shapes = []
 orig_call = ops._call
-def rec(fn_name, params, prof=None, prof_params=None, extra=()):
+def rec(fn_name, params, prof=None, extra=()):
     if fn_name == "miseg_gemm" and prof is not None and prof[0] == "gemm_nt":
         shapes.append((params.M, params.N, params.K, bool(params.res), bool(params.stat), params.act, getattr(params, "scat_d", 0)))
-    return orig_call(fn_name, params, prof=prof, prof_params=prof_params, extra=extra)
+    return orig_call(fn_name, params, prof=prof, extra=extra)
 ops._call = rec
 prof = roofline.profile_step(step)
 ops._call = orig_call

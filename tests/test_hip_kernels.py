@@ -359,7 +359,7 @@ def test_gemm_nt_epilogues(dtype, M, N, K):
 def test_fused_mlp_forward_and_backward(M, Cm):
     """the one-launch MLP of the 48-channel Swin stage (hidden tile fed from the first product's accumulator into the second) and its
     backward (pre-activation recomputed; dz, h written for the weight-gradient products) against fp32 torch on the bf16-rounded operands,
-    the fused statistics against a statistics pass over y, and the two-GEMM path it replaces (MISEG_NO_FUSED_MLP, read per call)."""
+    the fused statistics against a statistics pass over y, and the two-GEMM path it replaces (gemm_nt twice, called directly)."""
     ops = _ops()
     dt = torch.bfloat16
     Hm = 4 * Cm      # (round 5: the 96-channel stage too - weights resident in 155 KB of LDS, W1^T read transposed in the backward kernel)

@@ -281,3 +281,18 @@ def test_window_grid_against_the_independent_restatement():
         got = sliding_window_inference(vol, roi, 3, pred, overlap=ov)
         assert got.shape == want.shape == (2, 3) + size
         assert torch.allclose(got, want, rtol=0, atol=1e-6), (size, roi, ov, float((got - want).abs().max()))
+
+
+def test_environment_variables_read_by_the_package_are_the_documented_ones():
+    """every MISEG_* name in an os.environ read under mi-seg_amd/ is a row of the INTEGRATION.md table whose reader column names the package,
+    and every such row is read somewhere: a new switch needs a row, a retired one loses it (plain text scan, nothing imported)"""
+    read = set()
+    for d, _, files in os.walk(os.path.join(ROOT, "mi-seg_amd")):
+        for f in files:
+            if f.endswith(".py"):
+                read |= set(re.findall(r"os\.environ(?:\.get\(|\[|\.pop\()\s*[\"'](MISEG_[A-Z0-9_]+)", open(os.path.join(d, f)).read()))
+    rows = re.findall(r"^\| ((?:`MISEG_[A-Z0-9_]+`(?:, )?)+) \| ([^|]*) \|", open(os.path.join(ROOT, "INTEGRATION.md")).read(), re.M)
+    assert rows, "INTEGRATION.md has no table of environment variables"
+    documented = {n for names, reader in rows if "mi-seg_amd/" in reader for n in re.findall(r"MISEG_[A-Z0-9_]+", names)}
+    assert read and read == documented, (sorted(read - documented), sorted(documented - read))
+
