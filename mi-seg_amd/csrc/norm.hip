@@ -602,9 +602,12 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_pair_bwd_apply_kernel(c
   }
   const bool live = ty < ty_n && c < cv;
   if (!live && !r1x) return;
-  float dwacc[VEC];
+  // the rank-1 weight gradient all but vanishes (the norm behind the 1x1x1 convolution removes its scale): thousands of terms that cancel a
+  // thousandfold.  The per-thread chains and the workgroup's column sums run in float64 (fp32 chains left single elements 1e-4 of the
+  // gradient's scale off, differently from run to run); one fp32 atomic per channel and workgroup remains.
+  double dwacc[VEC];
 #pragma unroll
-  for (int i = 0; i < VEC; ++i) dwacc[i] = 0.f;
+  for (int i = 0; i < VEC; ++i) dwacc[i] = 0.0;
   if (live) {
   const int r0 = chunk * rpb, r1 = min(S, r0 + rpb);
   const float* ga = spa.gamma[st];
@@ -651,7 +654,7 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_pair_bwd_apply_kernel(c
     oa.store(dxa + (boff + r) * lddxa + c * VEC);
     if (r1x) {
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) dwacc[i] = fmaf(to_f32(from_f32<T>(ob.v[i])), xs, dwacc[i]);
+      for (int i = 0; i < VEC; ++i) dwacc[i] = fma((double)to_f32(from_f32<T>(ob.v[i])), (double)xs, dwacc[i]);
     } else {
       ob.store(dxb + (boff + r) * lddxb + c * VEC);
     }
@@ -662,14 +665,14 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_pair_bwd_apply_kernel(c
     __syncthreads();       // the statistics in `sums` have been read by everyone
     if (ty < ty_n) {
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) redf[(ty * tx_n + tx) * VEC + i] = dwacc[i];
+      for (int i = 0; i < VEC; ++i) redf[(ty * tx_n + tx) * VEC + i] = (float)dwacc[i];
     }
     __syncthreads();
     for (int e = threadIdx.x; e < tx_n * VEC; e += NORM_THREADS) {
       const int ch = blockIdx.z * tx_n * VEC + e;
-      float tot = 0.f;
-      for (int t = 0; t < ty_n; ++t) tot += redf[t * tx_n * VEC + e];
-      if (ch < C) atomicAdd(r1dw + ch, tot);
+      double tot = 0.0;
+      for (int t = 0; t < ty_n; ++t) tot += (double)redf[t * tx_n * VEC + e];
+      if (ch < C) atomicAdd(r1dw + ch, (float)tot);
     }
   }
 }

@@ -1,12 +1,15 @@
 """GPU tests of the smaller API surface the reference's hot path accepts ("what's missing" 2-4): the `batch` / `group` norm
 kinds of networks/norms/utils.py:11-14 (factories.py:219-257), multi-channel images in the res-block stem (--in_channels, dynunet_block.py:82-98)
-and the UNet activations beyond PReLU (--activation, networks/nets/unet.py:116-134) - each against plain torch fp32 on the same device."""
+and the UNet activations beyond PReLU (--activation, networks/nets/unet.py:116-134) - each against plain torch in float64 on the same (fp32 or bf16-rounded) inputs, on the
+same device, by the pooled and the per-element metric of tests/parity.py."""
+import copy
+
 import pytest
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from conftest import rel_err
+from parity import assert_parity
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -31,23 +34,26 @@ def test_group_and_batch_norm_match_torch(kind, dtype, tol):
         m.weight.copy_(torch.rand(C) + 0.5)
         m.bias.copy_(torch.randn(C) * 0.2)
     ref.load_state_dict(m.state_dict())
+    ref = ref.double()
     x = (torch.randn(B, C, *S, device=DEV) * 1.5 + 0.7)
     g = torch.randn(B, C, *S, device=DEV)
-    xr = x.clone().requires_grad_(True)
+    xr = x.to(dtype).double().requires_grad_(True)          # float64 on the operands as the kernels see them
     yr = ref(xr)
-    yr.backward(g)
+    yr.backward(g.to(dtype).double())
     xh = _cl(x).to(dtype).requires_grad_(True)
     y = apply_norm(m, xh, None)
     y.backward(_cl(g).to(dtype))
-    assert rel_err(y.float().permute(0, 4, 1, 2, 3), yr) < tol
-    assert rel_err(xh.grad.float().permute(0, 4, 1, 2, 3), xr.grad) < tol
-    assert rel_err(m.weight.grad, ref.weight.grad) < tol and rel_err(m.bias.grad, ref.bias.grad) < tol
+    assert_parity(y.float().permute(0, 4, 1, 2, 3), yr, tol, "y")
+    assert_parity(xh.grad.float().permute(0, 4, 1, 2, 3), xr.grad, tol, "dx")
+    assert_parity(m.weight.grad, ref.weight.grad, tol, "m.weight.grad")
+    assert_parity(m.bias.grad, ref.bias.grad, tol, "m.bias.grad")
     if kind == "batch":
-        assert rel_err(m.running_mean, ref.running_mean) < 1e-4 + tol and rel_err(m.running_var, ref.running_var) < 1e-4 + tol
+        assert_parity(m.running_mean, ref.running_mean, 1e-4 + tol, "m.running_mean")
+        assert_parity(m.running_var, ref.running_var, 1e-4 + tol, "m.running_var")
         assert int(m.num_batches_tracked) == 1
         m.eval(), ref.eval()
         with torch.no_grad():
-            assert rel_err(apply_norm(m, _cl(x).to(dtype), None).float().permute(0, 4, 1, 2, 3), ref(x)) < tol + 1e-3
+            assert_parity(apply_norm(m, _cl(x).to(dtype), None).float().permute(0, 4, 1, 2, 3), ref(x.to(dtype).double()), tol + 1e-3, "eval mode")
         with pytest.raises(NotImplementedError):
             apply_norm(m, _cl(x).to(dtype).requires_grad_(True), None)
 
@@ -75,27 +81,26 @@ def test_res_block_with_other_norm_kinds_and_multi_channel_images(kind, cin, ima
             return F.batch_norm(t, None, None, m.weight, m.bias, True, 0.1, m.eps)
         return F.instance_norm(t, weight=m.weight, bias=m.bias, eps=m.eps)
 
-    xr = x.clone().requires_grad_(image == 0)
-    o = F.leaky_relu(tnorm(blk.norm1, F.conv3d(xr, blk.conv1.conv.weight, padding=1)), 0.01)
-    o = tnorm(blk.norm2, F.conv3d(o, blk.conv2.conv.weight, padding=1))
-    o = F.leaky_relu(o + tnorm(blk.norm3, F.conv3d(xr, blk.conv3.conv.weight)), 0.01)
-    o.backward(g)
-    want = {k: p.grad.clone() for k, p in blk.named_parameters()}
-    for p in blk.parameters():
-        p.grad = None
+    rb = copy.deepcopy(blk).double()                         # the same parameters in float64, used through torch ops only
+    xr = x.double().requires_grad_(image == 0)
+    o = F.leaky_relu(tnorm(rb.norm1, F.conv3d(xr, rb.conv1.conv.weight, padding=1)), 0.01)
+    o = tnorm(rb.norm2, F.conv3d(o, rb.conv2.conv.weight, padding=1))
+    o = F.leaky_relu(o + tnorm(rb.norm3, F.conv3d(xr, rb.conv3.conv.weight)), 0.01)
+    o.backward(g.double())
+    want = {k: p.grad.clone() for k, p in rb.named_parameters()}
     if image:
         y = blk(None, None, image=x, dtype=torch.float32)
     else:
         xh = _cl(x).requires_grad_(True)
         y = blk(xh, None)
     y.backward(_cl(g))
-    assert rel_err(y.permute(0, 4, 1, 2, 3), o) < 1e-4
+    assert_parity(y.permute(0, 4, 1, 2, 3), o, 1e-4, "y")
     if not image:
-        assert rel_err(xh.grad.permute(0, 4, 1, 2, 3), xr.grad) < 1e-3
+        assert_parity(xh.grad.permute(0, 4, 1, 2, 3), xr.grad, 1e-3, "dx")
     for k, p in blk.named_parameters():
         if "running" in k:
             continue
-        assert rel_err(p.grad, want[k]) < 2e-3, k
+        assert_parity(p.grad, want[k], 2e-3, f"p.grad {k}")
 
 
 @pytest.mark.parametrize("act", ["relu", "leakyrelu", "gelu", ("leakyrelu", {"negative_slope": 0.2})])
@@ -118,7 +123,7 @@ def test_unet_activations_beyond_prelu(act):
     kind = act if isinstance(act, str) else act[0]
     slope = 0.0 if kind == "relu" else (0.01 if isinstance(act, str) else act[1]["negative_slope"])
     got = HF.gelu(t) if kind == "gelu" else HF.leaky_relu(t, slope)
-    want = F.gelu(t.detach()) if kind == "gelu" else F.leaky_relu(t.detach(), slope)
-    assert rel_err(got, want) < 1e-6
+    want = F.gelu(t.detach().double()) if kind == "gelu" else F.leaky_relu(t.detach().double(), slope)
+    assert_parity(got, want, 1e-6, kind)
     with pytest.raises(NotImplementedError):
         UNet(3, 1, 3, channels=(8, 16), strides=(2,), act="mish")

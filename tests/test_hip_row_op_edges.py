@@ -1,0 +1,610 @@
+"""Layout edges of the plain row kernels (csrc/elementwise.hip, the layer norm of csrc/norm.hip, permute3 of csrc/gemm.hip).
+
+Every launcher picks between a 16-byte vector instantiation and a scalar one (C % N, every ld % N, every pointer 16-byte aligned; N = 8 bf16 or
+4 fp32 elements) and walks a grid-stride loop under a workgroup cap.  The network hands these kernels channel slices of wider buffers.  So each op
+runs here, per dtype, on: whole-vector contiguous rows; ragged channel counts (scalar instantiation); aligned channel slices (vector instantiation
+with ld != C); each clause of the vector predicate broken alone, per operand (an 8-byte offset with ld % N == 0, an ld % N != 0 with an aligned
+base); one shape per instantiation with more items than cap x 256 (the loop wraps); odd spatial extents; 1- and 33-row tiles for the 32 x 32
+transposes.  Inputs sit in NaN-filled buffers (a read outside the view poisons the result), outputs in sentinel-filled buffers whose every
+byte outside the view must survive.  References are float64 (tests/parity.py judges them) or exact torch indexing for pure data movement.
+
+What the broken-predicate cases can and cannot show: the card serves unaligned 16-byte global accesses, so a launcher that took the vector
+instantiation on an 8-byte-offset base or an odd ld would still give the right numbers here.  Which instantiation ran is not observed; the
+cases show that the result is right and the neighbouring bytes survive on every such operand, whichever path the launcher picks."""
+import ctypes as C
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from parity import assert_parity
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+TOL = {torch.float32: 2e-4, torch.bfloat16: 2e-2}
+DTYPES = [torch.float32, torch.bfloat16]
+SENT = 1536.0          # exact in bf16
+ROWS = 301             # odd, several workgroups even at 8 elements per item
+# workgroup caps of the launchers (x 256 threads = items per pass of the grid-stride loop):
+#   ew_grid 8192 (add, gelu, rowbias, prelu_fwd, copy2d, resample2, space<->channel, cast_matrix, ncdhw_to_rows) -> 2 097 152 items
+#   miseg_affine2 4096, miseg_permute3 4096 -> 1 048 576 items;  miseg_prelu_bwd 1024 -> 262 144 items
+CAP_ITEMS = {"ew": 8192 * 256, "affine2": 4096 * 256, "permute3": 4096 * 256, "prelu_bwd": 1024 * 256}
+
+
+def _ops():
+    from mi_seg_amd.hip import ops
+    return ops
+
+
+def _L():
+    from mi_seg_amd.hip import lib
+    return lib
+
+
+def _name(dt):
+    return {torch.float32: "fp32", torch.bfloat16: "bf16"}[dt]
+
+
+def _nvec(dtype):
+    return 16 // torch.empty(0, dtype=dtype).element_size()
+
+
+def _bits(t):
+    return t.view(torch.int16 if t.element_size() == 2 else torch.int32)
+
+
+def rnd(*shape, dtype=torch.float32, seed=0, scale=1.0, shift=0.0):
+    big = 1
+    for v in shape:
+        big *= v
+    if big > 1 << 20:          # the grid-wrapping shapes: drawn on the device
+        g = torch.Generator(device=DEV).manual_seed(seed + 7 * sum(shape))
+        return (torch.randn(*shape, generator=g, device=DEV) * scale + shift).to(dtype)
+    g = torch.Generator().manual_seed(seed + 7 * sum(shape))
+    return (torch.randn(*shape, generator=g) * scale + shift).to(DEV).to(dtype)
+
+
+class Slot:
+    """a channels-last view of `shape` = (..., C) inside a larger buffer.  layout: "contig" (the buffer is the view), "slice" (16-byte aligned
+    channel slice of wider rows, ld % N == 0), "off8" (slice that starts 8 bytes into a 16-byte unit, ld % N == 0), "ldodd" (aligned base,
+    ld % N != 0).  The non-contiguous layouts have 16 leading and one trailing slab of rows around the view (16 keeps the base aligned)."""
+
+    def __init__(self, shape, dtype, layout, fill):
+        n = _nvec(dtype)
+        c = shape[-1]
+        cp = -(-c // n) * n
+        self.layout = layout
+        if layout == "contig":
+            self.buf = torch.full(shape, fill, dtype=dtype, device=DEV)
+            self.view = self.buf
+            self.index = None
+            return
+        off, ld = {"slice": (n, cp + 3 * n), "off8": (n // 2, cp + 2 * n), "ldodd": (0, cp + n + 1)}[layout]
+        pre = 16
+        self.buf = torch.full((pre + shape[0] + 1,) + tuple(shape[1:-1]) + (ld,), fill, dtype=dtype, device=DEV)
+        self.index = (slice(pre, pre + shape[0]),) + (slice(None),) * (len(shape) - 2) + (slice(off, off + c),)
+        self.view = self.buf[self.index]
+        es = self.buf.element_size()
+        assert self.buf.data_ptr() % 16 == 0
+        assert (self.view.data_ptr() % 16 == 0) == (layout != "off8") and (ld % n == 0) == (layout != "ldodd") and ld * es >= c * es
+
+
+def place_in(values, layout):
+    """an input operand: `values` copied into a view of the given layout, NaN all around it"""
+    s = Slot(tuple(values.shape), values.dtype, layout, float("nan"))
+    s.view.copy_(values)
+    return s.view
+
+
+def place_out(shape, dtype, layout):
+    return Slot(tuple(shape), dtype, layout, SENT)
+
+
+def assert_untouched(slot, what):
+    """every element of the buffer outside the view still holds the sentinel, bit for bit"""
+    if slot.index is None:
+        return
+    keep = torch.ones(slot.buf.shape, dtype=torch.bool, device=DEV)
+    keep[slot.index] = False
+    want = int(_bits(torch.tensor([SENT], dtype=slot.buf.dtype))[0])
+    bad = (_bits(slot.buf) != want) & keep
+    assert not bool(bad.any()), f"{what}: {int(bad.sum())} element(s) outside the output view were written, first at {tuple(bad.nonzero()[0].tolist())}"
+
+
+def P(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+# ----------------------------------------------------------------------------------------------------------------- the row ops
+# each: inputs (list of names), run(ops, L, ins, out, aux) -> launches into `out`, ref(ins as float64, aux) -> float64 reference
+def _aux(op, Cc, rows):
+    if op == "rowbias_add":
+        return rnd(Cc, seed=91)
+    if op in ("prelu_fwd", "prelu_bwd"):
+        return torch.tensor([0.21], device=DEV)
+    if op == "affine2":
+        B = 7 if rows % 7 == 0 else 2
+        return rnd(B, Cc, 3, seed=92)
+    return None
+
+
+def _run_add(ops, L, ins, out, aux):
+    assert ops.add(ins[0], ins[1], out=out) is out
+
+
+def _run_gelu_fwd(ops, L, ins, out, aux):
+    ld, n, Cc = ops.rows(ins[0])
+    ops._call("miseg_gelu_fwd", L.GeluFwd(P(ins[0]), ld, P(out), ops.rows(out)[0], n, Cc, ops._dt(ins[0])))
+
+
+def _run_gelu_bwd(ops, L, ins, out, aux):
+    dy, x = ins
+    ld, n, Cc = ops.rows(x)
+    ops._call("miseg_gelu_bwd", L.GeluBwd(P(dy), ops.rows(dy)[0], P(x), ld, P(out), ops.rows(out)[0], n, Cc, ops._dt(x)))
+
+
+def _run_rowbias(ops, L, ins, out, aux):
+    ld, n, Cc = ops.rows(ins[0])
+    ops._call("miseg_rowbias_add", L.Rowbias(P(ins[0]), ld, P(aux), P(out), ops.rows(out)[0], n, Cc, ops._dt(ins[0])))
+
+
+def _run_prelu_fwd(ops, L, ins, out, aux):
+    ld, n, Cc = ops.rows(ins[0])
+    ops._call("miseg_prelu_fwd", L.PreluFwd(P(ins[0]), ld, P(aux), P(out), ops.rows(out)[0], n, Cc, ops._dt(ins[0])))
+
+
+def _run_prelu_bwd(ops, L, ins, out, aux, dslope=None):
+    dy, x = ins
+    ld, n, Cc = ops.rows(x)
+    scratch = torch.zeros(2, dtype=torch.float64, device=DEV) if dslope is not None else None
+    ops._call("miseg_prelu_bwd", L.PreluBwd(P(dy), ops.rows(dy)[0], P(x), ld, P(aux), P(out), ops.rows(out)[0], P(dslope), n, Cc, ops._dt(x), P(scratch)))
+
+
+def _run_affine2(ops, L, ins, out, aux):
+    a, x = ins
+    lda, n, Cc = ops.rows(a)
+    B = aux.shape[0]
+    ops._call("miseg_affine2", L.Affine2(C.sizeof(L.Affine2), P(a), lda, P(x), ops.rows(x)[0], P(out), ops.rows(out)[0], P(aux), B, n // B, Cc, ops._dt(a)))
+
+
+def _gelu_grad(x):
+    return 0.5 * (1 + torch.erf(x * 0.5 ** 0.5)) + x * torch.exp(-0.5 * x * x) * (2 * torch.pi) ** -0.5
+
+
+def _ref_affine2(ins, aux):
+    a, x = ins
+    B = aux.shape[0]
+    k = aux.double()[:, None]                                  # [B, 1, C, 3]
+    sh = (B, a.shape[0] // B, a.shape[1])
+    return (k[..., 0] * a.reshape(sh) + (k[..., 1] * x.reshape(sh) + k[..., 2])).reshape(a.shape)
+
+
+ROW_OPS = {
+    "add": (2, _run_add, lambda ins, aux: ins[0] + ins[1]),
+    "gelu_fwd": (1, _run_gelu_fwd, lambda ins, aux: F.gelu(ins[0])),
+    "gelu_bwd": (2, _run_gelu_bwd, lambda ins, aux: ins[0] * _gelu_grad(ins[1])),
+    "rowbias_add": (1, _run_rowbias, lambda ins, aux: ins[0] + aux.double()),
+    "prelu_fwd": (1, _run_prelu_fwd, lambda ins, aux: torch.where(ins[0] > 0, ins[0], aux.double() * ins[0])),
+    "prelu_bwd": (2, _run_prelu_bwd, lambda ins, aux: torch.where(ins[1] > 0, ins[0], aux.double() * ins[0])),
+    "affine2": (2, _run_affine2, _ref_affine2),
+}
+ROW_CAP = {"affine2": "affine2", "prelu_bwd": "prelu_bwd"}
+
+
+def _row_inputs(op, nin, rows, Cc, dtype):
+    """deliberate values in front of the random ones: +-0 (PReLU: the x > 0 ? g : a g convention sends x = 0 down the slope branch, as torch
+    does), |x| up to 10 (the bf16 GELU derivative takes the fast exponential)"""
+    scale = 3.0 if op.startswith("gelu") else 1.0
+    ins = [rnd(rows, Cc, dtype=dtype, seed=11 + 5 * i, scale=scale) for i in range(nin)]
+    special = torch.tensor([0.0, -0.0, 10.0, -10.0, 9.5, -7.25, 1e-3, -1e-3, 4.0, -4.0], device=DEV).to(dtype)
+    flat = ins[-1].reshape(-1)                                 # the activation's own input (x) is the last operand
+    k = min(special.numel(), flat.numel())
+    flat[:k] = special[:k]
+    if op.startswith("gelu"):
+        ins[-1].clamp_(-10.0, 10.0)
+    return ins
+
+
+def _row_cases():
+    cases = []
+    for op, (nin, _, _) in ROW_OPS.items():
+        for dt in DTYPES:
+            base = [("contig", 48, None, None), ("ragged", 6, None, None), ("ragged", 10, None, None), ("ragged", 50, None, None), ("slice", 48, None, None)]
+            for k in range(nin + 1):
+                base += [("off8", 48, k, None), ("ldodd", 48, k, None)]
+            cap = CAP_ITEMS[ROW_CAP.get(op, "ew")]
+            n = _nvec(dt)
+            # rows chosen so that rows * 48 / N (vector) and rows * 50 (scalar) exceed the op's cap x 256 by 3 %: about 360000 x 48 bf16 / 180000 x 48
+            # fp32 / 43200 x 50 clear ew_grid's 8192, 180000 / 90000 / 21600 affine2's 4096, 45000 / 22500 / 5400 prelu_bwd's 1024
+            base += [("wrapvec", 48, None, -(-int(cap * 1.03) // (48 // n))), ("wrapscalar", 50, None, -(-int(cap * 1.03) // 50))]
+            for kind, Cc, k, rows in base:
+                cid = f"{op}-{_name(dt)}-{kind}" + (f"{Cc}" if kind == "ragged" else "") + (f"-operand{k}" if k is not None else "")
+                cases.append(pytest.param(op, dt, kind, Cc, k, rows, id=cid))
+    return cases
+
+
+@pytest.mark.parametrize("op,dtype,kind,Cc,which,rows", _row_cases())
+def test_row_op_layouts(op, dtype, kind, Cc, which, rows):
+    ops, L = _ops(), _L()
+    nin, run, ref = ROW_OPS[op]
+    rows = rows or ROWS
+    if op == "affine2" and rows % 7 and rows % 2:
+        rows += 1
+    n = _nvec(dtype)
+    if kind.startswith("wrap"):
+        items = rows * (Cc // n if Cc % n == 0 else Cc)
+        assert items > CAP_ITEMS[ROW_CAP.get(op, "ew")], "the shape must make the grid-stride loop wrap"
+    vals = _row_inputs(op, nin, rows, Cc, dtype)
+    aux = _aux(op, Cc, rows)
+    lay = ["contig"] * (nin + 1)
+    if kind == "slice":
+        lay = ["slice"] * (nin + 1)
+    elif which is not None:
+        lay[which] = kind
+    ins = [place_in(v, l) for v, l in zip(vals, lay[:nin])]
+    out = place_out((rows, Cc), dtype, lay[nin])
+    run(ops, L, ins, out.view, aux)
+    want = ref([v.double() for v in vals], aux)
+    what = f"{op} {_name(dtype)} {kind} C={Cc} rows={rows}"
+    assert_untouched(out, what)
+    if op == "add":
+        assert torch.equal(out.view, want.to(dtype)), what          # one rounding of the exact sum
+    else:
+        assert_parity(out.view, want, TOL[dtype], what)
+    if kind == "contig" and op != "add":
+        # the public wrapper (allocates its own output) launches the same kernel on the same operands
+        got = {"gelu_fwd": lambda: ops.gelu_fwd(ins[0]), "gelu_bwd": lambda: ops.gelu_bwd(ins[0], ins[1]), "rowbias_add": lambda: ops.rowbias_add(ins[0], aux),
+               "prelu_fwd": lambda: ops.prelu_fwd(ins[0], aux), "prelu_bwd": lambda: ops.prelu_bwd(ins[0], ins[1], aux, None),
+               "affine2": lambda: ops.affine2(ins[0], ins[1], aux, aux.shape[0], rows // aux.shape[0])}[op]()
+        assert torch.equal(got, out.view)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=_name)
+@pytest.mark.parametrize("rows,Cc,layout", [(ROWS, 48, "contig"), (ROWS, 50, "contig"), (ROWS, 48, "slice"), (ROWS, 48, "off8"), (ROWS, 48, "ldodd"),
+                                            (45000, 48, "contig"), (5400, 50, "contig")])      # the last two wrap prelu_bwd's 1024 workgroups
+def test_prelu_bwd_slope_gradient(dtype, rows, Cc, layout):
+    """dslope += sum dy * min(x, 0): the kernel keeps one fp32 partial per thread (fmaf chain), adds the 64 lanes of a wave by shuffles and the
+    workgroups in float64, and adds the total onto dslope in fp32.  With t terms per thread the fp32 part is bounded by (t + 6 + 1) u sum|term|
+    (u = 2^-24; t = items per thread x vector width: 8 at 301 rows, 16 at 45000 x 48 bf16, 6 at 5400 x 50), the final fp32 add by 2 u (|old| + |sum|).
+    Measured on the card: 2e-6 .. 8e-6 at 301 rows (bound 2e-3 .. 4e-3), 8e-5 at 45000 x 48 (bound 0.8 .. 0.9), 9e-6 at 5400 x 50 (bound 5e-2):
+    at most 0.4 % of the bound.  At the two grid-wrapping shapes the bound (0.8 / 0.05) is of the size of a single term (about 0.3): there the slope
+    gradient is checked only coarsely (a lost wave or a double-counted pass of the loop would show, a single lost element would not); the 301-row
+    cases (bound 2e-3 .. 4e-3) see a single element, and the dx leg of test_row_op_layouts covers the wrap element by element."""
+    ops, L = _ops(), _L()
+    dy, x = _row_inputs("prelu_bwd", 2, rows, Cc, dtype)
+    slope = _aux("prelu_bwd", Cc, rows)
+    dyv, xv = place_in(dy, layout), place_in(x, layout)
+    out = place_out((rows, Cc), dtype, layout)
+    dslope = torch.tensor([3.25], device=DEV)                  # accumulates onto a non-zero value
+    _run_prelu_bwd(ops, L, [dyv, xv], out.view, slope, dslope=dslope)
+    assert_untouched(out, "prelu_bwd dx")
+    terms = dy.double() * x.double().clamp(max=0.0)
+    total, scale = float(terms.sum()), float(terms.abs().sum())
+    n = _nvec(dtype)
+    vec = Cc % n == 0 and layout in ("contig", "slice")
+    items = rows * (Cc // n if vec else Cc)
+    grid = min(-(-items // 256), 1024)
+    t = -(-items // (grid * 256)) * (n if vec else 1)
+    u = 2.0 ** -24
+    bound = (t + 7) * u * scale + 2 * u * (3.25 + abs(total)) + 2.0 ** -23 * abs(3.25 + total)      # (+ the representation of the result itself)
+    err = abs(float(dslope) - (3.25 + total))
+    assert err <= bound, (err, bound, float(dslope), 3.25 + total)
+    # x == 0 (either sign) contributes nothing to the slope gradient and takes the slope branch for dx
+    z = torch.zeros(4, Cc, dtype=dtype, device=DEV)
+    z[1::2] = -0.0
+    g = rnd(4, Cc, dtype=dtype, seed=5)
+    ds = torch.tensor([1.5], device=DEV)
+    dx = ops.prelu_bwd(g, z, slope, ds)
+    assert float(ds) == 1.5
+    assert_parity(dx, g.double() * 0.21, TOL[dtype], "prelu_bwd dx at x = +-0")
+
+
+# ----------------------------------------------------------------------------------------------------------------- copy2d
+@pytest.mark.parametrize("sdt,ddt", [(a, b) for a in DTYPES for b in DTYPES], ids=lambda d: _name(d))
+@pytest.mark.parametrize("kind,Cc,rows", [("contig", 48, ROWS), ("contig", 6, ROWS), ("contig", 10, ROWS), ("contig", 50, ROWS), ("slice", 48, ROWS), ("off8-src", 48, ROWS), ("ldodd-src", 48, ROWS),
+                                          ("off8-dst", 48, ROWS), ("ldodd-dst", 48, ROWS), ("wrap", 50, 45000)])      # 2 250 000 elements: ew_grid's 8192 (copy2d is scalar)
+def test_copy2d_layouts(sdt, ddt, kind, Cc, rows):
+    ops = _ops()
+    src = rnd(rows, Cc, dtype=sdt, seed=21)
+    ls = ld = "contig"
+    if kind == "slice":
+        ls = ld = "slice"
+    elif kind.endswith("-src"):
+        ls = kind[:-4]
+    elif kind.endswith("-dst"):
+        ld = kind[:-4]
+    sv = place_in(src, ls)
+    dst = place_out((rows, Cc), ddt, ld)
+    assert ops.copy2d(sv, dst.view) is dst.view
+    assert_untouched(dst, f"copy2d {kind}")
+    assert torch.equal(dst.view, src.to(ddt))
+
+
+# ----------------------------------------------------------------------------------------------------------------- colsum
+@pytest.mark.parametrize("dtype", DTYPES, ids=_name)
+@pytest.mark.parametrize("accumulate", [False, True], ids=["plain", "accumulate"])
+@pytest.mark.parametrize("rows,Cc,layout", [(ROWS, 48, "contig"), (ROWS, 6, "contig"), (ROWS, 10, "contig"), (ROWS, 50, "contig"), (ROWS, 48, "slice"), (ROWS, 48, "off8"),
+                                            (ROWS, 48, "ldodd"), (1, 48, "contig"), (70001, 48, "slice"), (70001, 50, "contig"), (5, 300, "contig")])
+def test_colsum_layouts(dtype, accumulate, rows, Cc, layout):
+    """fp32 column sums (plain: the output is overwritten; accumulate: added onto what it holds); 70001 rows take the 512-row workgroups.  The
+    output is a run of C floats inside a sentinel-filled buffer."""
+    ops = _ops()
+    x = rnd(rows, Cc, dtype=dtype, seed=31)
+    xv = place_in(x, layout)
+    buf = torch.full((3, Cc + 8), SENT, device=DEV)
+    out = buf[1, 4:4 + Cc]
+    base = rnd(Cc, seed=32)
+    out.copy_(base)
+    assert ops.DEFAULT_QUEUES is None
+    got = ops.colsum(xv, out, accumulate=accumulate)
+    assert got is out
+    keep = torch.ones_like(buf, dtype=torch.bool)
+    keep[1, 4:4 + Cc] = False
+    assert bool((buf[keep] == SENT).all()), "colsum wrote outside its C outputs"
+    want = x.double().sum(0) + (base.double() if accumulate else 0.0)
+    assert_parity(out, want, TOL[dtype], f"colsum {_name(dtype)} {rows}x{Cc} {layout}")
+    if not accumulate:
+        assert torch.equal(ops.colsum(xv), out) or rows > 128      # (several workgroups add in arrival order)
+
+
+# ----------------------------------------------------------------------------------------------------------------- 2x2x2 resampling and space <-> channel
+GRIDS = [(2, 5, 6, 7), (1, 1, 1, 3), (1, 4, 2, 6)]
+
+
+def _spatial_cases(extra_wrap):
+    cases = []
+    for dt in DTYPES:
+        for grid in GRIDS:
+            for kind, Cc in (("contig", 48), ("ragged", 6), ("ragged", 10), ("ragged", 50), ("slice", 48), ("off8-in", 48), ("ldodd-in", 48), ("off8-out", 48), ("ldodd-out", 48)):
+                if grid != GRIDS[0] and kind not in ("contig", "slice") and Cc != 10:
+                    continue
+                cases.append(pytest.param(dt, grid, kind, Cc, id=f"{_name(dt)}-{'x'.join(map(str, grid))}-{kind}{Cc}"))
+        for grid, Cc in extra_wrap[dt]:
+            cases.append(pytest.param(dt, grid, "wrap", Cc, id=f"{_name(dt)}-{'x'.join(map(str, grid))}-wrap{Cc}"))
+    return cases
+
+
+def _lay(kind):
+    li = lo = "contig"
+    if kind == "slice":
+        li = lo = "slice"
+    elif kind.endswith("-in"):
+        li = kind[:-3]
+    elif kind.endswith("-out"):
+        lo = kind[:-4]
+    return li, lo
+
+
+def _half(v):
+    return (v + 1) // 2
+
+
+# items = output voxels x C / N (vector) or x C (scalar); each shape clears ew_grid's 8192 x 256 = 2 097 152
+RESAMPLE_WRAP = {torch.bfloat16: [((1, 72, 72, 72), 48), ((1, 36, 36, 36), 50)], torch.float32: [((1, 57, 57, 57), 48), ((1, 36, 36, 36), 50)]}
+
+
+@pytest.mark.parametrize("up", [False, True], ids=["down", "up"])
+@pytest.mark.parametrize("dtype,grid,kind,Cc", _spatial_cases(RESAMPLE_WRAP))
+def test_resample2_layouts(dtype, grid, kind, Cc, up):
+    """dir 0: the even voxels of the fine grid; dir 1: zero insertion into the fine grid (the output grid is `grid` in both directions)"""
+    ops, L = _ops(), _L()
+    B, D, H, W = grid
+    wraps = kind == "wrap" and (up or Cc == 50)
+    if wraps and not up:
+        # the coarse OUTPUT is the grid that wraps: the input is eight times as large, so only the scalar instantiation wraps in this direction
+        # (the vector instantiation's loop is the same code for both directions and wraps in the other one)
+        D, H, W = 2 * D, 2 * H, 2 * W
+    coarse = (B, _half(D), _half(H), _half(W), Cc)
+    fine = (B, D, H, W, Cc)
+    li, lo = _lay(kind)
+    x = rnd(*(coarse if up else fine), dtype=dtype, seed=41)
+    xv = place_in(x, li)
+    out = place_out(fine if up else coarse, dtype, lo)
+    if wraps:
+        n = _nvec(dtype)
+        assert out.view.numel() // (n if Cc % n == 0 else 1) > CAP_ITEMS["ew"]
+    ops._call("miseg_resample2", L.Resample2(P(xv), ops.rows(xv)[0], P(out.view), ops.rows(out.view)[0], B, D, H, W, Cc, ops._dt(xv), int(up)))
+    assert_untouched(out, f"resample2 {kind}")
+    if up:
+        want = torch.zeros(fine, dtype=dtype, device=DEV)
+        want[:, ::2, ::2, ::2] = x
+    else:
+        want = x[:, ::2, ::2, ::2]
+    assert torch.equal(out.view, want)
+    if kind == "contig":
+        assert torch.equal(ops.resample2(xv, up, fine_shape=(D, H, W)), want)
+
+
+S2C_WRAP = {torch.bfloat16: [((1, 36, 36, 36), 48), ((1, 18, 18, 18), 50)], torch.float32: [((1, 30, 30, 30), 48), ((1, 18, 18, 18), 50)]}      # coarse voxels x 8 blocks x C / N
+C2S_WRAP = {torch.bfloat16: [((1, 72, 72, 72), 48), ((1, 36, 36, 36), 50)], torch.float32: [((1, 57, 57, 57), 48), ((1, 36, 36, 36), 50)]}      # fine voxels x C / N
+
+
+def _offsets(name):
+    from mi_seg_amd.hip.functional import MERGE_V1_OFFSETS, STD_OFFSETS
+    return {"std": STD_OFFSETS, "merge_v1": MERGE_V1_OFFSETS}[name]
+
+
+@pytest.mark.parametrize("table", ["std", "merge_v1"])
+@pytest.mark.parametrize("dtype,grid,kind,Cc", _spatial_cases(S2C_WRAP))
+def test_space_to_channel_layouts(dtype, grid, kind, Cc, table):
+    ops = _ops()
+    offs = _offsets(table)
+    B, D, H, W = grid
+    if kind == "wrap":
+        D, H, W = 2 * D, 2 * H, 2 * W
+    li, lo = _lay(kind)
+    x = rnd(B, D, H, W, Cc, dtype=dtype, seed=51)
+    xv = place_in(x, li)
+    out = place_out((B, _half(D), _half(H), _half(W), 8 * Cc), dtype, lo)
+    if kind == "wrap":
+        n = _nvec(dtype)
+        assert out.view.numel() // (n if Cc % n == 0 else 1) > CAP_ITEMS["ew"]
+    assert ops.space_to_channel(xv, offs, out=out.view) is out.view
+    assert_untouched(out, f"space_to_channel {kind}")
+    xp = F.pad(x, (0, 0, 0, W % 2, 0, H % 2, 0, D % 2))
+    want = torch.cat([xp[:, i::2, j::2, k::2, :] for (i, j, k) in offs], -1)
+    assert torch.equal(out.view, want)
+    if kind == "contig":
+        assert torch.equal(ops.space_to_channel(xv, offs), want)
+
+
+@pytest.mark.parametrize("table", ["std", "merge_v1"])
+@pytest.mark.parametrize("dtype,grid,kind,Cc", _spatial_cases(C2S_WRAP))
+def test_channel_to_space_layouts(dtype, grid, kind, Cc, table):
+    """the adjoint: a fine voxel receives the sum of the blocks that reference it (the v0.9 merge table references some twice, some never)"""
+    ops = _ops()
+    offs = _offsets(table)
+    B, D, H, W = grid
+    li, lo = _lay(kind)
+    g = rnd(B, _half(D), _half(H), _half(W), 8 * Cc, dtype=dtype, seed=61)
+    gv = place_in(g, li)
+    out = place_out((B, D, H, W, Cc), dtype, lo)
+    if kind == "wrap":
+        n = _nvec(dtype)
+        assert out.view.numel() // (n if Cc % n == 0 else 1) > CAP_ITEMS["ew"]
+    assert ops.channel_to_space(gv, offs, (B, D, H, W, Cc), out=out.view) is out.view
+    assert_untouched(out, f"channel_to_space {kind}")
+    want = torch.zeros(B, 2 * _half(D), 2 * _half(H), 2 * _half(W), Cc, dtype=torch.float64, device=DEV)
+    gd = g.double()
+    for j, (a, b, c) in enumerate(offs):
+        want[:, a::2, b::2, c::2] += gd[..., j * Cc:(j + 1) * Cc]
+    want = want[:, :D, :H, :W]
+    if table == "std":
+        assert torch.equal(out.view, want.to(dtype))          # one block per voxel: pure data movement
+    else:
+        assert_parity(out.view, want, TOL[dtype], f"channel_to_space {table} {kind}")
+
+
+# ----------------------------------------------------------------------------------------------------------------- layout transposes
+@pytest.mark.parametrize("dtype", DTYPES, ids=_name)
+@pytest.mark.parametrize("B,S,Cc,layout", [(2, 1, 1, "contig"), (1, 33, 31, "contig"), (2, 33, 33, "contig"), (1, 1, 33, "slice"), (2, 33, 1, "ldodd"), (1, 210, 48, "slice"),
+                                           (2, 210, 6, "off8"), (1, 32, 32, "contig"), (1, 65, 31, "ldodd")])
+def test_rows_to_ncdhw_and_back(dtype, B, S, Cc, layout):
+    """the 32 x 32 tile transposes of miseg_layout_ncdhw, both directions: partial tiles on either side (rows of 1 / 33, C of 1 / 31 / 33), strided rows"""
+    ops, L = _ops(), _L()
+    lib = L.load()
+    x = rnd(B, S, 1, 1, Cc, dtype=dtype, seed=71)
+    xv = place_in(x, layout)
+    y = ops.rows_to_ncdhw(xv)
+    assert y.dtype == torch.float32 and torch.equal(y, x.float().permute(0, 4, 1, 2, 3).contiguous())
+    g = rnd(B, Cc, S, 1, 1, seed=72)
+    assert torch.equal(ops.ncdhw_to_rows_exact(g, dtype), g.permute(0, 2, 3, 4, 1).contiguous().to(dtype))
+    # the same direction into a strided destination (the entry point takes the rows' leading dimension)
+    out = place_out((B, S, 1, 1, Cc), dtype, layout)
+    L.check(lib.miseg_layout_ncdhw(P(out.view), ops.rows(out.view)[0], P(g), B, Cc, S, ops._dt(out.view), 1, ops._stream()), "layout_ncdhw")
+    assert_untouched(out, "layout_ncdhw dir 1")
+    assert torch.equal(out.view, g.permute(0, 2, 3, 4, 1).to(dtype))
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=_name)
+@pytest.mark.parametrize("B,Cin,grid", [(2, 1, (5, 6, 7)), (1, 3, (1, 1, 3)), (1, 4, (3, 3, 3)), (1, 1, (130, 130, 130))])      # 2 197 000 voxels: the 8192-workgroup cap
+def test_ncdhw_to_rows_pads_to_one_vector(dtype, B, Cin, grid):
+    ops = _ops()
+    x = rnd(B, Cin, *grid, seed=81)
+    y = ops.ncdhw_to_rows(x, dtype)
+    n = _nvec(dtype)
+    want = torch.zeros(B, *grid, n, dtype=dtype, device=DEV)
+    want[..., :Cin] = x.permute(0, 2, 3, 4, 1).to(dtype)
+    assert torch.equal(y, want)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=_name)
+@pytest.mark.parametrize("R,Cc", [(1, 1), (1, 33), (33, 1), (31, 33), (33, 31), (32, 32), (37, 53), (1500, 1500)])      # 2 250 000 elements: ew_grid's cap (plain cast)
+@pytest.mark.parametrize("transpose", [False, True], ids=["plain", "transposed"])
+def test_cast_matrix_edges(dtype, R, Cc, transpose):
+    ops = _ops()
+    w = rnd(R, Cc, seed=91)
+    got = ops.cast_matrix(w, dtype, transpose=transpose)
+    want = (w.t().contiguous() if transpose else w).to(dtype)
+    assert got.shape == want.shape and torch.equal(got, want)
+
+
+@pytest.mark.parametrize("n,strides,accumulate", [((3, 5, 7), (35, 7, 1), False), ((7, 5, 3), (1, 7, 35), True), ((33, 1, 31), (31, 0, 1), False), ((8, 6, 4), (4, 32, 1), True),
+                                                  ((101, 102, 103), (103, 103 * 101, 1), False)])      # 1 061 106 elements: the 4096-workgroup cap
+def test_permute3_edges(n, strides, accumulate):
+    """dst[i0][i1][i2] (+)= src[i0 s0 + i1 s1 + i2 s2], fp32"""
+    ops = _ops()
+    numel = 1 + sum((k - 1) * s for k, s in zip(n, strides))
+    src = rnd(numel, seed=95)
+    buf = torch.full((n[0] * n[1] * n[2] + 16,), SENT, device=DEV)
+    dst = buf[8:8 + n[0] * n[1] * n[2]].view(*n)
+    base = rnd(*n, seed=96)
+    dst.copy_(base)
+    ops.permute3(src, dst, n, strides, accumulate=accumulate)
+    want = torch.as_strided(src, n, strides)
+    assert torch.equal(dst, base + want if accumulate else want)
+    assert bool((buf[:8] == SENT).all()) and bool((buf[-8:] == SENT).all())
+
+
+# ----------------------------------------------------------------------------------------------------------------- layer norm
+def _ln_cases():
+    cases = []
+    for Cc in (12, 48, 64, 65, 96, 100, 768):
+        for rows in (1, 3, 5, 777):
+            cases.append((rows, Cc, 0.0, True, "contig"))
+    cases += [(110592, 48, 0.0, True, "contig"), (110592, 12, 0.0, True, "contig")]
+    cases += [(777, Cc, 30.0, True, "contig") for Cc in (48, 65, 768)]                 # mean 30, std 1: the variance must be the two-pass one
+    cases += [(rows, Cc, 0.0, False, "contig") for rows in (5, 777) for Cc in (12, 100)]      # gamma = beta = None
+    cases += [(777, Cc, 0.0, True, lay) for Cc in (48, 65) for lay in ("slice", "off8", "ldodd")]      # x, dy, y and dx strided
+    return [pytest.param(*c, id=f"{c[0]}x{c[1]}-mean{int(c[2])}-{'affine' if c[3] else 'plain'}-{c[4]}") for c in cases]
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=_name)
+@pytest.mark.parametrize("rows,Cc,mean,affine,layout", _ln_cases())
+def test_layernorm_edges(dtype, rows, Cc, mean, affine, layout):
+    """one wave per row, four rows per workgroup; the parameter gradients are reduced in 256-row slabs and ADDED onto dgamma / dbeta"""
+    ops, L = _ops(), _L()
+    x = rnd(rows, Cc, dtype=dtype, seed=101, shift=mean)
+    dy = rnd(rows, Cc, dtype=dtype, seed=102)
+    gamma = rnd(Cc, seed=103) * 0.2 + 1 if affine else None
+    beta = rnd(Cc, seed=104) * 0.1 if affine else None
+    xv, dyv = place_in(x, layout), place_in(dy, layout)
+    y, dx = place_out((rows, Cc), dtype, layout), place_out((rows, Cc), dtype, layout)
+    m = torch.empty(rows, device=DEV)
+    rs = torch.empty(rows, device=DEV)
+    ops._call("miseg_layernorm_fwd", L.LayernormFwd(P(xv), ops.rows(xv)[0], P(y.view), ops.rows(y.view)[0], rows, Cc, ops._dt(xv), 1e-5, P(gamma), P(beta), P(m), P(rs)))
+    xf = x.double().requires_grad_(True)
+    gp = gamma.double().requires_grad_(True) if affine else None
+    bp = beta.double().requires_grad_(True) if affine else None
+    yr = F.layer_norm(xf, (Cc,), gp, bp, 1e-5)
+    what = f"layernorm {_name(dtype)} {rows}x{Cc} mean {mean} {layout}"
+    assert_untouched(y, what)
+    assert_parity(y.view, yr, TOL[dtype], what + ": y")
+    xd = x.double()
+    assert_parity(m, xd.mean(1), TOL[torch.float32], what + ": mean")
+    assert_parity(rs, (xd.var(1, unbiased=False) + 1e-5).rsqrt(), TOL[torch.float32], what + ": rstd")
+    yr.backward(dy.double())
+    dg0, db0 = rnd(Cc, seed=105), rnd(Cc, seed=106)
+    dg, db = (dg0.clone(), db0.clone()) if affine else (None, None)
+    ops._call("miseg_layernorm_bwd", L.LayernormBwd(P(dyv), ops.rows(dyv)[0], P(xv), ops.rows(xv)[0], P(dx.view), ops.rows(dx.view)[0], rows, Cc, ops._dt(xv), P(gamma),
+                                                      P(m), P(rs), P(dg), P(db)))
+    assert_untouched(dx, what)
+    assert_parity(dx.view, xf.grad, TOL[dtype], what + ": dx")
+    if affine:
+        assert_parity(dg, dg0.double() + gp.grad, TOL[dtype], what + ": dgamma (accumulated)")
+        assert_parity(db, db0.double() + bp.grad, TOL[dtype], what + ": dbeta (accumulated)")
+    if layout == "contig":
+        y2, m2, rs2 = ops.layernorm_fwd(xv, gamma, beta)
+        assert torch.equal(y2, y.view) and torch.equal(m2, m) and torch.equal(rs2, rs)
+
+
+# ----------------------------------------------------------------------------------------------------------------- ops.rows
+def test_rows_refuses_views_that_are_no_uniform_rows():
+    ops = _ops()
+    x = rnd(2, 4, 5, 6, 16, dtype=torch.bfloat16, seed=111)
+    out = torch.full((2, 4, 5, 6, 16), SENT, dtype=torch.bfloat16, device=DEV)
+    assert ops.rows(x) == (16, 2 * 4 * 5 * 6, 16) and ops.rows(x[..., 8:]) == (16, 240, 8) and ops.rows(x[1:]) == (16, 120, 16)
+    for bad in (x[:, 1:3], x[:, :, :, 2:5], x[:, :, 1:4, :, 8:], x[..., ::2], x.permute(0, 1, 2, 4, 3)):
+        with pytest.raises(ValueError):
+            ops.rows(bad)
+        with pytest.raises(ValueError):
+            ops.gelu_fwd(bad)
+        with pytest.raises(ValueError):
+            ops.add(bad, bad, out=out[tuple(slice(0, s) for s in bad.shape)])
+    with pytest.raises(ValueError):
+        ops.add(x, x, out=out[..., ::2])
+    with pytest.raises(ValueError):
+        ops.rows(x.reshape(-1))
+    torch.cuda.synchronize()
+    assert bool((out == SENT).all()), "nothing may run on a refused view"

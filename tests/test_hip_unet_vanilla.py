@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import compare_grads, rel_err, sample
+from parity import assert_parity
 from test_hip_predict import _host_reference, _mods as _predict_mods
 
 pytestmark = pytest.mark.gpu
@@ -124,10 +125,16 @@ def test_unet_vanilla_matches_the_reference(golden, tag, dtype):
     side = c["x"][2] // c["strides"][0]
     assert y.dtype == torch.float32 and list(y.shape) == [c["x"][0], 8, side, side, side]
     tol = TOL if dtype == torch.float32 else TOL_BF16
-    assert rel_err(sample(y), G.t(f"{tag}/logits_samples")) < tol
     whole = G.t(f"{tag}/logits") if G.has(f"{tag}/logits") else G.t(f"{tag}/logits_sub")
     got = y if G.has(f"{tag}/logits") else y[:, :, ::2, ::2, ::4]
-    assert rel_err(got, whole) < tol
+    if dtype == torch.float32:
+        assert_parity(sample(y), G.t(f"{tag}/logits_samples"), tol, "sampled logits")
+        assert_parity(got, whole, tol, "logits")
+    else:
+        # a whole bf16 network against recorded vectors is a module-level golden comparison and stays on its pooled bar: no torch composition
+        # of the same arithmetic is at hand to measure a per-element yardstick with (measured local error 6.5e-2 at pooled 1.1e-2)
+        assert rel_err(sample(y), G.t(f"{tag}/logits_samples")) < tol
+        assert rel_err(got, whole) < tol
     y.backward(det_input(4321, tuple(y.shape)).to(DEV))
     named = dict(m.named_parameters())
     if dtype == torch.float32:
