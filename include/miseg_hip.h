@@ -33,7 +33,7 @@ enum { MISEG_ACT_NONE = 0, MISEG_ACT_LEAKY = 1, MISEG_ACT_GELU = 2, MISEG_ACT_PR
 #define MISEG_MAX_STYLES 4
 
 /* bumped on EVERY change of a struct layout or prototype; bindings must refuse a library whose version differs from the header they mirror */
-#define MISEG_ABI_VERSION 14
+#define MISEG_ABI_VERSION 15
 int miseg_abi_version(void);
 const char* miseg_last_error(void);
 /* writes e.g. "gfx950" for the code objects embedded in the library */
@@ -284,6 +284,19 @@ int miseg_gemm_tn_reduce_batch(const miseg_tn_reduce_desc* descs_host, int n, mi
  * (unetr_block.py:51-59) without a permute pass */
 typedef struct { const void* A; int64_t lda; const void* B; int64_t ldb; float* C; int64_t ldc; int32_t M, N, K, zeroed, regroup, pad_; } miseg_gemm_tn_desc;
 int miseg_gemm_tn_group(const miseg_gemm_tn_desc* descs_host, int n, int dtype, miseg_stream_t stream);
+
+/* up to MISEG_TN_STREAM_GROUP TN products of the STREAMING path (bf16 operands, fp32 C, M and N multiples of 48, K >= 2048 rows, 16-byte
+ * aligned operands: what miseg_gemm_tn_fuses_colsum says yes to) in ONE launch (ABI 15): the tall weight gradients of one block of the
+ * backward pass.  The group as a whole gets the workgroup count a lone product takes for itself, shared between the problems by the bytes
+ * they stream (K may differ between them); a problem's plan tells its splits.  splits > 1: the launch leaves partial[split][M][N] fp32 in
+ * `partial` (plan.workspace_bytes; required) for miseg_gemm_tn_reduce_batch, which ADDS to C (and regroups); splits == 1: C (+)= the
+ * product (accumulate 0 stores) - unless `partial` is set all the same (M * N * 4 bytes): the one tile then goes there, for a sum that regroups.  colsum (optional): as miseg_gemm_params::tn_colsum.  `descs` / `plans` are HOST arrays. */
+#define MISEG_TN_STREAM_GROUP 8
+typedef struct { const void* A; int64_t lda; const void* B; int64_t ldb; float* C; int64_t ldc; float* partial; float* colsum; int32_t M, N, K, accumulate; } miseg_gemm_tn_stream_desc;
+typedef struct { int32_t wm, wn, gx, gy, splits, tps, block0, pad_; int64_t workspace_bytes; } miseg_gemm_tn_stream_plan;
+int miseg_gemm_tn_stream_group_plan(const miseg_gemm_tn_stream_desc* descs_host, int n, miseg_gemm_tn_stream_plan* plans_host);   /* host only: launches nothing */
+int miseg_gemm_tn_stream_group(const miseg_gemm_tn_stream_desc* descs_host, int n, miseg_stream_t stream);
+int miseg_gemm_tn_stream_group_target(void);      /* the workgroup count a whole group is planned for */
 
 /* fp32 re-layout: dst[i0][i1][i2] (+)= src[i0*s0 + i1*s1 + i2*s2]  (weight-gradient unpacking) */
 int miseg_permute3(const float* src, float* dst, int n0, int n1, int n2, int64_t s0, int64_t s1, int64_t s2, int accumulate,

@@ -862,16 +862,16 @@ __global__ void __launch_bounds__(256) gemm_tn_group_kernel(TnGroup g) {
 // token range; 64-token stages are double-buffered in LDS (one barrier per stage, the next stage's 16-byte chunks in
 // registers while the current one feeds the MFMAs through transposed LDS reads), few token splits so that the fp32
 // atomics of the epilogue stay a small fraction of the stream.
-__global__ void __launch_bounds__(256, 2) gemm_tn_stream_kernel(const bf16* __restrict__ A, int64_t lda, const bf16* __restrict__ B, int64_t ldb,
-                                                                float* __restrict__ C, int64_t ldc, int M, int N, int T, int wm, int wn, int tps, int mode,
-                                                                float* __restrict__ partial, float* __restrict__ colsum) {
+// (the body is shared by the lone launch and the grouped one below: bx, by, bz are the workgroup's coordinates inside ITS problem)
+__device__ __forceinline__ void gemm_tn_stream_body(const bf16* __restrict__ A, int64_t lda, const bf16* __restrict__ B, int64_t ldb, float* __restrict__ C, int64_t ldc,
+                                                    int M, int N, int T, int wm, int wn, int tps, int mode, float* __restrict__ partial, float* __restrict__ colsum,
+                                                    char* lds, int bx, int by, int bz) {
   constexpr int BK = 64, MAXC = 8;
-  extern __shared__ __attribute__((aligned(16))) char lds[];
   const int BM = wm * 48, BN = wn * 48, RA = BM * 2 + 16, RB = BN * 2 + 16;
   const int stage_bytes = BK * (RA + RB);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-  const int t0 = blockIdx.z * tps, t1 = min(T, t0 + tps);
+  const int m0 = bx * BM, n0 = by * BN;
+  const int t0 = bz * tps, t1 = min(T, t0 + tps);
   const int wmi = wave % wm, wni = wave / wm;
   const bool active = (m0 + wmi * 48 < M) && (n0 + wni * 48 < N);
   // per-thread copy slots (fixed across stages)
@@ -922,7 +922,7 @@ __global__ void __launch_bounds__(256, 2) gemm_tn_stream_kernel(const bf16* __re
   // Round 5: the column sums of A ride along (dW = dy^T x is called with A = dy: they are the bias gradient of the linear layer - until now
   // a separate pass over dy, 240 MB per step at the end of the backward pass - and the A fragments already in registers give them as one
   // more MFMA block against a fragment of ones).  One wave per row block (workgroup column 0 only); fp32 atomics into the bias-gradient slot.
-  const bool csum = colsum != nullptr && blockIdx.y == 0 && wni == 0 && active;
+  const bool csum = colsum != nullptr && by == 0 && wni == 0 && active;
   f32x4 cs[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) cs[j] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -970,7 +970,7 @@ __global__ void __launch_bounds__(256, 2) gemm_tn_stream_kernel(const bf16* __re
   if (active) {
     const int fi = lane & 15, fq = lane >> 4;
     if (partial) {   // partial[split][M][N]: 16-byte stores, summed by gemm_tn_partial_reduce_kernel
-      float* pp = partial + (int64_t)blockIdx.z * M * N;
+      float* pp = partial + (int64_t)bz * M * N;
 #pragma unroll
       for (int mt = 0; mt < 3; ++mt)
 #pragma unroll
@@ -984,6 +984,33 @@ __global__ void __launch_bounds__(256, 2) gemm_tn_stream_kernel(const bf16* __re
           store_out4<float>(C, ldc, m0 + wmi * 48 + mt * 16 + fi, n0 + wni * 48 + nt * 16 + fq * 4, M, N, acc[mt][nt], Epi{nullptr, MISEG_ACT_NONE, nullptr, 0, nullptr, 0, 0, nullptr}, mode);
     }
   }
+}
+
+__global__ void __launch_bounds__(256, 2) gemm_tn_stream_kernel(const bf16* __restrict__ A, int64_t lda, const bf16* __restrict__ B, int64_t ldb,
+                                                                float* __restrict__ C, int64_t ldc, int M, int N, int T, int wm, int wn, int tps, int mode,
+                                                                float* __restrict__ partial, float* __restrict__ colsum) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  gemm_tn_stream_body(A, lda, B, ldb, C, ldc, M, N, T, wm, wn, tps, mode, partial, colsum, lds, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+
+// grouped form: the tall products of ONE block of the backward pass (a Swin block's qkv / proj / fc1 / fc2, a decoder's shortcut and
+// transposed convolution) in one launch whose workgroups fill the chip TOGETHER: each product gets its share of the splits instead of
+// a chip-wide split of its own - longer token ranges per workgroup, fewer partial tiles for the batched sum, one launch.  Descriptors
+// travel in the kernel arguments; blockIdx.x -> (problem, bx, by, split) through block0 as in gemm_tn_group_kernel.
+struct TnStreamGroup {
+  struct P { const bf16* A; int64_t lda; const bf16* B; int64_t ldb; float* C; int64_t ldc; float* partial; float* colsum;
+             int M, N, T, wm, wn, tps, mode, gx, gy, block0; } p[MISEG_TN_STREAM_GROUP];
+  int n;
+};
+
+__global__ void __launch_bounds__(256, 2) gemm_tn_stream_group_kernel(TnStreamGroup g) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  int k = 0;
+  while (k + 1 < g.n && g.p[k + 1].block0 <= (int)blockIdx.x) ++k;
+  const TnStreamGroup::P& q = g.p[k];
+  const int local = blockIdx.x - q.block0;
+  const int bx = local % q.gx, by = (local / q.gx) % q.gy, bz = local / (q.gx * q.gy);
+  gemm_tn_stream_body(q.A, q.lda, q.B, q.ldb, q.C, q.ldc, q.M, q.N, q.T, q.wm, q.wn, q.tps, q.mode, q.partial, q.colsum, lds, bx, by, bz);
 }
 
 // C[m][n] (+)= sum over splits of partial[s][m][n]; one thread per 4 consecutive n and per group of TN_RG splits
@@ -1430,6 +1457,77 @@ extern "C" int miseg_gemm_tn_fuses_colsum(const miseg_gemm_params* p) {
 extern "C" int miseg_gemm_tn_splits(const miseg_gemm_params* p) {
   TnStreamPlan pl;
   return (p && tn_stream_plan(p, &pl)) ? pl.splits : 0;
+}
+
+// the workgroup target of a whole group: what a lone product aims at by itself (tn_stream_plan).  Step A/B on one box, parent 166.9 / 166.6
+// patches/s: 256 -> 168.9, 384 -> 169.5 / 168.8, 512 -> 169.2 - no difference beyond the run-to-run spread, the lone plan's figure stays
+static constexpr int TN_STREAM_GROUP_TARGET = 384;
+extern "C" int miseg_gemm_tn_stream_group_target(void) { return TN_STREAM_GROUP_TARGET; }
+
+static void tn_stream_desc_params(const miseg_gemm_tn_stream_desc& d, miseg_gemm_params* p) {
+  *p = miseg_gemm_params{};
+  p->A = d.A; p->lda = d.lda; p->B = d.B; p->ldb = d.ldb; p->C = d.C; p->ldc = d.ldc; p->M = d.M; p->N = d.N; p->K = d.K;
+  p->ta = p->tb = 1; p->dtype = MISEG_BF16; p->out_dtype = MISEG_F32;
+}
+
+// Host only.  Tile form and eligibility per problem are tn_stream_plan's; the group's workgroup target is shared between the problems
+// in proportion to the bytes they stream, T * (M + N), so that they end together (rounded DOWN to whole splits: the group stays within
+// the target unless a problem's tiles alone exceed its share - it then takes one split).
+extern "C" int miseg_gemm_tn_stream_group_plan(const miseg_gemm_tn_stream_desc* descs, int n, miseg_gemm_tn_stream_plan* plans) {
+  MISEG_REQUIRE(descs && plans && n > 0 && n <= MISEG_TN_STREAM_GROUP, MISEG_E_BADARG, "gemm_tn_stream_group_plan: 1..%d problems", MISEG_TN_STREAM_GROUP);
+  TnStreamPlan pl[MISEG_TN_STREAM_GROUP];
+  int64_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    MISEG_REQUIRE(descs[i].M > 0 && descs[i].N > 0 && descs[i].K > 0, MISEG_E_BADARG, "gemm_tn_stream_group_plan: problem %d: bad shape", i);
+    miseg_gemm_params p;
+    tn_stream_desc_params(descs[i], &p);
+    if (!tn_stream_plan(&p, &pl[i])) return set_error(MISEG_E_UNSUPPORTED, "gemm_tn_stream_group_plan: problem %d (M=%d N=%d K=%d) does not take the streaming path", i, descs[i].M, descs[i].N, descs[i].K);
+    total += (int64_t)descs[i].K * (descs[i].M + descs[i].N);
+  }
+  int blocks = 0;
+  for (int i = 0; i < n; ++i) {
+    const miseg_gemm_tn_stream_desc& d = descs[i];
+    const int tiles = pl[i].gx * pl[i].gy;
+    int splits = (int)(((int64_t)TN_STREAM_GROUP_TARGET * d.K * (d.M + d.N)) / (total * tiles));
+    const int max_splits = cdiv(d.K, 4 * 64);
+    if (splits > max_splits) splits = max_splits;
+    if (splits < 1) splits = 1;
+    const int tps = cdiv(cdiv(d.K, splits), 64) * 64;
+    splits = cdiv(d.K, tps);
+    miseg_gemm_tn_stream_plan& o = plans[i];
+    o.wm = pl[i].wm; o.wn = pl[i].wn; o.gx = pl[i].gx; o.gy = pl[i].gy; o.splits = splits; o.tps = tps; o.block0 = blocks; o.pad_ = 0;
+    o.workspace_bytes = splits > 1 ? (int64_t)splits * d.M * d.N * 4 : 0;
+    blocks += tiles * splits;
+  }
+  return MISEG_OK;
+}
+
+extern "C" int miseg_gemm_tn_stream_group(const miseg_gemm_tn_stream_desc* descs, int n, miseg_stream_t s_) {
+  miseg_gemm_tn_stream_plan plans[MISEG_TN_STREAM_GROUP];
+  const int rc = miseg_gemm_tn_stream_group_plan(descs, n, plans);
+  if (rc != MISEG_OK) return rc;
+  miseg::TnStreamGroup g;
+  g.n = n;
+  size_t lds = 0;
+  int blocks = 0;
+  for (int i = 0; i < n; ++i) {
+    const miseg_gemm_tn_stream_desc& d = descs[i];
+    const miseg_gemm_tn_stream_plan& pl = plans[i];
+    MISEG_REQUIRE(d.A && d.B && d.C, MISEG_E_BADARG, "gemm_tn_stream_group: problem %d: null pointer", i);
+    MISEG_REQUIRE(pl.splits == 1 || d.partial, MISEG_E_BADARG, "gemm_tn_stream_group: problem %d: %d splits need their partial tiles (miseg_gemm_tn_stream_group_plan)", i, pl.splits);
+    miseg::TnStreamGroup::P& q = g.p[i];
+    q.A = (const bf16*)d.A; q.lda = d.lda; q.B = (const bf16*)d.B; q.ldb = d.ldb; q.C = d.C; q.ldc = d.ldc;
+    q.partial = d.partial;      // (set for a single split too: a caller whose batched sum regroups the columns)
+    q.colsum = d.colsum;
+    q.M = d.M; q.N = d.N; q.T = d.K; q.wm = pl.wm; q.wn = pl.wn; q.tps = pl.tps; q.mode = d.accumulate ? 1 : 0; q.gx = pl.gx; q.gy = pl.gy; q.block0 = pl.block0;
+    const size_t need = (size_t)2 * 64 * (pl.wm * 48 * 2 + pl.wn * 48 * 2 + 32);
+    if (need > lds) lds = need;
+    blocks = pl.block0 + pl.gx * pl.gy * pl.splits;
+  }
+  hipFuncSetAttribute((const void*)miseg::gemm_tn_stream_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  miseg::gemm_tn_stream_group_kernel<<<blocks, 256, lds, (hipStream_t)s_>>>(g);
+  MISEG_LAUNCH_CHECK("gemm_tn_stream_group");
+  return MISEG_OK;
 }
 
 namespace miseg {

@@ -626,6 +626,7 @@ class _NormLinear(Function):
                 dxn, dstat = ops.gemm_nt(dy, wt), None
             dx = _norm_bwd_from(dxn, x, S, stat, dstat, styles_dev, gammas if affine else None, dgam, dbet, eps, _rv(gskip))
         dw, db = _wb_grads_into(pw, pb, dy, xn, ctx.needs_input_grad[8], ctx.needs_input_grad[9])
+        ops.tn_stream_close()      # the qkv projection is the last node of a Swin block's backward: the block's tall weight gradients go out as one launch
         return (dx, None, None, None, None, None, None, None, dw, db, *build())
 
 
@@ -1308,6 +1309,7 @@ class _UpCat(Function):
                 dwf = ops.gemm_tn(dy8, x)                                                 # [(j,co)][ci]
                 dw = torch.empty(weight.shape, dtype=torch.float32, device=x.device)
                 ops.permute3(dwf, dw, (Cin, Cout, 8), (1, Cin, Cout * Cin))
+        ops.tn_stream_close()      # the last node of a decoder block's backward: its shortcut and transposed-convolution weight gradients share one launch
         return dx, dskip, dw
 
 

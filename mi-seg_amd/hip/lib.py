@@ -20,7 +20,7 @@ class _S(C.Structure):
     pass
 
 
-ABI_VERSION = 14         # == MISEG_ABI_VERSION of include/miseg_hip.h; load() refuses a library that reports another
+ABI_VERSION = 15         # == MISEG_ABI_VERSION of include/miseg_hip.h; load() refuses a library that reports another
 C_NAMES = {}             # ctypes mirror -> name of the C struct it mirrors (tests/test_abi.py checks sizeof / offsetof of every field)
 
 
@@ -64,6 +64,11 @@ TnReduceDesc = _struct("TnReduceDesc", cname="miseg_tn_reduce_desc", fields=[("p
 ColsumDesc = _struct("ColsumDesc", cname="miseg_colsum_desc", fields=[("x", vp), ("ldx", i64), ("rows", i64), ("out", vp), ("C", i32), ("block0", i32)])
 GemmTnDesc = _struct("GemmTnDesc", cname="miseg_gemm_tn_desc", fields=[("A", vp), ("lda", i64), ("B", vp), ("ldb", i64), ("C", vp), ("ldc", i64), ("M", i32), ("N", i32), ("K", i32), ("zeroed", i32),
                                                                       ("regroup", i32), ("pad_", i32)])
+GemmTnStreamDesc = _struct("GemmTnStreamDesc", cname="miseg_gemm_tn_stream_desc", fields=[("A", vp), ("lda", i64), ("B", vp), ("ldb", i64), ("C", vp), ("ldc", i64), ("partial", vp),
+                                                                                  ("colsum", vp), ("M", i32), ("N", i32), ("K", i32), ("accumulate", i32)])
+GemmTnStreamPlan = _struct("GemmTnStreamPlan", cname="miseg_gemm_tn_stream_plan", fields=[("wm", i32), ("wn", i32), ("gx", i32), ("gy", i32), ("splits", i32), ("tps", i32), ("block0", i32),
+                                                                                  ("pad_", i32), ("workspace_bytes", i64)])
+TN_STREAM_GROUP_CAP = 8      # MISEG_TN_STREAM_GROUP
 Colsum = _struct("Colsum", cname="miseg_colsum_params", fields=[("x", vp), ("ldx", i64), ("rows", i64), ("C", i32), ("dtype", i32), ("out", vp), ("accumulate", i32)])
 Conv3 = _struct("Conv3", cname="miseg_conv3_params", fields=[("x", vp), ("ldx", i64), ("y", vp), ("ldy", i64), ("wpk", vp), ("B", i32), ("D", i32), ("H", i32),
                           ("W", i32), ("Cin", i32), ("Cout", i32), ("dtype", i32), ("workspace", vp), ("res", vp), ("ldres", i64), ("stat", vp), ("background", i32), ("defer_slabs", i32),
@@ -202,6 +207,9 @@ PROTOS = {
     "miseg_gemm_tn_fuses_colsum": (i32, [C.POINTER(Gemm)]),
     "miseg_gemm_tn_reduce_batch": (i32, [vp, i32, vp]),
     "miseg_gemm_tn_group": (i32, [vp, i32, i32, vp]),
+    "miseg_gemm_tn_stream_group_plan": (i32, [vp, i32, vp]),
+    "miseg_gemm_tn_stream_group": (i32, [vp, i32, vp]),
+    "miseg_gemm_tn_stream_group_target": (i32, []),
     "miseg_colsum_batch": (i32, [vp, i32, i32, vp]),
     "miseg_conv3_fwd_plan": (i32, [C.POINTER(Conv3), C.POINTER(Conv3Plan)]),
     "miseg_conv3_fwd": (i32, [C.POINTER(Conv3), vp]),

@@ -636,6 +636,16 @@ def gemm_tn(a, b, out=None, accumulate=False, split_k=0, regroup=0, colsum_out=N
         if colsum_out is not None:
             colsum(a, colsum_out, accumulate=True)
         return out
+    if q is not None and TN_STREAM_GROUP and split_k == 0:
+        # the streaming kernel: the product waits for the other tall products of its block and shares ONE launch with them (tn_stream_close)
+        cs = None
+        if colsum_out is not None:
+            if colsum_out.dtype == torch.float32:
+                cs = colsum_out
+            else:
+                colsum(a, colsum_out, accumulate=True)
+        _tn_stream_enqueue(q.lists(), (a, b, out, int(accumulate), int(regroup), cs))
+        return out
     if colsum_out is not None:
         if split_k == 0 and colsum_out.dtype == torch.float32 and lib.miseg_gemm_tn_fuses_colsum(C.byref(p)):
             p.tn_colsum = colsum_out.data_ptr()
@@ -651,6 +661,76 @@ def gemm_tn(a, b, out=None, accumulate=False, split_k=0, regroup=0, colsum_out=N
     assert not regroup or p.defer_reduce, "gemm_tn: regroup on a path without a deferred sum (ask gemm_tn_regroups first)"
     _call("miseg_gemm", p)
     return out
+
+
+TN_STREAM_GROUP = True           # False: every streaming TN product is a launch of its own where it is issued (the tests' reference path)
+TN_STREAM_GROUP_LAUNCHES = 0     # running count of grouped streaming launches (one per closed group)
+
+
+def tn_stream_group_launch(items, reduces):
+    """ONE launch for up to lib.TN_STREAM_GROUP_CAP streaming TN products on the current stream.  items: (a, b, out, accumulate, regroup,
+    colsum_out) as gemm_tn takes them (accumulate 0: out is overwritten); every product the plan splits - and every regrouped one - leaves its
+    partial tiles to the batched sum: one (ws, out, ldc, M, N, splits, regroup) entry is appended to `reduces` for each (_flush_tn_reduces)."""
+    global TN_STREAM_GROUP_LAUNCHES
+    lib = L.load()
+    n = len(items)
+    descs, plans = (L.GemmTnStreamDesc * n)(), (L.GemmTnStreamPlan * n)()
+    shapes = []
+    for j, (a, b, out, acc, regroup, cs) in enumerate(items):
+        lda, K, M = rows(a)
+        ldb, _, N = rows(b)
+        descs[j] = L.GemmTnStreamDesc(_ptr(a), lda, _ptr(b), ldb, _ptr(out), N, None, _ptr(cs), M, N, K, 1 if acc else 0)
+        shapes.append((M, N, K))
+    L.check(lib.miseg_gemm_tn_stream_group_plan(descs, n, plans), "gemm_tn_stream_group_plan")
+    for j, (a, b, out, acc, regroup, cs) in enumerate(items):
+        M, N, K = shapes[j]
+        if plans[j].splits > 1 or regroup:
+            ws = torch.empty(plans[j].splits * M * N, dtype=torch.float32, device=a.device)
+            descs[j].partial = ws.data_ptr()
+            if not acc:
+                fill32(out)          # the batched sum adds
+            reduces.append((ws, out, N, M, N, plans[j].splits, int(regroup)))
+    fl = sum(2.0 * M * N * K for M, N, K in shapes)
+    nb = sum(2.0 * K * (M + N) + 4.0 * M * N * plans[j].splits for j, (M, N, K) in enumerate(shapes))
+    with _ProfRegion("gemm_tn_stream_group", fl, nb):
+        L.check(lib.miseg_gemm_tn_stream_group(descs, n, _stream()), "gemm_tn_stream_group")
+    _stamp_launch("gemm_tn_stream_group")
+    TN_STREAM_GROUP_LAUNCHES += 1
+
+
+def _tn_stream_enqueue(lst, item):
+    cur = torch.cuda.current_stream()
+    if lst.tn_stream and lst.tn_stream_on != cur:      # a group never mixes products issued on different streams
+        _close_tn_stream(lst)
+    lst.tn_stream_on = cur
+    lst.tn_stream.append(item)
+    if len(lst.tn_stream) >= L.TN_STREAM_GROUP_CAP:
+        _close_tn_stream(lst)
+
+
+def _close_tn_stream(lst):
+    """plan and issue the open group of `lst` (a StepQueues or its side queue) on the stream its products were issued on"""
+    if lst is None or not lst.tn_stream:
+        return
+    items = list(lst.tn_stream)
+    lst.tn_stream.clear()
+    on, lst.tn_stream_on = lst.tn_stream_on, None
+    if on != torch.cuda.current_stream():
+        with torch.cuda.stream(on):
+            tn_stream_group_launch(items, lst.tn_reduce)
+    else:
+        tn_stream_group_launch(items, lst.tn_reduce)
+
+
+def _all_queues():
+    return list(QUEUES.values()) + ([DEFAULT_QUEUES] if DEFAULT_QUEUES is not None else [])
+
+
+def tn_stream_close():
+    """the backward pass leaves a block: its queued streaming weight-gradient products go out now, as one launch, where they are in the
+    chain - leaf work never piles into the tail and the queued operands live no longer than one block"""
+    for q in _all_queues():
+        _close_tn_stream(q.lists())
 
 
 def permute3(src, dst, n, strides, accumulate=False):
@@ -760,6 +840,9 @@ def join_branch(flush_deferred=True, queues=None, flush_main=False):
     stream) made the hipGraph executor run the WHOLE branch behind the main stream's segment, 146.5 -> 114.0 patches/s, and so did a third
     stream forked for that launch (147 -> 118)."""
     global _FLUSHING
+    for q in ([queues] if queues is not None else _all_queues()):      # an open group goes out on its own stream, in front of the sums of its partial tiles
+        _close_tn_stream(q)
+        _close_tn_stream(q.side)
     if flush_deferred:
         for q in ([queues] if queues is not None else list(QUEUES.values())):
             if q.branch_deferred:
@@ -824,11 +907,13 @@ def join_wgrad():
 class StepQueues:
     """launch-bound tails of ONE model's backward pass, queued by the host and issued as grouped launches at the end of it
     (runtime/arena.py::end_backward): bias-gradient column sums, the small weight-gradient GEMMs, the partial-tile sums of the
-    streaming ones, the conv weight gradients of the 48^3-and-smaller layers.  One instance per training arena, found through the
+    streaming ones, the conv weight gradients of the 48^3-and-smaller layers - and, block by block DURING the pass, the open group of
+    streaming weight-gradient GEMMs (tn_stream: one launch per block, tn_stream_close).  One instance per training arena, found through the
     storage of the gradient slot a kernel accumulates into - two models (two arenas) in one process do not share anything."""
 
     def __init__(self, side=True, writes=None):
         self.colsum, self.gemm_tn, self.tn_reduce, self.conv_wgrad = [], [], [], []
+        self.tn_stream, self.tn_stream_on = [], None      # the open group of streaming TN products (gemm_tn / tn_stream_close) and the stream they were issued on
         self.unzeroed = set()        # data_ptr of arena slots the step's fill left out (their weight-gradient kernel overwrites them whole: arena.begin_step);
                                      # conv3_wgrad zero-fills one first if the launch it is about to issue would read or only add to it
         self.inline_final = []       # arena slots whose ONLY write of the step happened inline, as a plain store (the tiny-volume conv weight gradients):
@@ -851,11 +936,13 @@ class StepQueues:
     def flush_small(self):
         """the queued GEMM weight gradients, partial-tile sums and column sums only (the grouped conv weight gradients keep waiting): what
         completes the small parameters of a range whose conv weights were written inline (tiny-volume layers), cheaply, mid-chain"""
+        _close_tn_stream(self)
         _flush_gemm_tn(self.gemm_tn, self.writes)
         _flush_tn_reduces(self.tn_reduce)
         _flush_colsums(self.colsum)
 
     def flush(self, side=True):
+        _close_tn_stream(self)
         _flush_conv_wgrads(self.conv_wgrad)
         _flush_gemm_tn(self.gemm_tn, self.writes)
         _flush_tn_reduces(self.tn_reduce)
@@ -1025,8 +1112,20 @@ def check_no_pending():
         n = sum(len(d) for d in _ALL_PENDING)
         for d in _ALL_PENDING:
             d.clear()
+    check_tn_stream_closed()
     if n:
         raise RuntimeError(f"{n} deferred data-gradient slab sum(s) were never consumed (conv3(..., dx_to_norm=True) in front of something that is no instance norm)")
+
+
+def check_tn_stream_closed(queues=None):
+    """no streaming weight-gradient product may still wait for its group's launch at the end of a pass (every flush closes the open group)"""
+    for q in ([queues] if queues is not None else _all_queues()):
+        n = len(q.tn_stream) + (len(q.side.tn_stream) if q.side is not None else 0)
+        if n:
+            q.tn_stream.clear()
+            if q.side is not None:
+                q.side.tn_stream.clear()
+            raise RuntimeError(f"{n} streaming weight-gradient product(s) were queued and never launched (tn_stream_close / flush)")
 
 
 FRESH = 256      # stand-in pointer of a buffer that is not allocated yet (fresh allocations are 256-byte aligned): the plans test pointers for NULL / alignment only

@@ -302,6 +302,7 @@ class ParamArena:
         ops.join_branch(queues=self.queues, flush_main=True)
         if self.queues is not None:
             self.queues.flush()
+            ops.check_tn_stream_closed(self.queues)
             # parameters whose gradient was complete when the main chain of the pass ended (see StepQueues.inline_final)
             ptrs = {t.data_ptr() for t in self.queues.inline_final}
             self.inline_final_params = [p for p, v in zip(self.params, self.views) if v.data_ptr() in ptrs]
