@@ -33,7 +33,7 @@ enum { MISEG_ACT_NONE = 0, MISEG_ACT_LEAKY = 1, MISEG_ACT_GELU = 2, MISEG_ACT_PR
 #define MISEG_MAX_STYLES 4
 
 /* bumped on EVERY change of a struct layout or prototype; bindings must refuse a library whose version differs from the header they mirror */
-#define MISEG_ABI_VERSION 15
+#define MISEG_ABI_VERSION 16
 int miseg_abi_version(void);
 const char* miseg_last_error(void);
 /* writes e.g. "gfx950" for the code objects embedded in the library */
@@ -679,6 +679,29 @@ typedef struct {
 } miseg_surface_distance_params;
 size_t miseg_surface_distance_workspace_bytes(int B, int C, int D, int H, int W);
 int miseg_surface_distance(const miseg_surface_distance_params* p, miseg_stream_t stream);
+
+/* The average surface distance above and / or the Hausdorff distance (MONAI 1.1.0 metrics/hausdorff_distance.py::compute_hausdorff_distance,
+ * parity unpinned) from ONE launch set: same edge sets, same one-way distance lists d(A -> B).  h(A -> B) is NaN for an empty list, inf for
+ * a list of infs (one edge set empty; numpy's percentile would give NaN there), else the maximum of the list
+ * (percentile <= 0) or numpy's "linear" percentile of it: v_lo + (v_hi - v_lo) (pos - lo) with pos = percentile / 100 (n - 1), lo = floor(pos),
+ * hi = min(lo + 1, n - 1) over the ascending list.  hd[b][c'] = h(P -> G) if `directed`, else max(h(P -> G), h(G -> P)).  The order statistics
+ * are taken on the exact integer squared distances with integer counters only: bit-reproducible, like the ASD.  At least one of asd / hd; the
+ * ASD written is the one miseg_surface_distance writes, bit for bit.  With hd the volume must hold fewer than 2^32 voxels (32-bit bin counts).
+ * Same limits otherwise (C 1..64, every side 1..4096, synchronises the stream, cannot be captured). */
+typedef struct {
+  uint32_t struct_size;
+  const float* logits; const int32_t* pred;
+  const void* label; int label_dtype;
+  int B, C, D, H, W;
+  int include_background, symmetric;   /* symmetric: of the ASD only */
+  void* workspace;                 /* miseg_surface_metrics_workspace_bytes(B, C, D, H, W) bytes, uninitialised */
+  double* asd;                     /* out fp64 [B][C'] or NULL */
+  double* hd;                      /* out fp64 [B][C'] or NULL */
+  double percentile;               /* of hd: (0, 100]; <= 0: the maximum; > 100 (or NaN): MISEG_E_BADARG */
+  int directed;                    /* of hd */
+} miseg_surface_metrics_params;
+size_t miseg_surface_metrics_workspace_bytes(int B, int C, int D, int H, int W);
+int miseg_surface_metrics(const miseg_surface_metrics_params* p, miseg_stream_t stream);
 
 /* One optimiser step for every parameter of a model in ONE launch (lightning_monai.py:255-278: AdamW / Adam / SGD-nesterov), over the flat
  * fp32 gradient arena the weight-gradient kernels accumulate into.  Descriptor i: parameter tensor `param` of n elements whose gradient, and

@@ -11,9 +11,19 @@
 //   4. surface_edt_d_gather_kernel: the same along D, fused with the gather: sqrt(d^2) summed in double at every edge voxel of the other set
 //   5. surface_finalize_kernel: fixed-order sum of the per-workgroup partials, inf / NaN rules, fp64 [B][C'] out
 // Squared distances are int32 and exact (every box side <= 4096: d^2 < 2^26 < SD_INF).
+// Hausdorff distance (MONAI 1.1.0 metrics/hausdorff_distance.py) from the same launch set: an exact order statistic of
+// the integer d^2 of every direction's list (sqrt is monotone), found by a two-level radix select, 2^26 = 8192 coarse x 8192 fine bins:
+//   4'. surface_edt_d_select_kernel: pass 4 that also leaves each edge voxel's d^2 in the H pass's dead input buffer and counts d^2 >> 13
+//       (LDS histogram, non-zero bins flushed with one integer atomic each into coarse[item][dir][8192])
+//   4a. surface_rank_kernel:   prefix scan of one coarse table: the coarse bins that hold ranks lo and hi, and the ranks inside them
+//   4b. surface_select_kernel: d^2 & 8191 of the edge voxels whose coarse bin is one of those (at most two), LDS histogram -> fine[item][dir][2][8192]
+//   5'. surface_finalize_hd_kernel: the two exact d^2 from the fine tables, sqrt in double, the percentile's interpolation, inf / NaN rules; the
+//       ASD by the same sums in the same order as pass 5
+// Integer counters and integer atomics only: no result depends on arrival order.
 #include "common.h"
 #include <limits.h>
 #include <math.h>
+#include <algorithm>
 #include <type_traits>
 #include <vector>
 
@@ -37,6 +47,17 @@ struct SdItem {
 };
 
 struct SdPartial { double sum; unsigned long long n; };
+
+constexpr int SD_SHIFT = 13;
+constexpr int SD_BINS = 1 << SD_SHIFT;   // coarse bins d^2 >> 13 and fine bins d^2 & 8191 (d^2 < 2^26)
+constexpr int SD_LBINS = 2048;           // coarse bins the D pass counts in LDS (d < 4096); the rare farther ones go to global memory one by one
+constexpr uint32_t SD_NOBIN = 0xffffffffu;
+
+// ranks lo / hi of one direction's list as (coarse bin, rank among the values of that bin); SD_NOBIN: the list is empty
+struct SdSel { uint32_t bin_lo, rank_lo, bin_hi, rank_hi; };
+
+// the Hausdorff tables behind the buffers of sd_layout, indexed by item over all groups (like the partials)
+struct SdHdLayout { size_t coarse, fine, sel, total; };
 
 struct SdLayout {
   size_t pcls, lcls, boxes, index, items, partials, edges, buf0, buf1, stack, total;
@@ -63,6 +84,17 @@ SdLayout sd_layout(int B, int C, int D, int H, int W) {
   L.stack = o;     o = align256(o + (size_t)2 * S * 4);
   L.total = o;
   return L;
+}
+
+SdHdLayout sd_hd_layout(const SdLayout& L, int B, int C) {
+  SdHdLayout Q;
+  const size_t items = (size_t)B * C;
+  size_t o = L.total;
+  Q.coarse = o;    o = align256(o + items * 2 * SD_BINS * 4);
+  Q.fine = o;      o = align256(o + items * 2 * 2 * SD_BINS * 4);
+  Q.sel = o;       o = align256(o + items * 2 * sizeof(SdSel));
+  Q.total = o;
+  return Q;
 }
 
 template <class L> __device__ __forceinline__ int sd_label_at(const L* lab, int64_t i) { return (int)lab[i]; }
@@ -294,50 +326,190 @@ __device__ __forceinline__ void block_sum_partial(double s, unsigned long long n
 }
 
 // pass 4: along D, one thread per (direction, h, w) line, fused with the gather: direction 0 sums sqrt(d^2) over E_P (distance to E_G),
-// direction 1 over E_G (distance to E_P); one partial per workgroup, in slot dblk0 + the workgroup's index within the box
-__global__ void __launch_bounds__(256) surface_edt_d_gather_kernel(const SdItem* __restrict__ items, int nitems, int64_t dblk_base, const int32_t* __restrict__ in,
-                                                                   const uint8_t* __restrict__ edges, uint32_t* __restrict__ stack, SdPartial* __restrict__ partials) {
-  const SdItem it = items[find_item(items, nitems, (int64_t)blockIdx.x + dblk_base, [](const SdItem& x) { return x.dblk0; })];
+// direction 1 over E_G (distance to E_P); one partial per workgroup, in slot dblk0 + the workgroup's index within the box.
+// HD: every edge voxel's d^2 is also left in dout (the layout of `in`) and counted by d^2 >> 13 (values without a seed fall into the last bin:
+// their lists are all inf and never selected from) in hist (LDS, SD_LBINS bins + the last one), then in coarse[item_base + item][dir][].
+template <bool HD>
+__device__ __forceinline__ void sd_d_pass(const SdItem* __restrict__ items, int nitems, int64_t dblk_base, const int32_t* __restrict__ in,
+                                          const uint8_t* __restrict__ edges, uint32_t* __restrict__ stack, SdPartial* __restrict__ partials, int item_base,
+                                          int32_t* __restrict__ dout, uint32_t* __restrict__ coarse, uint32_t* hist) {
+  const int k = find_item(items, nitems, (int64_t)blockIdx.x + dblk_base, [](const SdItem& x) { return x.dblk0; });
+  const SdItem it = items[k];
   const int64_t nl = (int64_t)it.nh * it.nw, vol = nl * it.nd;
   const int64_t nb = cdiv(nl, 256);
   const int64_t lb = (int64_t)blockIdx.x + dblk_base - it.dblk0;
   const int dir = lb >= nb;
   const int64_t l = (lb - dir * nb) * 256 + threadIdx.x;
+  uint32_t* ctab = nullptr;
+  if constexpr (HD) {
+    ctab = coarse + ((int64_t)(item_base + k) * 2 + dir) * SD_BINS;
+    for (int j = threadIdx.x; j <= SD_LBINS; j += 256) hist[j] = 0u;
+    __syncthreads();
+  }
   double sum = 0.0;
   unsigned long long cnt = 0;
   if (l < nl) {
     const uint8_t* eb = edges + it.off / 2 + l;
     const uint8_t bit = dir == 0 ? 1 : 2;
+    int32_t* o = nullptr;
+    if constexpr (HD) o = dout + it.off + dir * vol + l;
     envelope_line(in + it.off + dir * vol + l, nl, it.nd, stack + it.off + dir * vol + l, nl, [&](int u, int32_t v) {
       if (eb[(int64_t)u * nl] & bit) {
         sum += sqrt((double)v);
         ++cnt;
+        if constexpr (HD) {
+          o[(int64_t)u * nl] = v;
+          const int bin = min(v >> SD_SHIFT, SD_BINS - 1);
+          if (bin < SD_LBINS) atomicAdd(&hist[bin], 1u);
+          else if (bin == SD_BINS - 1) atomicAdd(&hist[SD_LBINS], 1u);       // no seed: a whole list at one address
+          else atomicAdd(&ctab[bin], 1u);
+        }
       }
     });
   }
-  block_sum_partial(sum, cnt, partials + it.dblk0 + lb);
+  block_sum_partial(sum, cnt, partials + it.dblk0 + lb);        // its barrier also closes the histogram
+  if constexpr (HD) {
+    for (int j = threadIdx.x; j <= SD_LBINS; j += 256) {
+      const uint32_t c = hist[j];
+      if (c) atomicAdd(&ctab[j < SD_LBINS ? j : SD_BINS - 1], c);
+    }
+  }
 }
 
-// pass 5: one thread per (b, c'); rules of MONAI's get_surface_distance / compute_average_surface_distance
-__global__ void surface_finalize_kernel(const int32_t* __restrict__ index, const SdItem* __restrict__ items, const SdPartial* __restrict__ partials, int B, int C,
-                                        int c0, int symmetric, double* __restrict__ asd) {
-  const int Cp = C - c0;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * Cp) return;
-  const int b = i / Cp, c = c0 + i % Cp;
-  const int k = index[b * C + c];
-  const double nan = __longlong_as_double(0x7ff8000000000000ll), inf = __longlong_as_double(0x7ff0000000000000ll);
-  if (k < 0) { asd[i] = nan; return; }            // no foreground: both edge sets empty
+__global__ void __launch_bounds__(256) surface_edt_d_gather_kernel(const SdItem* __restrict__ items, int nitems, int64_t dblk_base, const int32_t* __restrict__ in,
+                                                                   const uint8_t* __restrict__ edges, uint32_t* __restrict__ stack, SdPartial* __restrict__ partials) {
+  sd_d_pass<false>(items, nitems, dblk_base, in, edges, stack, partials, 0, nullptr, nullptr, nullptr);
+}
+
+__global__ void __launch_bounds__(256) surface_edt_d_select_kernel(const SdItem* __restrict__ items, int nitems, int64_t dblk_base, const int32_t* __restrict__ in,
+                                                                   const uint8_t* __restrict__ edges, uint32_t* __restrict__ stack, SdPartial* __restrict__ partials,
+                                                                   int item_base, int32_t* __restrict__ dout, uint32_t* __restrict__ coarse) {
+  __shared__ uint32_t hist[SD_LBINS + 1];
+  sd_d_pass<true>(items, nitems, dblk_base, in, edges, stack, partials, item_base, dout, coarse, hist);
+}
+
+// ranks of the percentile in an ascending list of n > 0 values (numpy's "linear" method; pct <= 0: the maximum): value = v_lo + (v_hi - v_lo) frac
+__device__ __forceinline__ void sd_ranks(double pct, unsigned long long n, unsigned long long& lo, unsigned long long& hi, double& frac) {
+  if (!(pct > 0.0)) { lo = hi = n - 1; frac = 0.0; return; }
+  const double pos = pct / 100.0 * (double)(n - 1);
+  lo = (unsigned long long)floor(pos);
+  if (lo > n - 1) lo = n - 1;
+  hi = lo + 1 < n ? lo + 1 : n - 1;
+  frac = pos - (double)lo;
+}
+
+// 256 threads over one table of SD_BINS counters: thread t owns bins [32 t, 32 t + 32).  sd_block_prefix: the count before and inside the
+// thread's bins, the total in sh[256] (sh: 257 words of LDS, free again on return).  sd_resolve: the one thread whose bins hold rank r
+// (r < total) writes the bin and r's rank inside it.
+struct SdPrefix { unsigned long long excl, sum; };
+
+__device__ __forceinline__ SdPrefix sd_block_prefix(const uint32_t* __restrict__ tab, unsigned long long* sh) {
+  const int t = threadIdx.x;
+  SdPrefix p;
+  p.sum = 0;
+  for (int j = 0; j < SD_BINS / 256; ++j) p.sum += tab[t * (SD_BINS / 256) + j];
+  sh[t] = p.sum;
+  __syncthreads();
+  p.excl = 0;
+  for (int j = 0; j < t; ++j) p.excl += sh[j];
+  if (t == 255) sh[256] = p.excl + p.sum;
+  __syncthreads();
+  return p;
+}
+
+__device__ __forceinline__ void sd_resolve(const uint32_t* __restrict__ tab, const SdPrefix& p, unsigned long long r, uint32_t* bin, uint32_t* rank) {
+  if (r < p.excl || r >= p.excl + p.sum) return;
+  unsigned long long acc = p.excl;
+  for (int j = 0; j < SD_BINS / 256; ++j) {
+    const int b = threadIdx.x * (SD_BINS / 256) + j;
+    const uint32_t c = tab[b];
+    if (r < acc + c) { *bin = (uint32_t)b; *rank = (uint32_t)(r - acc); return; }
+    acc += c;
+  }
+}
+
+// pass 4a: one workgroup per (item of the group, direction): where ranks lo and hi of the direction's list fall in its coarse table
+__global__ void __launch_bounds__(256) surface_rank_kernel(const uint32_t* __restrict__ coarse, int item_base, double pct, SdSel* __restrict__ sels) {
+  __shared__ unsigned long long sh[257];
+  __shared__ uint32_t res[4];
+  const int64_t slot = (int64_t)(item_base + blockIdx.x) * 2 + blockIdx.y;
+  const uint32_t* tab = coarse + slot * SD_BINS;
+  if (threadIdx.x == 0) { res[0] = SD_NOBIN; res[1] = 0u; res[2] = SD_NOBIN; res[3] = 0u; }
+  const SdPrefix p = sd_block_prefix(tab, sh);
+  const unsigned long long n = sh[256];
+  if (n > 0) {
+    unsigned long long lo, hi;
+    double frac;
+    sd_ranks(pct, n, lo, hi, frac);
+    sd_resolve(tab, p, lo, &res[0], &res[1]);
+    sd_resolve(tab, p, hi, &res[2], &res[3]);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) { SdSel s; s.bin_lo = res[0]; s.rank_lo = res[1]; s.bin_hi = res[2]; s.rank_hi = res[3]; sels[slot] = s; }
+}
+
+// pass 4b: workgroups (x, item of the group x direction, which of lo / hi) stride over the box: the low 13 bits of the edge voxels' d^2 whose
+// coarse bin is the selected one, counted in LDS, then in fine[item][dir][which][].  hi shares lo's table when both fall in one coarse bin.
+// The edge bytes are read 16 at a time from 16-byte aligned addresses (up to 15 bytes before and after the box are read and masked off: they
+// lie inside the workspace); d^2 is read at the edge voxels only.
+__global__ void __launch_bounds__(256) surface_select_kernel(const SdItem* __restrict__ items, int item_base, const SdSel* __restrict__ sels,
+                                                             const uint8_t* __restrict__ edges, const int32_t* __restrict__ d2, uint32_t* __restrict__ fine) {
+  __shared__ uint32_t hist[SD_BINS];
+  const int k = item_base + (blockIdx.y >> 1), dir = blockIdx.y & 1, which = blockIdx.z;
   const SdItem it = items[k];
+  const int64_t vol = (int64_t)it.nd * it.nh * it.nw;
+  const uint8_t* eb = edges + it.off / 2;
+  const int a = (int)((uintptr_t)eb & 15);
+  const int64_t nchunk = (vol + a + 15) >> 4;
+  if ((int64_t)blockIdx.x * 256 >= nchunk) return;
+  const SdSel sel = sels[(int64_t)k * 2 + dir];
+  const uint32_t target = which ? sel.bin_hi : sel.bin_lo;
+  if (target == SD_NOBIN || (which && sel.bin_hi == sel.bin_lo)) return;
+  for (int j = threadIdx.x; j < SD_BINS; j += 256) hist[j] = 0u;
+  __syncthreads();
+  const int32_t* v = d2 + it.off + dir * vol;
+  const uint32_t mask = (dir == 0 ? 1u : 2u) * 0x01010101u;
+  for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < nchunk; c += (int64_t)gridDim.x * 256) {
+    const int64_t i0 = c * 16 - a;
+    const uint4 q = *reinterpret_cast<const uint4*>(eb + i0);
+    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      uint32_t e = w[j] & mask;
+      while (e) {
+        const int64_t i = i0 + j * 4 + ((__ffs((int)e) - 1) >> 3);
+        e &= e - 1;
+        if (i >= 0 && i < vol) {
+          const int32_t x = v[i];
+          if ((uint32_t)min(x >> SD_SHIFT, SD_BINS - 1) == target) atomicAdd(&hist[x & (SD_BINS - 1)], 1u);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  uint32_t* ftab = fine + (((int64_t)k * 2 + dir) * 2 + which) * SD_BINS;
+  for (int j = threadIdx.x; j < SD_BINS; j += 256) {
+    const uint32_t c = hist[j];
+    if (c) atomicAdd(&ftab[j], c);
+  }
+}
+
+// the partials of one box in their fixed order: s[dir], n[dir] (n[0] = |E_P|, n[1] = |E_G|)
+__device__ __forceinline__ void sd_sum_partials(const SdItem& it, const SdPartial* __restrict__ partials, double* s, unsigned long long* n) {
   const int64_t nb = cdiv((int64_t)it.nh * it.nw, 256);
-  double s[2] = {0.0, 0.0};
-  unsigned long long n[2] = {0, 0};
+  s[0] = s[1] = 0.0;
+  n[0] = n[1] = 0;
   for (int dir = 0; dir < 2; ++dir)
     for (int64_t j = 0; j < nb; ++j) {
       const SdPartial p = partials[it.dblk0 + dir * nb + j];
       s[dir] += p.sum;
       n[dir] += p.n;
     }
+}
+
+// rules of MONAI's get_surface_distance / compute_average_surface_distance
+__device__ __forceinline__ double sd_asd_value(const double* s, const unsigned long long* n, int symmetric) {
+  const double nan = __longlong_as_double(0x7ff8000000000000ll), inf = __longlong_as_double(0x7ff0000000000000ll);
   const unsigned long long np = n[0], ng = n[1];   // |E_P|, |E_G|
   // d(P -> G): |E_P| infs if E_G is empty, else |E_G| infs if E_P is empty, else the distances
   unsigned long long tot = 0;
@@ -351,7 +523,79 @@ __global__ void surface_finalize_kernel(const int32_t* __restrict__ index, const
     else if (ng == 0) { tot += np; has_inf = true; }
     else { tot += ng; sum += s[1]; }
   }
-  asd[i] = tot == 0 ? nan : has_inf ? inf : sum / (double)tot;
+  return tot == 0 ? nan : has_inf ? inf : sum / (double)tot;
+}
+
+// pass 5: one thread per (b, c')
+__global__ void surface_finalize_kernel(const int32_t* __restrict__ index, const SdItem* __restrict__ items, const SdPartial* __restrict__ partials, int B, int C,
+                                        int c0, int symmetric, double* __restrict__ asd) {
+  const int Cp = C - c0;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * Cp) return;
+  const int b = i / Cp, c = c0 + i % Cp;
+  const int k = index[b * C + c];
+  if (k < 0) { asd[i] = __longlong_as_double(0x7ff8000000000000ll); return; }            // no foreground: both edge sets empty
+  const SdItem it = items[k];
+  double s[2];
+  unsigned long long n[2];
+  sd_sum_partials(it, partials, s, n);
+  asd[i] = sd_asd_value(s, n, symmetric);
+}
+
+// pass 5': one workgroup per (b, c'): the ASD as pass 5 (thread 0), and the Hausdorff distance from the fine tables.  h(A -> B): NaN for an
+// empty list, inf when one edge set is empty (every percentile: DESIGN.md section 7.5 rule 2), else the percentile of the list.
+__global__ void __launch_bounds__(256) surface_finalize_hd_kernel(const int32_t* __restrict__ index, const SdItem* __restrict__ items, const SdPartial* __restrict__ partials,
+                                                                  const SdSel* __restrict__ sels, const uint32_t* __restrict__ fine, int C, int c0, int symmetric,
+                                                                  int directed, double pct, double* __restrict__ asd, double* __restrict__ hd) {
+  __shared__ unsigned long long sh[257];
+  __shared__ unsigned long long sn[2];
+  __shared__ uint32_t res[4];
+  const double nan = __longlong_as_double(0x7ff8000000000000ll), inf = __longlong_as_double(0x7ff0000000000000ll);
+  const int Cp = C - c0;
+  const int i = blockIdx.x;
+  const int b = i / Cp, c = c0 + i % Cp;
+  const int k = index[b * C + c];
+  if (k < 0) {                                     // no foreground: both edge sets empty
+    if (threadIdx.x == 0) { if (asd) asd[i] = nan; hd[i] = nan; }
+    return;
+  }
+  if (threadIdx.x == 0) {
+    const SdItem it = items[k];
+    double s[2];
+    unsigned long long n[2];
+    sd_sum_partials(it, partials, s, n);
+    if (asd) asd[i] = sd_asd_value(s, n, symmetric);
+    sn[0] = n[0]; sn[1] = n[1];
+  }
+  __syncthreads();
+  if (sn[0] == 0 || sn[1] == 0) {                  // both directions' lists are empty together, or all inf together
+    if (threadIdx.x == 0) hd[i] = (sn[0] == 0 && sn[1] == 0) ? nan : inf;
+    return;
+  }
+  double h[2] = {0.0, 0.0};
+  for (int dir = 0; dir < (directed ? 1 : 2); ++dir) {
+    const SdSel sel = sels[(int64_t)k * 2 + dir];
+    const uint32_t* tlo = fine + ((int64_t)k * 2 + dir) * 2 * SD_BINS;
+    uint32_t unused;
+    SdPrefix p = sd_block_prefix(tlo, sh);
+    sd_resolve(tlo, p, sel.rank_lo, &res[0], &unused);
+    if (sel.bin_hi == sel.bin_lo) {
+      sd_resolve(tlo, p, sel.rank_hi, &res[1], &unused);
+    } else {
+      p = sd_block_prefix(tlo + SD_BINS, sh);
+      sd_resolve(tlo + SD_BINS, p, sel.rank_hi, &res[1], &unused);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long lo, hi;
+      double frac;
+      sd_ranks(pct, sn[dir], lo, hi, frac);
+      const double vlo = sqrt((double)((sel.bin_lo << SD_SHIFT) | res[0])), vhi = sqrt((double)((sel.bin_hi << SD_SHIFT) | res[1]));
+      h[dir] = __dadd_rn(vlo, __dmul_rn(vhi - vlo, frac));          // two roundings, as the CPU restatement: no fused multiply-add
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) hd[i] = directed ? h[0] : fmax(h[0], h[1]);
 }
 
 template <class F> int sd_dispatch_label(int dt, F&& f) {
@@ -375,18 +619,28 @@ extern "C" size_t miseg_surface_distance_workspace_bytes(int B, int C, int D, in
   return sd_layout(B, C, D, H, W).total;
 }
 
-extern "C" int miseg_surface_distance(const miseg_surface_distance_params* p, miseg_stream_t s_) {
-  hipStream_t s = (hipStream_t)s_;
-  MISEG_REQUIRE(p && p->struct_size == sizeof(miseg_surface_distance_params), MISEG_E_BADARG, "surface_distance: struct_size %u != %zu",
-                p ? p->struct_size : 0u, sizeof(miseg_surface_distance_params));
-  MISEG_REQUIRE((p->logits != nullptr) != (p->pred != nullptr), MISEG_E_BADARG, "surface_distance: exactly one of logits / pred");
-  MISEG_REQUIRE(p->label && p->workspace && p->asd, MISEG_E_BADARG, "surface_distance: null pointer");
-  MISEG_REQUIRE(p->B > 0 && p->C >= 1 && p->C <= SD_MAXC, MISEG_E_UNSUPPORTED, "surface_distance: B %d, C %d (1..%d)", p->B, p->C, SD_MAXC);
+extern "C" size_t miseg_surface_metrics_workspace_bytes(int B, int C, int D, int H, int W) {
+  if (B <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
+  return sd_hd_layout(sd_layout(B, C, D, H, W), B, C).total;
+}
+
+namespace miseg {
+namespace {
+
+// both entry points: the ASD (p.asd), the Hausdorff distance (p.hd), or both from one launch set; `who` names the entry point in messages
+int surface_run(const miseg_surface_metrics_params& q, const char* who, hipStream_t s) {
+  const miseg_surface_metrics_params* p = &q;
+  MISEG_REQUIRE((p->logits != nullptr) != (p->pred != nullptr), MISEG_E_BADARG, "%s: exactly one of logits / pred", who);
+  MISEG_REQUIRE(p->label && p->workspace && (p->asd || p->hd), MISEG_E_BADARG, "%s: null pointer", who);
+  MISEG_REQUIRE(!p->hd || p->percentile <= 100.0, MISEG_E_BADARG, "%s: percentile %g (at most 100; <= 0: the maximum)", who, p->percentile);
+  MISEG_REQUIRE(p->B > 0 && p->C >= 1 && p->C <= SD_MAXC, MISEG_E_UNSUPPORTED, "%s: B %d, C %d (1..%d)", who, p->B, p->C, SD_MAXC);
   MISEG_REQUIRE(p->D > 0 && p->H > 0 && p->W > 0 && p->D <= SD_MAXDIM && p->H <= SD_MAXDIM && p->W <= SD_MAXDIM, MISEG_E_UNSUPPORTED,
-                "surface_distance: volume %d x %d x %d (a 3-D volume, every side 1..%d)", p->D, p->H, p->W, SD_MAXDIM);
+                "%s: volume %d x %d x %d (a 3-D volume, every side 1..%d)", who, p->D, p->H, p->W, SD_MAXDIM);
+  MISEG_REQUIRE(!p->hd || (int64_t)p->D * p->H * p->W < ((int64_t)1 << 32), MISEG_E_UNSUPPORTED, "%s: the Hausdorff distance counts in 32 bits: fewer than 2^32 voxels",
+                who);
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   MISEG_REQUIRE(hipStreamIsCapturing(s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone, MISEG_E_UNSUPPORTED,
-                "surface_distance: reads the class boxes back to the host, cannot be captured");
+                "%s: reads the class boxes back to the host, cannot be captured", who);
   const int B = p->B, C = p->C, c0 = p->include_background ? 0 : 1, Cp = C - c0;
   if (Cp == 0) return MISEG_OK;
   const int64_t S = (int64_t)p->D * p->H * p->W;
@@ -402,9 +656,13 @@ extern "C" int miseg_surface_distance(const miseg_surface_distance_params* p, mi
   int32_t* buf0 = (int32_t*)(ws + L.buf0);
   int32_t* buf1 = (int32_t*)(ws + L.buf1);
   uint32_t* stack = (uint32_t*)(ws + L.stack);
+  const SdHdLayout Q = sd_hd_layout(L, B, C);        // read only with hd: miseg_surface_distance's workspace ends at L.total
+  uint32_t* coarse = (uint32_t*)(ws + Q.coarse);
+  uint32_t* fine = (uint32_t*)(ws + Q.fine);
+  SdSel* sels = (SdSel*)(ws + Q.sel);
 
   // 1. class maps + boxes
-  if (fill_words_async(boxes, 0x7fffffffu, (size_t)B * C * 6, s) != hipSuccess) return set_error(MISEG_E_LAUNCH, "surface_distance: fill");
+  if (fill_words_async(boxes, 0x7fffffffu, (size_t)B * C * 6, s) != hipSuccess) return set_error(MISEG_E_LAUNCH, "%s: fill", who);
   const int rc = sd_dispatch_label(p->label_dtype, [&](auto* tag) -> int {
     typedef typename std::remove_const<typename std::remove_pointer<decltype(tag)>::type>::type LT;
     int gx = cdiv(S, 256 * 8);
@@ -421,7 +679,7 @@ extern "C" int miseg_surface_distance(const miseg_surface_distance_params* p, mi
   // 2. the boxes decide the work: read them back (B x C x 24 bytes), pack the boxes into groups that fit the buffers
   std::vector<int> hbox((size_t)B * C * 6);
   if (hipMemcpyAsync(hbox.data(), boxes, hbox.size() * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-    return set_error(MISEG_E_LAUNCH, "surface_distance: box read-back");
+    return set_error(MISEG_E_LAUNCH, "%s: box read-back", who);
   std::vector<int32_t> hindex((size_t)B * C, -1);
   std::vector<SdItem> hitems;
   std::vector<int> group_first;                  // index of the first item of every group
@@ -447,12 +705,16 @@ extern "C" int miseg_surface_distance(const miseg_surface_distance_params* p, mi
       hitems.push_back(it);
     }
   if (hipMemcpyAsync(index, hindex.data(), hindex.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess)
-    return set_error(MISEG_E_LAUNCH, "surface_distance: index upload");
+    return set_error(MISEG_E_LAUNCH, "%s: index upload", who);
   if (!hitems.empty() && hipMemcpyAsync(items, hitems.data(), hitems.size() * sizeof(SdItem), hipMemcpyHostToDevice, s) != hipSuccess)
-    return set_error(MISEG_E_LAUNCH, "surface_distance: item upload");
+    return set_error(MISEG_E_LAUNCH, "%s: item upload", who);
 
-  // 3. per group: W pass, H pass, D pass + gather (the groups reuse the buffers; stream order serialises them)
+  // 3. per group: W pass, H pass, D pass + gather (the groups reuse the buffers; stream order serialises them).  With hd the group's select
+  // passes follow at once: they read the d^2 the D pass left in buf0, which the next group's W pass overwrites.
   group_first.push_back((int)hitems.size());
+  if (p->hd && !hitems.empty() &&
+      (fill_words_async(coarse, 0u, hitems.size() * 2 * SD_BINS, s) != hipSuccess || fill_words_async(fine, 0u, hitems.size() * 4 * SD_BINS, s) != hipSuccess))
+    return set_error(MISEG_E_LAUNCH, "%s: table fill", who);
   for (size_t g = 0; g + 1 < group_first.size(); ++g) {
     const int f = group_first[g], n = group_first[g + 1] - f;
     const SdItem& last = hitems[f + n - 1];
@@ -463,12 +725,53 @@ extern "C" int miseg_surface_distance(const miseg_surface_distance_params* p, mi
     MISEG_LAUNCH_CHECK("surface_edt_w");
     surface_edt_h_kernel<<<(unsigned)hblocks, 256, 0, s>>>(items + f, n, buf0, buf1, stack);
     MISEG_LAUNCH_CHECK("surface_edt_h");
-    surface_edt_d_gather_kernel<<<(unsigned)dblocks, 256, 0, s>>>(items + f, n, hitems[f].dblk0, buf1, edges, stack, partials);
-    MISEG_LAUNCH_CHECK("surface_edt_d_gather");
+    if (!p->hd) {
+      surface_edt_d_gather_kernel<<<(unsigned)dblocks, 256, 0, s>>>(items + f, n, hitems[f].dblk0, buf1, edges, stack, partials);
+      MISEG_LAUNCH_CHECK("surface_edt_d_gather");
+      continue;
+    }
+    surface_edt_d_select_kernel<<<(unsigned)dblocks, 256, 0, s>>>(items + f, n, hitems[f].dblk0, buf1, edges, stack, partials, f, buf0, coarse);
+    MISEG_LAUNCH_CHECK("surface_edt_d_select");
+    surface_rank_kernel<<<dim3(n, 2), 256, 0, s>>>(coarse, f, p->percentile, sels);
+    MISEG_LAUNCH_CHECK("surface_rank");
+    int64_t maxvol = 0;
+    for (int i = f; i < f + n; ++i) maxvol = std::max(maxvol, (int64_t)hitems[i].nd * hitems[i].nh * hitems[i].nw);
+    const int64_t sx = std::min<int64_t>(cdiv(maxvol, 256 * 16 * 8), 512);  // >= 8 chunks of 16 voxels per thread before a workgroup pays for its table
+    for (int i = 0; i < n; i += 16384) {                                     // grid.y holds 65535
+      surface_select_kernel<<<dim3((unsigned)sx, 2 * std::min(n - i, 16384), 2), 256, 0, s>>>(items, f + i, sels, edges, buf0, fine);
+      MISEG_LAUNCH_CHECK("surface_select");
+    }
   }
-  surface_finalize_kernel<<<cdiv((long)B * Cp, 64), 64, 0, s>>>(index, items, partials, B, C, c0, p->symmetric, p->asd);
-  MISEG_LAUNCH_CHECK("surface_finalize");
+  if (p->hd) {
+    surface_finalize_hd_kernel<<<B * Cp, 256, 0, s>>>(index, items, partials, sels, fine, C, c0, p->symmetric, p->directed, p->percentile, p->asd, p->hd);
+    MISEG_LAUNCH_CHECK("surface_finalize_hd");
+  } else {
+    surface_finalize_kernel<<<cdiv((long)B * Cp, 64), 64, 0, s>>>(index, items, partials, B, C, c0, p->symmetric, p->asd);
+    MISEG_LAUNCH_CHECK("surface_finalize");
+  }
   // the host vectors above are the sources of the two uploads: they must outlive them
-  if (hipStreamSynchronize(s) != hipSuccess) return set_error(MISEG_E_LAUNCH, "surface_distance: synchronize");
+  if (hipStreamSynchronize(s) != hipSuccess) return set_error(MISEG_E_LAUNCH, "%s: synchronize", who);
   return MISEG_OK;
+}
+
+}  // namespace
+}  // namespace miseg
+
+extern "C" int miseg_surface_distance(const miseg_surface_distance_params* p, miseg_stream_t s_) {
+  MISEG_REQUIRE(p && p->struct_size == sizeof(miseg_surface_distance_params), MISEG_E_BADARG, "surface_distance: struct_size %u != %zu",
+                p ? p->struct_size : 0u, sizeof(miseg_surface_distance_params));
+  MISEG_REQUIRE(p->asd, MISEG_E_BADARG, "surface_distance: null pointer");
+  miseg_surface_metrics_params q = {};
+  q.struct_size = sizeof(q);
+  q.logits = p->logits; q.pred = p->pred; q.label = p->label; q.label_dtype = p->label_dtype;
+  q.B = p->B; q.C = p->C; q.D = p->D; q.H = p->H; q.W = p->W;
+  q.include_background = p->include_background; q.symmetric = p->symmetric;
+  q.workspace = p->workspace; q.asd = p->asd;          // hd stays NULL: the launch set of the ASD alone
+  return surface_run(q, "surface_distance", (hipStream_t)s_);
+}
+
+extern "C" int miseg_surface_metrics(const miseg_surface_metrics_params* p, miseg_stream_t s_) {
+  MISEG_REQUIRE(p && p->struct_size == sizeof(miseg_surface_metrics_params), MISEG_E_BADARG, "surface_metrics: struct_size %u != %zu",
+                p ? p->struct_size : 0u, sizeof(miseg_surface_metrics_params));
+  return surface_run(*p, "surface_metrics", (hipStream_t)s_);
 }

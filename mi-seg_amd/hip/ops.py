@@ -1709,31 +1709,37 @@ def dice_metric(logits, label, gdice=None):
     return dice, score
 
 
-def surface_distance(label, logits=None, pred=None, num_classes=None, include_background=True, symmetric=True):
-    """fp64 [B, C'] symmetric (or one-way) average surface distance per class after argmax of fp32 logits [B, C, D, H, W], or of an integer
-    class map pred [B, (1,) D, H, W] with num_classes classes (miseg_surface_distance; C' = C - (0 if include_background else 1)).
-    Synchronises the stream: the kernel reads the per-class boxes back to size its passes."""
+def _surface_args(who, label, logits, pred, num_classes):
+    """the checked arguments both surface entry points share: (logits, pred as an int32 class map, label, label dtype code, B, C, D, H, W, device)"""
     if (logits is None) == (pred is None):
-        raise ValueError("surface_distance: exactly one of logits / pred")
+        raise ValueError(f"{who}: exactly one of logits / pred")
     if logits is not None:
         if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.dim() != 5:
-            raise ValueError("surface_distance: logits must be contiguous float32 [B, C, D, H, W]")
+            raise ValueError(f"{who}: logits must be contiguous float32 [B, C, D, H, W]")
         B, Cc, D, H, W = logits.shape
         dev = logits.device
     else:
         if num_classes is None:
-            raise ValueError("surface_distance: a class map needs num_classes")
+            raise ValueError(f"{who}: a class map needs num_classes")
         B, Cc = pred.shape[0], int(num_classes)
         if pred.dim() == 5 and pred.shape[1] == 1:
             pred = pred[:, 0]
         if pred.dim() != 4:
-            raise ValueError("surface_distance: pred must be a class map [B, (1,) D, H, W]")
+            raise ValueError(f"{who}: pred must be a class map [B, (1,) D, H, W]")
         D, H, W = pred.shape[1:]
         pred = pred.to(torch.int32).contiguous()
         dev = pred.device
     if label.numel() != B * D * H * W:
-        raise ValueError("surface_distance: label does not match the prediction")
+        raise ValueError(f"{who}: label does not match the prediction")
     lab, ldt = _label(label.to(dev))
+    return logits, pred, lab, ldt, B, Cc, D, H, W, dev
+
+
+def surface_distance(label, logits=None, pred=None, num_classes=None, include_background=True, symmetric=True):
+    """fp64 [B, C'] symmetric (or one-way) average surface distance per class after argmax of fp32 logits [B, C, D, H, W], or of an integer
+    class map pred [B, (1,) D, H, W] with num_classes classes (miseg_surface_distance; C' = C - (0 if include_background else 1)).
+    Synchronises the stream: the kernel reads the per-class boxes back to size its passes."""
+    logits, pred, lab, ldt, B, Cc, D, H, W, dev = _surface_args("surface_distance", label, logits, pred, num_classes)
     cp = Cc - (0 if include_background else 1)
     asd = torch.empty(B, max(cp, 0), dtype=torch.float64, device=dev)
     nbytes = L.load().miseg_surface_distance_workspace_bytes(B, Cc, D, H, W)
@@ -1741,6 +1747,28 @@ def surface_distance(label, logits=None, pred=None, num_classes=None, include_ba
     _call("miseg_surface_distance", L.SurfaceDistance(C.sizeof(L.SurfaceDistance), _ptr(logits), _ptr(pred), _ptr(lab), ldt, B, Cc, D, H, W,
                                                       int(bool(include_background)), int(bool(symmetric)), _ptr(ws), _ptr(asd)))
     return asd
+
+
+def surface_metrics(label, logits=None, pred=None, num_classes=None, include_background=True, symmetric=True, percentile=None, directed=False,
+                    want=("asd", "hd")):
+    """the average surface distance of surface_distance (`symmetric`) and / or the Hausdorff distance (`percentile`: None or 0 for the maximum,
+    else in (0, 100]; `directed`: pred -> label only) per class, from ONE launch set (miseg_surface_metrics): a tuple of the fp64 [B, C']
+    tensors named in `want`, in that order.  Synchronises the stream like surface_distance."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("asd", "hd") for w in want) or len(set(want)) != len(want):
+        raise ValueError(f"surface_metrics: want {want!r} (some of 'asd', 'hd')")
+    pct = 0.0 if percentile is None else float(percentile)
+    if not 0.0 <= pct <= 100.0:
+        raise ValueError(f"surface_metrics: percentile should be a value between 0 and 100, got {percentile}.")
+    logits, pred, lab, ldt, B, Cc, D, H, W, dev = _surface_args("surface_metrics", label, logits, pred, num_classes)
+    cp = Cc - (0 if include_background else 1)
+    out = {w: torch.empty(B, max(cp, 0), dtype=torch.float64, device=dev) for w in want}
+    nbytes = L.load().miseg_surface_metrics_workspace_bytes(B, Cc, D, H, W)
+    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    _call("miseg_surface_metrics", L.SurfaceMetrics(C.sizeof(L.SurfaceMetrics), _ptr(logits), _ptr(pred), _ptr(lab), ldt, B, Cc, D, H, W,
+                                                    int(bool(include_background)), int(bool(symmetric)), _ptr(ws), _ptr(out.get("asd")), _ptr(out.get("hd")),
+                                                    pct, int(bool(directed))))
+    return tuple(out[w] for w in want)
 
 
 _EXPORT_DTYPES = {torch.uint8: 1, torch.uint16: 2, torch.uint32: 4}

@@ -1,15 +1,17 @@
-"""Test-set evaluation: Dice and average surface distance per class, per modality and over the whole set (reference test.py:17-123).
+"""Test-set evaluation: Dice, average surface distance and (optionally) Hausdorff distance per class, per modality and over the whole set
+(reference test.py:17-123).
 
 With float32 logits on a HIP device, this module's AsDiscrete post-transforms, DiceMetric and SurfaceDistanceMetric, the batch takes the fused
 path (dice_from_logits + surface_distance_from_logits: no one-hot volume is built); anything else runs the reference's decollate / post-transform
 / metric chain.  `additional_metrics` (reference utils/trainer.py:145-149,246-250): a GeneralizedDiceScore rides on the fused path, fed from the
 same miseg_dice_metric call as the Dice; any other metric object sends the batch down the unfused chain.  The checkpoint loading and MONAI's
-get_loaders of the reference's main() stay with the caller."""
+get_loaders of the reference's main() stay with the caller.  A HausdorffDistanceMetric (`hausdorff_distance`, DESIGN.md
+section 7.5) rides on the fused path too: its values and the surface distance's come out of ONE surface_metrics_from_logits call per batch."""
 import torch
 import torch.nn.functional as F
 
-from .metrics import (Cumulative, DiceMetric, GeneralizedDiceScore, SurfaceDistanceMetric, dice_from_logits, generalized_dice_from_logits,
-                      surface_distance_from_logits)
+from .metrics import (Cumulative, DiceMetric, GeneralizedDiceScore, HausdorffDistanceMetric, SurfaceDistanceMetric, dice_from_logits,
+                      generalized_dice_from_logits, surface_distance_from_logits, surface_metrics_from_logits)
 
 
 class AsDiscrete:
@@ -30,14 +32,15 @@ def decollate_batch(t):
     return list(t.unbind(0))
 
 
-def _fused(output, post_label, post_pred, acc_func, surface_distance, additional_metrics=None):
+def _fused(output, post_label, post_pred, acc_func, surface_distance, additional_metrics=None, hausdorff_distance=None):
     """the batch can skip the one-hot volumes: the post-transforms and metrics are the ones this module knows the semantics of"""
     C = output.shape[1]
     return (output.is_cuda and output.dtype == torch.float32 and output.dim() == 5 and C <= 64
             and isinstance(post_pred, AsDiscrete) and post_pred.argmax and post_pred.to_onehot == C
             and isinstance(post_label, AsDiscrete) and not post_label.argmax and post_label.to_onehot == C
             and type(acc_func) is DiceMetric and (surface_distance is None or type(surface_distance) is SurfaceDistanceMetric)
-            and all(type(m) is GeneralizedDiceScore for m in additional_metrics or ()))
+            and all(type(m) is GeneralizedDiceScore for m in additional_metrics or ())
+            and (hausdorff_distance is None or type(hausdorff_distance) is HausdorffDistanceMetric))
 
 
 def compute_metric_modality(metric_func, include_background=0):
@@ -65,15 +68,18 @@ def compute_metric_modality(metric_func, include_background=0):
 
 
 def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=None, amp=True, surface_distance=None, results=None,
-         additional_metrics=None):
+         additional_metrics=None, hausdorff_distance=None):
     """the reference's evaluation loop (test.py:46-123): returns the mean total Dice over the classes with a value (and the mean total surface
     distance when `surface_distance` is given).  `results`, a dict, receives the printed values: "dice_modality", "dice_total" and, with
     `surface_distance`, "surface_distance_modality", "surface_distance_total", each {printed key: value}.  `additional_metrics`: a list of
     cumulative metric objects updated with every batch and aggregated (`metric.aggregate().item()`) and reset at the end, as the reference's
-    validation loop does (utils/trainer.py:145-149,246-250); their values are printed and stored in results["additional_metrics"]."""
+    validation loop does (utils/trainer.py:145-149,246-250); their values are printed and stored in results["additional_metrics"].
+    `hausdorff_distance`: a HausdorffDistanceMetric accumulated, printed and reset like the surface distance; `results` then also holds
+    "hausdorff_distance_modality" and "hausdorff_distance_total".  The return value does not change."""
     model.eval()
     acc_mod_cumulative = Cumulative()
     surface_mod_cumulative = Cumulative() if surface_distance is not None else None
+    hausdorff_mod_cumulative = Cumulative() if hausdorff_distance is not None else None
     dev_type = torch.device(device).type
     with torch.no_grad():
         for batch in loader:
@@ -81,7 +87,7 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
             modality = batch["modality"].to(device) if "modality" in batch.keys() else None
             with torch.autocast(device_type=dev_type, enabled=amp and dev_type == "cuda"):
                 output = model_inferer(data, modalities=modality) if model_inferer is not None else model(data, modality)
-            fused = _fused(output, post_label, post_pred, acc_func, surface_distance, additional_metrics)
+            fused = _fused(output, post_label, post_pred, acc_func, surface_distance, additional_metrics, hausdorff_distance)
             if fused:
                 C = output.shape[1]
                 if additional_metrics:      # the first score comes out of the Dice's own pass; a further one (other settings) re-reads the volume
@@ -101,7 +107,25 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
                 for m in additional_metrics or ():
                     m(y_pred=val_output_convert, y=val_labels_convert)
             acc_mod_cumulative.extend(batch_acc, modality)
-            if surface_distance is not None:
+            if hausdorff_distance is not None:
+                hd = hausdorff_distance
+                if fused and surface_distance is not None:      # both from one launch set; with the background and sliced if the two disagree
+                    inc = bool(surface_distance.include_background or hd.include_background)
+                    batch_surface, batch_hd = surface_metrics_from_logits(output, target, output.shape[1], include_background=inc,
+                                                                          symmetric=surface_distance.symmetric, percentile=hd.percentile, directed=hd.directed)
+                    batch_surface = batch_surface[:, int(inc and not surface_distance.include_background):]
+                    batch_hd = batch_hd[:, int(inc and not hd.include_background):]
+                    surface_distance.extend(batch_surface)
+                    hd.extend(batch_hd)
+                    surface_mod_cumulative.extend(batch_surface, modality)
+                elif fused:
+                    batch_hd = surface_metrics_from_logits(output, target, output.shape[1], include_background=hd.include_background, percentile=hd.percentile,
+                                                           directed=hd.directed, want=("hd",))[0]
+                    hd.extend(batch_hd)
+                else:
+                    batch_hd = hd(y_pred=val_output_convert, y=val_labels_convert)
+                hausdorff_mod_cumulative.extend(batch_hd, modality)
+            if surface_distance is not None and not (fused and hausdorff_distance is not None):
                 if fused:
                     batch_surface = surface_distance_from_logits(output, target, output.shape[1], include_background=surface_distance.include_background,
                                                                  symmetric=surface_distance.symmetric)
@@ -117,6 +141,10 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
     if surface_distance is not None:
         include_background_surf = int(not surface_distance.include_background)
         results["surface_distance_modality"] = compute_metric_modality(surface_mod_cumulative, include_background_surf)
+    if hausdorff_distance is not None:
+        print("Hausdorff Distance per modality")
+        include_background_hd = int(not hausdorff_distance.include_background)
+        results["hausdorff_distance_modality"] = compute_metric_modality(hausdorff_mod_cumulative, include_background_hd)
     accuracy, not_nans = acc_func.aggregate()
     dict_acc_class = {f"val_total_dice/class{c + include_background_acc}": v for c, v in enumerate(accuracy.tolist())}
     print(dict_acc_class)
@@ -128,6 +156,14 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
         results["surface_distance_total"] = dict_surf_class
         surface_distance.reset()
         surface_mod_cumulative.reset()
+    if hausdorff_distance is not None:
+        hausdorff = hausdorff_distance.aggregate()
+        hausdorff = hausdorff[0] if isinstance(hausdorff, tuple) else hausdorff          # get_not_nans or not
+        dict_hd_class = {f"val_total_hausdorff_distance/class{c + include_background_hd}": v for c, v in enumerate(hausdorff.reshape(-1).tolist())}
+        print(dict_hd_class)
+        results["hausdorff_distance_total"] = dict_hd_class
+        hausdorff_distance.reset()
+        hausdorff_mod_cumulative.reset()
     acc_func.reset()
     acc_mod_cumulative.reset()
     if additional_metrics:

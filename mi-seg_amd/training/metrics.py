@@ -1,6 +1,8 @@
 """Dice metric / AsDiscrete with MONAI 1.1.0 semantics (reference lightning_monai.py:68-79,190-195).  Parity unpinned (Appendix B).
 Average surface distance and the cumulative metric objects of the reference's evaluation script (test.py:17-171).
-Generalized Dice score of the reference's validation (tune.py:124-129,208-213)."""
+Generalized Dice score of the reference's validation (tune.py:124-129,208-213).
+Hausdorff distance (MONAI 1.1.0 metrics/hausdorff_distance.py) on the surface-distance machinery."""
+import math
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -207,6 +209,93 @@ def surface_distance_from_logits(logits, label, num_classes, include_background=
     return torch.from_numpy(asd).to(logits.device)
 
 
+# ------------------------------------------------------------------------------------------ Hausdorff distance
+# MONAI 1.1.0 metrics/hausdorff_distance.py restated (parity unpinned): the edge sets and one-way distance lists of the surface distance above.
+
+def _check_percentile(percentile):
+    if percentile is not None and not 0 <= percentile <= 100:
+        raise ValueError(f"percentile should be a value between 0 and 100, got {percentile}.")
+
+
+def _list_percentile(d, percentile):
+    """h of one distance list: NaN if it is empty, inf if it is all inf (one edge set is empty: numpy's percentile would interpolate
+    inf - inf into NaN there), the maximum without a percentile (None or 0), else numpy's default ("linear") percentile written out"""
+    n = d.shape[0]
+    if n == 0:
+        return math.nan
+    if np.isinf(d).all():
+        return math.inf
+    if not percentile:
+        return float(d.max())
+    v = np.sort(d.astype(np.float64))
+    pos = (percentile / 100) * (n - 1)
+    lo = int(math.floor(pos))
+    hi = min(lo + 1, n - 1)
+    return float(v[lo] + (v[hi] - v[lo]) * (pos - lo))
+
+
+def hausdorff_distance_numpy(pred, gt, percentile=None, directed=False, use_scipy=True):
+    """pred, gt: bool [B, C, *spatial] -> float64 [B, C] (compute_hausdorff_distance after ignore_background): per (b, c) the percentile
+    (None or 0: the maximum) of d(pred -> gt), and the larger of that and d(gt -> pred)'s unless `directed`.  use_scipy as in
+    average_surface_distance_numpy."""
+    _check_percentile(percentile)
+    nd = _ndimage() if use_scipy else None
+    B, Cc = pred.shape[:2]
+    hd = np.empty((B, Cc))
+    for b, c in np.ndindex(B, Cc):
+        ep, eg = _mask_edges(pred[b, c], gt[b, c], nd)
+        h = _list_percentile(_surface_distance(ep, eg, nd), percentile)
+        if not directed:
+            h2 = _list_percentile(_surface_distance(eg, ep, nd), percentile)
+            h = max(h, h2)              # NaN together (both lists empty) or inf together (one edge set empty)
+        hd[b, c] = h
+    return hd
+
+
+def compute_hausdorff_distance(y_pred, y, include_background=False, distance_metric="euclidean", percentile=None, directed=False):
+    """MONAI's compute_hausdorff_distance on one-hot [B, C, *spatial] inputs -> float64 [B, C'] on the device of y_pred.  On a HIP device with
+    exclusive one-hot 3-D inputs: class maps into csrc/surface.hip; otherwise the CPU restatement."""
+    _check_metric(distance_metric)
+    _check_percentile(percentile)
+    if y_pred.shape != y.shape:
+        raise ValueError(f"y_pred and y should have same shapes, got {tuple(y_pred.shape)} and {tuple(y.shape)}.")
+    Cc = y_pred.shape[1]
+    if (y_pred.is_cuda and y_pred.dim() == 5 and Cc <= 64 and max(y_pred.shape[2:]) <= 4096 and
+            _exclusive_onehot(y_pred) and _exclusive_onehot(y.to(y_pred.device))):
+        from ..hip import ops
+        return ops.surface_metrics(y.to(y_pred.device).argmax(dim=1).to(torch.uint8), pred=y_pred.argmax(dim=1), num_classes=Cc,
+                                   include_background=include_background, percentile=percentile, directed=directed, want=("hd",))[0]
+    if not include_background:
+        y_pred, y = y_pred[:, 1:], y[:, 1:]
+    hd = hausdorff_distance_numpy(y_pred.detach().cpu().numpy().astype(bool), y.detach().cpu().numpy().astype(bool), percentile, directed)
+    return torch.from_numpy(hd).to(y_pred.device)
+
+
+def surface_metrics_from_logits(logits, label, num_classes, include_background=True, symmetric=True, percentile=None, directed=False,
+                                want=("asd", "hd")):
+    """surface_distance_from_logits and the Hausdorff distance of the same argmax, fused: (asd, hd), fp64 [B, C'] each, from ONE launch set on a
+    HIP device (the classify pass and the three distance passes are shared; csrc/surface.hip); on CPU tensors the restatements above."""
+    _check_percentile(percentile)
+    if (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 5 and logits.shape[1] == num_classes and num_classes <= 64
+            and max(logits.shape[2:]) <= 4096):
+        from ..hip import ops
+        return ops.surface_metrics(label.to(logits.device), logits=logits.contiguous(), include_background=include_background, symmetric=symmetric,
+                                   percentile=percentile, directed=directed, want=want)
+    classes = torch.arange(num_classes, device=logits.device).view(1, -1, *([1] * (logits.dim() - 2)))
+    pred = logits.argmax(dim=1, keepdim=True) == classes
+    lab = label.to(logits.device).reshape(logits.shape[0], 1, *logits.shape[2:]).long() == classes
+    c0 = 0 if include_background else 1
+    p, g = pred[:, c0:].cpu().numpy(), lab[:, c0:].cpu().numpy()
+    out = {"asd": lambda: average_surface_distance_numpy(p, g, symmetric), "hd": lambda: hausdorff_distance_numpy(p, g, percentile, directed)}
+    return tuple(torch.from_numpy(out[w]()).to(logits.device) for w in want)
+
+
+def hausdorff_distance_from_logits(logits, label, num_classes, include_background=True, percentile=None, directed=False):
+    """AsDiscrete(argmax, to_onehot) on the logits + AsDiscrete(to_onehot) on the label + HausdorffDistanceMetric, fused: fp64 [B, C']"""
+    return surface_metrics_from_logits(logits, label, num_classes, include_background=include_background, percentile=percentile, directed=directed,
+                                       want=("hd",))[0]
+
+
 # ------------------------------------------------------------------------------------------ cumulative metrics (MONAI 1.1.0 metrics/metric.py)
 _REDUCTIONS = ("none", "mean", "sum", "mean_batch", "sum_batch", "mean_channel", "sum_channel")
 
@@ -308,6 +397,20 @@ class SurfaceDistanceMetric(_CumulativeMetric):
     def _compute(self, y_pred, y):
         return compute_average_surface_distance(y_pred, y, include_background=self.include_background, symmetric=self.symmetric,
                                                 distance_metric=self.distance_metric)
+
+
+class HausdorffDistanceMetric(_CumulativeMetric):
+    """monai.metrics.HausdorffDistanceMetric on one-hot [B, C, ...] inputs (compute_hausdorff_distance above), float64 [B, C']"""
+
+    def __init__(self, include_background=False, distance_metric="euclidean", percentile=None, directed=False, reduction="mean", get_not_nans=False):
+        _check_metric(distance_metric)
+        _check_percentile(percentile)
+        super().__init__(include_background, reduction, get_not_nans)
+        self.distance_metric, self.percentile, self.directed = distance_metric, percentile, directed
+
+    def _compute(self, y_pred, y):
+        return compute_hausdorff_distance(y_pred, y, include_background=self.include_background, distance_metric=self.distance_metric,
+                                          percentile=self.percentile, directed=self.directed)
 
 
 class GeneralizedDiceScore(_CumulativeMetric):

@@ -1,7 +1,10 @@
 """the fused average surface distance (csrc/surface.hip, miseg_surface_distance) at the bench.py --workload c5 volume size: a seeded synthetic
 512 x 512 x 363 label of 6 classes (nested and overlapping ellipsoids, some cut by the volume border), the prediction a perturbed copy, fp32
 logits.  Times the metric from logits with device events after warm-up (include_background True / False, symmetric), prints the bytes the
-passes move (from the shapes and the class boxes), the share of HBM peak, and the CPU restatement's time on a cropped volume."""
+passes move (from the shapes and the class boxes), the share of HBM peak, and the CPU restatement's time on a cropped volume.
+--combined [PERCENTILE] (default 95) also times the Hausdorff distance on the same kernels (miseg_surface_metrics): the
+ASD + HD call, the HD-only call and their workspace next to the ASD call's; --no-cpu leaves out the CPU restatement."""
+import argparse
 import os
 import sys
 import time
@@ -63,7 +66,41 @@ def traffic(pred, lab, include_background):
     return total
 
 
+def median_ms(fn, warm=2, runs=5):
+    for _ in range(warm):
+        out = fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(runs):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return sorted(ts)[len(ts) // 2], out
+
+
+def combined(logits, label, pct):
+    """ASD alone, ASD + HD in one call, HD alone: medians of 5, and the workspace of the two entry points"""
+    from mi_seg_amd.hip import lib as L
+    for inc in (True, False):
+        kw = dict(include_background=inc, symmetric=True)
+        asd_ms, asd = median_ms(lambda: M.surface_distance_from_logits(logits, label, C, **kw))
+        both_ms, (asd2, hd) = median_ms(lambda: M.surface_metrics_from_logits(logits, label, C, percentile=pct, directed=False, **kw))
+        hd_ms, _ = median_ms(lambda: M.hausdorff_distance_from_logits(logits, label, C, include_background=inc, percentile=pct))
+        assert torch.equal(asd, asd2)
+        print(f"include_background={inc!s:5}  ASD {asd_ms:7.2f} ms   ASD + HD{pct:g} in one call {both_ms:7.2f} ms (+{both_ms - asd_ms:5.2f})   "
+              f"HD alone {hd_ms:7.2f} ms   ASD call + HD call {asd_ms + hd_ms:7.2f} ms   hd {[round(v, 3) for v in hd[0].tolist()]}")
+    a, b = L.load().miseg_surface_distance_workspace_bytes(1, C, D, H, W), L.load().miseg_surface_metrics_workspace_bytes(1, C, D, H, W)
+    print(f"workspace: ASD {a} bytes, ASD + HD {b} bytes (+{b - a} = {(b - a) // (2 * C)} per (class, direction))")
+
+
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--combined", nargs="?", type=float, const=95.0, default=None, metavar="PERCENTILE")
+    ap.add_argument("--no-cpu", action="store_true")
+    args = ap.parse_args()
     pred, lab = volume()
     logits = torch.nn.functional.one_hot(pred.long(), C).permute(3, 0, 1, 2).float()[None].contiguous()
     logits += 0.1 * torch.rand_like(logits)
@@ -84,6 +121,10 @@ def main():
         nb = traffic(pred, lab, inc)
         print(f"include_background={inc!s:5}  {ms:8.2f} ms (median of 5)  {nb / 1e9:6.2f} GB  {nb / ms / 1e9:6.3f} TB/s = {100 * nb / ms / 1e9 / (HBM_PEAK / 1e12):5.1f} % "
               f"of HBM peak  asd {[round(v, 3) for v in out[0].tolist()]}")
+    if args.combined is not None:
+        combined(logits, label, args.combined)
+    if args.no_cpu:
+        return
     # the CPU restatement (scipy.ndimage when it imports: MONAI's recipe) on a crop, one thread
     crop = (slice(100, 228), slice(140, 268), slice(150, 246))
     p, g = pred[crop].cpu().numpy().astype(np.int64), lab[crop].cpu().numpy().astype(np.int64)
