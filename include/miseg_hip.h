@@ -749,7 +749,12 @@ int miseg_opt_step_pack_conv3(const miseg_opt_step_params* p, const miseg_pack_c
  * Slab form (ABI 5; volumes whose window logits do not fit in memory at once): d_count > 0 writes only the depths [d_begin, d_begin + d_count)
  * of `out` / `count` (which still address the whole [C][D][H][W] volume) from the nd RESIDENT depth layers whose starts are start_d[0..nd):
  * every depth of the slab must be covered by resident layers only, i.e. start_d[0] <= d_begin, no gaps, and the layer after the last
- * resident one starts at or behind d_begin + d_count (the caller's promise; MONAI's accumulation order is kept inside the slab). */
+ * resident one starts at or behind d_begin + d_count (the caller's promise; MONAI's accumulation order is kept inside the slab).
+ * Weighted form (the struct's last two fields; the leading struct_size tells the layouts apart - a caller built against the shorter struct
+ * is refused, MISEG_ABI_VERSION stays 16; MONAI's mode="gaussian" or any roi_weight_map): `weight` is the dense importance map of one window.  The same
+ * ONE gather pass writes out = (sum of fl(weight[voxel in window] * win), windows in index order, product and add rounded separately - no
+ * FMA) / (sum of the weights in the same order), a true division: bit-identical to MONAI's `out[win] += map * pred; wsum[win] += map`
+ * loop.  weight == NULL is the constant form above, unchanged. */
 #define MISEG_STITCH_MAX_WINDOWS 64
 typedef struct {
   uint32_t struct_size;
@@ -757,6 +762,8 @@ typedef struct {
   int C, D, H, W, rd, rh, rw, nd, nh, nw;
   const int32_t* start_d; const int32_t* start_h; const int32_t* start_w;
   int d_begin, d_count;            /* d_count == 0: the whole volume */
+  const float* weight;             /* fp32 [rd][rh][rw] importance map of a window (device); NULL: every window weighs 1 (mode="constant") */
+  float* wsum;                     /* optional, only with `weight`: fp32 [D][H][W], the summed weights of a voxel (the weighted `count`) */
 } miseg_stitch_params;
 int miseg_stitch_windows(const miseg_stitch_params* p, miseg_stream_t stream);
 

@@ -498,6 +498,81 @@ static __global__ void __launch_bounds__(256) stitch_kernel(const float* __restr
   }
 }
 
+// Weighted blend (MONAI mode="gaussian" / roi_weight_map): the same one-pass gather with a dense importance map wmap[rd][rh][rw].
+//   out = (0 + fl(m_1 * p_1) + fl(m_2 * p_2) ...) / (0 + m_1 + m_2 ...)   over the covering windows in window-index order
+// product and add are rounded SEPARATELY (contraction is switched off below: an FMA would differ from MONAI's `out[win] += map * pred` in the
+// last bit).  The weights and the window offsets of a voxel do not depend on the channel: with a cover of <= STITCH_COVER_REGS windows (8 at
+// overlap 0.5) they are read / computed once per voxel into registers (statically indexed: no scratch) and every channel only streams its
+// window values, 8 independent loads in flight per lane; a larger cover (up to 64 at overlap 0.75) re-reads the map, which lives in L2 (96^3 fp32 = 3.5 MB), per channel.
+#define STITCH_COVER_REGS 8
+static __global__ void __launch_bounds__(256) stitch_weighted_kernel(const float* __restrict__ win, const float* __restrict__ wmap, float* __restrict__ out,
+                                                                     uint16_t* __restrict__ count, float* __restrict__ wsum, StitchArgs a) {
+#pragma clang fp contract(off)
+  const int w = blockIdx.x * 256 + threadIdx.x, h = blockIdx.y, d = a.d0 + blockIdx.z;
+  if (w >= a.W) return;
+  int dl, dh_, hl, hh, wl, wh;
+  cover(a.sd, a.nd, a.rd, d, dl, dh_);
+  cover(a.sh, a.nh, a.rh, h, hl, hh);
+  cover(a.sw, a.nw, a.rw, w, wl, wh);
+  const int n = (dh_ - dl + 1) * (hh - hl + 1) * (wh - wl + 1);
+  const int64_t rvol = (int64_t)a.rd * a.rh * a.rw, vox = (int64_t)a.D * a.H * a.W;
+  const int64_t o = ((int64_t)d * a.H + h) * a.W + w;
+  if (count) count[o] = (uint16_t)n;
+  if (n <= STITCH_COVER_REGS) {
+    float m[STITCH_COVER_REGS];
+    int64_t off[STITCH_COVER_REGS];
+    int id = dl, ih = hl, iw = wl;
+    float ws = 0.f;
+#pragma unroll
+    for (int k = 0; k < STITCH_COVER_REGS; ++k) {
+      m[k] = 0.f; off[k] = 0;
+      if (k < n) {
+        const int rel = ((d - a.sd[id]) * a.rh + (h - a.sh[ih])) * a.rw + (w - a.sw[iw]);
+        m[k] = wmap[rel];
+        off[k] = (((int64_t)id * a.nh + ih) * a.nw + iw) * a.C * rvol + rel;
+        ws = ws + m[k];
+        if (++iw > wh) { iw = wl; if (++ih > hh) { ih = hl; ++id; } }       // the next window in index order
+      }
+    }
+    if (wsum) wsum[o] = ws;
+    for (int c = 0; c < a.C; ++c) {
+      const float* __restrict__ src = win + (int64_t)c * rvol;
+      // all loads of a channel are issued before the first add (a load under `k < n` waits for the one before it: the gather is latency
+      // bound); a slot beyond the cover reads window 0's first voxel (off = 0: a valid address) and its value is dropped by the select
+      float v[STITCH_COVER_REGS];
+#pragma unroll
+      for (int k = 0; k < STITCH_COVER_REGS; ++k) v[k] = src[off[k]];
+      float acc = 0.f;
+#pragma unroll
+      for (int k = 0; k < STITCH_COVER_REGS; ++k) {
+        const float t = m[k] * v[k];
+        const float sum = acc + t;
+        acc = k < n ? sum : acc;
+      }
+      out[(int64_t)c * vox + o] = acc / ws;
+    }
+    return;
+  }
+  float ws = 0.f;
+  for (int id = dl; id <= dh_; ++id)
+    for (int ih = hl; ih <= hh; ++ih)
+      for (int iw = wl; iw <= wh; ++iw)
+        ws = ws + wmap[((d - a.sd[id]) * a.rh + (h - a.sh[ih])) * a.rw + (w - a.sw[iw])];
+  if (wsum) wsum[o] = ws;
+  for (int c = 0; c < a.C; ++c) {
+    float acc = 0.f;
+    for (int id = dl; id <= dh_; ++id)
+      for (int ih = hl; ih <= hh; ++ih)
+        for (int iw = wl; iw <= wh; ++iw) {
+          const int64_t wi = ((int64_t)id * a.nh + ih) * a.nw + iw;
+          const int rel = ((d - a.sd[id]) * a.rh + (h - a.sh[ih])) * a.rw + (w - a.sw[iw]);
+          const float t = wmap[rel] * win[(wi * a.C + c) * rvol + rel];
+          acc = acc + t;
+        }
+    out[(int64_t)c * vox + o] = acc / ws;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ augmentation
 struct AugArgs {
   int C, D, H, W, rd, rh, rw, n, lb;
@@ -796,6 +871,9 @@ extern "C" int miseg_stitch_windows(const miseg_stitch_params* p, miseg_stream_t
   MISEG_REQUIRE(p->nd > 0 && p->nh > 0 && p->nw > 0 && p->nd <= MISEG_STITCH_MAX_WINDOWS && p->nh <= MISEG_STITCH_MAX_WINDOWS && p->nw <= MISEG_STITCH_MAX_WINDOWS,
                 MISEG_E_UNSUPPORTED, "stitch_windows: %d x %d x %d windows (max %d per axis)", p->nd, p->nh, p->nw, MISEG_STITCH_MAX_WINDOWS);
   MISEG_REQUIRE(p->C > 0 && p->D > 0 && p->H > 0 && p->W > 0 && p->H <= 65535 && p->D <= 65535, MISEG_E_BADARG, "stitch_windows: bad volume");
+  MISEG_REQUIRE(p->rd > 0 && p->rh > 0 && p->rw > 0 && (int64_t)p->rd * p->rh * p->rw <= INT32_MAX, MISEG_E_BADARG, "stitch_windows: bad roi %d x %d x %d", p->rd,
+                p->rh, p->rw);
+  MISEG_REQUIRE(p->weight || !p->wsum, MISEG_E_BADARG, "stitch_windows: wsum is the weighted count: it needs a weight map");
   StitchArgs a;
   a.C = p->C; a.D = p->D; a.H = p->H; a.W = p->W; a.rd = p->rd; a.rh = p->rh; a.rw = p->rw; a.nd = p->nd; a.nh = p->nh; a.nw = p->nw;
   const int* src[3] = {p->start_d, p->start_h, p->start_w};
@@ -826,7 +904,9 @@ extern "C" int miseg_stitch_windows(const miseg_stitch_params* p, miseg_stream_t
     }
     MISEG_REQUIRE(reach == size[ax], MISEG_E_BADARG, "stitch_windows: axis %d is covered up to %d of %d", ax, reach, size[ax]);
   }
-  stitch_kernel<<<dim3(cdiv(p->W, 256), p->H, slab ? p->d_count : p->D), 256, 0, s>>>(p->win, p->out, p->count, a);
+  const dim3 grid(cdiv(p->W, 256), p->H, slab ? p->d_count : p->D);
+  if (p->weight) stitch_weighted_kernel<<<grid, 256, 0, s>>>(p->win, p->weight, p->out, p->count, p->wsum, a);
+  else stitch_kernel<<<grid, 256, 0, s>>>(p->win, p->out, p->count, a);
   MISEG_LAUNCH_CHECK("stitch_windows");
   return MISEG_OK;
 }

@@ -153,7 +153,8 @@ OptStep = _struct("OptStep", cname="miseg_opt_step_params", fields=[
     ("index", vp), ("count_n", i32)])
 Stitch = _struct("Stitch", cname="miseg_stitch_params", fields=[
     ("struct_size", u32), ("win", vp), ("out", vp), ("count", vp), ("C", i32), ("D", i32), ("H", i32), ("W", i32), ("rd", i32), ("rh", i32), ("rw", i32),
-    ("nd", i32), ("nh", i32), ("nw", i32), ("start_d", vp), ("start_h", vp), ("start_w", vp), ("d_begin", i32), ("d_count", i32)])
+    ("nd", i32), ("nh", i32), ("nw", i32), ("start_d", vp), ("start_h", vp), ("start_w", vp), ("d_begin", i32), ("d_count", i32),
+    ("weight", vp), ("wsum", vp)])
 AugSample = _struct("AugSample", cname="miseg_aug_sample", fields=[("origin", i32 * 3), ("flip", i32 * 3), ("rot_k", i32), ("scale", f32), ("shift", f32)])
 Augment = _struct("Augment", cname="miseg_augment_params", fields=[
     ("struct_size", u32), ("image", vp), ("label", vp), ("label_bytes", i32), ("C", i32), ("D", i32), ("H", i32), ("W", i32), ("rd", i32), ("rh", i32),

@@ -1836,10 +1836,12 @@ def label_export(logits, tables, axes, lut, dtype=torch.uint16):
     return out
 
 
-def stitch_windows(win, out, starts, roi, count=None, slab=None):
+def stitch_windows(win, out, starts, roi, count=None, slab=None, weight=None, wsum=None):
     """win fp32 [nd*nh*nw, C, rd, rh, rw] (the windows of the nd depth layers `starts[0]`, all resident), out fp32 [C, D, H, W];
     starts = (list_d, list_h, list_w).  slab = (d_begin, d_count): write only these depths of `out` from the resident layers (which then
-    need not cover the whole depth axis, miseg_stitch_params)."""
+    need not cover the whole depth axis, miseg_stitch_params).  weight: fp32 [rd, rh, rw] importance map of a window on win's device
+    (MONAI mode="gaussian" / roi_weight_map): out = sum(weight * win) / sum(weight) instead of sum(win) / count; None is the constant blend.
+    wsum (only with weight): fp32 [D, H, W], receives the summed weights."""
     nd, nh, nw = (len(s) for s in starts)
     Cc, D, H, W = out.shape
     assert win.dtype == torch.float32 and out.dtype == torch.float32 and win.is_contiguous() and out.is_contiguous()
@@ -1848,9 +1850,20 @@ def stitch_windows(win, out, starts, roi, count=None, slab=None):
     arr = [(C.c_int32 * len(s))(*s) for s in starts]
     if count is not None:
         assert count.dtype == torch.int16 and count.is_contiguous() and tuple(count.shape) == (D, H, W)
+    if weight is not None:
+        if tuple(weight.shape) != tuple(roi):
+            raise ValueError(f"stitch_windows: weight map {tuple(weight.shape)} does not have the roi's shape {tuple(roi)}")
+        if weight.dtype != torch.float32 or not weight.is_contiguous() or weight.device != win.device:
+            raise ValueError(f"stitch_windows: the weight map must be a contiguous fp32 tensor on {win.device} (got {weight.dtype} on {weight.device})")
+    if wsum is not None:
+        if weight is None:
+            raise ValueError("stitch_windows: wsum is the sum of the weights: it needs a weight map")
+        if tuple(wsum.shape) != (D, H, W) or wsum.dtype != torch.float32 or not wsum.is_contiguous() or wsum.device != win.device:
+            raise ValueError(f"stitch_windows: wsum must be a contiguous fp32 tensor of shape {(D, H, W)} on {win.device}")
     d0, dn = slab if slab is not None else (0, 0)
     _call("miseg_stitch_windows", L.Stitch(C.sizeof(L.Stitch), _ptr(win), _ptr(out), _ptr(count), Cc, D, H, W, roi[0], roi[1], roi[2], nd, nh, nw,
-                                           C.cast(arr[0], C.c_void_p), C.cast(arr[1], C.c_void_p), C.cast(arr[2], C.c_void_p), int(d0), int(dn)))
+                                           C.cast(arr[0], C.c_void_p), C.cast(arr[1], C.c_void_p), C.cast(arr[2], C.c_void_p), int(d0), int(dn),
+                                           _ptr(weight), _ptr(wsum)))
     return out
 
 

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ..training.inferer import sliding_window_inference
+from ..training.inferer import sigma_scale_arg, sliding_window_inference
 from ..training.losses import DiceCELoss, DiceFocalLoss, GeneralizedDiceFocalLoss
 from ..training.metrics import dice_from_logits
 from ..training.schedulers import WarmupCosineSchedule
@@ -30,7 +30,8 @@ class LitMonai(_Base):
                  smooth_dr: float = 1e-6, learning_rate: float = 1e-4, optim_name: str = "adamw", reg_weight: float = 1e-5, momentum: float = 0.99,
                  roi_size: Union[Sequence[int], int] = (96, 96, 96), infer_overlap: float = 0.5, sw_batch_size: int = 1, infer_cpu: bool = False,
                  batch_size: int = 1, scheduler: str = "reduce_on_plateau", warmup_epochs=None, patience=None, check_val_every_n_epoch=None,
-                 max_epochs: int = 5000, t_max: int = 200, cycles: float = 1, include_background: bool = False, **kwargs):
+                 max_epochs: int = 5000, t_max: int = 200, cycles: float = 1, include_background: bool = False, infer_mode: str = "constant",
+                 infer_sigma_scale: Union[Sequence[float], float] = 0.125, infer_padding_mode: str = "constant", **kwargs):
         super().__init__()
         self.model = model
         if criterion == "dice_focal":      # squared_pred hard-coded True like the reference (:53)
@@ -48,7 +49,8 @@ class LitMonai(_Base):
         self.learning_rate, self.batch_size, self.optim_name = learning_rate, batch_size, optim_name
         self.reg_weight, self.momentum, self.infer_cpu = reg_weight, momentum, infer_cpu
         self.model_inferer = partial(sliding_window_inference, predictor=self.model, roi_size=roi_size, overlap=infer_overlap,
-                                     sw_batch_size=sw_batch_size, device=torch.device("cpu") if infer_cpu else None)
+                                     sw_batch_size=sw_batch_size, device=torch.device("cpu") if infer_cpu else None, mode=infer_mode,
+                                     sigma_scale=sigma_scale_arg(infer_sigma_scale), padding_mode=infer_padding_mode)
         self.scheduler, self.warmup_epochs, self.patience = scheduler, warmup_epochs, patience
         self.check_val_every_n_epoch, self.max_epochs, self.t_max, self.cycles = check_val_every_n_epoch, max_epochs, t_max, cycles
         self.__dict__.update(kwargs)
@@ -77,7 +79,9 @@ class LitMonai(_Base):
                    infer_cpu=args.infer_cpu, batch_size=args.batch_size, scheduler=args.scheduler, warmup_epochs=args.warmup_epochs,
                    patience=args.patience_scheduler, check_val_every_n_epoch=getattr(args, "check_val_every_n_epoch", None),
                    max_epochs=getattr(args, "max_epochs", 5000), t_max=args.t_max, cycles=args.cycles,
-                   include_background=not args.no_include_background, **extra)
+                   include_background=not args.no_include_background, infer_mode=getattr(args, "infer_mode", "constant"),
+                   infer_sigma_scale=getattr(args, "infer_sigma_scale", 0.125), infer_padding_mode=getattr(args, "infer_padding_mode", "constant"),
+                   **extra)
 
     def forward(self, x, modalities=None):
         return self.model(x, modalities) if modalities is not None else self.model(x)

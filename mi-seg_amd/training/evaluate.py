@@ -75,7 +75,9 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
     cumulative metric objects updated with every batch and aggregated (`metric.aggregate().item()`) and reset at the end, as the reference's
     validation loop does (utils/trainer.py:145-149,246-250); their values are printed and stored in results["additional_metrics"].
     `hausdorff_distance`: a HausdorffDistanceMetric accumulated, printed and reset like the surface distance; `results` then also holds
-    "hausdorff_distance_modality" and "hausdorff_distance_total".  The return value does not change."""
+    "hausdorff_distance_modality" and "hausdorff_distance_total".  The return value does not change.
+    `model_inferer` is the caller's, e.g. the reference's partial(sliding_window_inference, predictor=model, roi_size=..., sw_batch_size=...,
+    overlap=...); MONAI's Gaussian window blend is the same partial with mode="gaussian" (and sigma_scale= / padding_mode= as wanted)."""
     model.eval()
     acc_mod_cumulative = Cumulative()
     surface_mod_cumulative = Cumulative() if surface_distance is not None else None

@@ -15,7 +15,7 @@ from ..data.preprocess import load_image_for_prediction
 from ..hip import ops
 from ..networks.utils.utils import model_from_argparse_args
 from ..utils.parser import add_model_argparse_args
-from .inferer import sliding_window_inference
+from .inferer import sigma_scale_arg, sliding_window_inference
 
 LABEL_MAP = {1: 500, 2: 600, 3: 420, 4: 550, 5: 205, 6: 820, 7: 850}      # predict_whs.py:18-26 (_MAP): class -> MM-WHS label code
 NO_GPU_MESSAGE = "predict_whs: the model and the label export run on the HIP device only (--no_gpu given, or no device visible)"
@@ -75,7 +75,9 @@ def predict_volume(model, item, args):
     image, geom = load_image_for_prediction(item["image"], (args.space_x, args.space_y, args.space_z), roi, device)
     t1 = _sync(device)
     modality = torch.tensor([modality_id(item.get("modality", 0))], device=device)
-    logits = sliding_window_inference(image, roi, args.sw_batch_size, model, overlap=args.infer_overlap, modalities=modality)
+    logits = sliding_window_inference(image, roi, args.sw_batch_size, model, overlap=args.infer_overlap, modalities=modality,
+                                      mode=getattr(args, "infer_mode", "constant"), sigma_scale=sigma_scale_arg(getattr(args, "infer_sigma_scale", 0.125)),
+                                      padding_mode=getattr(args, "infer_padding_mode", "constant"))
     del image
     t2 = _sync(device)
     label = invert_prediction(logits, geom, label_lut(logits.shape[1]))
@@ -101,7 +103,8 @@ def predict(model, datalist, args):
 
 
 def build_parser():
-    """the reference's command line (predict_whs.py:117-127): the model options plus its own, with its defaults"""
+    """the reference's command line (predict_whs.py:117-127): the model options plus its own, with its defaults (the model options carry
+    --infer_mode / --infer_sigma_scale / --infer_padding_mode, the window blend of predict_volume)"""
     parser = add_model_argparse_args(ArgumentParser())
     parser.add_argument("--checkpoint", default="", type=str, help="Checkpoint")
     parser.add_argument("--sample", default="", type=str, help="accepted for compatibility, unused")

@@ -1,4 +1,5 @@
-"""Command-line surface of MI-Seg (reference utils/parser.py:5-150): same flags, types and defaults, expressed as tables."""
+"""Command-line surface of MI-Seg (reference utils/parser.py:5-150): same flags, types and defaults, expressed as tables
+(plus --infer_mode / --infer_sigma_scale / --infer_padding_mode, whose defaults are what the reference gets from MONAI)."""
 from argparse import ArgumentParser
 
 _T = "store_true"
@@ -43,6 +44,10 @@ MODEL_ARGS = {
     ],
     "inference": [
         ("--infer_overlap", dict(default=0.5, type=float)), ("--sw_batch_size", dict(default=1, type=int)), ("--infer_cpu", dict(action=_T)),
+        # not flags of the reference (it always blends with MONAI's defaults, which these are): MONAI's other blending arguments
+        ("--infer_mode", dict(default="constant", type=str, help="constant | gaussian: how overlapping windows are blended")),
+        ("--infer_sigma_scale", dict(default=0.125, type=float, nargs="+", help="gaussian mode: sigma = roi * this (one value, or one per axis)")),
+        ("--infer_padding_mode", dict(default="constant", type=str, help="constant | reflect | replicate | circular: pad of an image smaller than the roi")),
     ],
     "early_stop": [("--patience", dict(default=6, type=int)), ("--min_delta", dict(default=0.001, type=float))],
     "checkpointing": [("--save_top_k", dict(default=3, type=int))],
