@@ -840,9 +840,40 @@ typedef struct {
   const int32_t* lut;              /* device int32 [C]: the value written for each class */
   void* workspace;                 /* miseg_label_export_workspace_bytes(box_nd, box_nh, box_nw) bytes, uninitialised */
   void* out; int out_bytes;
+  /* a class map [D][H][W] of cls_bytes = 1 (uint8) or 4 (int32) instead of logits, e.g. miseg_keep_largest's out; exactly one of logits / cls.
+   * The argmax launch is skipped and the gather reads the map in place (the workspace is not touched); a value outside [0, C) is written as 0. */
+  const void* cls; int cls_bytes;
 } miseg_label_export_params;
 size_t miseg_label_export_workspace_bytes(int box_nd, int box_nh, int box_nw);
 int miseg_label_export(const miseg_label_export_params* p, miseg_stream_t stream);
+
+/* Keep-largest-connected-component post-processing (MONAI 1.1.0 transforms/post/array.py::KeepLargestConnectedComponent with
+ * num_components = 1, restated; parity unpinned - DESIGN.md section 7.7).  The class map is `cls` (cls_bytes 1: uint8, 4: int32), or the
+ * first-maximum argmax of fp32 `logits` under miseg_label_export's strict `>` rule; exactly one of the two.  `applied`: bit c set = class c is
+ * filtered.  independent != 0: of every applied class the largest component of {cls == c} stays and its other voxels become 0.  independent
+ * == 0: the components are those of {cls in applied} (adjacent applied voxels of different classes are connected), the largest stays with
+ * its classes, every other applied voxel becomes 0.  connectivity 1 / 2 / 3: the 6- / 18- / 26-neighbourhood; neighbours never wrap around
+ * a row, slice or sample end.  Among components of equal largest size the one holding the smallest linear voxel index stays.  Unapplied classes
+ * are never changed and connect nothing; a map value outside [0, C) belongs to no class and is copied through (truncated to out_bytes).
+ *   One union-find labelling serves all classes (csrc/components.hip): classify, tile-local union-find in LDS, unions across tile borders with
+ * atomicMin on an int32 parent volume, a flatten launch, one 64-bit atomicMax per root, apply.  Parents only ever decrease and every root is
+ * its component's smallest linear index, so the result does not depend on scheduling; integer atomics only.  The call only enqueues and reads
+ * nothing back: it can be captured into a graph.  C 1..64, every side 1..65535, each sample below 2^31 voxels, B >= 1.
+ *   stats (optional): int64 [B][C][3] = voxels of class c before, voxels of class c kept, roots whose voxel has class c (components of an
+ * applied class; in joint mode their sum over c is the component count; 0 for an unapplied class). */
+typedef struct {
+  uint32_t struct_size;
+  const float* logits;             /* fp32 [B][C][D][H][W], or NULL */
+  const void* cls; int cls_bytes;  /* [B][D][H][W] uint8 / int32, or NULL */
+  int B, C, D, H, W;
+  uint64_t applied;
+  int independent, connectivity;
+  void* workspace;                 /* miseg_keep_largest_workspace_bytes(B, D, H, W) bytes, uninitialised */
+  void* out; int out_bytes;        /* [B][D][H][W] of 1 (uint8) or 4 (int32) byte elements; may be `cls` itself when cls_bytes == out_bytes */
+  int64_t* stats;                  /* [B][C][3] or NULL */
+} miseg_keep_largest_params;
+size_t miseg_keep_largest_workspace_bytes(int B, int D, int H, int W);
+int miseg_keep_largest(const miseg_keep_largest_params* p, miseg_stream_t stream);
 
 /* sizeof() of a params struct as this library was compiled ("miseg_gemm_params", ...), 0 for an unknown name: bindings compare it with
  * their own mirror at load time (together with miseg_abi_version) so that header and binding cannot drift silently. */

@@ -694,7 +694,8 @@ static __global__ void __launch_bounds__(256) export_argmax_kernel(const float* 
 
 // Pass 2: one workgroup = a 64 (X) x 64 (axis f) output tile at one coordinate of axis g.  The class-map bytes under the tile are read with the
 // lanes along whichever of X / f indexes the map's fast axis, staged in LDS, then written out with the lanes along X (whole 128-B lines of
-// uint16), through the LUT.
+// uint16), through the LUT.  M: the class map's element - the argmax pass's uint8 map of the box, or a caller's uint8 / int32 map of the whole volume,
+// whose values outside [0, C) take the LUT's extra entry 64 (= 0).
 constexpr int EXPORT_TILE = 64, EXPORT_LD = EXPORT_TILE + 1;
 struct ExportArgs {
   const int32_t* tab[3];           // output axis X, Y, Z -> table
@@ -702,24 +703,28 @@ struct ExportArgs {
   int f, g, fast_x, C;
 };
 
-template <class O>
-__global__ void __launch_bounds__(256) export_gather_kernel(const uint8_t* __restrict__ cls, const int32_t* __restrict__ lut, O* __restrict__ out, ExportArgs a) {
+template <class M, class O>
+__global__ void __launch_bounds__(256) export_gather_kernel(const M* __restrict__ cls, const int32_t* __restrict__ lut, O* __restrict__ out, ExportArgs a) {
   __shared__ int offs[2][EXPORT_TILE];
   __shared__ uint8_t tile[EXPORT_TILE * EXPORT_LD];         // [j along f][i along X]
-  __shared__ O lut_s[64];
+  __shared__ O lut_s[65];
   const int tid = threadIdx.x, x0 = blockIdx.x * EXPORT_TILE, j0 = blockIdx.y * EXPORT_TILE, cg = blockIdx.z;
   const int nx = a.n[0], nf = a.n[a.f];
   if (tid < 2 * EXPORT_TILE) {
     const int ax = tid < EXPORT_TILE ? 0 : a.f, i = tid & (EXPORT_TILE - 1), c = (ax == 0 ? x0 : j0) + i;
     offs[tid >> 6][i] = c < a.n[ax] ? min(max(a.tab[ax][c] - a.lo[ax], 0), a.bn[ax] - 1) * a.st[ax] : 0;
   } else if (tid < 2 * EXPORT_TILE + a.C) lut_s[tid - 2 * EXPORT_TILE] = (O)lut[tid - 2 * EXPORT_TILE];
+  else if (tid == 255) lut_s[64] = (O)0;
   __syncthreads();
   const int og = min(max(a.tab[a.g][cg] - a.lo[a.g], 0), a.bn[a.g] - 1) * a.st[a.g];
 #pragma unroll 4
   for (int k = 0; k < EXPORT_TILE * EXPORT_TILE / 256; ++k) {
     const int e = tid + 256 * k;
     const int i = a.fast_x ? (e & 63) : (e >> 6), j = a.fast_x ? (e >> 6) : (e & 63);
-    if (x0 + i < nx && j0 + j < nf) tile[j * EXPORT_LD + i] = cls[(int64_t)offs[0][i] + offs[1][j] + og];
+    if (x0 + i < nx && j0 + j < nf) {
+      const uint32_t c = (uint32_t)cls[(int64_t)offs[0][i] + offs[1][j] + og];
+      tile[j * EXPORT_LD + i] = c < (uint32_t)a.C ? (uint8_t)c : (uint8_t)64;
+    }
   }
   __syncthreads();
   const int64_t ost[3] = {1, (int64_t)nx, (int64_t)nx * a.n[1]};
@@ -969,7 +974,9 @@ extern "C" int miseg_label_export(const miseg_label_export_params* p, miseg_stre
   hipStream_t s = (hipStream_t)s_;
   MISEG_REQUIRE(p && p->struct_size == sizeof(miseg_label_export_params), MISEG_E_BADARG, "label_export: struct_size %u != %zu", p ? p->struct_size : 0u,
                 sizeof(miseg_label_export_params));
-  MISEG_REQUIRE(p->logits && p->table_x && p->table_y && p->table_z && p->lut && p->workspace && p->out, MISEG_E_BADARG, "label_export: null pointer");
+  MISEG_REQUIRE((p->logits != nullptr) != (p->cls != nullptr), MISEG_E_BADARG, "label_export: exactly one of logits / cls");
+  MISEG_REQUIRE(p->table_x && p->table_y && p->table_z && p->lut && (p->workspace || p->cls) && p->out, MISEG_E_BADARG, "label_export: null pointer");
+  MISEG_REQUIRE(!p->cls || p->cls_bytes == 1 || p->cls_bytes == 4, MISEG_E_BADARG, "label_export: cls_bytes %d (1 or 4)", p->cls_bytes);
   MISEG_REQUIRE(p->C >= 1 && p->C <= 64, MISEG_E_BADARG, "label_export: C %d (1..64)", p->C);
   MISEG_REQUIRE(p->out_bytes == 1 || p->out_bytes == 2 || p->out_bytes == 4, MISEG_E_BADARG, "label_export: out_bytes %d (1, 2 or 4)", p->out_bytes);
   const int dims[3] = {p->D, p->H, p->W}, lo[3] = {p->box_d0, p->box_h0, p->box_w0}, bn[3] = {p->box_nd, p->box_nh, p->box_nw};
@@ -985,12 +992,19 @@ extern "C" int miseg_label_export(const miseg_label_export_params* p, miseg_stre
   const int64_t nbox = (int64_t)bn[0] * bn[1] * bn[2];
   MISEG_REQUIRE(nbox < ((int64_t)1 << 31), MISEG_E_UNSUPPORTED, "label_export: box of %lld voxels (below 2^31)", (long long)nbox);
   uint8_t* cls = (uint8_t*)p->workspace;
-  int g1 = cdiv(nbox, 256 * 4);
-  if (g1 > 8192) g1 = 8192;
-  export_argmax_kernel<<<g1, 256, 0, s>>>(p->logits, cls, p->C, p->H, p->W, (int64_t)p->D * p->H * p->W, lo[0], lo[1], lo[2], bn[1], bn[2], (int)nbox);
-  MISEG_LAUNCH_CHECK("label_export argmax");
+  if (p->logits) {
+    int g1 = cdiv(nbox, 256 * 4);
+    if (g1 > 8192) g1 = 8192;
+    export_argmax_kernel<<<g1, 256, 0, s>>>(p->logits, cls, p->C, p->H, p->W, (int64_t)p->D * p->H * p->W, lo[0], lo[1], lo[2], bn[1], bn[2], (int)nbox);
+    MISEG_LAUNCH_CHECK("label_export argmax");
+  } else {
+    MISEG_REQUIRE((int64_t)p->D * p->H * p->W < ((int64_t)1 << 31), MISEG_E_UNSUPPORTED, "label_export: a class map of %lld voxels (below 2^31)",
+                  (long long)p->D * p->H * p->W);
+  }
   ExportArgs a;
-  const int st[3] = {bn[1] * bn[2], bn[2], 1};
+  // the argmax pass packs the box; a given map is read where it lies: the whole volume's strides, from the box's first voxel
+  const int st[3] = {p->logits ? bn[1] * bn[2] : p->H * p->W, p->logits ? bn[2] : p->W, 1};
+  const int64_t first = p->logits ? 0 : ((int64_t)lo[0] * p->H + lo[1]) * p->W + lo[2];
   const int32_t* tab[3] = {p->table_x, p->table_y, p->table_z};
   for (int k = 0; k < 3; ++k) { a.tab[k] = tab[k]; a.n[k] = n[k]; a.lo[k] = lo[axis[k]]; a.bn[k] = bn[axis[k]]; a.st[k] = st[axis[k]]; }
   // the tile's second axis: the one that indexes the class map's fast axis W, unless X does (then Y)
@@ -1000,9 +1014,14 @@ extern "C" int miseg_label_export(const miseg_label_export_params* p, miseg_stre
   a.C = p->C;
   const dim3 grid(cdiv(n[0], EXPORT_TILE), cdiv(n[a.f], EXPORT_TILE), n[a.g]);
   const void* lut = p->lut;
-  if (p->out_bytes == 1) export_gather_kernel<uint8_t><<<grid, 256, 0, s>>>(cls, (const int32_t*)lut, (uint8_t*)p->out, a);
-  else if (p->out_bytes == 2) export_gather_kernel<uint16_t><<<grid, 256, 0, s>>>(cls, (const int32_t*)lut, (uint16_t*)p->out, a);
-  else export_gather_kernel<uint32_t><<<grid, 256, 0, s>>>(cls, (const int32_t*)lut, (uint32_t*)p->out, a);
+  auto gather = [&](auto* m) {
+    if (p->out_bytes == 1) export_gather_kernel<<<grid, 256, 0, s>>>(m, (const int32_t*)lut, (uint8_t*)p->out, a);
+    else if (p->out_bytes == 2) export_gather_kernel<<<grid, 256, 0, s>>>(m, (const int32_t*)lut, (uint16_t*)p->out, a);
+    else export_gather_kernel<<<grid, 256, 0, s>>>(m, (const int32_t*)lut, (uint32_t*)p->out, a);
+  };
+  if (p->logits) gather((const uint8_t*)cls);
+  else if (p->cls_bytes == 1) gather((const uint8_t*)p->cls + first);
+  else gather((const int32_t*)p->cls + first);
   MISEG_LAUNCH_CHECK("label_export gather");
   return MISEG_OK;
 }

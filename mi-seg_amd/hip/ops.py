@@ -1786,20 +1786,66 @@ def first_max_argmax(x):
     return arg
 
 
-def label_export(logits, tables, axes, lut, dtype=torch.uint16):
-    """[nz, ny, nx] label map (C-contiguous: a NIfTI file's Fortran order) of out[z][y][x] = lut[argmax_c logits[c][i_D][i_H][i_W]], the
-    logits index along axes[a] being tables[a][coordinate a] for the output axes a = X, Y, Z (miseg_label_export).  logits fp32 [(1,) C, D, H,
-    W]; tables three int32 vectors; axes a permutation of (0, 1, 2); lut int [C]; dtype uint8 / uint16 / uint32 (lut values truncated to it).
-    First-maximum argmax (first_max_argmax).  CPU logits take the same arithmetic in torch."""
-    if logits.dim() == 5 and logits.shape[0] == 1:
-        logits = logits[0]
-    if logits.dim() != 4 or logits.dtype != torch.float32:
-        raise ValueError("label_export: logits must be float32 [C, D, H, W]")
-    if dtype not in _EXPORT_DTYPES:
-        raise ValueError(f"label_export: dtype {dtype} (uint8 / uint16 / uint32)")
+_MAP_DTYPES = {torch.uint8: 1, torch.int32: 4}
+
+
+def keep_largest_component(logits=None, pred=None, num_classes=None, applied_labels=None, independent=True, connectivity=None, out_dtype=torch.uint8,
+                           stats=False):
+    """Keep-largest-connected-component filter of a class map (miseg_keep_largest, csrc/components.hip; training/postprocess.py states the
+    rules): [B, D, H, W] of out_dtype (uint8 / int32) in which every voxel of an applied class outside that class's largest component
+    (independent) or outside the largest component of all applied classes together (independent=False) is 0.  The map is the first-maximum
+    argmax of fp32 `logits` [B, C, D, H, W], or the integer map `pred` [B, (1,) D, H, W] with `num_classes` classes (values outside
+    [0, num_classes) are copied through).  applied_labels: None = every class but 0.  connectivity 1 / 2 / 3 (None = 3).  stats=True also
+    returns int64 [B, C, 3]: voxels of class c before, kept, components rooted in class c.  Only enqueues (no read-back): graph-capturable.
+    CPU tensors take the numpy restatement (postprocess.keep_largest_numpy)."""
+    from ..training import postprocess as PP
+    if (logits is None) == (pred is None):
+        raise ValueError("keep_largest_component: exactly one of logits / pred")
+    if out_dtype not in _MAP_DTYPES:
+        raise ValueError(f"keep_largest_component: out_dtype {out_dtype} (uint8 / int32)")
+    conn = PP.check_connectivity(connectivity)
+    if logits is not None:
+        if logits.dtype != torch.float32 or logits.dim() != 5:
+            raise ValueError("keep_largest_component: logits must be float32 [B, C, D, H, W]")
+        B, Cc, D, H, W = logits.shape
+        if num_classes is not None and int(num_classes) != Cc:
+            raise ValueError(f"keep_largest_component: num_classes {num_classes} for logits of {Cc} channels")
+        src = logits = logits.contiguous()
+    else:
+        if num_classes is None:
+            raise ValueError("keep_largest_component: a class map needs num_classes")
+        if pred.dim() == 5 and pred.shape[1] == 1:
+            pred = pred[:, 0]
+        if pred.dim() != 4 or pred.dtype.is_floating_point or pred.dtype == torch.bool:
+            raise ValueError("keep_largest_component: pred must be an integer class map [B, (1,) D, H, W]")
+        B, Cc = pred.shape[0], int(num_classes)
+        D, H, W = pred.shape[1:]
+        if pred.dtype not in _MAP_DTYPES:
+            big = torch.iinfo(torch.int32).max
+            pred = pred.clamp(-1, big).to(torch.int32)      # whatever does not fit is no class either way
+        src = pred = pred.contiguous()
+    applied = PP.applied_mask(applied_labels, Cc)
+    if B < 1 or min(D, H, W) < 1 or max(D, H, W) > 65535 or D * H * W >= 2 ** 31:
+        raise ValueError(f"keep_largest_component: batch {B} of {D}x{H}x{W} volumes (sides 1..65535, below 2^31 voxels)")
+    if not src.is_cuda:
+        cls = torch.stack([first_max_argmax(x) for x in logits]) if logits is not None else pred
+        labels = [c for c in range(Cc) if (applied >> c) & 1]
+        out, st = PP.keep_largest_numpy(cls.numpy(), Cc, labels, independent, conn, return_stats=True)
+        out = torch.from_numpy(out).to(out_dtype)
+        return (out, torch.from_numpy(st)) if stats else out
+    dev = src.device
+    out = torch.empty(B, D, H, W, dtype=out_dtype, device=dev)
+    st = torch.empty(B, Cc, 3, dtype=torch.int64, device=dev) if stats else None
+    ws = torch.empty(max(int(L.load().miseg_keep_largest_workspace_bytes(B, D, H, W)), 1), dtype=torch.uint8, device=dev)
+    _call("miseg_keep_largest", L.KeepLargest(C.sizeof(L.KeepLargest), _ptr(logits), _ptr(pred), _MAP_DTYPES[pred.dtype] if pred is not None else 0,
+                                              B, Cc, D, H, W, applied, int(bool(independent)), conn, _ptr(ws), _ptr(out), _MAP_DTYPES[out_dtype], _ptr(st)))
+    return (out, st) if stats else out
+
+
+def _export_tables(Cc, dims, dev, tables, axes, lut):
+    """the checked arguments both forms of label_export share: (lut as int64 on dev, the three int32 tables, per logits axis (first index, count))"""
     if sorted(int(a) for a in axes) != [0, 1, 2] or len(tables) != 3:
         raise ValueError(f"label_export: axes {tuple(axes)} are not a permutation of (0, 1, 2)")
-    Cc, dims, dev = logits.shape[0], logits.shape[1:], logits.device
     if not 1 <= Cc <= 64:
         raise ValueError(f"label_export: {Cc} channels (1..64)")
     lut = torch.as_tensor(lut).to(device=dev, dtype=torch.int64)
@@ -1816,6 +1862,27 @@ def label_export(logits, tables, axes, lut, dtype=torch.uint16):
             raise ValueError(f"label_export: table {'XYZ'[a]} spans [{lo}, {hi}], outside the logits side {dims[k]}")
         tabs.append(t)
         box[k] = (lo, hi - lo + 1)
+    return lut, tabs, box
+
+
+def label_export(logits, tables, axes, lut, dtype=torch.uint16, pred=None):
+    """[nz, ny, nx] label map (C-contiguous: a NIfTI file's Fortran order) of out[z][y][x] = lut[argmax_c logits[c][i_D][i_H][i_W]], the
+    logits index along axes[a] being tables[a][coordinate a] for the output axes a = X, Y, Z (miseg_label_export).  logits fp32 [(1,) C, D, H,
+    W]; tables three int32 vectors; axes a permutation of (0, 1, 2); lut int [C]; dtype uint8 / uint16 / uint32 (lut values truncated to it).
+    First-maximum argmax (first_max_argmax).  CPU logits take the same arithmetic in torch.  pred= (with logits=None): an integer class map
+    [(1,) D, H, W] of len(lut) classes instead of the logits' argmax, e.g. keep_largest_component's; a value outside the classes is written as 0."""
+    if (logits is None) == (pred is None):
+        raise ValueError("label_export: exactly one of logits / pred")
+    if pred is not None:
+        return _label_export_map(pred, tables, axes, lut, dtype)
+    if logits.dim() == 5 and logits.shape[0] == 1:
+        logits = logits[0]
+    if logits.dim() != 4 or logits.dtype != torch.float32:
+        raise ValueError("label_export: logits must be float32 [C, D, H, W]")
+    if dtype not in _EXPORT_DTYPES:
+        raise ValueError(f"label_export: dtype {dtype} (uint8 / uint16 / uint32)")
+    Cc, dims, dev = logits.shape[0], logits.shape[1:], logits.device
+    lut, tabs, box = _export_tables(Cc, dims, dev, tables, axes, lut)
     n = [t.numel() for t in tabs]
     mask = (1 << (8 * _EXPORT_DTYPES[dtype])) - 1
     if not logits.is_cuda:
@@ -1833,6 +1900,35 @@ def label_export(logits, tables, axes, lut, dtype=torch.uint16):
     _call("miseg_label_export", L.LabelExport(C.sizeof(L.LabelExport), _ptr(logits), Cc, *dims, box[0][0], box[1][0], box[2][0], box[0][1], box[1][1],
                                               box[2][1], *n, *(int(a) for a in axes), *(_ptr(t) for t in tabs), _ptr(lut32), _ptr(ws), _ptr(out),
                                               _EXPORT_DTYPES[dtype]))
+    return out
+
+
+def _label_export_map(pred, tables, axes, lut, dtype):
+    """label_export of a given class map (miseg_label_export_params.cls): the gather reads the map in place, no argmax launch"""
+    if pred.dim() == 4 and pred.shape[0] == 1:
+        pred = pred[0]
+    if pred.dim() != 3 or pred.dtype not in _MAP_DTYPES:
+        raise ValueError("label_export: pred must be a uint8 / int32 class map [D, H, W]")
+    if dtype not in _EXPORT_DTYPES:
+        raise ValueError(f"label_export: dtype {dtype} (uint8 / uint16 / uint32)")
+    Cc, dims, dev = int(torch.as_tensor(lut).numel()), pred.shape, pred.device
+    lut, tabs, box = _export_tables(Cc, dims, dev, tables, axes, lut)
+    n = [t.numel() for t in tabs]
+    mask = (1 << (8 * _EXPORT_DTYPES[dtype])) - 1
+    if not pred.is_cuda:
+        cls = pred.long()
+        for k in range(3):
+            a = [int(v) for v in axes].index(k)
+            cls = cls.index_select(k, tabs[a].long())
+        cls = cls.permute(int(axes[2]), int(axes[1]), int(axes[0]))
+        known = (cls >= 0) & (cls < Cc)
+        return torch.where(known, (lut & mask)[cls.clamp(0, Cc - 1)], torch.zeros_like(cls)).to(dtype).contiguous()
+    pred = pred.contiguous()
+    out = torch.empty(n[2], n[1], n[0], dtype=dtype, device=dev)
+    lut32 = (lut & mask).to(torch.int32)
+    _call("miseg_label_export", L.LabelExport(C.sizeof(L.LabelExport), None, Cc, *dims, box[0][0], box[1][0], box[2][0], box[0][1], box[1][1],
+                                              box[2][1], *n, *(int(a) for a in axes), *(_ptr(t) for t in tabs), _ptr(lut32), None, _ptr(out),
+                                              _EXPORT_DTYPES[dtype], _ptr(pred), _MAP_DTYPES[pred.dtype]))
     return out
 
 

@@ -6,12 +6,15 @@ path (dice_from_logits + surface_distance_from_logits: no one-hot volume is buil
 / metric chain.  `additional_metrics` (reference utils/trainer.py:145-149,246-250): a GeneralizedDiceScore rides on the fused path, fed from the
 same miseg_dice_metric call as the Dice; any other metric object sends the batch down the unfused chain.  The checkpoint loading and MONAI's
 get_loaders of the reference's main() stay with the caller.  A HausdorffDistanceMetric (`hausdorff_distance`, DESIGN.md
-section 7.5) rides on the fused path too: its values and the surface distance's come out of ONE surface_metrics_from_logits call per batch."""
+section 7.5) rides on the fused path too: its values and the surface distance's come out of ONE surface_metrics_from_logits call per batch.
+`keep_largest` (a postprocess.KeepLargestConnectedComponent) filters the argmax before every metric: on the fused path the
+filtered int32 class map is computed once on the device and feeds the Dice counts and ops.surface_metrics(pred=)."""
 import torch
 import torch.nn.functional as F
 
-from .metrics import (Cumulative, DiceMetric, GeneralizedDiceScore, HausdorffDistanceMetric, SurfaceDistanceMetric, dice_from_logits,
-                      generalized_dice_from_logits, surface_distance_from_logits, surface_metrics_from_logits)
+from .metrics import (Cumulative, DiceMetric, GeneralizedDiceScore, HausdorffDistanceMetric, SurfaceDistanceMetric, dice_from_class_map,
+                      dice_from_logits, generalized_dice_from_class_map, generalized_dice_from_logits, surface_distance_from_logits,
+                      surface_metrics_from_logits)
 
 
 class AsDiscrete:
@@ -43,6 +46,38 @@ def _fused(output, post_label, post_pred, acc_func, surface_distance, additional
             and (hausdorff_distance is None or type(hausdorff_distance) is HausdorffDistanceMetric))
 
 
+def _post_pred_filtered(post_pred, keep_largest):
+    """post_pred with the keep-largest transform between its argmax and its one-hot (after it, for a post-transform of the caller's own)"""
+    if isinstance(post_pred, AsDiscrete) and post_pred.argmax:
+        discrete, onehot = AsDiscrete(argmax=True), AsDiscrete(to_onehot=post_pred.to_onehot)
+        return lambda t: onehot(keep_largest(discrete(t)))
+    return lambda t: keep_largest(post_pred(t))
+
+
+def _filtered_batch(output, target, keep_largest, acc_func, surface_distance, additional_metrics, hausdorff_distance):
+    """the fused path with a keep-largest filter: (dice [B, C], surface distance or None, Hausdorff distance or None) from the filtered int32
+    class map, computed once on the device; the generalized Dice scores are extended here"""
+    from ..hip import ops
+    C = output.shape[1]
+    pred = keep_largest.class_map(logits=output.contiguous(), out_dtype=torch.int32)
+    dice = dice_from_class_map(pred, target, C)
+    for m in additional_metrics or ():
+        m.extend(generalized_dice_from_class_map(pred, target, C, m.include_background, m.weight_type))
+    sd, hd = surface_distance, hausdorff_distance
+    batch_surface = batch_hd = None
+    if sd is not None or hd is not None:
+        inc = bool((sd is not None and sd.include_background) or (hd is not None and hd.include_background))
+        want = (("asd",) if sd is not None else ()) + (("hd",) if hd is not None else ())
+        got = dict(zip(want, ops.surface_metrics(target, pred=pred, num_classes=C, include_background=inc, symmetric=sd.symmetric if sd is not None else True,
+                                                 percentile=hd.percentile if hd is not None else None, directed=hd.directed if hd is not None else False,
+                                                 want=want)))
+        if sd is not None:
+            batch_surface = got["asd"][:, int(inc and not sd.include_background):]
+        if hd is not None:
+            batch_hd = got["hd"][:, int(inc and not hd.include_background):]
+    return dice, batch_surface, batch_hd
+
+
 def compute_metric_modality(metric_func, include_background=0):
     """per-modality batch average of every class (NaNs left out, as do_metric_reduction's mean_batch) and their mean over the classes that
     have a value (reference test.py:17-43); prints and returns {key: value}"""
@@ -68,7 +103,7 @@ def compute_metric_modality(metric_func, include_background=0):
 
 
 def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=None, amp=True, surface_distance=None, results=None,
-         additional_metrics=None, hausdorff_distance=None):
+         additional_metrics=None, hausdorff_distance=None, keep_largest=None):
     """the reference's evaluation loop (test.py:46-123): returns the mean total Dice over the classes with a value (and the mean total surface
     distance when `surface_distance` is given).  `results`, a dict, receives the printed values: "dice_modality", "dice_total" and, with
     `surface_distance`, "surface_distance_modality", "surface_distance_total", each {printed key: value}.  `additional_metrics`: a list of
@@ -77,8 +112,12 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
     `hausdorff_distance`: a HausdorffDistanceMetric accumulated, printed and reset like the surface distance; `results` then also holds
     "hausdorff_distance_modality" and "hausdorff_distance_total".  The return value does not change.
     `model_inferer` is the caller's, e.g. the reference's partial(sliding_window_inference, predictor=model, roi_size=..., sw_batch_size=...,
-    overlap=...); MONAI's Gaussian window blend is the same partial with mode="gaussian" (and sigma_scale= / padding_mode= as wanted)."""
+    overlap=...); MONAI's Gaussian window blend is the same partial with mode="gaussian" (and sigma_scale= / padding_mode= as wanted).
+    `keep_largest`: a postprocess.KeepLargestConnectedComponent applied to the argmax before every metric (MONAI places it between
+    AsDiscrete(argmax=True) and the metrics); None leaves the loop exactly as it is without one."""
     model.eval()
+    if keep_largest is not None:
+        post_pred_kl = _post_pred_filtered(post_pred, keep_largest)
     acc_mod_cumulative = Cumulative()
     surface_mod_cumulative = Cumulative() if surface_distance is not None else None
     hausdorff_mod_cumulative = Cumulative() if hausdorff_distance is not None else None
@@ -90,6 +129,19 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
             with torch.autocast(device_type=dev_type, enabled=amp and dev_type == "cuda"):
                 output = model_inferer(data, modalities=modality) if model_inferer is not None else model(data, modality)
             fused = _fused(output, post_label, post_pred, acc_func, surface_distance, additional_metrics, hausdorff_distance)
+            if fused and keep_largest is not None:
+                dice, batch_surface, batch_hd = _filtered_batch(output, target, keep_largest, acc_func, surface_distance, additional_metrics,
+                                                                hausdorff_distance)
+                batch_acc = dice if acc_func.include_background else dice[:, 1:]
+                acc_func.extend(batch_acc)
+                acc_mod_cumulative.extend(batch_acc, modality)
+                if surface_distance is not None:
+                    surface_distance.extend(batch_surface)
+                    surface_mod_cumulative.extend(batch_surface, modality)
+                if hausdorff_distance is not None:
+                    hausdorff_distance.extend(batch_hd)
+                    hausdorff_mod_cumulative.extend(batch_hd, modality)
+                continue
             if fused:
                 C = output.shape[1]
                 if additional_metrics:      # the first score comes out of the Dice's own pass; a further one (other settings) re-reads the volume
@@ -103,7 +155,7 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
                 batch_acc = dice if acc_func.include_background else dice[:, 1:]
                 acc_func.extend(batch_acc)
             else:
-                val_output_convert = torch.stack([post_pred(t) for t in decollate_batch(output)])
+                val_output_convert = torch.stack([(post_pred if keep_largest is None else post_pred_kl)(t) for t in decollate_batch(output)])
                 val_labels_convert = torch.stack([post_label(t) for t in decollate_batch(target)])
                 batch_acc = acc_func(y_pred=val_output_convert, y=val_labels_convert)
                 for m in additional_metrics or ():

@@ -61,17 +61,51 @@ def compute_generalized_dice(y_pred, y, include_background=True, weight_type="sq
     y = y.to(y_pred.device)
     if not include_background and y_pred.shape[1] > 1:
         y_pred, y = y_pred[:, 1:], y[:, 1:]
-    from .losses import generalized_dice_weights
     dims = tuple(range(2, y_pred.dim()))
     yp, yt = y_pred.double(), y.double()
-    inter = (yp * yt).sum(dims)
-    y_o, y_pred_o = yt.sum(dims), yp.sum(dims)
+    return _generalized_dice_of_sums((yp * yt).sum(dims), yt.sum(dims), yp.sum(dims), weight_type)
+
+
+def _generalized_dice_of_sums(inter, y_o, y_pred_o, weight_type):
+    """compute_generalized_dice from the float64 [B, C'] sums of the kept classes: intersection, label, prediction"""
+    from .losses import generalized_dice_weights
     w = generalized_dice_weights(y_o, weight_type)
     numer = 2.0 * (inter * w).sum(1)
     denom = ((y_o + y_pred_o) * w).sum(1)
     score = numer / denom.clamp(min=1e-300)
     empty = torch.where(y_pred_o.sum(1) == 0, torch.ones_like(score), torch.zeros_like(score))
     return torch.where(denom == 0, empty, score).float()
+
+
+def class_map_counts(pred, label, num_classes):
+    """int64 [B, C] voxel counts (intersection, label, prediction) per class of two integer class maps [B, ...] (label: [B, (1,) ...]) from one
+    torch.bincount of the per-sample confusion matrix; values outside [0, C) belong to no class on either side"""
+    B, Cc = pred.shape[0], int(num_classes)
+    p, g = pred.reshape(B, -1).long(), label.to(pred.device).reshape(B, -1).long()
+    p = torch.where((p >= 0) & (p < Cc), p, torch.full_like(p, Cc))
+    g = torch.where((g >= 0) & (g < Cc), g, torch.full_like(g, Cc))
+    n = (Cc + 1) * (Cc + 1)
+    key = p * (Cc + 1) + g + n * torch.arange(B, device=pred.device).view(B, 1)
+    conf = torch.bincount(key.reshape(-1), minlength=B * n).view(B, Cc + 1, Cc + 1)
+    return conf.diagonal(dim1=1, dim2=2)[:, :Cc], conf.sum(1)[:, :Cc], conf.sum(2)[:, :Cc]
+
+
+def dice_from_class_map(pred, label, num_classes):
+    """dice_metric (fp32 [B, C], NaN where the label has no voxel of the class) of an already discrete prediction, from class_map_counts: the
+    one-hot volumes' float sums are these counts"""
+    inter, y_o, p_o = (t.float() for t in class_map_counts(pred, label, num_classes))
+    den = y_o + p_o
+    out = 2.0 * inter / den.clamp(min=1e-30)
+    out = torch.where(den > 0, out, torch.ones_like(out))
+    return torch.where(y_o > 0, out, torch.full_like(out, float("nan")))
+
+
+def generalized_dice_from_class_map(pred, label, num_classes, include_background=True, weight_type="square"):
+    """compute_generalized_dice (fp32 [B]) of an already discrete prediction, from class_map_counts"""
+    _check_weight_type(weight_type)
+    c0 = 0 if include_background or num_classes == 1 else 1
+    inter, y_o, p_o = (t[:, c0:].double() for t in class_map_counts(pred, label, num_classes))
+    return _generalized_dice_of_sums(inter, y_o, p_o, weight_type)
 
 
 def generalized_dice_from_logits(logits, label, num_classes, include_background=True, weight_type="square", with_dice=False):

@@ -1,7 +1,8 @@
 """Prediction export: the reference's predict_whs.py (35-114).  Each image of a data list's "test" entries goes through the prediction transforms
 (data/preprocess.py::load_image_for_prediction), the sliding-window inference with its modality, and then the way back - argmax, the inverse
 of the pad, the spacing and the orientation, the MM-WHS label codes - as one miseg_label_export call on the device, into a uint16 NIfTI
-label map in the image's own grid and affine."""
+label map in the image's own grid and affine.  --keep_largest puts MONAI's KeepLargestConnectedComponent between the
+argmax and the way back, on the device (hip/ops.py::keep_largest_component)."""
 import os
 import time
 from argparse import ArgumentParser
@@ -35,15 +36,25 @@ def label_lut(C, mapping=LABEL_MAP):
     return torch.tensor(lut, dtype=torch.int32)
 
 
-def invert_prediction(logits, geometry, lut, dtype=torch.uint16):
+def invert_prediction(logits, geometry, lut, dtype=torch.uint16, pred=None):
     """logits [(1,) C, D, H, W] on the padded, resampled RAS grid -> label map in the file's grid: an [X, Y, Z] view of a C-contiguous [Z, Y, X]
     buffer (the file's Fortran order), lut[first-maximum argmax] per voxel.  Device logits take miseg_label_export, CPU logits the same
-    arithmetic in torch (hip/ops.py::label_export)."""
-    shape = tuple(logits.shape[-3:])
+    arithmetic in torch (hip/ops.py::label_export).  pred= (logits None): a uint8 / int32 class map [(1,) D, H, W] of len(lut) classes on that
+    grid instead of the logits' argmax."""
+    src = logits if pred is None else pred
+    shape = tuple(src.shape[-3:])
     if shape != geometry.padded_shape:
         raise ValueError(f"invert_prediction: logits grid {shape} is not the geometry's padded grid {geometry.padded_shape}")
-    tables, axes = geometry.index_tables(logits.device if logits.is_cuda else None)
-    return ops.label_export(logits, tables, axes, lut, dtype).permute(2, 1, 0)
+    tables, axes = geometry.index_tables(src.device if src.is_cuda else None)
+    return ops.label_export(logits, tables, axes, lut, dtype, pred=pred).permute(2, 1, 0)
+
+
+def keep_largest_options(args):
+    """the keyword arguments of ops.keep_largest_component the command line asks for, None without --keep_largest"""
+    if not getattr(args, "keep_largest", False):
+        return None
+    return dict(applied_labels=getattr(args, "keep_largest_labels", None), independent=not getattr(args, "keep_largest_joint", False),
+                connectivity=getattr(args, "keep_largest_connectivity", 3))
 
 
 def to_host(label_xyz):
@@ -80,7 +91,17 @@ def predict_volume(model, item, args):
                                       padding_mode=getattr(args, "infer_padding_mode", "constant"))
     del image
     t2 = _sync(device)
-    label = invert_prediction(logits, geom, label_lut(logits.shape[1]))
+    keep = keep_largest_options(args)
+    filtered, tk = "", t2
+    if keep is None:
+        label = invert_prediction(logits, geom, label_lut(logits.shape[1]))
+    else:
+        cls, stats = ops.keep_largest_component(logits=logits, stats=True, **keep)
+        tk = _sync(device)
+        label = invert_prediction(None, geom, label_lut(logits.shape[1]), pred=cls[0])
+        removed = (stats[0, :, 0] - stats[0, :, 1]).tolist()          # (read back after the stage was timed)
+        filtered = f"keep-largest {1e3 * (tk - t2):.2f} ms (voxels removed per class: {removed}), "
+        del cls
     del logits                                    # the next volume's inference starts without this one's logits
     t3 = _sync(device)
     host = to_host(label)
@@ -90,7 +111,7 @@ def predict_volume(model, item, args):
     write_nifti(path, host, geom.affine, compresslevel=COMPRESSLEVEL, mtime=0)
     t5 = time.perf_counter()
     print(f"{os.path.basename(path)}: {'x'.join(str(s) for s in host.shape)} read+preprocess {t1 - t0:.3f} s, inference {t2 - t1:.3f} s, "
-          f"inverse {1e3 * (t3 - t2):.2f} ms, device-to-host {1e3 * (t4 - t3):.2f} ms, write {t5 - t4:.3f} s", flush=True)
+          f"{filtered}inverse {1e3 * (t3 - tk):.2f} ms, device-to-host {1e3 * (t4 - t3):.2f} ms, write {t5 - t4:.3f} s", flush=True)
     return path
 
 
@@ -115,6 +136,10 @@ def build_parser():
     parser.add_argument("--data_dir", default="dataset/MM-WHS", type=str, help="dataset directory(ies)")
     parser.add_argument("--json_list", default="CT_test.json", help="Json list(s) of input dataset(s)", type=str)
     parser.add_argument("--result_dir", default="dataset/MM_WHS/MM_WHS_test/CT/", help="Directory for results", type=str)
+    parser.add_argument("--keep_largest", action="store_true", help="keep only the largest connected component of each class before the export")
+    parser.add_argument("--keep_largest_labels", default=None, type=int, nargs="+", help="classes the filter applies to (default: all foreground)")
+    parser.add_argument("--keep_largest_joint", action="store_true", help="one largest component of all applied classes together (MONAI independent=False)")
+    parser.add_argument("--keep_largest_connectivity", default=3, type=int, choices=(1, 2, 3), help="6 / 18 / 26 neighbourhood")
     return parser
 
 
