@@ -875,6 +875,34 @@ typedef struct {
 size_t miseg_keep_largest_workspace_bytes(int B, int D, int H, int W);
 int miseg_keep_largest(const miseg_keep_largest_params* p, miseg_stream_t stream);
 
+/* Fill-holes post-processing (MONAI 1.1.0 transforms/utils.py::fill_holes / transforms/post/array.py::FillHoles, restated; parity unpinned -
+ * DESIGN.md section 7.8).  The class map is `cls` (cls_bytes 1: uint8, 4: int32), or the first-maximum argmax of fp32 `logits` as in
+ * miseg_keep_largest; exactly one of the two.  `applied`: bit L set = label L is filled; bit 0 (the background) is ignored.  The applied labels
+ * are processed in ascending order, each on the map as the previous one left it.  Pass L: a voxel is passable iff its value is not L (values
+ * outside [0, C) included); passable voxels are connected through the 6- / 18- / 26-neighbourhood of connectivity 1 / 2 / 3, never across a row,
+ * slice or sample end; a component holding a voxel on one of the six faces of the volume is open; every voxel of every other component becomes
+ * L, whatever it held.  A volume with a side of 1 is all face: nothing is filled.  Untouched voxels are copied through (a value outside [0, C)
+ * truncated to out_bytes).
+ *   csrc/components.hip: per label the keep-largest labelling (tile-local union-find in LDS, atomicMin unions across tile borders, flatten) on
+ * the passable voxels of the label's bounding box grown by one voxel, a flag on the root of every passable voxel on that box's faces, and a
+ * rewrite of the unflagged passable voxels; a uint8 working map is updated in place between the passes.  Integer atomics only, the result does
+ * not depend on scheduling, an absent label's launches return on a device-side empty box; the call only enqueues and reads nothing back: it
+ * can be captured into a graph.  C 1..64, every side 1..65535, each sample below 2^31 voxels, B >= 1.
+ *   stats (optional): int64 [B][C] = voxels whose value pass L changed to L (0 for an unapplied label). */
+typedef struct {
+  uint32_t struct_size;
+  const float* logits;             /* fp32 [B][C][D][H][W], or NULL */
+  const void* cls; int cls_bytes;  /* [B][D][H][W] uint8 / int32, or NULL */
+  int B, C, D, H, W;
+  uint64_t applied;
+  int connectivity;
+  void* workspace;                 /* miseg_fill_holes_workspace_bytes(B, D, H, W) bytes, uninitialised */
+  void* out; int out_bytes;        /* [B][D][H][W] of 1 (uint8) or 4 (int32) byte elements; may be `cls` itself when cls_bytes == out_bytes */
+  int64_t* stats;                  /* [B][C] or NULL */
+} miseg_fill_holes_params;
+size_t miseg_fill_holes_workspace_bytes(int B, int D, int H, int W);
+int miseg_fill_holes(const miseg_fill_holes_params* p, miseg_stream_t stream);
+
 /* sizeof() of a params struct as this library was compiled ("miseg_gemm_params", ...), 0 for an unknown name: bindings compare it with
  * their own mirror at load time (together with miseg_abi_version) so that header and binding cannot drift silently. */
 size_t miseg_abi_struct_size(const char* struct_name);

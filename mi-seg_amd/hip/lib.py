@@ -170,6 +170,9 @@ LabelExport = _struct("LabelExport", cname="miseg_label_export_params", fields=[
 KeepLargest = _struct("KeepLargest", cname="miseg_keep_largest_params", fields=[
     ("struct_size", u32), ("logits", vp), ("cls", vp), ("cls_bytes", i32), ("B", i32), ("C", i32), ("D", i32), ("H", i32), ("W", i32),
     ("applied", C.c_uint64), ("independent", i32), ("connectivity", i32), ("workspace", vp), ("out", vp), ("out_bytes", i32), ("stats", vp)])
+FillHoles = _struct("FillHoles", cname="miseg_fill_holes_params", fields=[
+    ("struct_size", u32), ("logits", vp), ("cls", vp), ("cls_bytes", i32), ("B", i32), ("C", i32), ("D", i32), ("H", i32), ("W", i32),
+    ("applied", C.c_uint64), ("connectivity", i32), ("workspace", vp), ("out", vp), ("out_bytes", i32), ("stats", vp)])
 Dropout = _struct("Dropout", cname="miseg_dropout_params", fields=[
     ("struct_size", u32), ("x", vp), ("ldx", i64), ("y", vp), ("ldy", i64), ("rows", i64), ("C", i32), ("dtype", i32), ("rows_per_sample", i64),
     ("p", f32), ("seed", C.c_uint64), ("stream_id", C.c_uint64), ("step_dev", vp)])
@@ -279,6 +282,8 @@ PROTOS = {
     "miseg_label_export": (i32, [C.POINTER(LabelExport), vp]),
     "miseg_keep_largest_workspace_bytes": (C.c_size_t, [i32, i32, i32, i32]),
     "miseg_keep_largest": (i32, [C.POINTER(KeepLargest), vp]),
+    "miseg_fill_holes_workspace_bytes": (C.c_size_t, [i32, i32, i32, i32]),
+    "miseg_fill_holes": (i32, [C.POINTER(FillHoles), vp]),
     "miseg_dropout": (i32, [C.POINTER(Dropout), vp]),
     "miseg_counter_add": (i32, [vp, C.c_uint64, vp]),
     "miseg_counter_copy": (i32, [vp, vp, vp]),

@@ -1842,6 +1842,58 @@ def keep_largest_component(logits=None, pred=None, num_classes=None, applied_lab
     return (out, st) if stats else out
 
 
+def fill_holes(logits=None, pred=None, num_classes=None, applied_labels=None, connectivity=None, out_dtype=torch.uint8, stats=False):
+    """Fill-holes filter of a class map (miseg_fill_holes, csrc/components.hip; training/postprocess.py and DESIGN.md section 7.8 state the
+    rules): [B, D, H, W] of out_dtype (uint8 / int32) in which, label after label in ascending order, every component of the voxels that are
+    not the label and that touches no face of the volume has become the label.  The map is the first-maximum argmax of fp32 `logits`
+    [B, C, D, H, W], or the integer map `pred` [B, (1,) D, H, W] with `num_classes` classes (a value outside [0, num_classes) is passable, is
+    overwritten inside a hole and copied through elsewhere).  applied_labels: None = every class but 0; 0 is discarded.  connectivity 1 / 2 / 3
+    (None = 3) is that of the hole.  stats=True also returns int64 [B, C]: voxels the pass of label c changed to c.  Only enqueues (no
+    read-back): graph-capturable.  CPU tensors take the numpy restatement (postprocess.fill_holes_numpy)."""
+    from ..training import postprocess as PP
+    if (logits is None) == (pred is None):
+        raise ValueError("fill_holes: exactly one of logits / pred")
+    if out_dtype not in _MAP_DTYPES:
+        raise ValueError(f"fill_holes: out_dtype {out_dtype} (uint8 / int32)")
+    conn = PP.check_connectivity(connectivity)
+    if logits is not None:
+        if logits.dtype != torch.float32 or logits.dim() != 5:
+            raise ValueError("fill_holes: logits must be float32 [B, C, D, H, W]")
+        B, Cc, D, H, W = logits.shape
+        if num_classes is not None and int(num_classes) != Cc:
+            raise ValueError(f"fill_holes: num_classes {num_classes} for logits of {Cc} channels")
+        src = logits = logits.contiguous()
+    else:
+        if num_classes is None:
+            raise ValueError("fill_holes: a class map needs num_classes")
+        if pred.dim() == 5 and pred.shape[1] == 1:
+            pred = pred[:, 0]
+        if pred.dim() != 4 or pred.dtype.is_floating_point or pred.dtype == torch.bool:
+            raise ValueError("fill_holes: pred must be an integer class map [B, (1,) D, H, W]")
+        B, Cc = pred.shape[0], int(num_classes)
+        D, H, W = pred.shape[1:]
+        if pred.dtype not in _MAP_DTYPES:
+            big = torch.iinfo(torch.int32).max
+            pred = pred.clamp(-1, big).to(torch.int32)      # whatever does not fit is no class either way
+        src = pred = pred.contiguous()
+    applied = PP.applied_mask(applied_labels, Cc) & ~1
+    if B < 1 or min(D, H, W) < 1 or max(D, H, W) > 65535 or D * H * W >= 2 ** 31:
+        raise ValueError(f"fill_holes: batch {B} of {D}x{H}x{W} volumes (sides 1..65535, below 2^31 voxels)")
+    if not src.is_cuda:
+        cls = torch.stack([first_max_argmax(x) for x in logits]) if logits is not None else pred
+        labels = [c for c in range(Cc) if (applied >> c) & 1]
+        out, st = PP.fill_holes_numpy(cls.numpy(), Cc, labels, conn, return_stats=True)
+        out = torch.from_numpy(out).to(out_dtype)
+        return (out, torch.from_numpy(st)) if stats else out
+    dev = src.device
+    out = torch.empty(B, D, H, W, dtype=out_dtype, device=dev)
+    st = torch.empty(B, Cc, dtype=torch.int64, device=dev) if stats else None
+    ws = torch.empty(max(int(L.load().miseg_fill_holes_workspace_bytes(B, D, H, W)), 1), dtype=torch.uint8, device=dev)
+    _call("miseg_fill_holes", L.FillHoles(C.sizeof(L.FillHoles), _ptr(logits), _ptr(pred), _MAP_DTYPES[pred.dtype] if pred is not None else 0,
+                                          B, Cc, D, H, W, applied, conn, _ptr(ws), _ptr(out), _MAP_DTYPES[out_dtype], _ptr(st)))
+    return (out, st) if stats else out
+
+
 def _export_tables(Cc, dims, dev, tables, axes, lut):
     """the checked arguments both forms of label_export share: (lut as int64 on dev, the three int32 tables, per logits axis (first index, count))"""
     if sorted(int(a) for a in axes) != [0, 1, 2] or len(tables) != 3:

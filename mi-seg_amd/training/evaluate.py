@@ -8,7 +8,8 @@ same miseg_dice_metric call as the Dice; any other metric object sends the batch
 get_loaders of the reference's main() stay with the caller.  A HausdorffDistanceMetric (`hausdorff_distance`, DESIGN.md
 section 7.5) rides on the fused path too: its values and the surface distance's come out of ONE surface_metrics_from_logits call per batch.
 `keep_largest` (a postprocess.KeepLargestConnectedComponent) filters the argmax before every metric: on the fused path the
-filtered int32 class map is computed once on the device and feeds the Dice counts and ops.surface_metrics(pred=)."""
+filtered int32 class map is computed once on the device and feeds the Dice counts and ops.surface_metrics(pred=).  `fill_holes` (a
+postprocess.FillHoles) follows it, or stands alone, in the same two places."""
 import torch
 import torch.nn.functional as F
 
@@ -46,20 +47,27 @@ def _fused(output, post_label, post_pred, acc_func, surface_distance, additional
             and (hausdorff_distance is None or type(hausdorff_distance) is HausdorffDistanceMetric))
 
 
-def _post_pred_filtered(post_pred, keep_largest):
-    """post_pred with the keep-largest transform between its argmax and its one-hot (after it, for a post-transform of the caller's own)"""
+def _post_pred_filtered(post_pred, filters):
+    """post_pred with the post-transforms `filters` (keep-largest, then fill-holes) between its argmax and its one-hot (after it, for a
+    post-transform of the caller's own)"""
+    def chain(t):
+        for f in filters:
+            t = f(t)
+        return t
     if isinstance(post_pred, AsDiscrete) and post_pred.argmax:
         discrete, onehot = AsDiscrete(argmax=True), AsDiscrete(to_onehot=post_pred.to_onehot)
-        return lambda t: onehot(keep_largest(discrete(t)))
-    return lambda t: keep_largest(post_pred(t))
+        return lambda t: onehot(chain(discrete(t)))
+    return lambda t: chain(post_pred(t))
 
 
-def _filtered_batch(output, target, keep_largest, acc_func, surface_distance, additional_metrics, hausdorff_distance):
-    """the fused path with a keep-largest filter: (dice [B, C], surface distance or None, Hausdorff distance or None) from the filtered int32
+def _filtered_batch(output, target, filters, acc_func, surface_distance, additional_metrics, hausdorff_distance):
+    """the fused path with post-transforms: (dice [B, C], surface distance or None, Hausdorff distance or None) from the filtered int32
     class map, computed once on the device; the generalized Dice scores are extended here"""
     from ..hip import ops
     C = output.shape[1]
-    pred = keep_largest.class_map(logits=output.contiguous(), out_dtype=torch.int32)
+    pred = filters[0].class_map(logits=output.contiguous(), out_dtype=torch.int32)
+    for f in filters[1:]:
+        pred = f.class_map(pred=pred, num_classes=C, out_dtype=torch.int32)
     dice = dice_from_class_map(pred, target, C)
     for m in additional_metrics or ():
         m.extend(generalized_dice_from_class_map(pred, target, C, m.include_background, m.weight_type))
@@ -103,7 +111,7 @@ def compute_metric_modality(metric_func, include_background=0):
 
 
 def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=None, amp=True, surface_distance=None, results=None,
-         additional_metrics=None, hausdorff_distance=None, keep_largest=None):
+         additional_metrics=None, hausdorff_distance=None, keep_largest=None, fill_holes=None):
     """the reference's evaluation loop (test.py:46-123): returns the mean total Dice over the classes with a value (and the mean total surface
     distance when `surface_distance` is given).  `results`, a dict, receives the printed values: "dice_modality", "dice_total" and, with
     `surface_distance`, "surface_distance_modality", "surface_distance_total", each {printed key: value}.  `additional_metrics`: a list of
@@ -114,10 +122,12 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
     `model_inferer` is the caller's, e.g. the reference's partial(sliding_window_inference, predictor=model, roi_size=..., sw_batch_size=...,
     overlap=...); MONAI's Gaussian window blend is the same partial with mode="gaussian" (and sigma_scale= / padding_mode= as wanted).
     `keep_largest`: a postprocess.KeepLargestConnectedComponent applied to the argmax before every metric (MONAI places it between
-    AsDiscrete(argmax=True) and the metrics); None leaves the loop exactly as it is without one."""
+    AsDiscrete(argmax=True) and the metrics); None leaves the loop exactly as it is without one.
+    `fill_holes`: a postprocess.FillHoles applied in the same place, after `keep_largest` when both are given; None changes nothing."""
     model.eval()
-    if keep_largest is not None:
-        post_pred_kl = _post_pred_filtered(post_pred, keep_largest)
+    filters = [f for f in (keep_largest, fill_holes) if f is not None]
+    if filters:
+        post_pred_kl = _post_pred_filtered(post_pred, filters)
     acc_mod_cumulative = Cumulative()
     surface_mod_cumulative = Cumulative() if surface_distance is not None else None
     hausdorff_mod_cumulative = Cumulative() if hausdorff_distance is not None else None
@@ -129,8 +139,8 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
             with torch.autocast(device_type=dev_type, enabled=amp and dev_type == "cuda"):
                 output = model_inferer(data, modalities=modality) if model_inferer is not None else model(data, modality)
             fused = _fused(output, post_label, post_pred, acc_func, surface_distance, additional_metrics, hausdorff_distance)
-            if fused and keep_largest is not None:
-                dice, batch_surface, batch_hd = _filtered_batch(output, target, keep_largest, acc_func, surface_distance, additional_metrics,
+            if fused and filters:
+                dice, batch_surface, batch_hd = _filtered_batch(output, target, filters, acc_func, surface_distance, additional_metrics,
                                                                 hausdorff_distance)
                 batch_acc = dice if acc_func.include_background else dice[:, 1:]
                 acc_func.extend(batch_acc)
@@ -155,7 +165,7 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
                 batch_acc = dice if acc_func.include_background else dice[:, 1:]
                 acc_func.extend(batch_acc)
             else:
-                val_output_convert = torch.stack([(post_pred if keep_largest is None else post_pred_kl)(t) for t in decollate_batch(output)])
+                val_output_convert = torch.stack([(post_pred_kl if filters else post_pred)(t) for t in decollate_batch(output)])
                 val_labels_convert = torch.stack([post_label(t) for t in decollate_batch(target)])
                 batch_acc = acc_func(y_pred=val_output_convert, y=val_labels_convert)
                 for m in additional_metrics or ():

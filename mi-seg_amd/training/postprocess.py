@@ -6,7 +6,12 @@ CPU tensors take keep_largest_numpy below, the restatement the device tests comp
 The rules: `applied` classes are filtered, every other value is left alone and connects nothing.  independent: per applied class c the
 components of {cls == c}; joint: the components of {cls in applied}, adjacent applied voxels of different classes connected.  The largest
 component stays (among equals the one holding the smallest linear voxel index), every other voxel of the group becomes 0.  connectivity
-1 / 2 / 3 (None = 3): 6 / 18 / 26 neighbours, never across the end of a row, slice or sample."""
+1 / 2 / 3 (None = 3): 6 / 18 / 26 neighbours, never across the end of a row, slice or sample.
+
+Fill-holes (MONAI 1.1.0 transforms/post/array.py::FillHoles and transforms/utils.py::fill_holes restated, DESIGN.md section 7.8): FillHoles,
+fill_holes_numpy and, on a HIP device, hip/ops.py::fill_holes.  The applied labels (never 0) are taken in ascending order, each on the map as
+the previous one left it; for label L the voxels that are not L are connected through the chosen neighbourhood, a component that holds a voxel
+on a face of the volume is open, and every voxel of every other component becomes L."""
 import numpy as np
 import torch
 
@@ -138,6 +143,106 @@ def keep_largest_numpy(cls, num_classes, applied_labels=None, independent=True, 
             stats[b, c, 1] = np.count_nonzero((vol == c) & ~dropped)
     out = out[0] if single else out
     return (out, stats[0] if single else stats) if return_stats else out
+
+
+def fill_labels(applied_labels, num_classes):
+    """the ascending list of filled labels: every class but 0 by default; 0, the background, is discarded"""
+    applied = applied_mask(applied_labels, num_classes) & ~1
+    return [c for c in range(1, num_classes) if (applied >> c) & 1]
+
+
+def _enclosed(passable, connectivity, nd):
+    """bool volume of the passable voxels in components that touch no face of the 3-d volume `passable`"""
+    if nd is not None:          # MONAI's recipe, literally: grow an empty seed from the border through the mask until nothing changes
+        tmp = np.zeros(passable.shape, dtype=bool)
+        nd.binary_dilation(tmp, structure=nd.generate_binary_structure(3, connectivity), iterations=-1, mask=passable, origin=0, border_value=1,
+                           output=tmp)
+        return passable & ~tmp
+    lab = label_components_numpy(passable, connectivity)
+    face = np.zeros(passable.shape, dtype=bool)
+    for ax in range(3):
+        sl = [slice(None)] * 3
+        for end in (0, -1):
+            sl[ax] = end
+            face[tuple(sl)] = True
+    open_roots = np.unique(lab[face & passable])
+    return passable & ~np.isin(lab, open_roots)
+
+
+def fill_holes_numpy(cls, num_classes, applied_labels=None, connectivity=None, use_scipy=True, return_stats=False):
+    """the device op's restatement on an integer class map [B, D, H, W] (or [D, H, W]): a copy with the holes of every applied label filled.
+    A value outside [0, num_classes) is passable like any other and is overwritten inside a hole.  use_scipy=False takes the numpy labelling
+    plus a face flag even where scipy imports.  return_stats: also int64 [B, C] = voxels whose value the pass of label c changed to c."""
+    conn = check_connectivity(connectivity)
+    labels = fill_labels(applied_labels, num_classes)
+    nd = _ndimage() if use_scipy else None
+    cls = np.asarray(cls)
+    single = cls.ndim == 3
+    vols = cls[None] if single else cls
+    if vols.ndim != 4:
+        raise ValueError(f"fill_holes_numpy: class map of shape {cls.shape} ([B,] D, H, W)")
+    out = vols.copy()
+    stats = np.zeros((vols.shape[0], num_classes), dtype=np.int64)
+    for b in range(out.shape[0]):
+        vol = out[b]
+        for c in labels:
+            passable = vol != c
+            if passable.all() or min(vol.shape) == 1:      # an absent label has no holes; with a side of 1 every voxel lies on a face
+                continue
+            hole = _enclosed(passable, conn, nd)
+            stats[b, c] = np.count_nonzero(hole)
+            vol[hole] = c
+    out = out[0] if single else out
+    return (out, stats[0] if single else stats) if return_stats else out
+
+
+class FillHoles:
+    """monai.transforms.FillHoles on one channel-first sample [C, *spatial] (up to 3 spatial dims; leading spatial axes of size 1 are added, so a
+    sample of fewer dims has a side of 1 and is returned as it is).  One channel: a class map of the labels 1..63 (applied_labels default: all of
+    them); values of 64 and above and non-integral values are passable like any other voxel, are overwritten inside a hole, and are no labels
+    themselves.  Several channels: one-hot - every applied channel (default: all but channel 0) is a binary map of its own (non-zero = the
+    label), sent through as an extra batch entry with two classes; as in MONAI the channel comes back as 0 / 1.  Device tensors go through the
+    fill-holes kernels, CPU tensors through fill_holes_numpy."""
+
+    def __init__(self, applied_labels=None, connectivity=None):
+        if isinstance(applied_labels, (int, np.integer)):
+            applied_labels = [applied_labels]
+        self.applied_labels = None if applied_labels is None else tuple(sorted({int(c) for c in applied_labels} - {0}))
+        self.connectivity = connectivity
+        check_connectivity(connectivity)
+
+    def class_map(self, logits=None, pred=None, num_classes=None, out_dtype=torch.int32, stats=False):
+        """the filter on a batch: fp32 logits [B, C, D, H, W] (first-maximum argmax) or an integer class map [B, D, H, W] -> [B, D, H, W]"""
+        from ..hip import ops
+        return ops.fill_holes(logits=logits, pred=pred, num_classes=num_classes, applied_labels=self.applied_labels, connectivity=self.connectivity,
+                              out_dtype=out_dtype, stats=stats)
+
+    def __call__(self, img):
+        from ..hip import ops
+        if not isinstance(img, torch.Tensor):
+            img = torch.as_tensor(img)
+        if img.dim() < 2 or img.dim() > 4:
+            raise ValueError(f"FillHoles: a channel-first sample [C, *spatial] with 1..3 spatial dims, got {tuple(img.shape)}")
+        sp = tuple(img.shape[1:])
+        vol_shape = (1,) * (3 - len(sp)) + sp
+        out = img.clone()
+        if img.shape[0] == 1:
+            whole = img[0].reshape((1,) + vol_shape).to(torch.int32)
+            whole = torch.where(whole.to(img.dtype) == img[0].reshape((1,) + vol_shape), whole, torch.full_like(whole, -1))      # a non-integral value is no label
+            res = self.class_map(pred=whole.contiguous(), num_classes=MAX_CLASSES)
+            changed = (res != whole).reshape(sp)
+            out[0][changed] = res.reshape(sp)[changed].to(img.dtype)
+            return out
+        applied = tuple(range(1, img.shape[0])) if self.applied_labels is None else self.applied_labels
+        if any(not 0 <= c < img.shape[0] for c in applied):
+            raise ValueError(f"applied labels {applied} for {img.shape[0]} channels")
+        if not applied:
+            return out
+        idx = torch.as_tensor(applied, device=img.device)
+        fg = (img[idx] != 0).reshape((len(applied),) + vol_shape).to(torch.uint8).contiguous()
+        res = ops.fill_holes(pred=fg, num_classes=2, applied_labels=(1,), connectivity=self.connectivity)
+        out[idx] = res.reshape((len(applied),) + sp).to(img.dtype)
+        return out
 
 
 class KeepLargestConnectedComponent:

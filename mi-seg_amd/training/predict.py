@@ -2,7 +2,8 @@
 (data/preprocess.py::load_image_for_prediction), the sliding-window inference with its modality, and then the way back - argmax, the inverse
 of the pad, the spacing and the orientation, the MM-WHS label codes - as one miseg_label_export call on the device, into a uint16 NIfTI
 label map in the image's own grid and affine.  --keep_largest puts MONAI's KeepLargestConnectedComponent between the
-argmax and the way back, on the device (hip/ops.py::keep_largest_component, DESIGN.md section 7.7)."""
+argmax and the way back, on the device (hip/ops.py::keep_largest_component, DESIGN.md section 7.7); --fill_holes puts MONAI's FillHoles
+there too, after the keep-largest filter when both are given (hip/ops.py::fill_holes, DESIGN.md section 7.8)."""
 import os
 import time
 from argparse import ArgumentParser
@@ -57,6 +58,13 @@ def keep_largest_options(args):
                 connectivity=getattr(args, "keep_largest_connectivity", 3))
 
 
+def fill_holes_options(args):
+    """the keyword arguments of ops.fill_holes the command line asks for, None without --fill_holes"""
+    if not getattr(args, "fill_holes", False):
+        return None
+    return dict(applied_labels=getattr(args, "fill_holes_labels", None), connectivity=getattr(args, "fill_holes_connectivity", 3))
+
+
 def to_host(label_xyz):
     """device [X, Y, Z] view of a [Z, Y, X] buffer -> numpy [X, Y, Z] in Fortran order, copied as it lies (no transpose on either side)"""
     buf = label_xyz.permute(2, 1, 0)
@@ -91,16 +99,23 @@ def predict_volume(model, item, args):
                                       padding_mode=getattr(args, "infer_padding_mode", "constant"))
     del image
     t2 = _sync(device)
-    keep = keep_largest_options(args)
+    keep, fill = keep_largest_options(args), fill_holes_options(args)
     filtered, tk = "", t2
-    if keep is None:
+    if keep is None and fill is None:
         label = invert_prediction(logits, geom, label_lut(logits.shape[1]))
     else:
-        cls, stats = ops.keep_largest_component(logits=logits, stats=True, **keep)
-        tk = _sync(device)
+        cls = None
+        if keep is not None:
+            cls, stats = ops.keep_largest_component(logits=logits, stats=True, **keep)
+            tk = _sync(device)
+            removed = (stats[0, :, 0] - stats[0, :, 1]).tolist()          # (read back after the stage was timed)
+            filtered = f"keep-largest {1e3 * (tk - t2):.2f} ms (voxels removed per class: {removed}), "
+        if fill is not None:
+            tf = tk
+            cls, filled = ops.fill_holes(logits=logits if cls is None else None, pred=cls, num_classes=logits.shape[1], stats=True, **fill)
+            tk = _sync(device)
+            filtered += f"fill-holes {1e3 * (tk - tf):.2f} ms (voxels filled per class: {filled[0].tolist()}), "
         label = invert_prediction(None, geom, label_lut(logits.shape[1]), pred=cls[0])
-        removed = (stats[0, :, 0] - stats[0, :, 1]).tolist()          # (read back after the stage was timed)
-        filtered = f"keep-largest {1e3 * (tk - t2):.2f} ms (voxels removed per class: {removed}), "
         del cls
     del logits                                    # the next volume's inference starts without this one's logits
     t3 = _sync(device)
@@ -140,6 +155,9 @@ def build_parser():
     parser.add_argument("--keep_largest_labels", default=None, type=int, nargs="+", help="classes the filter applies to (default: all foreground)")
     parser.add_argument("--keep_largest_joint", action="store_true", help="one largest component of all applied classes together (MONAI independent=False)")
     parser.add_argument("--keep_largest_connectivity", default=3, type=int, choices=(1, 2, 3), help="6 / 18 / 26 neighbourhood")
+    parser.add_argument("--fill_holes", action="store_true", help="fill the enclosed holes of each class before the export (after --keep_largest)")
+    parser.add_argument("--fill_holes_labels", default=None, type=int, nargs="+", help="classes whose holes are filled (default: all foreground)")
+    parser.add_argument("--fill_holes_connectivity", default=3, type=int, choices=(1, 2, 3), help="6 / 18 / 26 neighbourhood of a hole")
     return parser
 
 
