@@ -1789,6 +1789,48 @@ def first_max_argmax(x):
 _MAP_DTYPES = {torch.uint8: 1, torch.int32: 4}
 
 
+def _class_map_source(name, logits, pred, num_classes, applied_labels, connectivity, out_dtype):
+    """the checked arguments the connected-component filters share: (logits, pred, src, B, Cc, D, H, W, applied, conn) - of logits (fp32
+    [B, C, D, H, W]) / pred (uint8 or int32 [B, D, H, W]) the one that was given, contiguous, which is also src; the 64-bit set of applied
+    classes; the connectivity 1..3"""
+    from ..training import postprocess as PP
+    if (logits is None) == (pred is None):
+        raise ValueError(f"{name}: exactly one of logits / pred")
+    if out_dtype not in _MAP_DTYPES:
+        raise ValueError(f"{name}: out_dtype {out_dtype} (uint8 / int32)")
+    conn = PP.check_connectivity(connectivity)
+    if logits is not None:
+        if logits.dtype != torch.float32 or logits.dim() != 5:
+            raise ValueError(f"{name}: logits must be float32 [B, C, D, H, W]")
+        B, Cc, D, H, W = logits.shape
+        if num_classes is not None and int(num_classes) != Cc:
+            raise ValueError(f"{name}: num_classes {num_classes} for logits of {Cc} channels")
+        src = logits = logits.contiguous()
+    else:
+        if num_classes is None:
+            raise ValueError(f"{name}: a class map needs num_classes")
+        if pred.dim() == 5 and pred.shape[1] == 1:
+            pred = pred[:, 0]
+        if pred.dim() != 4 or pred.dtype.is_floating_point or pred.dtype == torch.bool:
+            raise ValueError(f"{name}: pred must be an integer class map [B, (1,) D, H, W]")
+        B, Cc = pred.shape[0], int(num_classes)
+        D, H, W = pred.shape[1:]
+        if pred.dtype not in _MAP_DTYPES:
+            big = torch.iinfo(torch.int32).max
+            pred = pred.clamp(-1, big).to(torch.int32)      # whatever does not fit is no class either way
+        src = pred = pred.contiguous()
+    applied = PP.applied_mask(applied_labels, Cc)
+    if B < 1 or min(D, H, W) < 1 or max(D, H, W) > 65535 or D * H * W >= 2 ** 31:
+        raise ValueError(f"{name}: batch {B} of {D}x{H}x{W} volumes (sides 1..65535, below 2^31 voxels)")
+    return logits, pred, src, B, Cc, D, H, W, applied, conn
+
+
+def _cpu_class_map(logits, pred, Cc, applied):
+    """what the numpy restatements take for CPU tensors: (the class map as an array, the list of applied labels)"""
+    cls = torch.stack([first_max_argmax(x) for x in logits]) if logits is not None else pred
+    return cls.numpy(), [c for c in range(Cc) if (applied >> c) & 1]
+
+
 def keep_largest_component(logits=None, pred=None, num_classes=None, applied_labels=None, independent=True, connectivity=None, out_dtype=torch.uint8,
                            stats=False):
     """Keep-largest-connected-component filter of a class map (miseg_keep_largest, csrc/components.hip; training/postprocess.py states the
@@ -1799,38 +1841,11 @@ def keep_largest_component(logits=None, pred=None, num_classes=None, applied_lab
     returns int64 [B, C, 3]: voxels of class c before, kept, components rooted in class c.  Only enqueues (no read-back): graph-capturable.
     CPU tensors take the numpy restatement (postprocess.keep_largest_numpy)."""
     from ..training import postprocess as PP
-    if (logits is None) == (pred is None):
-        raise ValueError("keep_largest_component: exactly one of logits / pred")
-    if out_dtype not in _MAP_DTYPES:
-        raise ValueError(f"keep_largest_component: out_dtype {out_dtype} (uint8 / int32)")
-    conn = PP.check_connectivity(connectivity)
-    if logits is not None:
-        if logits.dtype != torch.float32 or logits.dim() != 5:
-            raise ValueError("keep_largest_component: logits must be float32 [B, C, D, H, W]")
-        B, Cc, D, H, W = logits.shape
-        if num_classes is not None and int(num_classes) != Cc:
-            raise ValueError(f"keep_largest_component: num_classes {num_classes} for logits of {Cc} channels")
-        src = logits = logits.contiguous()
-    else:
-        if num_classes is None:
-            raise ValueError("keep_largest_component: a class map needs num_classes")
-        if pred.dim() == 5 and pred.shape[1] == 1:
-            pred = pred[:, 0]
-        if pred.dim() != 4 or pred.dtype.is_floating_point or pred.dtype == torch.bool:
-            raise ValueError("keep_largest_component: pred must be an integer class map [B, (1,) D, H, W]")
-        B, Cc = pred.shape[0], int(num_classes)
-        D, H, W = pred.shape[1:]
-        if pred.dtype not in _MAP_DTYPES:
-            big = torch.iinfo(torch.int32).max
-            pred = pred.clamp(-1, big).to(torch.int32)      # whatever does not fit is no class either way
-        src = pred = pred.contiguous()
-    applied = PP.applied_mask(applied_labels, Cc)
-    if B < 1 or min(D, H, W) < 1 or max(D, H, W) > 65535 or D * H * W >= 2 ** 31:
-        raise ValueError(f"keep_largest_component: batch {B} of {D}x{H}x{W} volumes (sides 1..65535, below 2^31 voxels)")
+    logits, pred, src, B, Cc, D, H, W, applied, conn = _class_map_source("keep_largest_component", logits, pred, num_classes, applied_labels,
+                                                                         connectivity, out_dtype)
     if not src.is_cuda:
-        cls = torch.stack([first_max_argmax(x) for x in logits]) if logits is not None else pred
-        labels = [c for c in range(Cc) if (applied >> c) & 1]
-        out, st = PP.keep_largest_numpy(cls.numpy(), Cc, labels, independent, conn, return_stats=True)
+        cls, labels = _cpu_class_map(logits, pred, Cc, applied)
+        out, st = PP.keep_largest_numpy(cls, Cc, labels, independent, conn, return_stats=True)
         out = torch.from_numpy(out).to(out_dtype)
         return (out, torch.from_numpy(st)) if stats else out
     dev = src.device
@@ -1851,38 +1866,11 @@ def fill_holes(logits=None, pred=None, num_classes=None, applied_labels=None, co
     (None = 3) is that of the hole.  stats=True also returns int64 [B, C]: voxels the pass of label c changed to c.  Only enqueues (no
     read-back): graph-capturable.  CPU tensors take the numpy restatement (postprocess.fill_holes_numpy)."""
     from ..training import postprocess as PP
-    if (logits is None) == (pred is None):
-        raise ValueError("fill_holes: exactly one of logits / pred")
-    if out_dtype not in _MAP_DTYPES:
-        raise ValueError(f"fill_holes: out_dtype {out_dtype} (uint8 / int32)")
-    conn = PP.check_connectivity(connectivity)
-    if logits is not None:
-        if logits.dtype != torch.float32 or logits.dim() != 5:
-            raise ValueError("fill_holes: logits must be float32 [B, C, D, H, W]")
-        B, Cc, D, H, W = logits.shape
-        if num_classes is not None and int(num_classes) != Cc:
-            raise ValueError(f"fill_holes: num_classes {num_classes} for logits of {Cc} channels")
-        src = logits = logits.contiguous()
-    else:
-        if num_classes is None:
-            raise ValueError("fill_holes: a class map needs num_classes")
-        if pred.dim() == 5 and pred.shape[1] == 1:
-            pred = pred[:, 0]
-        if pred.dim() != 4 or pred.dtype.is_floating_point or pred.dtype == torch.bool:
-            raise ValueError("fill_holes: pred must be an integer class map [B, (1,) D, H, W]")
-        B, Cc = pred.shape[0], int(num_classes)
-        D, H, W = pred.shape[1:]
-        if pred.dtype not in _MAP_DTYPES:
-            big = torch.iinfo(torch.int32).max
-            pred = pred.clamp(-1, big).to(torch.int32)      # whatever does not fit is no class either way
-        src = pred = pred.contiguous()
-    applied = PP.applied_mask(applied_labels, Cc) & ~1
-    if B < 1 or min(D, H, W) < 1 or max(D, H, W) > 65535 or D * H * W >= 2 ** 31:
-        raise ValueError(f"fill_holes: batch {B} of {D}x{H}x{W} volumes (sides 1..65535, below 2^31 voxels)")
+    logits, pred, src, B, Cc, D, H, W, applied, conn = _class_map_source("fill_holes", logits, pred, num_classes, applied_labels, connectivity, out_dtype)
+    applied &= ~1
     if not src.is_cuda:
-        cls = torch.stack([first_max_argmax(x) for x in logits]) if logits is not None else pred
-        labels = [c for c in range(Cc) if (applied >> c) & 1]
-        out, st = PP.fill_holes_numpy(cls.numpy(), Cc, labels, conn, return_stats=True)
+        cls, labels = _cpu_class_map(logits, pred, Cc, applied)
+        out, st = PP.fill_holes_numpy(cls, Cc, labels, conn, return_stats=True)
         out = torch.from_numpy(out).to(out_dtype)
         return (out, torch.from_numpy(st)) if stats else out
     dev = src.device

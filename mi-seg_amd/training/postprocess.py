@@ -196,6 +196,27 @@ def fill_holes_numpy(cls, num_classes, applied_labels=None, connectivity=None, u
     return (out, stats[0] if single else stats) if return_stats else out
 
 
+def _class_volume(img):
+    """one-channel sample [1, *spatial] -> (int32 [1, D, H, W] with -1 wherever the value is non-integral: no class / label; the spatial shape)"""
+    cls = img.reshape((1,) * (5 - img.dim()) + img.shape[1:])      # leading spatial axes of size 1 are added
+    whole = cls.to(torch.int32)
+    return torch.where(whole.to(cls.dtype) == cls, whole, torch.full_like(whole, -1)).contiguous(), img.shape[1:]
+
+
+def _applied_channels(img, applied_labels):
+    """index tensor of the applied channels of a one-hot sample [C, *spatial] (default: all but channel 0), validated; None if there are none"""
+    applied = tuple(range(1, img.shape[0])) if applied_labels is None else applied_labels
+    if any(not 0 <= c < img.shape[0] for c in applied):
+        raise ValueError(f"applied labels {applied} for {img.shape[0]} channels")
+    return torch.as_tensor(applied, device=img.device) if applied else None
+
+
+def _binary_batch(op, maps, connectivity):
+    """bool [N, *spatial] through the device op `op` as N samples of two classes (leading spatial axes of size 1 added) -> its result in maps' shape"""
+    vol = maps.reshape(maps.shape[:1] + (1,) * (4 - maps.dim()) + maps.shape[1:]).to(torch.uint8).contiguous()
+    return op(pred=vol, num_classes=2, applied_labels=(1,), connectivity=connectivity).reshape(maps.shape)
+
+
 class FillHoles:
     """monai.transforms.FillHoles on one channel-first sample [C, *spatial] (up to 3 spatial dims; leading spatial axes of size 1 are added, so a
     sample of fewer dims has a side of 1 and is returned as it is).  One channel: a class map of the labels 1..63 (applied_labels default: all of
@@ -223,25 +244,17 @@ class FillHoles:
             img = torch.as_tensor(img)
         if img.dim() < 2 or img.dim() > 4:
             raise ValueError(f"FillHoles: a channel-first sample [C, *spatial] with 1..3 spatial dims, got {tuple(img.shape)}")
-        sp = tuple(img.shape[1:])
-        vol_shape = (1,) * (3 - len(sp)) + sp
         out = img.clone()
         if img.shape[0] == 1:
-            whole = img[0].reshape((1,) + vol_shape).to(torch.int32)
-            whole = torch.where(whole.to(img.dtype) == img[0].reshape((1,) + vol_shape), whole, torch.full_like(whole, -1))      # a non-integral value is no label
-            res = self.class_map(pred=whole.contiguous(), num_classes=MAX_CLASSES)
+            whole, sp = _class_volume(img)
+            res = self.class_map(pred=whole, num_classes=MAX_CLASSES)
             changed = (res != whole).reshape(sp)
             out[0][changed] = res.reshape(sp)[changed].to(img.dtype)
             return out
-        applied = tuple(range(1, img.shape[0])) if self.applied_labels is None else self.applied_labels
-        if any(not 0 <= c < img.shape[0] for c in applied):
-            raise ValueError(f"applied labels {applied} for {img.shape[0]} channels")
-        if not applied:
+        idx = _applied_channels(img, self.applied_labels)
+        if idx is None:
             return out
-        idx = torch.as_tensor(applied, device=img.device)
-        fg = (img[idx] != 0).reshape((len(applied),) + vol_shape).to(torch.uint8).contiguous()
-        res = ops.fill_holes(pred=fg, num_classes=2, applied_labels=(1,), connectivity=self.connectivity)
-        out[idx] = res.reshape((len(applied),) + sp).to(img.dtype)
+        out[idx] = _binary_batch(ops.fill_holes, img[idx] != 0, self.connectivity).to(img.dtype)
         return out
 
 
@@ -267,14 +280,6 @@ class KeepLargestConnectedComponent:
         return ops.keep_largest_component(logits=logits, pred=pred, num_classes=num_classes, applied_labels=self.applied_labels,
                                           independent=self.independent, connectivity=self.connectivity, out_dtype=out_dtype, stats=stats)
 
-    def _binary(self, maps):
-        """bool [N, *spatial] -> the largest component of each"""
-        sp = maps.shape[1:]
-        vol = maps.reshape((maps.shape[0],) + (1,) * (3 - len(sp)) + tuple(sp)).to(torch.uint8).contiguous()
-        from ..hip import ops
-        conn = check_connectivity(self.connectivity)
-        return ops.keep_largest_component(pred=vol, num_classes=2, applied_labels=(1,), independent=True, connectivity=conn).reshape(maps.shape) != 0
-
     def __call__(self, img):
         if not isinstance(img, torch.Tensor):
             img = torch.as_tensor(img)
@@ -285,25 +290,16 @@ class KeepLargestConnectedComponent:
         if not is_onehot:
             if img.shape[0] != 1:
                 raise ValueError(f"KeepLargestConnectedComponent: a class map has one channel, got {img.shape[0]}")
-            sp = img.shape[1:]
-            cls = img[0].reshape((1,) + (1,) * (3 - len(sp)) + tuple(sp))
-            whole = cls.to(torch.int32)
-            whole = torch.where(whole.to(cls.dtype) == cls, whole, torch.full_like(whole, -1))      # a non-integral value is no class
-            res = self.class_map(pred=whole.contiguous(), num_classes=MAX_CLASSES)
+            whole, sp = _class_volume(img)
+            res = self.class_map(pred=whole, num_classes=MAX_CLASSES)
             out[0][((res == 0) & (whole > 0)).reshape(sp)] = 0
             return out
-        applied = tuple(range(1, img.shape[0])) if self.applied_labels is None else self.applied_labels
-        if any(not 0 <= c < img.shape[0] for c in applied):
-            raise ValueError(f"applied labels {applied} for {img.shape[0]} channels")
-        if not applied:
+        idx = _applied_channels(img, self.applied_labels)
+        if idx is None:
             return out
-        idx = torch.as_tensor(applied, device=img.device)
+        from ..hip import ops
         fg = img[idx] > 0
-        if self.independent:
-            keep = self._binary(fg)
-            out[idx] = torch.where(fg & ~keep, torch.zeros_like(img[idx]), img[idx])
-            return out
-        union = (img[idx] == 1).any(0, keepdim=True)
-        drop = union & ~self._binary(union)
+        maps = fg if self.independent else (img[idx] == 1).any(0, keepdim=True)      # each channel's own map, or the union of them
+        drop = maps & (_binary_batch(ops.keep_largest_component, maps, self.connectivity) == 0)
         out[idx] = torch.where(drop.expand_as(fg), torch.zeros_like(img[idx]), img[idx])
         return out

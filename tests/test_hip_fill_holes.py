@@ -11,18 +11,12 @@ import numpy as np
 import pytest
 import torch
 
+from components_common import large_batch, mods as _mods, snake
 from test_fill_holes_cpu import SMALL, blob_map, hand_cases, noise_map
-from test_hip_keep_largest import snake
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 BIG = (19, 21, 150)
-
-
-def _mods():
-    from mi_seg_amd.hip import lib, ops
-    from mi_seg_amd.training import postprocess
-    return ops, lib, postprocess
 
 
 def check(cls, Cc, applied=None, connectivity=3, min_filled=0):
@@ -134,6 +128,36 @@ def test_batch_of_two_fills_nothing_across_the_sample_end():
     for b in range(2):
         alone = ops.fill_holes(pred=torch.from_numpy(cls[b:b + 1]).to(DEV), num_classes=3)
         assert np.array_equal(alone.cpu().numpy()[0], got[b])
+
+
+def large_batch_patterns():
+    """8 class maps of 3 x 3 x 3 voxels with 3 classes: only the centre voxel can be a hole"""
+    pats = np.zeros((8, 3, 3, 3), dtype=np.uint8)
+    pats[0:2] = 1                          # solid label 1 with the centre 0: filled
+    pats[0:2, 1, 1, 1] = 0
+    pats[1, 1, 1, 0] = 0                   # the same with the hole cut through to the face w = 0: not filled
+    pats[2] = 2                            # solid label 2 around a voxel of label 1: filled with 2
+    pats[2, 1, 1, 1] = 1
+    rng = np.random.default_rng(0)
+    pats[3:] = rng.integers(0, 3, (5, 3, 3, 3))
+    return pats
+
+
+@pytest.mark.parametrize("out_dt", [torch.uint8, torch.int32], ids=["u8", "i32"])
+def test_batch_above_the_grid_limit(out_dt):
+    """65537 samples: more than a grid has rows, so every kernel's loop over the samples takes a second round; sample b is pattern b % 8 and the
+    restatement runs on the 8 patterns only"""
+    ops, _, PP = _mods()
+    pats = large_batch_patterns()
+    want, wst = PP.fill_holes_numpy(pats, 3, return_stats=True)
+    changed = [k for k in range(8) if not np.array_equal(want[k], pats[k])]
+    assert 2 <= len(changed) < 8, changed                              # some patterns are filled, some are left as they are
+    assert want[0, 1, 1, 1] == 1 and np.array_equal(want[1], pats[1]) and want[2, 1, 1, 1] == 2 and wst[0, 1] == 1 and wst[2, 2] == 1
+    k, vols = large_batch(pats)
+    got, st = ops.fill_holes(pred=torch.from_numpy(vols).to(DEV), num_classes=3, out_dtype=out_dt, stats=True)
+    assert got.dtype == out_dt and got.shape == vols.shape and st.shape == (len(k), 3)
+    assert torch.equal(got.cpu(), torch.from_numpy(want[k]).to(out_dt))
+    assert torch.equal(st.cpu(), torch.from_numpy(wst[k]))
 
 
 def test_64_classes():

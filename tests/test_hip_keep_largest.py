@@ -11,17 +11,12 @@ import numpy as np
 import pytest
 import torch
 
+from components_common import large_batch, mods as _mods, snake
 from test_keep_largest_cpu import oracle, random_map
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 BIG = (19, 21, 150)
-
-
-def _mods():
-    from mi_seg_amd.hip import lib, ops
-    from mi_seg_amd.training import postprocess
-    return ops, lib, postprocess
 
 
 def check(cls, Cc, applied=None, independent=True, connectivity=3, brute=False):
@@ -55,26 +50,6 @@ def test_single_voxels_and_slabs():
         for conn in (1, 2, 3):
             for independent in (True, False):
                 check(random_map(conn, shape, 3, p), 3, None, independent, conn, brute=True)
-
-
-def snake(shape, order, gap=2):
-    """a one-voxel-wide serpentine filling `shape`: full lines along axis order[2], stepping `gap` along order[1] with one-voxel connectors at
-    alternating ends, layers `gap` apart along order[0] joined where the last line ended"""
-    m = np.zeros(shape, dtype=bool)
-    v = np.moveaxis(m, order, (0, 1, 2))                       # a view: v[i, j, k] with k along the lines
-    n0, n1, n2 = v.shape
-    rows, k_at = list(range(0, n1, gap)), 0
-    for li, i in enumerate(range(0, n0, gap)):
-        js = rows if li % 2 == 0 else rows[::-1]
-        for ri, j in enumerate(js):
-            v[i, j, :] = True
-            k_at = n2 - 1 - k_at                                   # the line was walked to its other end
-            if ri + 1 < len(js):
-                lo, hi = sorted((j, js[ri + 1]))
-                v[i, lo:hi + 1, k_at] = True
-        if i + gap < n0:
-            v[i:i + gap + 1, js[-1], k_at] = True
-    return m
 
 
 @pytest.mark.parametrize("order,gap", [((0, 1, 2), 2), ((2, 1, 0), 2), ((1, 2, 0), 4), ((0, 1, 2), 4)])
@@ -138,6 +113,35 @@ def test_batch_of_two_connects_nothing_across_samples():
         for b in range(2):
             alone = ops.keep_largest_component(pred=torch.from_numpy(cls[b:b + 1]).to(DEV), num_classes=3, independent=independent)
             assert np.array_equal(alone.cpu().numpy()[0], got[b])
+
+
+def large_batch_patterns():
+    """8 class maps of 3 x 3 x 3 voxels with 3 classes"""
+    pats = np.zeros((8, 3, 3, 3), dtype=np.uint8)
+    pats[0, 0, 0, 0:2] = 1                 # two components of class 1, of 2 and of 3 voxels: the first goes
+    pats[0, 2, 2, :] = 1
+    pats[1, 0, 0, 0:2] = 1                 # two of 2 voxels each: the one holding linear index 0 stays
+    pats[1, 2, 2, 1:3] = 1
+    for k in range(2, 8):
+        pats[k] = random_map(k, (3, 3, 3), 3, 0.5)
+    return pats
+
+
+@pytest.mark.parametrize("out_dt", [torch.uint8, torch.int32], ids=["u8", "i32"])
+def test_batch_above_the_grid_limit(out_dt):
+    """65537 samples: more than a grid has rows, so every kernel's loop over the samples takes a second round; sample b is pattern b % 8 and the
+    restatement runs on the 8 patterns only"""
+    ops, _, PP = _mods()
+    pats = large_batch_patterns()
+    want, wst = PP.keep_largest_numpy(pats, 3, return_stats=True)
+    changed = [k for k in range(8) if not np.array_equal(want[k], pats[k])]
+    assert 2 <= len(changed) < 8, changed                              # some patterns lose voxels, some are left as they are
+    assert (want[0, 2, 2] == 1).all() and want[0].sum() == 3 and (want[1, 0, 0, 0:2] == 1).all() and want[1].sum() == 2
+    k, vols = large_batch(pats)
+    got, st = ops.keep_largest_component(pred=torch.from_numpy(vols).to(DEV), num_classes=3, out_dtype=out_dt, stats=True)
+    assert got.dtype == out_dt and got.shape == vols.shape and st.shape == (len(k), 3, 3)
+    assert torch.equal(got.cpu(), torch.from_numpy(want[k]).to(out_dt))
+    assert torch.equal(st.cpu(), torch.from_numpy(wst[k]))
 
 
 def test_64_classes():
