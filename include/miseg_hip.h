@@ -703,6 +703,32 @@ typedef struct {
 size_t miseg_surface_metrics_workspace_bytes(int B, int C, int D, int H, int W);
 int miseg_surface_metrics(const miseg_surface_metrics_params* p, miseg_stream_t stream);
 
+/* The two metrics above and / or the normalized surface Dice (NSD; MONAI's SurfaceDiceMetric / compute_surface_dice, parity unpinned) from ONE
+ * launch set, on the objects of DESIGN.md section 7.1 (rules in section 7.9): the same edge sets E_P, E_G, cropped to the box of P | G and
+ * squeezed, and the same one-way lists d(P -> G), d(G -> P).  With tau = thresholds[c'] (voxel units, one per class AFTER include_background):
+ *   nsd[b][c'] = (#{d in d(P -> G) : d <= tau} + #{d in d(G -> P) : d <= tau}) / (|d(P -> G)| + |d(G -> P)|)   in double;
+ * both lists empty (no foreground, or a union of one voxel) => NaN; one edge set empty => both lists all inf => 0.0.  `d <= tau` is the double
+ * comparison on sqrt(d^2); it is made on the exact integer d^2 against the largest integer k with sqrt((double)k) <= tau, so the result is
+ * bit-reproducible and equals the CPU restatement's.  `thresholds` is a HOST array, read during the call; every value finite and >= 0.  At
+ * least one of asd / hd / nsd; with nsd NULL the call is miseg_surface_metrics (same kernels), and asd / hd are bit for bit those of the two
+ * calls above in every case.  Same limits (C 1..64, every side 1..4096, fewer than 2^32 voxels with hd, synchronises, cannot be captured). */
+typedef struct {
+  uint32_t struct_size;
+  const float* logits; const int32_t* pred;
+  const void* label; int label_dtype;
+  int B, C, D, H, W;
+  int include_background, symmetric;   /* symmetric: of the ASD only */
+  void* workspace;                 /* miseg_surface_dice_workspace_bytes(B, C, D, H, W) bytes, uninitialised */
+  double* asd;                     /* out fp64 [B][C'] or NULL */
+  double* hd;                      /* out fp64 [B][C'] or NULL */
+  double percentile;               /* of hd: (0, 100]; <= 0: the maximum; > 100 (or NaN): MISEG_E_BADARG */
+  int directed;                    /* of hd */
+  double* nsd;                     /* out fp64 [B][C'] or NULL */
+  const double* thresholds;        /* of nsd: HOST array of C' = C - (include_background ? 0 : 1) tolerances */
+} miseg_surface_dice_params;
+size_t miseg_surface_dice_workspace_bytes(int B, int C, int D, int H, int W);
+int miseg_surface_dice(const miseg_surface_dice_params* p, miseg_stream_t stream);
+
 /* One optimiser step for every parameter of a model in ONE launch (lightning_monai.py:255-278: AdamW / Adam / SGD-nesterov), over the flat
  * fp32 gradient arena the weight-gradient kernels accumulate into.  Descriptor i: parameter tensor `param` of n elements whose gradient, and
  * whose two state slots, live at element offset `off` of grad / state1 / state2 (state2 unused by SGD).  used[i] == 0 => the parameter had no

@@ -19,8 +19,12 @@
 //   4b. surface_select_kernel: d^2 & 8191 of the edge voxels whose coarse bin is one of those (at most two), LDS histogram -> fine[item][dir][2][8192]
 //   5'. surface_finalize_hd_kernel: the two exact d^2 from the fine tables, sqrt in double, the percentile's interpolation, inf / NaN rules; the
 //       ASD by the same sums in the same order as pass 5
+// Normalized surface Dice at per-class tolerances: the share of both lists' distances that are <= tau_c, counted on the
+// integer d^2 against the host-made bound T_c = max {k : sqrt((double)k) <= tau_c} by the NSD instantiations of pass 4 / 4' (one uint32 count per
+// workgroup beside its partial) and divided once, in double, by passes 5 / 5'.
 // Integer counters and integer atomics only: no result depends on arrival order.
 #include "common.h"
+#include <float.h>
 #include <limits.h>
 #include <math.h>
 #include <algorithm>
@@ -59,6 +63,9 @@ struct SdSel { uint32_t bin_lo, rank_lo, bin_hi, rank_hi; };
 // the Hausdorff tables behind the buffers of sd_layout, indexed by item over all groups (like the partials)
 struct SdHdLayout { size_t coarse, fine, sel, total; };
 
+// the surface Dice's tables behind those: the per-workgroup counts of d^2 <= T (indexed like the partials) and T per class
+struct SdNsdLayout { size_t within, bound, total; };
+
 struct SdLayout {
   size_t pcls, lcls, boxes, index, items, partials, edges, buf0, buf1, stack, total;
   int64_t cap;       // voxels of boxes one group may hold (the volume S)
@@ -95,6 +102,27 @@ SdHdLayout sd_hd_layout(const SdLayout& L, int B, int C) {
   Q.sel = o;       o = align256(o + items * 2 * sizeof(SdSel));
   Q.total = o;
   return Q;
+}
+
+SdNsdLayout sd_nsd_layout(const SdHdLayout& Q, int B, int C, int H, int W) {
+  SdNsdLayout N;
+  const size_t nblk = (size_t)B * C * 2 * cdiv((long)H * W, 256);
+  size_t o = Q.total;
+  N.within = o;    o = align256(o + nblk * 4);
+  N.bound = o;     o = align256(o + (size_t)C * 4);
+  N.total = o;
+  return N;
+}
+
+// the largest integer k with sqrt((double)k) <= tau (tau >= 0, finite), at most 2^26 - 1: above every real d^2 (sides <= 4096), below SD_INF.
+// d <= tau <=> d^2 <= k for every d = sqrt((double)d2) the CPU restatement compares.
+int32_t sd_nsd_bound(double tau) {
+  const double lim = (double)((1 << 26) - 1);
+  const double t2 = tau * tau;
+  int64_t k = t2 < lim ? (int64_t)floor(t2) : (int64_t)lim;
+  while (k > 0 && sqrt((double)k) > tau) --k;
+  while (k + 1 <= (int64_t)lim && sqrt((double)(k + 1)) <= tau) ++k;
+  return (int32_t)k;
 }
 
 template <class L> __device__ __forceinline__ int sd_label_at(const L* lab, int64_t i) { return (int)lab[i]; }
@@ -325,14 +353,26 @@ __device__ __forceinline__ void block_sum_partial(double s, unsigned long long n
   }
 }
 
+// the workgroup's count of d^2 <= T (at most 256 x 4096), after block_sum_partial: its own LDS words, one more barrier
+__device__ __forceinline__ void block_sum_within(uint32_t m, uint32_t* __restrict__ slot) {
+  __shared__ uint32_t wm[4];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m += __shfl_xor(m, o, 64);
+  if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) *slot = wm[0] + wm[1] + wm[2] + wm[3];
+}
+
 // pass 4: along D, one thread per (direction, h, w) line, fused with the gather: direction 0 sums sqrt(d^2) over E_P (distance to E_G),
 // direction 1 over E_G (distance to E_P); one partial per workgroup, in slot dblk0 + the workgroup's index within the box.
 // HD: every edge voxel's d^2 is also left in dout (the layout of `in`) and counted by d^2 >> 13 (values without a seed fall into the last bin:
 // their lists are all inf and never selected from) in hist (LDS, SD_LBINS bins + the last one), then in coarse[item_base + item][dir][].
-template <bool HD>
+// NSD: the edge voxels with d^2 <= bound[class of the item] are counted too, one count per workgroup in within[the partial's slot].
+template <bool HD, bool NSD>
 __device__ __forceinline__ void sd_d_pass(const SdItem* __restrict__ items, int nitems, int64_t dblk_base, const int32_t* __restrict__ in,
                                           const uint8_t* __restrict__ edges, uint32_t* __restrict__ stack, SdPartial* __restrict__ partials, int item_base,
-                                          int32_t* __restrict__ dout, uint32_t* __restrict__ coarse, uint32_t* hist) {
+                                          int32_t* __restrict__ dout, uint32_t* __restrict__ coarse, uint32_t* hist, const int32_t* __restrict__ bound,
+                                          uint32_t* __restrict__ within) {
   const int k = find_item(items, nitems, (int64_t)blockIdx.x + dblk_base, [](const SdItem& x) { return x.dblk0; });
   const SdItem it = items[k];
   const int64_t nl = (int64_t)it.nh * it.nw, vol = nl * it.nd;
@@ -348,6 +388,9 @@ __device__ __forceinline__ void sd_d_pass(const SdItem* __restrict__ items, int 
   }
   double sum = 0.0;
   unsigned long long cnt = 0;
+  int32_t T = 0;
+  uint32_t hit = 0;
+  if constexpr (NSD) T = bound[it.c];
   if (l < nl) {
     const uint8_t* eb = edges + it.off / 2 + l;
     const uint8_t bit = dir == 0 ? 1 : 2;
@@ -357,6 +400,7 @@ __device__ __forceinline__ void sd_d_pass(const SdItem* __restrict__ items, int 
       if (eb[(int64_t)u * nl] & bit) {
         sum += sqrt((double)v);
         ++cnt;
+        if constexpr (NSD) hit += v <= T;
         if constexpr (HD) {
           o[(int64_t)u * nl] = v;
           const int bin = min(v >> SD_SHIFT, SD_BINS - 1);
@@ -368,6 +412,7 @@ __device__ __forceinline__ void sd_d_pass(const SdItem* __restrict__ items, int 
     });
   }
   block_sum_partial(sum, cnt, partials + it.dblk0 + lb);        // its barrier also closes the histogram
+  if constexpr (NSD) block_sum_within(hit, within + it.dblk0 + lb);
   if constexpr (HD) {
     for (int j = threadIdx.x; j <= SD_LBINS; j += 256) {
       const uint32_t c = hist[j];
@@ -378,14 +423,29 @@ __device__ __forceinline__ void sd_d_pass(const SdItem* __restrict__ items, int 
 
 __global__ void __launch_bounds__(256) surface_edt_d_gather_kernel(const SdItem* __restrict__ items, int nitems, int64_t dblk_base, const int32_t* __restrict__ in,
                                                                    const uint8_t* __restrict__ edges, uint32_t* __restrict__ stack, SdPartial* __restrict__ partials) {
-  sd_d_pass<false>(items, nitems, dblk_base, in, edges, stack, partials, 0, nullptr, nullptr, nullptr);
+  sd_d_pass<false, false>(items, nitems, dblk_base, in, edges, stack, partials, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 __global__ void __launch_bounds__(256) surface_edt_d_select_kernel(const SdItem* __restrict__ items, int nitems, int64_t dblk_base, const int32_t* __restrict__ in,
                                                                    const uint8_t* __restrict__ edges, uint32_t* __restrict__ stack, SdPartial* __restrict__ partials,
                                                                    int item_base, int32_t* __restrict__ dout, uint32_t* __restrict__ coarse) {
   __shared__ uint32_t hist[SD_LBINS + 1];
-  sd_d_pass<true>(items, nitems, dblk_base, in, edges, stack, partials, item_base, dout, coarse, hist);
+  sd_d_pass<true, false>(items, nitems, dblk_base, in, edges, stack, partials, item_base, dout, coarse, hist, nullptr, nullptr);
+}
+
+// passes 4 and 4' with the surface Dice's count
+__global__ void __launch_bounds__(256) surface_edt_d_gather_nsd_kernel(const SdItem* __restrict__ items, int nitems, int64_t dblk_base, const int32_t* __restrict__ in,
+                                                                       const uint8_t* __restrict__ edges, uint32_t* __restrict__ stack, SdPartial* __restrict__ partials,
+                                                                       const int32_t* __restrict__ bound, uint32_t* __restrict__ within) {
+  sd_d_pass<false, true>(items, nitems, dblk_base, in, edges, stack, partials, 0, nullptr, nullptr, nullptr, bound, within);
+}
+
+__global__ void __launch_bounds__(256) surface_edt_d_select_nsd_kernel(const SdItem* __restrict__ items, int nitems, int64_t dblk_base, const int32_t* __restrict__ in,
+                                                                       const uint8_t* __restrict__ edges, uint32_t* __restrict__ stack, SdPartial* __restrict__ partials,
+                                                                       int item_base, int32_t* __restrict__ dout, uint32_t* __restrict__ coarse,
+                                                                       const int32_t* __restrict__ bound, uint32_t* __restrict__ within) {
+  __shared__ uint32_t hist[SD_LBINS + 1];
+  sd_d_pass<true, true>(items, nitems, dblk_base, in, edges, stack, partials, item_base, dout, coarse, hist, bound, within);
 }
 
 // ranks of the percentile in an ascending list of n > 0 values (numpy's "linear" method; pct <= 0: the maximum): value = v_lo + (v_hi - v_lo) frac
@@ -526,27 +586,44 @@ __device__ __forceinline__ double sd_asd_value(const double* s, const unsigned l
   return tot == 0 ? nan : has_inf ? inf : sum / (double)tot;
 }
 
-// pass 5: one thread per (b, c')
+// the surface Dice of one box: its workgroups' counts of d^2 <= T in the order of sd_sum_partials, over both lists' lengths.  Both lists have
+// |E_P| + |E_G| entries in all whichever edge set is empty (DESIGN.md section 7.1 rule 4): NaN if that is 0; all inf, so 0, if one set is empty.
+__device__ __forceinline__ double sd_nsd_value(const SdItem& it, const uint32_t* __restrict__ within, const unsigned long long* n) {
+  if (n[0] == 0 && n[1] == 0) return __longlong_as_double(0x7ff8000000000000ll);
+  if (n[0] == 0 || n[1] == 0) return 0.0;
+  const int64_t nb = cdiv((int64_t)it.nh * it.nw, 256);
+  unsigned long long m = 0;
+  for (int64_t j = 0; j < 2 * nb; ++j) m += within[it.dblk0 + j];
+  return (double)m / (double)(n[0] + n[1]);
+}
+
+// pass 5: one thread per (b, c'); asd or nsd may be NULL (not both)
 __global__ void surface_finalize_kernel(const int32_t* __restrict__ index, const SdItem* __restrict__ items, const SdPartial* __restrict__ partials, int B, int C,
-                                        int c0, int symmetric, double* __restrict__ asd) {
+                                        int c0, int symmetric, double* __restrict__ asd, const uint32_t* __restrict__ within, double* __restrict__ nsd) {
   const int Cp = C - c0;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * Cp) return;
   const int b = i / Cp, c = c0 + i % Cp;
   const int k = index[b * C + c];
-  if (k < 0) { asd[i] = __longlong_as_double(0x7ff8000000000000ll); return; }            // no foreground: both edge sets empty
+  if (k < 0) {                                     // no foreground: both edge sets empty
+    if (asd) asd[i] = __longlong_as_double(0x7ff8000000000000ll);
+    if (nsd) nsd[i] = __longlong_as_double(0x7ff8000000000000ll);
+    return;
+  }
   const SdItem it = items[k];
   double s[2];
   unsigned long long n[2];
   sd_sum_partials(it, partials, s, n);
-  asd[i] = sd_asd_value(s, n, symmetric);
+  if (asd) asd[i] = sd_asd_value(s, n, symmetric);
+  if (nsd) nsd[i] = sd_nsd_value(it, within, n);
 }
 
-// pass 5': one workgroup per (b, c'): the ASD as pass 5 (thread 0), and the Hausdorff distance from the fine tables.  h(A -> B): NaN for an
+// pass 5': one workgroup per (b, c'): the ASD and the surface Dice as pass 5 (thread 0), and the Hausdorff distance from the fine tables.  h(A -> B): NaN for an
 // empty list, inf when one edge set is empty (every percentile: DESIGN.md section 7.5 rule 2), else the percentile of the list.
 __global__ void __launch_bounds__(256) surface_finalize_hd_kernel(const int32_t* __restrict__ index, const SdItem* __restrict__ items, const SdPartial* __restrict__ partials,
                                                                   const SdSel* __restrict__ sels, const uint32_t* __restrict__ fine, int C, int c0, int symmetric,
-                                                                  int directed, double pct, double* __restrict__ asd, double* __restrict__ hd) {
+                                                                  int directed, double pct, double* __restrict__ asd, double* __restrict__ hd,
+                                                                  const uint32_t* __restrict__ within, double* __restrict__ nsd) {
   __shared__ unsigned long long sh[257];
   __shared__ unsigned long long sn[2];
   __shared__ uint32_t res[4];
@@ -556,7 +633,7 @@ __global__ void __launch_bounds__(256) surface_finalize_hd_kernel(const int32_t*
   const int b = i / Cp, c = c0 + i % Cp;
   const int k = index[b * C + c];
   if (k < 0) {                                     // no foreground: both edge sets empty
-    if (threadIdx.x == 0) { if (asd) asd[i] = nan; hd[i] = nan; }
+    if (threadIdx.x == 0) { if (asd) asd[i] = nan; hd[i] = nan; if (nsd) nsd[i] = nan; }
     return;
   }
   if (threadIdx.x == 0) {
@@ -565,6 +642,7 @@ __global__ void __launch_bounds__(256) surface_finalize_hd_kernel(const int32_t*
     unsigned long long n[2];
     sd_sum_partials(it, partials, s, n);
     if (asd) asd[i] = sd_asd_value(s, n, symmetric);
+    if (nsd) nsd[i] = sd_nsd_value(it, within, n);
     sn[0] = n[0]; sn[1] = n[1];
   }
   __syncthreads();
@@ -624,14 +702,21 @@ extern "C" size_t miseg_surface_metrics_workspace_bytes(int B, int C, int D, int
   return sd_hd_layout(sd_layout(B, C, D, H, W), B, C).total;
 }
 
+extern "C" size_t miseg_surface_dice_workspace_bytes(int B, int C, int D, int H, int W) {
+  if (B <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
+  return sd_nsd_layout(sd_hd_layout(sd_layout(B, C, D, H, W), B, C), B, C, H, W).total;
+}
+
 namespace miseg {
 namespace {
 
-// both entry points: the ASD (p.asd), the Hausdorff distance (p.hd), or both from one launch set; `who` names the entry point in messages
-int surface_run(const miseg_surface_metrics_params& q, const char* who, hipStream_t s) {
-  const miseg_surface_metrics_params* p = &q;
+// the three entry points: the ASD (p.asd), the Hausdorff distance (p.hd), the surface Dice (p.nsd), or several from one launch set; `who` names
+// the entry point in messages
+int surface_run(const miseg_surface_dice_params& q, const char* who, hipStream_t s) {
+  const miseg_surface_dice_params* p = &q;
   MISEG_REQUIRE((p->logits != nullptr) != (p->pred != nullptr), MISEG_E_BADARG, "%s: exactly one of logits / pred", who);
-  MISEG_REQUIRE(p->label && p->workspace && (p->asd || p->hd), MISEG_E_BADARG, "%s: null pointer", who);
+  MISEG_REQUIRE(p->label && p->workspace && (p->asd || p->hd || p->nsd), MISEG_E_BADARG, "%s: null pointer", who);
+  MISEG_REQUIRE(!p->nsd || p->thresholds, MISEG_E_BADARG, "%s: nsd without thresholds", who);
   MISEG_REQUIRE(!p->hd || p->percentile <= 100.0, MISEG_E_BADARG, "%s: percentile %g (at most 100; <= 0: the maximum)", who, p->percentile);
   MISEG_REQUIRE(p->B > 0 && p->C >= 1 && p->C <= SD_MAXC, MISEG_E_UNSUPPORTED, "%s: B %d, C %d (1..%d)", who, p->B, p->C, SD_MAXC);
   MISEG_REQUIRE(p->D > 0 && p->H > 0 && p->W > 0 && p->D <= SD_MAXDIM && p->H <= SD_MAXDIM && p->W <= SD_MAXDIM, MISEG_E_UNSUPPORTED,
@@ -642,6 +727,13 @@ int surface_run(const miseg_surface_metrics_params& q, const char* who, hipStrea
   MISEG_REQUIRE(hipStreamIsCapturing(s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone, MISEG_E_UNSUPPORTED,
                 "%s: reads the class boxes back to the host, cannot be captured", who);
   const int B = p->B, C = p->C, c0 = p->include_background ? 0 : 1, Cp = C - c0;
+  std::vector<int32_t> hbound((size_t)C, 0);       // T per class c (class 0 without the background: never read)
+  if (p->nsd)
+    for (int j = 0; j < Cp; ++j) {
+      const double tau = p->thresholds[j];
+      MISEG_REQUIRE(tau >= 0.0 && tau <= DBL_MAX, MISEG_E_BADARG, "%s: thresholds[%d] = %g (finite and >= 0)", who, j, tau);
+      hbound[(size_t)c0 + j] = sd_nsd_bound(tau);
+    }
   if (Cp == 0) return MISEG_OK;
   const int64_t S = (int64_t)p->D * p->H * p->W;
   const SdLayout L = sd_layout(B, C, p->D, p->H, p->W);
@@ -660,6 +752,9 @@ int surface_run(const miseg_surface_metrics_params& q, const char* who, hipStrea
   uint32_t* coarse = (uint32_t*)(ws + Q.coarse);
   uint32_t* fine = (uint32_t*)(ws + Q.fine);
   SdSel* sels = (SdSel*)(ws + Q.sel);
+  const SdNsdLayout N = sd_nsd_layout(Q, B, C, p->H, p->W);      // read only with nsd: the other entry points' workspaces end before it
+  uint32_t* within = (uint32_t*)(ws + N.within);
+  int32_t* bound = (int32_t*)(ws + N.bound);
 
   // 1. class maps + boxes
   if (fill_words_async(boxes, 0x7fffffffu, (size_t)B * C * 6, s) != hipSuccess) return set_error(MISEG_E_LAUNCH, "%s: fill", who);
@@ -708,6 +803,8 @@ int surface_run(const miseg_surface_metrics_params& q, const char* who, hipStrea
     return set_error(MISEG_E_LAUNCH, "%s: index upload", who);
   if (!hitems.empty() && hipMemcpyAsync(items, hitems.data(), hitems.size() * sizeof(SdItem), hipMemcpyHostToDevice, s) != hipSuccess)
     return set_error(MISEG_E_LAUNCH, "%s: item upload", who);
+  if (p->nsd && hipMemcpyAsync(bound, hbound.data(), hbound.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+    return set_error(MISEG_E_LAUNCH, "%s: bound upload", who);
 
   // 3. per group: W pass, H pass, D pass + gather (the groups reuse the buffers; stream order serialises them).  With hd the group's select
   // passes follow at once: they read the d^2 the D pass left in buf0, which the next group's W pass overwrites.
@@ -726,11 +823,18 @@ int surface_run(const miseg_surface_metrics_params& q, const char* who, hipStrea
     surface_edt_h_kernel<<<(unsigned)hblocks, 256, 0, s>>>(items + f, n, buf0, buf1, stack);
     MISEG_LAUNCH_CHECK("surface_edt_h");
     if (!p->hd) {
-      surface_edt_d_gather_kernel<<<(unsigned)dblocks, 256, 0, s>>>(items + f, n, hitems[f].dblk0, buf1, edges, stack, partials);
+      if (p->nsd)
+        surface_edt_d_gather_nsd_kernel<<<(unsigned)dblocks, 256, 0, s>>>(items + f, n, hitems[f].dblk0, buf1, edges, stack, partials, bound, within);
+      else
+        surface_edt_d_gather_kernel<<<(unsigned)dblocks, 256, 0, s>>>(items + f, n, hitems[f].dblk0, buf1, edges, stack, partials);
       MISEG_LAUNCH_CHECK("surface_edt_d_gather");
       continue;
     }
-    surface_edt_d_select_kernel<<<(unsigned)dblocks, 256, 0, s>>>(items + f, n, hitems[f].dblk0, buf1, edges, stack, partials, f, buf0, coarse);
+    if (p->nsd)
+      surface_edt_d_select_nsd_kernel<<<(unsigned)dblocks, 256, 0, s>>>(items + f, n, hitems[f].dblk0, buf1, edges, stack, partials, f, buf0, coarse, bound,
+                                                                        within);
+    else
+      surface_edt_d_select_kernel<<<(unsigned)dblocks, 256, 0, s>>>(items + f, n, hitems[f].dblk0, buf1, edges, stack, partials, f, buf0, coarse);
     MISEG_LAUNCH_CHECK("surface_edt_d_select");
     surface_rank_kernel<<<dim3(n, 2), 256, 0, s>>>(coarse, f, p->percentile, sels);
     MISEG_LAUNCH_CHECK("surface_rank");
@@ -743,13 +847,14 @@ int surface_run(const miseg_surface_metrics_params& q, const char* who, hipStrea
     }
   }
   if (p->hd) {
-    surface_finalize_hd_kernel<<<B * Cp, 256, 0, s>>>(index, items, partials, sels, fine, C, c0, p->symmetric, p->directed, p->percentile, p->asd, p->hd);
+    surface_finalize_hd_kernel<<<B * Cp, 256, 0, s>>>(index, items, partials, sels, fine, C, c0, p->symmetric, p->directed, p->percentile, p->asd, p->hd,
+                                                      p->nsd ? within : nullptr, p->nsd);
     MISEG_LAUNCH_CHECK("surface_finalize_hd");
   } else {
-    surface_finalize_kernel<<<cdiv((long)B * Cp, 64), 64, 0, s>>>(index, items, partials, B, C, c0, p->symmetric, p->asd);
+    surface_finalize_kernel<<<cdiv((long)B * Cp, 64), 64, 0, s>>>(index, items, partials, B, C, c0, p->symmetric, p->asd, p->nsd ? within : nullptr, p->nsd);
     MISEG_LAUNCH_CHECK("surface_finalize");
   }
-  // the host vectors above are the sources of the two uploads: they must outlive them
+  // the host vectors above are the sources of the uploads: they must outlive them
   if (hipStreamSynchronize(s) != hipSuccess) return set_error(MISEG_E_LAUNCH, "%s: synchronize", who);
   return MISEG_OK;
 }
@@ -761,17 +866,30 @@ extern "C" int miseg_surface_distance(const miseg_surface_distance_params* p, mi
   MISEG_REQUIRE(p && p->struct_size == sizeof(miseg_surface_distance_params), MISEG_E_BADARG, "surface_distance: struct_size %u != %zu",
                 p ? p->struct_size : 0u, sizeof(miseg_surface_distance_params));
   MISEG_REQUIRE(p->asd, MISEG_E_BADARG, "surface_distance: null pointer");
-  miseg_surface_metrics_params q = {};
+  miseg_surface_dice_params q = {};
   q.struct_size = sizeof(q);
   q.logits = p->logits; q.pred = p->pred; q.label = p->label; q.label_dtype = p->label_dtype;
   q.B = p->B; q.C = p->C; q.D = p->D; q.H = p->H; q.W = p->W;
   q.include_background = p->include_background; q.symmetric = p->symmetric;
-  q.workspace = p->workspace; q.asd = p->asd;          // hd stays NULL: the launch set of the ASD alone
+  q.workspace = p->workspace; q.asd = p->asd;          // hd and nsd stay NULL: the launch set of the ASD alone
   return surface_run(q, "surface_distance", (hipStream_t)s_);
 }
 
 extern "C" int miseg_surface_metrics(const miseg_surface_metrics_params* p, miseg_stream_t s_) {
   MISEG_REQUIRE(p && p->struct_size == sizeof(miseg_surface_metrics_params), MISEG_E_BADARG, "surface_metrics: struct_size %u != %zu",
                 p ? p->struct_size : 0u, sizeof(miseg_surface_metrics_params));
-  return surface_run(*p, "surface_metrics", (hipStream_t)s_);
+  MISEG_REQUIRE(p->asd || p->hd, MISEG_E_BADARG, "surface_metrics: null pointer");
+  miseg_surface_dice_params q = {};
+  q.struct_size = sizeof(q);
+  q.logits = p->logits; q.pred = p->pred; q.label = p->label; q.label_dtype = p->label_dtype;
+  q.B = p->B; q.C = p->C; q.D = p->D; q.H = p->H; q.W = p->W;
+  q.include_background = p->include_background; q.symmetric = p->symmetric;
+  q.workspace = p->workspace; q.asd = p->asd; q.hd = p->hd; q.percentile = p->percentile; q.directed = p->directed;      // nsd stays NULL
+  return surface_run(q, "surface_metrics", (hipStream_t)s_);
+}
+
+extern "C" int miseg_surface_dice(const miseg_surface_dice_params* p, miseg_stream_t s_) {
+  MISEG_REQUIRE(p && p->struct_size == sizeof(miseg_surface_dice_params), MISEG_E_BADARG, "surface_dice: struct_size %u != %zu",
+                p ? p->struct_size : 0u, sizeof(miseg_surface_dice_params));
+  return surface_run(*p, "surface_dice", (hipStream_t)s_);
 }

@@ -145,6 +145,10 @@ SurfaceDistance = _struct("SurfaceDistance", cname="miseg_surface_distance_param
 SurfaceMetrics = _struct("SurfaceMetrics", cname="miseg_surface_metrics_params", fields=[
     ("struct_size", u32), ("logits", vp), ("pred", vp), ("label", vp), ("label_dtype", i32), ("B", i32), ("C", i32), ("D", i32), ("H", i32), ("W", i32),
     ("include_background", i32), ("symmetric", i32), ("workspace", vp), ("asd", vp), ("hd", vp), ("percentile", C.c_double), ("directed", i32)])
+SurfaceDice = _struct("SurfaceDice", cname="miseg_surface_dice_params", fields=[
+    ("struct_size", u32), ("logits", vp), ("pred", vp), ("label", vp), ("label_dtype", i32), ("B", i32), ("C", i32), ("D", i32), ("H", i32), ("W", i32),
+    ("include_background", i32), ("symmetric", i32), ("workspace", vp), ("asd", vp), ("hd", vp), ("percentile", C.c_double), ("directed", i32),
+    ("nsd", vp), ("thresholds", C.POINTER(C.c_double))])
 OptDesc = _struct("OptDesc", cname="miseg_opt_desc", fields=[("param", vp), ("off", i64), ("n", i32), ("block0", i32)])
 OptPackMap = _struct("OptPackMap", cname="miseg_opt_pack_map", fields=[("off", i64), ("param_index", i32), ("pad_", i32)])
 OptStep = _struct("OptStep", cname="miseg_opt_step_params", fields=[
@@ -273,6 +277,8 @@ PROTOS = {
     "miseg_surface_distance": (i32, [C.POINTER(SurfaceDistance), vp]),
     "miseg_surface_metrics_workspace_bytes": (C.c_size_t, [i32, i32, i32, i32, i32]),
     "miseg_surface_metrics": (i32, [C.POINTER(SurfaceMetrics), vp]),
+    "miseg_surface_dice_workspace_bytes": (C.c_size_t, [i32, i32, i32, i32, i32]),
+    "miseg_surface_dice": (i32, [C.POINTER(SurfaceDice), vp]),
     "miseg_opt_step": (i32, [C.POINTER(OptStep), vp]),
     "miseg_opt_step_pack_conv3": (i32, [C.POINTER(OptStep), vp, vp, i32, i32, i32, vp, vp]),
     "miseg_stitch_windows": (i32, [C.POINTER(Stitch), vp]),

@@ -9,12 +9,13 @@ get_loaders of the reference's main() stay with the caller
 section 7.5) rides on the fused path too: its values and the surface distance's come out of ONE surface_metrics_from_logits call per batch.
 `keep_largest` (a postprocess.KeepLargestConnectedComponent) filters the argmax before every metric: on the fused path the
 filtered int32 class map is computed once on the device and feeds the Dice counts and ops.surface_metrics(pred=).  `fill_holes` (a
-postprocess.FillHoles) follows it, or stands alone, in the same two places."""
+postprocess.FillHoles) follows it, or stands alone, in the same two places.  A SurfaceDiceMetric (`surface_dice`, DESIGN.md
+section 7.9) rides on the fused path as well: the surface distance, the Hausdorff distance and the surface Dice of a batch come out of ONE call."""
 import torch
 import torch.nn.functional as F
 
-from .metrics import (Cumulative, DiceMetric, GeneralizedDiceScore, HausdorffDistanceMetric, SurfaceDistanceMetric, dice_from_class_map,
-                      dice_from_logits, generalized_dice_from_class_map, generalized_dice_from_logits, surface_distance_from_logits,
+from .metrics import (Cumulative, DiceMetric, GeneralizedDiceScore, HausdorffDistanceMetric, SurfaceDiceMetric, SurfaceDistanceMetric,
+                      dice_from_class_map, dice_from_logits, generalized_dice_from_class_map, generalized_dice_from_logits, surface_distance_from_logits,
                       surface_metrics_from_logits)
 
 
@@ -36,7 +37,7 @@ def decollate_batch(t):
     return list(t.unbind(0))
 
 
-def _fused(output, post_label, post_pred, acc_func, surface_distance, additional_metrics=None, hausdorff_distance=None):
+def _fused(output, post_label, post_pred, acc_func, surface_distance, additional_metrics=None, hausdorff_distance=None, surface_dice=None):
     """the batch can skip the one-hot volumes: the post-transforms and metrics are the ones this module knows the semantics of"""
     C = output.shape[1]
     return (output.is_cuda and output.dtype == torch.float32 and output.dim() == 5 and C <= 64
@@ -44,7 +45,8 @@ def _fused(output, post_label, post_pred, acc_func, surface_distance, additional
             and isinstance(post_label, AsDiscrete) and not post_label.argmax and post_label.to_onehot == C
             and type(acc_func) is DiceMetric and (surface_distance is None or type(surface_distance) is SurfaceDistanceMetric)
             and all(type(m) is GeneralizedDiceScore for m in additional_metrics or ())
-            and (hausdorff_distance is None or type(hausdorff_distance) is HausdorffDistanceMetric))
+            and (hausdorff_distance is None or type(hausdorff_distance) is HausdorffDistanceMetric)
+            and (surface_dice is None or type(surface_dice) is SurfaceDiceMetric))
 
 
 def _post_pred_filtered(post_pred, filters):
@@ -60,10 +62,28 @@ def _post_pred_filtered(post_pred, filters):
     return lambda t: chain(post_pred(t))
 
 
-def _filtered_batch(output, target, filters, acc_func, surface_distance, additional_metrics, hausdorff_distance):
-    """the fused path with post-transforms: (dice [B, C], surface distance or None, Hausdorff distance or None) from the filtered int32
-    class map, computed once on the device; the generalized Dice scores are extended here"""
-    from ..hip import ops
+def _fused_surface_metrics(output, target, C, sd, hd, nsd, pred=None):
+    """(surface distance, Hausdorff distance, surface Dice) of a batch, None for a metric object that is None, from ONE launch set over the logits
+    `output` (or the int32 class map `pred`): computed with the background if any of the objects wants it, and sliced for those that do not
+    (the surface Dice then gets a tolerance for class 0 whose column is dropped)"""
+    inc = any(m.include_background for m in (sd, hd, nsd) if m is not None)
+    want = tuple(k for k, m in (("asd", sd), ("hd", hd), ("nsd", nsd)) if m is not None)
+    kw = dict(include_background=inc, symmetric=sd.symmetric if sd is not None else True, percentile=hd.percentile if hd is not None else None,
+              directed=hd.directed if hd is not None else False, want=want)
+    if nsd is not None:
+        kw["class_thresholds"] = ([0.0] if inc and not nsd.include_background else []) + list(nsd.class_thresholds)
+    if pred is not None:
+        from ..hip import ops
+        got = ops.surface_metrics(target, pred=pred, num_classes=C, **kw)
+    else:
+        got = surface_metrics_from_logits(output, target, C, **kw)
+    got = dict(zip(want, got))
+    return tuple(None if m is None else got[k][:, int(inc and not m.include_background):] for k, m in (("asd", sd), ("hd", hd), ("nsd", nsd)))
+
+
+def _filtered_batch(output, target, filters, acc_func, surface_distance, additional_metrics, hausdorff_distance, surface_dice=None):
+    """the fused path with post-transforms: (dice [B, C], surface distance or None, Hausdorff distance or None, surface Dice or None) from the
+    filtered int32 class map, computed once on the device; the generalized Dice scores are extended here"""
     C = output.shape[1]
     pred = filters[0].class_map(logits=output.contiguous(), out_dtype=torch.int32)
     for f in filters[1:]:
@@ -71,19 +91,10 @@ def _filtered_batch(output, target, filters, acc_func, surface_distance, additio
     dice = dice_from_class_map(pred, target, C)
     for m in additional_metrics or ():
         m.extend(generalized_dice_from_class_map(pred, target, C, m.include_background, m.weight_type))
-    sd, hd = surface_distance, hausdorff_distance
-    batch_surface = batch_hd = None
-    if sd is not None or hd is not None:
-        inc = bool((sd is not None and sd.include_background) or (hd is not None and hd.include_background))
-        want = (("asd",) if sd is not None else ()) + (("hd",) if hd is not None else ())
-        got = dict(zip(want, ops.surface_metrics(target, pred=pred, num_classes=C, include_background=inc, symmetric=sd.symmetric if sd is not None else True,
-                                                 percentile=hd.percentile if hd is not None else None, directed=hd.directed if hd is not None else False,
-                                                 want=want)))
-        if sd is not None:
-            batch_surface = got["asd"][:, int(inc and not sd.include_background):]
-        if hd is not None:
-            batch_hd = got["hd"][:, int(inc and not hd.include_background):]
-    return dice, batch_surface, batch_hd
+    batch_surface = batch_hd = batch_nsd = None
+    if surface_distance is not None or hausdorff_distance is not None or surface_dice is not None:
+        batch_surface, batch_hd, batch_nsd = _fused_surface_metrics(None, target, C, surface_distance, hausdorff_distance, surface_dice, pred=pred)
+    return dice, batch_surface, batch_hd, batch_nsd
 
 
 def compute_metric_modality(metric_func, include_background=0):
@@ -111,7 +122,7 @@ def compute_metric_modality(metric_func, include_background=0):
 
 
 def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=None, amp=True, surface_distance=None, results=None,
-         additional_metrics=None, hausdorff_distance=None, keep_largest=None, fill_holes=None):
+         additional_metrics=None, hausdorff_distance=None, keep_largest=None, fill_holes=None, surface_dice=None):
     """the reference's evaluation loop (test.py:46-123): returns the mean total Dice over the classes with a value (and the mean total surface
     distance when `surface_distance` is given).  `results`, a dict, receives the printed values: "dice_modality", "dice_total" and, with
     `surface_distance`, "surface_distance_modality", "surface_distance_total", each {printed key: value}.  `additional_metrics`: a list of
@@ -123,7 +134,9 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
     overlap=...); MONAI's Gaussian window blend is the same partial with mode="gaussian" (and sigma_scale= / padding_mode= as wanted).
     `keep_largest`: a postprocess.KeepLargestConnectedComponent applied to the argmax before every metric (MONAI places it between
     AsDiscrete(argmax=True) and the metrics); None leaves the loop exactly as it is without one.
-    `fill_holes`: a postprocess.FillHoles applied in the same place, after `keep_largest` when both are given; None changes nothing."""
+    `fill_holes`: a postprocess.FillHoles applied in the same place, after `keep_largest` when both are given; None changes nothing.
+    `surface_dice`: a SurfaceDiceMetric accumulated, printed and reset like the Hausdorff metric; `results` then also holds
+    "surface_dice_modality" and "surface_dice_total" (keys val_total_surface_dice/class{c}).  None changes nothing."""
     model.eval()
     filters = [f for f in (keep_largest, fill_holes) if f is not None]
     if filters:
@@ -131,6 +144,7 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
     acc_mod_cumulative = Cumulative()
     surface_mod_cumulative = Cumulative() if surface_distance is not None else None
     hausdorff_mod_cumulative = Cumulative() if hausdorff_distance is not None else None
+    nsd_mod_cumulative = Cumulative() if surface_dice is not None else None
     dev_type = torch.device(device).type
     with torch.no_grad():
         for batch in loader:
@@ -138,10 +152,10 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
             modality = batch["modality"].to(device) if "modality" in batch.keys() else None
             with torch.autocast(device_type=dev_type, enabled=amp and dev_type == "cuda"):
                 output = model_inferer(data, modalities=modality) if model_inferer is not None else model(data, modality)
-            fused = _fused(output, post_label, post_pred, acc_func, surface_distance, additional_metrics, hausdorff_distance)
+            fused = _fused(output, post_label, post_pred, acc_func, surface_distance, additional_metrics, hausdorff_distance, surface_dice)
             if fused and filters:
-                dice, batch_surface, batch_hd = _filtered_batch(output, target, filters, acc_func, surface_distance, additional_metrics,
-                                                                hausdorff_distance)
+                dice, batch_surface, batch_hd, batch_nsd = _filtered_batch(output, target, filters, acc_func, surface_distance, additional_metrics,
+                                                                           hausdorff_distance, surface_dice)
                 batch_acc = dice if acc_func.include_background else dice[:, 1:]
                 acc_func.extend(batch_acc)
                 acc_mod_cumulative.extend(batch_acc, modality)
@@ -151,6 +165,9 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
                 if hausdorff_distance is not None:
                     hausdorff_distance.extend(batch_hd)
                     hausdorff_mod_cumulative.extend(batch_hd, modality)
+                if surface_dice is not None:
+                    surface_dice.extend(batch_nsd)
+                    nsd_mod_cumulative.extend(batch_nsd, modality)
                 continue
             if fused:
                 C = output.shape[1]
@@ -171,6 +188,17 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
                 for m in additional_metrics or ():
                     m(y_pred=val_output_convert, y=val_labels_convert)
             acc_mod_cumulative.extend(batch_acc, modality)
+            if surface_dice is not None and fused:      # every surface metric of the batch from one launch set
+                batch_surface, batch_hd, batch_nsd = _fused_surface_metrics(output, target, output.shape[1], surface_distance, hausdorff_distance,
+                                                                            surface_dice)
+                for m, cum, val in ((surface_distance, surface_mod_cumulative, batch_surface), (hausdorff_distance, hausdorff_mod_cumulative, batch_hd),
+                                    (surface_dice, nsd_mod_cumulative, batch_nsd)):
+                    if m is not None:
+                        m.extend(val)
+                        cum.extend(val, modality)
+                continue
+            if surface_dice is not None:
+                nsd_mod_cumulative.extend(surface_dice(y_pred=val_output_convert, y=val_labels_convert), modality)
             if hausdorff_distance is not None:
                 hd = hausdorff_distance
                 if fused and surface_distance is not None:      # both from one launch set; with the background and sliced if the two disagree
@@ -209,6 +237,10 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
         print("Hausdorff Distance per modality")
         include_background_hd = int(not hausdorff_distance.include_background)
         results["hausdorff_distance_modality"] = compute_metric_modality(hausdorff_mod_cumulative, include_background_hd)
+    if surface_dice is not None:
+        print("Surface Dice per modality")
+        include_background_nsd = int(not surface_dice.include_background)
+        results["surface_dice_modality"] = compute_metric_modality(nsd_mod_cumulative, include_background_nsd)
     accuracy, not_nans = acc_func.aggregate()
     dict_acc_class = {f"val_total_dice/class{c + include_background_acc}": v for c, v in enumerate(accuracy.tolist())}
     print(dict_acc_class)
@@ -228,6 +260,14 @@ def test(model, loader, device, acc_func, post_label, post_pred, model_inferer=N
         results["hausdorff_distance_total"] = dict_hd_class
         hausdorff_distance.reset()
         hausdorff_mod_cumulative.reset()
+    if surface_dice is not None:
+        nsd = surface_dice.aggregate()
+        nsd = nsd[0] if isinstance(nsd, tuple) else nsd          # get_not_nans or not
+        dict_nsd_class = {f"val_total_surface_dice/class{c + include_background_nsd}": v for c, v in enumerate(nsd.reshape(-1).tolist())}
+        print(dict_nsd_class)
+        results["surface_dice_total"] = dict_nsd_class
+        surface_dice.reset()
+        nsd_mod_cumulative.reset()
     acc_func.reset()
     acc_mod_cumulative.reset()
     if additional_metrics:

@@ -1,7 +1,8 @@
 """Dice metric / AsDiscrete with MONAI 1.1.0 semantics (reference lightning_monai.py:68-79,190-195).  Parity unpinned (Appendix B).
 Average surface distance and the cumulative metric objects of the reference's evaluation script (test.py:17-171).
 Generalized Dice score of the reference's validation (tune.py:124-129,208-213).
-Hausdorff distance (MONAI 1.1.0 metrics/hausdorff_distance.py) on the surface-distance machinery."""
+Hausdorff distance (MONAI 1.1.0 metrics/hausdorff_distance.py) on the surface-distance machinery.
+Normalized surface Dice at per-class tolerances (MONAI's SurfaceDiceMetric / compute_surface_dice) on the same machinery."""
 import math
 import numpy as np
 import torch
@@ -306,21 +307,26 @@ def compute_hausdorff_distance(y_pred, y, include_background=False, distance_met
 
 
 def surface_metrics_from_logits(logits, label, num_classes, include_background=True, symmetric=True, percentile=None, directed=False,
-                                want=("asd", "hd")):
+                                want=("asd", "hd"), class_thresholds=None):
     """surface_distance_from_logits and the Hausdorff distance of the same argmax, fused: (asd, hd), fp64 [B, C'] each, from ONE launch set on a
-    HIP device (the classify pass and the three distance passes are shared; csrc/surface.hip); on CPU tensors the restatements above."""
+    HIP device (the classify pass and the three distance passes are shared; csrc/surface.hip); on CPU tensors the restatements above.  "nsd" in
+    `want` adds the normalized surface Dice at `class_thresholds` (one per class after include_background) from the same launch set."""
     _check_percentile(percentile)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if "nsd" in want:
+        class_thresholds = _check_thresholds(class_thresholds, num_classes - (0 if include_background else 1))
     if (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 5 and logits.shape[1] == num_classes and num_classes <= 64
             and max(logits.shape[2:]) <= 4096):
         from ..hip import ops
         return ops.surface_metrics(label.to(logits.device), logits=logits.contiguous(), include_background=include_background, symmetric=symmetric,
-                                   percentile=percentile, directed=directed, want=want)
+                                   percentile=percentile, directed=directed, want=want, class_thresholds=class_thresholds)
     classes = torch.arange(num_classes, device=logits.device).view(1, -1, *([1] * (logits.dim() - 2)))
     pred = logits.argmax(dim=1, keepdim=True) == classes
     lab = label.to(logits.device).reshape(logits.shape[0], 1, *logits.shape[2:]).long() == classes
     c0 = 0 if include_background else 1
     p, g = pred[:, c0:].cpu().numpy(), lab[:, c0:].cpu().numpy()
-    out = {"asd": lambda: average_surface_distance_numpy(p, g, symmetric), "hd": lambda: hausdorff_distance_numpy(p, g, percentile, directed)}
+    out = {"asd": lambda: average_surface_distance_numpy(p, g, symmetric), "hd": lambda: hausdorff_distance_numpy(p, g, percentile, directed),
+           "nsd": lambda: surface_dice_numpy(p, g, class_thresholds)}
     return tuple(torch.from_numpy(out[w]()).to(logits.device) for w in want)
 
 
@@ -328,6 +334,83 @@ def hausdorff_distance_from_logits(logits, label, num_classes, include_backgroun
     """AsDiscrete(argmax, to_onehot) on the logits + AsDiscrete(to_onehot) on the label + HausdorffDistanceMetric, fused: fp64 [B, C']"""
     return surface_metrics_from_logits(logits, label, num_classes, include_background=include_background, percentile=percentile, directed=directed,
                                        want=("hd",))[0]
+
+
+# ------------------------------------------------------------------------------------------ normalized surface Dice (DESIGN.md section 7.9)
+# MONAI's SurfaceDiceMetric / compute_surface_dice (parity unpinned) stated on the edge sets and one-way distance lists of the surface distance
+# above, crop and squeeze included: the share of both lists' distances that are <= the class's tolerance.
+
+def _check_thresholds(class_thresholds, num_kept):
+    """the tolerances as a list of floats: one per class after include_background, each finite and >= 0"""
+    if class_thresholds is None:
+        raise ValueError("class_thresholds is required: one tolerance per class.")
+    taus = [float(t) for t in class_thresholds]
+    if len(taus) != num_kept:
+        raise ValueError(f"number of classes ({num_kept}) does not match number of class thresholds ({len(taus)}).")
+    if any(not 0.0 <= t < math.inf for t in taus):
+        raise ValueError(f"all class thresholds need to be finite and >= 0, got {taus}.")
+    return taus
+
+
+def _check_subvoxels(use_subvoxels):
+    if use_subvoxels:
+        raise NotImplementedError("use_subvoxels=True is not implemented")
+
+
+def surface_dice_bound(tau):
+    """the largest integer k with sqrt(float(k)) <= tau, at most 2^26 - 1 (above every squared distance in a volume of sides <= 4096): the
+    integer bound the kernel compares squared distances with, d <= tau <=> d^2 <= k (csrc/surface.hip::sd_nsd_bound restated)"""
+    lim = (1 << 26) - 1
+    t2 = tau * tau
+    k = int(math.floor(t2)) if t2 < lim else lim
+    while k > 0 and math.sqrt(float(k)) > tau:
+        k -= 1
+    while k + 1 <= lim and math.sqrt(float(k + 1)) <= tau:
+        k += 1
+    return k
+
+
+def surface_dice_numpy(pred, gt, class_thresholds, use_scipy=True):
+    """pred, gt: bool [B, C, *spatial], one tolerance per channel -> float64 [B, C]: (#{d(pred -> gt) <= tau} + #{d(gt -> pred) <= tau}) over
+    the two lists' lengths; NaN where both lists are empty, 0.0 where one edge set is empty (both lists all inf).  use_scipy as in
+    average_surface_distance_numpy."""
+    nd = _ndimage() if use_scipy else None
+    B, Cc = pred.shape[:2]
+    taus = _check_thresholds(class_thresholds, Cc)
+    nsd = np.empty((B, Cc))
+    for b, c in np.ndindex(B, Cc):
+        ep, eg = _mask_edges(pred[b, c], gt[b, c], nd)
+        d_pg, d_gp = _surface_distance(ep, eg, nd), _surface_distance(eg, ep, nd)
+        total = d_pg.shape[0] + d_gp.shape[0]
+        within = int((d_pg <= taus[c]).sum()) + int((d_gp <= taus[c]).sum())
+        nsd[b, c] = np.nan if total == 0 else np.float64(within) / np.float64(total)
+    return nsd
+
+
+def compute_surface_dice(y_pred, y, class_thresholds, include_background=False, distance_metric="euclidean", use_subvoxels=False):
+    """MONAI's compute_surface_dice on one-hot [B, C, *spatial] inputs -> float64 [B, C'] on the device of y_pred, with the rules of DESIGN.md
+    section 7.9.  On a HIP device with exclusive one-hot 3-D inputs: class maps into csrc/surface.hip; otherwise the CPU restatement."""
+    _check_metric(distance_metric)
+    _check_subvoxels(use_subvoxels)
+    if y_pred.shape != y.shape:
+        raise ValueError(f"y_pred and y should have same shapes, got {tuple(y_pred.shape)} and {tuple(y.shape)}.")
+    Cc = y_pred.shape[1]
+    taus = _check_thresholds(class_thresholds, Cc - (0 if include_background else 1))
+    if (y_pred.is_cuda and y_pred.dim() == 5 and Cc <= 64 and max(y_pred.shape[2:]) <= 4096 and
+            _exclusive_onehot(y_pred) and _exclusive_onehot(y.to(y_pred.device))):
+        from ..hip import ops
+        return ops.surface_metrics(y.to(y_pred.device).argmax(dim=1).to(torch.uint8), pred=y_pred.argmax(dim=1), num_classes=Cc,
+                                   include_background=include_background, want=("nsd",), class_thresholds=taus)[0]
+    if not include_background:
+        y_pred, y = y_pred[:, 1:], y[:, 1:]
+    nsd = surface_dice_numpy(y_pred.detach().cpu().numpy().astype(bool), y.detach().cpu().numpy().astype(bool), taus)
+    return torch.from_numpy(nsd).to(y_pred.device)
+
+
+def surface_dice_from_logits(logits, label, num_classes, class_thresholds, include_background=True):
+    """AsDiscrete(argmax, to_onehot) on the logits + AsDiscrete(to_onehot) on the label + SurfaceDiceMetric, fused: fp64 [B, C']"""
+    return surface_metrics_from_logits(logits, label, num_classes, include_background=include_background, want=("nsd",),
+                                       class_thresholds=class_thresholds)[0]
 
 
 # ------------------------------------------------------------------------------------------ cumulative metrics (MONAI 1.1.0 metrics/metric.py)
@@ -445,6 +528,22 @@ class HausdorffDistanceMetric(_CumulativeMetric):
     def _compute(self, y_pred, y):
         return compute_hausdorff_distance(y_pred, y, include_background=self.include_background, distance_metric=self.distance_metric,
                                           percentile=self.percentile, directed=self.directed)
+
+
+class SurfaceDiceMetric(_CumulativeMetric):
+    """monai.metrics.SurfaceDiceMetric on one-hot [B, C, ...] inputs (compute_surface_dice above), float64 [B, C']"""
+
+    def __init__(self, class_thresholds, include_background=False, distance_metric="euclidean", reduction="mean", get_not_nans=False,
+                 use_subvoxels=False):
+        _check_metric(distance_metric)
+        _check_subvoxels(use_subvoxels)
+        super().__init__(include_background, reduction, get_not_nans)
+        self.class_thresholds = _check_thresholds(class_thresholds, len(list(class_thresholds)) if class_thresholds is not None else 0)
+        self.distance_metric, self.use_subvoxels = distance_metric, use_subvoxels
+
+    def _compute(self, y_pred, y):
+        return compute_surface_dice(y_pred, y, self.class_thresholds, include_background=self.include_background,
+                                    distance_metric=self.distance_metric, use_subvoxels=self.use_subvoxels)
 
 
 class GeneralizedDiceScore(_CumulativeMetric):

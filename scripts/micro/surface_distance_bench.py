@@ -3,7 +3,9 @@
 logits.  Times the metric from logits with device events after warm-up (include_background True / False, symmetric), prints the bytes the
 passes move (from the shapes and the class boxes), the share of HBM peak, and the CPU restatement's time on a cropped volume.
 --combined [PERCENTILE] (default 95) also times the Hausdorff distance on the same kernels (miseg_surface_metrics): the
-ASD + HD call, the HD-only call and their workspace next to the ASD call's; --no-cpu leaves out the CPU restatement."""
+ASD + HD call, the HD-only call and their workspace next to the ASD call's; --dice [TOLERANCE] (default 2 voxels, every class) also times the
+normalized surface Dice (miseg_surface_dice, DESIGN.md section 7.9): ASD + HD + NSD in one call and the NSD alone, next to the ASD + HD call;
+--no-cpu leaves out the CPU restatement."""
 import argparse
 import os
 import sys
@@ -96,8 +98,25 @@ def combined(logits, label, pct):
     print(f"workspace: ASD {a} bytes, ASD + HD {b} bytes (+{b - a} = {(b - a) // (2 * C)} per (class, direction))")
 
 
+def dice(logits, label, pct, tau):
+    """ASD + HD in one call, ASD + HD + NSD in one call, NSD alone: medians of 5, and the workspace of the three entry points"""
+    from mi_seg_amd.hip import lib as L
+    for inc in (True, False):
+        kw = dict(include_background=inc, symmetric=True, percentile=pct, directed=False)
+        taus = [tau] * (C - (0 if inc else 1))
+        two_ms, (asd, hd) = median_ms(lambda: M.surface_metrics_from_logits(logits, label, C, **kw))
+        three_ms, (asd2, hd2, nsd) = median_ms(lambda: M.surface_metrics_from_logits(logits, label, C, want=("asd", "hd", "nsd"), class_thresholds=taus, **kw))
+        nsd_ms, nsd2 = median_ms(lambda: M.surface_dice_from_logits(logits, label, C, taus, include_background=inc))
+        assert torch.equal(asd, asd2) and torch.equal(hd, hd2) and torch.equal(nsd, nsd2)
+        print(f"include_background={inc!s:5}  ASD + HD{pct:g} {two_ms:7.2f} ms   ASD + HD{pct:g} + NSD in one call {three_ms:7.2f} ms (+{three_ms - two_ms:5.2f})   "
+              f"NSD alone {nsd_ms:7.2f} ms   nsd(tau = {tau:g}) {[round(v, 4) for v in nsd[0].tolist()]}")
+    a, b = L.load().miseg_surface_metrics_workspace_bytes(1, C, D, H, W), L.load().miseg_surface_dice_workspace_bytes(1, C, D, H, W)
+    print(f"workspace: ASD + HD {a} bytes, ASD + HD + NSD {b} bytes (+{b - a})")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dice", nargs="?", type=float, const=2.0, default=None, metavar="TOLERANCE")
     ap.add_argument("--combined", nargs="?", type=float, const=95.0, default=None, metavar="PERCENTILE")
     ap.add_argument("--no-cpu", action="store_true")
     args = ap.parse_args()
@@ -123,6 +142,8 @@ def main():
               f"of HBM peak  asd {[round(v, 3) for v in out[0].tolist()]}")
     if args.combined is not None:
         combined(logits, label, args.combined)
+    if args.dice is not None:
+        dice(logits, label, args.combined if args.combined is not None else 95.0, args.dice)
     if args.no_cpu:
         return
     # the CPU restatement (scipy.ndimage when it imports: MONAI's recipe) on a crop, one thread
