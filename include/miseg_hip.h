@@ -929,6 +929,32 @@ typedef struct {
 size_t miseg_fill_holes_workspace_bytes(int B, int D, int H, int W);
 int miseg_fill_holes(const miseg_fill_holes_params* p, miseg_stream_t stream);
 
+/* Flip test-time augmentation / model ensembling (MONAI 1.1.0 transforms/post/array.py::MeanEnsemble / VoteEnsemble and nnU-Net's mirror
+ * TTA, restated; parity unpinned - DESIGN.md section 7.10): folds ONE member's stitched logits into a running accumulator.
+ *   src: fp32 [B][C][D][H][W], the member's logits in the frame of the flipped volume; acc: fp32, same shape, in the volume's own frame.
+ *   flip: bit 0 / 1 / 2 = the member was predicted on the volume mirrored along D / H / W: the source voxel of acc[b][c][d][h][w] is
+ *     src[b][c][bit 0 ? D-1-d : d][bit 1 ? H-1-h : h][bit 2 ? W-1-w : w].
+ *   kind: the term t a voxel contributes - MEAN_LOGITS: t_c = x_c.  MEAN_PROB: t = softmax_c(x): the maximum subtracted (fmaxf from -inf),
+ *     expf, summed in channel order, times 1 / sum.  VOTE: t_c = 1 for the first-maximum argmax (a strict `>` scan from channel 0: a NaN in
+ *     channel 0 gives class 0, a NaN in a later channel never wins), 0 elsewhere; weight is ignored (every vote weighs 1).
+ *   acc' = fl(fl(acc + fl(weight[c] * t_c)) * out_scale[c]), fp32, every operation rounded on its own (no FMA); first != 0: "acc +" is absent
+ *     and acc is not read (it may be uninitialised memory); scaled == 0: "* out_scale[c]" is absent (the host sets it on the last member).
+ * One streaming pass: src is read once (C <= 16; more channels are read once per pass over them), acc is read unless first and written once.
+ * Refused before any launch (MISEG_E_BADARG): a null pointer, C outside 1..64, a dimension below 1, an unknown kind, flip outside 0..7, a
+ * non-finite or negative weight[c < C] (or out_scale[c < C] when scaled), src and acc ranges that overlap; MISEG_E_UNSUPPORTED: B * D * H *
+ * ceil(W / 4) of 2^32 or more (every element offset is 64-bit: a tensor may exceed 2^31 bytes).  The call only enqueues and reads nothing
+ * back: it can be captured into a graph. */
+enum { MISEG_ENSEMBLE_MEAN_LOGITS = 0, MISEG_ENSEMBLE_MEAN_PROB = 1, MISEG_ENSEMBLE_VOTE = 2 };
+typedef struct {
+  uint32_t struct_size;
+  const float* src; float* acc;
+  int B, C, D, H, W;
+  int flip, kind, first, scaled;
+  float weight[64];                /* per class; a scalar member weight is the same value repeated */
+  float out_scale[64];             /* per class, read when scaled != 0 */
+} miseg_ensemble_params;
+int miseg_ensemble_accumulate(const miseg_ensemble_params* p, miseg_stream_t stream);
+
 /* sizeof() of a params struct as this library was compiled ("miseg_gemm_params", ...), 0 for an unknown name: bindings compare it with
  * their own mirror at load time (together with miseg_abi_version) so that header and binding cannot drift silently. */
 size_t miseg_abi_struct_size(const char* struct_name);

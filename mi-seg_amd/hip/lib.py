@@ -180,6 +180,11 @@ FillHoles = _struct("FillHoles", cname="miseg_fill_holes_params", fields=[
 Dropout = _struct("Dropout", cname="miseg_dropout_params", fields=[
     ("struct_size", u32), ("x", vp), ("ldx", i64), ("y", vp), ("ldy", i64), ("rows", i64), ("C", i32), ("dtype", i32), ("rows_per_sample", i64),
     ("p", f32), ("seed", C.c_uint64), ("stream_id", C.c_uint64), ("step_dev", vp)])
+Ensemble = _struct("Ensemble", cname="miseg_ensemble_params", fields=[
+    ("struct_size", u32), ("src", vp), ("acc", vp), ("B", i32), ("C", i32), ("D", i32), ("H", i32), ("W", i32),
+    ("flip", i32), ("kind", i32), ("first", i32), ("scaled", i32), ("weight", f32 * 64), ("out_scale", f32 * 64)])
+ENSEMBLE_MEAN_LOGITS, ENSEMBLE_MEAN_PROB, ENSEMBLE_VOTE = 0, 1, 2      # MISEG_ENSEMBLE_*
+ENSEMBLE_KINDS = {"mean_logits": ENSEMBLE_MEAN_LOGITS, "mean_prob": ENSEMBLE_MEAN_PROB, "vote": ENSEMBLE_VOTE}
 AUG_MAX_SAMPLES = 16
 LABEL_F32, LABEL_I32, LABEL_I64, LABEL_U8 = 0, 1, 2, 3
 LOSS_DICE_FOCAL, LOSS_DICE_CE, LOSS_GDICE_FOCAL = 0, 1, 2
@@ -290,6 +295,7 @@ PROTOS = {
     "miseg_keep_largest": (i32, [C.POINTER(KeepLargest), vp]),
     "miseg_fill_holes_workspace_bytes": (C.c_size_t, [i32, i32, i32, i32]),
     "miseg_fill_holes": (i32, [C.POINTER(FillHoles), vp]),
+    "miseg_ensemble_accumulate": (i32, [C.POINTER(Ensemble), vp]),
     "miseg_dropout": (i32, [C.POINTER(Dropout), vp]),
     "miseg_counter_add": (i32, [vp, C.c_uint64, vp]),
     "miseg_counter_copy": (i32, [vp, vp, vp]),

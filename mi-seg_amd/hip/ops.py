@@ -2019,6 +2019,90 @@ def stitch_windows(win, out, starts, roi, count=None, slab=None, weight=None, ws
     return out
 
 
+# ------------------------------------------------------------------------------------------ flip TTA / model ensembling
+def _ensemble_vector(name, what, value, Cc):
+    """a scalar or per-class weight / scale as a list of Cc python floats rounded to fp32, finite and non-negative"""
+    v = torch.as_tensor(value, dtype=torch.float64).reshape(-1).cpu()
+    if v.numel() == 1:
+        v = v.repeat(Cc)
+    if v.numel() != Cc:
+        raise ValueError(f"{name}: {what} of {v.numel()} values for {Cc} classes (a scalar, or one value per class)")
+    if not bool(torch.isfinite(v).all()) or bool((v < 0).any()):
+        raise ValueError(f"{name}: {what} {v.tolist()} must be finite and non-negative")
+    return v.to(torch.float32).tolist()
+
+
+def _ensemble_args(name, src, acc, flip, kind, weight, out_scale):
+    if kind not in L.ENSEMBLE_KINDS:
+        raise ValueError(f"{name}: kind {kind!r} is not one of {tuple(L.ENSEMBLE_KINDS)}")
+    if not (torch.is_tensor(src) and torch.is_tensor(acc)) or src.dtype != torch.float32 or acc.dtype != torch.float32 or src.dim() != 5:
+        raise ValueError(f"{name}: src and acc must be float32 [B, C, D, H, W] tensors")
+    if src.shape != acc.shape or src.device != acc.device:
+        raise ValueError(f"{name}: src {tuple(src.shape)} on {src.device} and acc {tuple(acc.shape)} on {acc.device} differ")
+    if not (src.is_contiguous() and acc.is_contiguous()):
+        raise ValueError(f"{name}: src and acc must be contiguous")
+    Cc = src.shape[1]
+    if not 1 <= Cc <= 64 or min(src.shape) < 1:
+        raise ValueError(f"{name}: shape {tuple(src.shape)} (1..64 channels, no empty dimension)")
+    flip = tuple(flip)
+    if len(flip) != 3:
+        raise ValueError(f"{name}: flip {flip} is not one flag per spatial axis (D, H, W)")
+    bits = sum(1 << a for a in range(3) if flip[a])
+    w = _ensemble_vector(name, "weight", weight, Cc)
+    s = None if out_scale is None else _ensemble_vector(name, "out_scale", out_scale, Cc)
+    return bits, L.ENSEMBLE_KINDS[kind], w, s
+
+
+def ensemble_accumulate_torch(src, acc, *, flip=(False, False, False), kind="mean_logits", weight=1.0, first=False, out_scale=None):
+    """The arithmetic of miseg_ensemble_accumulate in torch, one rounded fp32 (the tensors' dtype: float64 tensors give the float64
+    restatement) op per step, in the kernel's order: un-flip, the term t (the logits | softmax over dim 1: maximum subtracted, exp, summed in
+    channel order, times 1 / sum | the one-hot of first_max_argmax), w_c * t, acc + that unless first, times out_scale[c] when given.  Writes
+    and returns acc.  Kinds mean_logits and vote give the kernel's bits; mean_prob differs by the two exp implementations."""
+    dims = [2 + a for a in range(3) if flip[a]]
+    x = torch.flip(src, dims) if dims else src
+    Cc = x.shape[1]
+    shape = (1, Cc, 1, 1, 1)
+    if kind == "mean_logits":
+        t = x
+    elif kind == "mean_prob":
+        e = torch.exp(x - x.amax(dim=1, keepdim=True))
+        total = e[:, 0:1]
+        for c in range(1, Cc):
+            total = total + e[:, c:c + 1]
+        t = e * (1.0 / total)
+    elif kind == "vote":
+        arg = torch.stack([first_max_argmax(v) for v in x])
+        t = torch.stack([(arg == c) for c in range(Cc)], 1).to(x.dtype)
+        weight = 1.0
+    else:
+        raise ValueError(f"ensemble_accumulate: kind {kind!r} is not one of {tuple(L.ENSEMBLE_KINDS)}")
+    w = torch.as_tensor(weight, dtype=torch.float64).reshape(-1).to(torch.float32).to(device=x.device, dtype=x.dtype)
+    term = t * (w.reshape(shape) if w.numel() == Cc else w)
+    total = term if first else acc + term
+    if out_scale is not None:
+        s = torch.as_tensor(out_scale, dtype=torch.float64).reshape(-1).to(torch.float32).to(device=x.device, dtype=x.dtype)
+        total = total * (s.reshape(shape) if s.numel() == Cc else s)
+    acc.copy_(total)
+    return acc
+
+
+def ensemble_accumulate(src, acc, *, flip=(False, False, False), kind="mean_logits", weight=1.0, first=False, out_scale=None):
+    """Fold one ensemble member into the accumulator (miseg_ensemble_accumulate, csrc/ensemble.hip):
+    acc' = fl(fl(acc + fl(w_c * t_c)) * s_c) with t the member's term at the voxel that `flip` (one flag per spatial axis D, H, W: the member
+    was predicted on the volume mirrored along it) maps onto acc's voxel.  src, acc: contiguous fp32 [B, C, D, H, W] on one device, not
+    overlapping.  kind "mean_logits" | "mean_prob" | "vote"; weight: a scalar or one value per class (ignored by "vote"); first: acc is
+    written and not read (it may be torch.empty); out_scale: None, a scalar or one value per class, multiplied in after the add (the last
+    member's 1 / sum of weights).  Writes and returns acc; only enqueues: graph-capturable.  CPU tensors take ensemble_accumulate_torch."""
+    bits, k, w, s = _ensemble_args("ensemble_accumulate", src, acc, flip, kind, weight, out_scale)
+    if not src.is_cuda:
+        return ensemble_accumulate_torch(src, acc, flip=flip, kind=kind, weight=w, first=first, out_scale=s)
+    B, Cc, D, H, W = src.shape
+    p = L.Ensemble(C.sizeof(L.Ensemble), _ptr(src), _ptr(acc), B, Cc, D, H, W, bits, k, int(bool(first)), int(s is not None),
+                   (C.c_float * 64)(*w), (C.c_float * 64)(*(s or ())))      # (a ctypes array is zero beyond the values given)
+    _call("miseg_ensemble_accumulate", p, prof=("ensemble_accumulate", 0.0, _nb(src, acc) + (0.0 if first else _nb(acc))))
+    return acc
+
+
 # ------------------------------------------------------------------------------------------ dropout / stochastic depth
 class _DropState:
     """keys of the counter-based dropout masks: `seed` (host, torch.initial_seed() unless set), a call counter that tells the call sites

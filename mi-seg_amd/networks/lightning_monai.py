@@ -6,12 +6,13 @@ otherwise it is an ``nn.Module`` with the same constructor, ``from_argparse_args
 Loss / metric / inferer arithmetic is MONAI's, restated in mi-seg_amd/training (parity unpinned)."""
 import inspect
 from functools import partial
-from typing import Sequence, Union
+from typing import Optional, Sequence, Union
 
 import numpy as np
 import torch
 import torch.nn as nn
 
+from ..training.ensemble import EnsembleInferer, tta_flip_sets
 from ..training.inferer import sigma_scale_arg, sliding_window_inference
 from ..training.losses import DiceCELoss, DiceFocalLoss, GeneralizedDiceFocalLoss
 from ..training.metrics import dice_from_logits
@@ -31,7 +32,8 @@ class LitMonai(_Base):
                  roi_size: Union[Sequence[int], int] = (96, 96, 96), infer_overlap: float = 0.5, sw_batch_size: int = 1, infer_cpu: bool = False,
                  batch_size: int = 1, scheduler: str = "reduce_on_plateau", warmup_epochs=None, patience=None, check_val_every_n_epoch=None,
                  max_epochs: int = 5000, t_max: int = 200, cycles: float = 1, include_background: bool = False, infer_mode: str = "constant",
-                 infer_sigma_scale: Union[Sequence[float], float] = 0.125, infer_padding_mode: str = "constant", **kwargs):
+                 infer_sigma_scale: Union[Sequence[float], float] = 0.125, infer_padding_mode: str = "constant",
+                 infer_tta_flips: Optional[Sequence[int]] = None, ensemble_mode: str = "mean_logits", **kwargs):
         super().__init__()
         self.model = model
         if criterion == "dice_focal":      # squared_pred hard-coded True like the reference (:53)
@@ -51,6 +53,10 @@ class LitMonai(_Base):
         self.model_inferer = partial(sliding_window_inference, predictor=self.model, roi_size=roi_size, overlap=infer_overlap,
                                      sw_batch_size=sw_batch_size, device=torch.device("cpu") if infer_cpu else None, mode=infer_mode,
                                      sigma_scale=sigma_scale_arg(infer_sigma_scale), padding_mode=infer_padding_mode)
+        if infer_tta_flips is not None:      # mirror TTA over these spatial axes (training/ensemble.py); None leaves the partial above as it is
+            kw = dict(self.model_inferer.keywords)
+            self.model_inferer = EnsembleInferer(kw.pop("predictor"), kw.pop("roi_size"), kw.pop("sw_batch_size"), kw.pop("overlap"),
+                                                 flips=tta_flip_sets(infer_tta_flips), mode=ensemble_mode, infer_mode=kw.pop("mode"), **kw)
         self.scheduler, self.warmup_epochs, self.patience = scheduler, warmup_epochs, patience
         self.check_val_every_n_epoch, self.max_epochs, self.t_max, self.cycles = check_val_every_n_epoch, max_epochs, t_max, cycles
         self.__dict__.update(kwargs)
@@ -81,6 +87,7 @@ class LitMonai(_Base):
                    max_epochs=getattr(args, "max_epochs", 5000), t_max=args.t_max, cycles=args.cycles,
                    include_background=not args.no_include_background, infer_mode=getattr(args, "infer_mode", "constant"),
                    infer_sigma_scale=getattr(args, "infer_sigma_scale", 0.125), infer_padding_mode=getattr(args, "infer_padding_mode", "constant"),
+                   infer_tta_flips=getattr(args, "infer_tta_flips", None), ensemble_mode=getattr(args, "ensemble_mode", "mean_logits"),
                    **extra)
 
     def forward(self, x, modalities=None):

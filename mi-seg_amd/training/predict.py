@@ -17,6 +17,7 @@ from ..data.preprocess import load_image_for_prediction
 from ..hip import ops
 from ..networks.utils.utils import model_from_argparse_args
 from ..utils.parser import add_model_argparse_args
+from .ensemble import EnsembleInferer, tta_flip_sets
 from .inferer import sigma_scale_arg, sliding_window_inference
 
 LABEL_MAP = {1: 500, 2: 600, 3: 420, 4: 550, 5: 205, 6: 820, 7: 850}      # predict_whs.py:18-26 (_MAP): class -> MM-WHS label code
@@ -87,16 +88,26 @@ def _sync(device):
 
 
 def predict_volume(model, item, args):
-    """one data-list item ({"image", "modality"}) -> path of the written label map; prints the time of each stage"""
+    """one data-list item ({"image", "modality"}) -> path of the written label map; prints the time of each stage.  `model`: one model, or a
+    list of them (--ensemble_checkpoints); more than one model or any --infer_tta_flips axis goes through an EnsembleInferer (DESIGN.md
+    section 7.10), one model without flips makes the call it always made."""
     device = args.device
     roi = (args.roi_x, args.roi_y, args.roi_z)
+    models = list(model) if isinstance(model, (list, tuple)) else [model]
+    flips = tta_flip_sets(getattr(args, "infer_tta_flips", None) or ())
     t0 = time.perf_counter()
     image, geom = load_image_for_prediction(item["image"], (args.space_x, args.space_y, args.space_z), roi, device)
     t1 = _sync(device)
     modality = torch.tensor([modality_id(item.get("modality", 0))], device=device)
-    logits = sliding_window_inference(image, roi, args.sw_batch_size, model, overlap=args.infer_overlap, modalities=modality,
-                                      mode=getattr(args, "infer_mode", "constant"), sigma_scale=sigma_scale_arg(getattr(args, "infer_sigma_scale", 0.125)),
-                                      padding_mode=getattr(args, "infer_padding_mode", "constant"))
+    blend = dict(sigma_scale=sigma_scale_arg(getattr(args, "infer_sigma_scale", 0.125)), padding_mode=getattr(args, "infer_padding_mode", "constant"))
+    members = len(models) * len(flips)
+    if members > 1:
+        inferer = EnsembleInferer(models, roi, args.sw_batch_size, args.infer_overlap, flips=flips, mode=getattr(args, "ensemble_mode", "mean_logits"),
+                                  infer_mode=getattr(args, "infer_mode", "constant"), **blend)
+        logits = inferer(image, modalities=modality)
+    else:
+        logits = sliding_window_inference(image, roi, args.sw_batch_size, models[0], overlap=args.infer_overlap, modalities=modality,
+                                          mode=getattr(args, "infer_mode", "constant"), **blend)
     del image
     t2 = _sync(device)
     keep, fill = keep_largest_options(args), fill_holes_options(args)
@@ -125,24 +136,28 @@ def predict_volume(model, item, args):
     path = output_path(item["image"], args.result_dir)
     write_nifti(path, host, geom.affine, compresslevel=COMPRESSLEVEL, mtime=0)
     t5 = time.perf_counter()
-    print(f"{os.path.basename(path)}: {'x'.join(str(s) for s in host.shape)} read+preprocess {t1 - t0:.3f} s, inference {t2 - t1:.3f} s, "
+    print(f"{os.path.basename(path)}: {'x'.join(str(s) for s in host.shape)} read+preprocess {t1 - t0:.3f} s, inference {t2 - t1:.3f} s "
+          f"({members} member{'s' if members > 1 else ''}: models {len(models)} x flips {len(flips)}), "
           f"{filtered}inverse {1e3 * (t3 - tk):.2f} ms, device-to-host {1e3 * (t4 - t3):.2f} ms, write {t5 - t4:.3f} s", flush=True)
     return path
 
 
 def predict(model, datalist, args):
-    """predict_volume over the data list into args.result_dir (created); returns the written paths"""
+    """predict_volume over the data list into args.result_dir (created); returns the written paths.  `model`: one model or a list of them"""
     os.makedirs(args.result_dir, exist_ok=True)
-    model.eval()
+    for m in (model if isinstance(model, (list, tuple)) else [model]):
+        m.eval()
     with torch.no_grad():
         return [predict_volume(model, item, args) for item in datalist]
 
 
 def build_parser():
     """the reference's command line (predict_whs.py:117-127): the model options plus its own, with its defaults (the model options carry
-    --infer_mode / --infer_sigma_scale / --infer_padding_mode, the window blend of predict_volume)"""
+    --infer_mode / --infer_sigma_scale / --infer_padding_mode, the window blend of predict_volume, and --infer_tta_flips / --ensemble_mode;
+    --ensemble_checkpoints names the further members of a model ensemble)"""
     parser = add_model_argparse_args(ArgumentParser())
     parser.add_argument("--checkpoint", default="", type=str, help="Checkpoint")
+    parser.add_argument("--ensemble_checkpoints", default=[], type=str, nargs="*", help="further checkpoints of the same architecture, ensembled with --checkpoint (--ensemble_mode)")
     parser.add_argument("--sample", default="", type=str, help="accepted for compatibility, unused")
     parser.add_argument("--space_x", default=1.0, type=float, help="spacing in x direction")
     parser.add_argument("--space_y", default=1.0, type=float, help="spacing in y direction")
@@ -170,8 +185,10 @@ def main(argv=None):
     args.device = "cuda:0"
     args.distributed = False
     torch.cuda.set_device(args.device)
-    model = model_from_argparse_args(args)
-    load_model_state(model, args.checkpoint)
-    model = model.to(args.device).eval()
+    models = []
+    for checkpoint in [args.checkpoint] + list(args.ensemble_checkpoints or []):
+        model = model_from_argparse_args(args)
+        load_model_state(model, checkpoint)
+        models.append(model.to(args.device).eval())
     datalist = load_decathlon_datalist_with_modality(os.path.join(args.data_dir, args.json_list), True, "test", base_dir=args.data_dir)
-    return predict(model, datalist, args)
+    return predict(models[0] if len(models) == 1 else models, datalist, args)

@@ -48,6 +48,9 @@ MODEL_ARGS = {
         ("--infer_mode", dict(default="constant", type=str, help="constant | gaussian: how overlapping windows are blended")),
         ("--infer_sigma_scale", dict(default=0.125, type=float, nargs="+", help="gaussian mode: sigma = roi * this (one value, or one per axis)")),
         ("--infer_padding_mode", dict(default="constant", type=str, help="constant | reflect | replicate | circular: pad of an image smaller than the roi")),
+        # flip test-time augmentation / ensembling (training/ensemble.py): none by default, which leaves the inference as it is
+        ("--infer_tta_flips", dict(default=None, type=int, nargs="*", choices=(0, 1, 2), help="spatial axes of the mirror TTA: every flip over them is predicted and averaged")),
+        ("--ensemble_mode", dict(default="mean_logits", type=str, choices=("mean_logits", "mean_prob", "vote"), help="what the members of an ensemble / the TTA flips contribute")),
     ],
     "early_stop": [("--patience", dict(default=6, type=int)), ("--min_delta", dict(default=0.001, type=float))],
     "checkpointing": [("--save_top_k", dict(default=3, type=int))],
