@@ -452,7 +452,12 @@ typedef struct {
   float* dqkv_bias;                /* accumulated: contribution of padded tokens; may be NULL */
   float* dbias_table;              /* accumulated fp32 [(2tw-1)^3][heads]; may be NULL */
 } miseg_winattn_bwd_params;
+/* dbias_table without f.bias_table is refused (MISEG_E_BADARG): there is no table to take the gradient of */
 int miseg_winattn_bwd(const miseg_winattn_bwd_params* p, miseg_stream_t stream);
+/* 1 when a matrix-core kernel takes this backward call (the head_dim-16 bf16 window kernel: as the forward's, and the table fits its LDS
+ * slots, qkv / dqkv 8-byte aligned with row strides % 4 == 0; or the head_dim-64 global kernel), 0 when the one-lane-per-query kernels do
+ * or the call would be refused.  No launch; the launcher decides by the same function.  (A new symbol: MISEG_ABI_VERSION stays 16.) */
+int miseg_winattn_bwd_on_matrix_cores(const miseg_winattn_bwd_params* p);
 
 /* ------------------------------------------------------------------------------------------------
  * Data-movement / small kernels (all channels-last rows)

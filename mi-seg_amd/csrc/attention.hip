@@ -127,6 +127,10 @@ __global__ void __launch_bounds__(384) winattn_fwd_kernel(const T* __restrict__ 
   const int tb = 2 * g.tw - 1;
   const int centre = ((g.tw - 1) * tb + (g.tw - 1)) * tb + (g.tw - 1);
   float m = -INFINITY, l = 0.f, o[HD];
+  // the log-sum-exp takes the denominator from a second sum in double: added one key at a time in fp32 over up to 384 keys, its rounding errors
+  // put lse at 1.6 to 3.2 times the error of torch's fp32 logsumexp on the same scores (2.6e-6 against 1.0e-6 at |lse| ~ 15); the double sum
+  // stands where torch's does.  `out` keeps the fp32 sum and its bits.
+  double lw = 0.0;
 #pragma unroll
   for (int d = 0; d < HD; ++d) o[d] = 0.f;
   // attn_drop: out = (P * mask / (1 - p)) V with P the full softmax (the denominator l sums every key, dropped or not)
@@ -151,6 +155,7 @@ __global__ void __launch_bounds__(384) winattn_fwd_kernel(const T* __restrict__ 
     const float alpha = exp_t<T>(m - mn);
     float p = exp_t<T>(sc - mn);
     l = l * alpha + p;
+    lw = lw * (double)alpha + (double)p;
     if (dr.thresh) {
       if ((j & 3) == 0) dh = dropout_group_hash(dk0, drow, dcg, j);
       p = dropout_keeps(dh, j, dr.thresh) ? p * dr.scale : 0.f;
@@ -167,7 +172,7 @@ __global__ void __launch_bounds__(384) winattn_fwd_kernel(const T* __restrict__ 
     m = mn;
   }
   const float inv = 1.f / l;
-  lse_out[((int64_t)win * g.heads + head) * n + t] = m + log_t<T>(l);
+  lse_out[((int64_t)win * g.heads + head) * n + t] = m + log_t<T>((float)lw);
   if (row >= 0) {
     T* op = out + (int64_t)row * ldo + head * HD;
 #pragma unroll
@@ -921,6 +926,7 @@ static size_t attn_mfma_fwd_smem(int tsize) {
 int global_attn_fwd(const miseg_winattn_params* p, const AttnDrop& dr, hipStream_t s, int* rc);
 int global_attn_bwd(const miseg_winattn_bwd_params* p, const AttnDrop& dr, hipStream_t s, int* rc);
 bool global_attn_takes(const miseg_winattn_params* p);
+bool global_attn_bwd_takes(const miseg_winattn_bwd_params* p);
 
 }  // namespace miseg
 
@@ -975,6 +981,19 @@ extern "C" int miseg_winattn_on_matrix_cores(const miseg_winattn_params* p) {
   return (fwd_takes_mfma(p, g) || global_attn_takes(p)) ? 1 : 0;
 }
 
+// the backward's own conditions: the table must fit the fixed LDS slots of both its copies, and dqkv / qkv take 8-byte accesses
+static bool bwd_takes_mfma(const miseg_winattn_bwd_params* p, const WinGeom& g) {
+  const int tb = 2 * g.tw - 1;
+  return p->f.dtype == MISEG_BF16 && g.hd == 16 && g.n <= ATT_NP && p->f.bias_table && tb * tb * tb <= ATT_TMAX && ((uintptr_t)p->dqkv % 8 == 0) && p->lddq % 4 == 0 &&
+         ((uintptr_t)p->f.qkv % 8 == 0) && p->f.ldq % 4 == 0;
+}
+
+extern "C" int miseg_winattn_bwd_on_matrix_cores(const miseg_winattn_bwd_params* p) {
+  WinGeom g;
+  if (!p || !p->dout || !p->dqkv || make_geom(&p->f, &g)) return 0;
+  return (bwd_takes_mfma(p, g) || global_attn_bwd_takes(p)) ? 1 : 0;
+}
+
 extern "C" int miseg_winattn_fwd(const miseg_winattn_params* p, miseg_stream_t s_) {
   hipStream_t s = (hipStream_t)s_;
   MISEG_REQUIRE(p, MISEG_E_BADARG, "winattn_fwd: null params");
@@ -1019,6 +1038,8 @@ extern "C" int miseg_winattn_fwd(const miseg_winattn_params* p, miseg_stream_t s
 extern "C" int miseg_winattn_bwd(const miseg_winattn_bwd_params* p, miseg_stream_t s_) {
   hipStream_t s = (hipStream_t)s_;
   MISEG_REQUIRE(p && p->dout && p->dqkv, MISEG_E_BADARG, "winattn_bwd: null pointer");
+  // without a table the kernels reserve no LDS for its gradient bins: the query-lane kernel's bin updates would land in its own log-sum-exp rows
+  MISEG_REQUIRE(!p->dbias_table || p->f.bias_table, MISEG_E_BADARG, "winattn_bwd: dbias_table given without a bias_table");
   WinGeom g;
   int rc = make_geom(&p->f, &g);
   if (rc) return rc;
@@ -1030,8 +1051,7 @@ extern "C" int miseg_winattn_bwd(const miseg_winattn_bwd_params* p, miseg_stream
   MISEG_REQUIRE(sh <= 160 * 1024, MISEG_E_UNSUPPORTED, "winattn_bwd: %zu bytes of LDS needed", sh);
   dim3 grid(g.B * g.nwd * g.nwh * g.nww, g.heads);
   const int threads = cdiv(g.n, 64) * 64;
-  if (p->f.dtype == MISEG_BF16 && g.hd == 16 && g.n <= ATT_NP && p->f.bias_table && tsize <= ATT_TMAX && ((uintptr_t)p->dqkv % 8 == 0) && p->lddq % 4 == 0 &&
-      ((uintptr_t)p->f.qkv % 8 == 0) && p->f.ldq % 4 == 0) {
+  if (bwd_takes_mfma(p, g)) {
     const bool vec = p->f.ldq % 8 == 0 && p->f.ldo % 8 == 0 && p->lddo % 8 == 0 && (uintptr_t)p->f.qkv % 16 == 0 && (uintptr_t)p->f.out % 16 == 0 &&
                      (uintptr_t)p->dout % 16 == 0;
     // fewer workgroups than CUs (stages 3 and 4): the 8-wave form
@@ -1058,7 +1078,7 @@ extern "C" int miseg_winattn_bwd(const miseg_winattn_bwd_params* p, miseg_stream
     HD_SWITCH(g.hd / 4, {
       MISEG_SET_SMEM((winattn_bwd_kernel<T, HD4>), sh);
       winattn_bwd_kernel<T, HD4><<<grid, threads, sh, s>>>((const T*)p->f.qkv, p->f.ldq, (const T*)p->f.out, p->f.ldo, (const T*)p->dout, p->lddo, (T*)p->dqkv, p->lddq,
-                                                           p->f.qkv_bias, p->f.bias_table, p->f.lse, p->dqkv_bias, p->dbias_table ? p->dbias_table : nullptr, g,
+                                                           p->f.qkv_bias, p->f.bias_table, p->f.lse, p->dqkv_bias, p->dbias_table, g,
                                                            tsize, dr);
     });
     MISEG_LAUNCH_CHECK("winattn_bwd");

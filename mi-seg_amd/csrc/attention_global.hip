@@ -381,11 +381,22 @@ int global_attn_fwd(const miseg_winattn_params* p, const AttnDrop& dr, hipStream
   return 1;
 }
 
+// the backward stages dO and O with 16-byte loads and stores dqkv in 8-byte pieces: stricter than the forward
+static bool ga_bwd_geom(const miseg_winattn_bwd_params* p, GaGeom* g) {
+  if (!ga_geom(&p->f, g)) return false;
+  if (p->lddo % 8 || p->lddq % 4 || p->f.ldo % 8 || ((uintptr_t)p->dout & 15) || ((uintptr_t)p->f.out & 15) || ((uintptr_t)p->dqkv & 7)) return false;
+  g->lddo = p->lddo; g->lddq = p->lddq;
+  return true;
+}
+
+bool global_attn_bwd_takes(const miseg_winattn_bwd_params* p) {
+  GaGeom g;
+  return ga_bwd_geom(p, &g) && g.NP / 16 >= 2 && g.NP / 16 <= 16;
+}
+
 int global_attn_bwd(const miseg_winattn_bwd_params* p, const AttnDrop& dr, hipStream_t s, int* rc) {
   GaGeom g;
-  if (!ga_geom(&p->f, &g)) return 0;
-  if (p->lddo % 8 || p->lddq % 4 || p->f.ldo % 8 || ((uintptr_t)p->dout & 15) || ((uintptr_t)p->f.out & 15) || ((uintptr_t)p->dqkv & 7)) return 0;
-  g.lddo = p->lddo; g.lddq = p->lddq;
+  if (!ga_bwd_geom(p, &g)) return 0;
   const int nqt = cdiv(g.n, 64);
   const size_t sh_q = (size_t)(2 * g.NP * GA_RS + GA_HD * (g.NP + 8)) * 2;
   const size_t sh_k = (size_t)(2 * g.NP * GA_RS + 2 * GA_HD * (g.NP + 8)) * 2 + (size_t)2 * g.NP * 4;

@@ -244,6 +244,7 @@ PROTOS = {
     "miseg_winattn_fwd": (i32, [C.POINTER(Winattn), vp]),
     "miseg_winattn_on_matrix_cores": (i32, [vp]),
     "miseg_winattn_bwd": (i32, [C.POINTER(WinattnBwd), vp]),
+    "miseg_winattn_bwd_on_matrix_cores": (i32, [vp]),
     "miseg_add": (i32, [C.POINTER(Add), vp]),
     "miseg_affine2": (i32, [C.POINTER(Affine2), vp]),
     "miseg_instnorm_bwd_reduce": (i32, [C.POINTER(InstnormBwd), vp]),

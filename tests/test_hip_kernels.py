@@ -9,6 +9,7 @@ import torch.nn.functional as F
 
 from conftest import rel_err
 from parity import assert_parity, local_err
+from winattn_ref import dqkv_local_tol as _dqkv_local_tol, ref_window_attention as _ref_window_attention
 
 pytestmark = pytest.mark.gpu
 
@@ -1147,58 +1148,6 @@ def test_param_cast_batch_every_layout_in_one_launch(dtype):
     for sh, d, r in zip(shapes, dsts, refs):
         assert torch.equal(d, r), sh
     assert int(ver[1]) == 6 and int(ver[2]) == 0
-
-
-def _ref_window_attention(qkv, qkv_bias, table, heads, ws, ss, tw, scale, drop_mask=None):
-    """plain PyTorch reference (in the dtype of its arguments: the tests hand it float64) of the fused attention core (pad with the bias row, roll, partition, softmax(QK^T+bias+mask)V,
-    reverse, roll back, crop) built from the oracle's helpers."""
-    from oracle.functional import compute_mask, relative_position_index, window_partition, window_reverse
-    B, D, H, W, C3 = qkv.shape
-    C = C3 // 3
-    hd = C // heads
-    pd, ph, pw = (-D) % ws[0], (-H) % ws[1], (-W) % ws[2]
-    x = qkv
-    if pd or ph or pw:
-        full = qkv_bias.view(1, 1, 1, 1, C3).expand(B, D + pd, H + ph, W + pw, C3).clone()
-        full[:, :D, :H, :W] = qkv
-        x = full
-    Dp, Hp, Wp = x.shape[1:4]
-    mask = None
-    if any(ss):
-        x = torch.roll(x, shifts=tuple(-s for s in ss), dims=(1, 2, 3))
-        mask = compute_mask((Dp, Hp, Wp), ws, ss).to(qkv.device)
-    win = window_partition(x, ws)
-    b, n, _ = win.shape
-    q, k, v = win.reshape(b, n, 3, heads, hd).permute(2, 0, 3, 1, 4)
-    attn = (q * scale) @ k.transpose(-2, -1)
-    idx = relative_position_index((tw, tw, tw)).to(qkv.device)[:n, :n].reshape(-1)
-    attn = attn + table[idx].reshape(n, n, -1).permute(2, 0, 1).unsqueeze(0)
-    if mask is not None:
-        nw = mask.shape[0]
-        mask = mask.to(attn.dtype)
-        attn = (attn.view(b // nw, nw, heads, n, n) + mask.unsqueeze(1).unsqueeze(0)).view(-1, heads, n, n)
-    prob = attn.softmax(-1)
-    if drop_mask is not None:         # attn_drop: [windows, heads, n, n] of 0 or 1 / (1 - p), window_attention.py:114
-        prob = (prob * drop_mask).to(v.dtype)
-    o = (prob @ v).transpose(1, 2).reshape(b, n, C)
-    o = window_reverse(o.view(-1, *ws, C), ws, (B, Dp, Hp, Wp))
-    if any(ss):
-        o = torch.roll(o, shifts=ss, dims=(1, 2, 3))
-    return o[:, :D, :H, :W].contiguous()
-
-
-def _dqkv_local_tol(tol, qkv, qb, table, g, heads, ws, ss, scale, want, drop_mask=None):
-    """bound of the local metric for the bf16 data gradient of the attention core: max(tol, 2 x yardstick), the yardstick being the local error of
-    the SAME composition run by torch in bf16 (bias row and table rounded to bf16 too) against the float64 gradient `want`.  A window that is
-    mostly padding holds hundreds of identical tokens (the bias row): their rounding errors add coherently instead of averaging out, so single
-    elements of dk stand 15 times above the pooled error - in torch's bf16 arithmetic as in the kernel's.  fp32: tol.
-    Measured, B = 2, [dims, heads, C]: yardstick 6.5e-2 / 5.8e-2 / 4.3e-2 / 3.8e-2 / 5.5e-2 for the five shapes of test_window_attention_core (kernel
-    2.8e-2 / 4.06e-2 / 2.0e-2 / 1.5e-2 / 9.6e-3 against tol 4e-2); with dropout 6.1e-2 / 4.1e-2 / 5.6e-2 (kernel 2.8e-2 / 2.1e-2 / 2.2e-2)."""
-    if qkv.dtype != torch.bfloat16:
-        return tol
-    qy = qkv.clone().requires_grad_(True)
-    _ref_window_attention(qy, qb.to(qkv.dtype), table.to(qkv.dtype), heads, ws, ss, 7, scale, drop_mask=drop_mask).backward(g)
-    return max(tol, 2 * local_err(qy.grad, want)[0])
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
