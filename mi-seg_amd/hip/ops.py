@@ -1735,56 +1735,53 @@ def _surface_args(who, label, logits, pred, num_classes):
     return logits, pred, lab, ldt, B, Cc, D, H, W, dev
 
 
+def _surface_launch(who, label, logits, pred, num_classes, include_background, symmetric, pct, directed, want, class_thresholds):
+    """one launch set of csrc/surface.hip through the smallest entry point that computes `want`: miseg_surface_dice with "nsd",
+    miseg_surface_metrics with "hd" and no "nsd", miseg_surface_distance for ("asd",) alone (the header guarantees the same bits from all
+    three); the fp64 [B, C'] tensors named in `want`, in that order.  Each parameter struct is a prefix of the next: `tail` is what follows
+    the workspace."""
+    logits, pred, lab, ldt, B, Cc, D, H, W, dev = _surface_args(who, label, logits, pred, num_classes)
+    cp = max(Cc - (0 if include_background else 1), 0)
+    out = {w: torch.empty(B, cp, dtype=torch.float64, device=dev) for w in want}
+    name, struct, tail = "miseg_surface_metrics", L.SurfaceMetrics, [_ptr(out.get("asd")), _ptr(out.get("hd")), pct, int(bool(directed))]
+    if "nsd" in want:
+        if class_thresholds is None:
+            raise ValueError(f"{who}: 'nsd' needs class_thresholds")
+        taus = [float(t) for t in class_thresholds]
+        if len(taus) != cp:
+            raise ValueError(f"{who}: number of classes ({cp}) does not match number of class thresholds ({len(taus)}).")
+        if any(not 0.0 <= t < float("inf") for t in taus):
+            raise ValueError(f"{who}: all class thresholds need to be finite and >= 0, got {taus}.")
+        name, struct, tail = "miseg_surface_dice", L.SurfaceDice, tail + [_ptr(out["nsd"]), (C.c_double * max(len(taus), 1))(*taus)]
+    elif "hd" not in want:
+        name, struct, tail = "miseg_surface_distance", L.SurfaceDistance, tail[:1]
+    nbytes = getattr(L.load(), name + "_workspace_bytes")(B, Cc, D, H, W)
+    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    _call(name, struct(C.sizeof(struct), _ptr(logits), _ptr(pred), _ptr(lab), ldt, B, Cc, D, H, W, int(bool(include_background)), int(bool(symmetric)),
+                       _ptr(ws), *tail))
+    return tuple(out[w] for w in want)
+
+
 def surface_distance(label, logits=None, pred=None, num_classes=None, include_background=True, symmetric=True):
     """fp64 [B, C'] symmetric (or one-way) average surface distance per class after argmax of fp32 logits [B, C, D, H, W], or of an integer
     class map pred [B, (1,) D, H, W] with num_classes classes (miseg_surface_distance; C' = C - (0 if include_background else 1)).
     Synchronises the stream: the kernel reads the per-class boxes back to size its passes."""
-    logits, pred, lab, ldt, B, Cc, D, H, W, dev = _surface_args("surface_distance", label, logits, pred, num_classes)
-    cp = Cc - (0 if include_background else 1)
-    asd = torch.empty(B, max(cp, 0), dtype=torch.float64, device=dev)
-    nbytes = L.load().miseg_surface_distance_workspace_bytes(B, Cc, D, H, W)
-    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-    _call("miseg_surface_distance", L.SurfaceDistance(C.sizeof(L.SurfaceDistance), _ptr(logits), _ptr(pred), _ptr(lab), ldt, B, Cc, D, H, W,
-                                                      int(bool(include_background)), int(bool(symmetric)), _ptr(ws), _ptr(asd)))
-    return asd
+    return _surface_launch("surface_distance", label, logits, pred, num_classes, include_background, symmetric, 0.0, False, ("asd",), None)[0]
 
 
 def surface_metrics(label, logits=None, pred=None, num_classes=None, include_background=True, symmetric=True, percentile=None, directed=False,
                     want=("asd", "hd"), class_thresholds=None):
     """the average surface distance of surface_distance (`symmetric`), the Hausdorff distance (`percentile`: None or 0 for the maximum, else in
     (0, 100]; `directed`: pred -> label only) and / or the normalized surface Dice ("nsd": `class_thresholds`, one finite tolerance >= 0 in
-    voxels per class after include_background) per class, from ONE launch set (miseg_surface_metrics; miseg_surface_dice when "nsd" is
-    asked for): a tuple of the fp64 [B, C'] tensors named in `want`, in that order.  Synchronises the stream like surface_distance."""
+    voxels per class after include_background) per class, from ONE launch set (_surface_launch picks the entry point): a tuple of the fp64
+    [B, C'] tensors named in `want`, in that order.  Synchronises the stream like surface_distance."""
     want = (want,) if isinstance(want, str) else tuple(want)
     if not want or any(w not in ("asd", "hd", "nsd") for w in want) or len(set(want)) != len(want):
         raise ValueError(f"surface_metrics: want {want!r} (some of 'asd', 'hd', 'nsd')")
     pct = 0.0 if percentile is None else float(percentile)
     if not 0.0 <= pct <= 100.0:
         raise ValueError(f"surface_metrics: percentile should be a value between 0 and 100, got {percentile}.")
-    logits, pred, lab, ldt, B, Cc, D, H, W, dev = _surface_args("surface_metrics", label, logits, pred, num_classes)
-    cp = Cc - (0 if include_background else 1)
-    out = {w: torch.empty(B, max(cp, 0), dtype=torch.float64, device=dev) for w in want}
-    if "nsd" in want:
-        if class_thresholds is None:
-            raise ValueError("surface_metrics: 'nsd' needs class_thresholds")
-        taus = [float(t) for t in class_thresholds]
-        if len(taus) != max(cp, 0):
-            raise ValueError(f"surface_metrics: number of classes ({max(cp, 0)}) does not match number of class thresholds ({len(taus)}).")
-        if any(not 0.0 <= t < float("inf") for t in taus):
-            raise ValueError(f"surface_metrics: all class thresholds need to be finite and >= 0, got {taus}.")
-        nbytes = L.load().miseg_surface_dice_workspace_bytes(B, Cc, D, H, W)
-        ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-        tarr = (C.c_double * max(len(taus), 1))(*taus)
-        _call("miseg_surface_dice", L.SurfaceDice(C.sizeof(L.SurfaceDice), _ptr(logits), _ptr(pred), _ptr(lab), ldt, B, Cc, D, H, W,
-                                                  int(bool(include_background)), int(bool(symmetric)), _ptr(ws), _ptr(out.get("asd")), _ptr(out.get("hd")),
-                                                  pct, int(bool(directed)), _ptr(out["nsd"]), tarr))
-        return tuple(out[w] for w in want)
-    nbytes = L.load().miseg_surface_metrics_workspace_bytes(B, Cc, D, H, W)
-    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-    _call("miseg_surface_metrics", L.SurfaceMetrics(C.sizeof(L.SurfaceMetrics), _ptr(logits), _ptr(pred), _ptr(lab), ldt, B, Cc, D, H, W,
-                                                    int(bool(include_background)), int(bool(symmetric)), _ptr(ws), _ptr(out.get("asd")), _ptr(out.get("hd")),
-                                                    pct, int(bool(directed))))
-    return tuple(out[w] for w in want)
+    return _surface_launch("surface_metrics", label, logits, pred, num_classes, include_background, symmetric, pct, directed, want, class_thresholds)
 
 
 _EXPORT_DTYPES = {torch.uint8: 1, torch.uint16: 2, torch.uint32: 4}

@@ -210,38 +210,46 @@ def _exclusive_onehot(t):
     return bool((((t == 0) | (t == 1)).all() & (t.sum(dim=1) == 1).all()).item())
 
 
-def compute_average_surface_distance(y_pred, y, include_background=False, symmetric=False, distance_metric="euclidean"):
-    """MONAI's compute_average_surface_distance on one-hot [B, C, *spatial] inputs -> float64 [B, C'] (C' = C - 1 without background), on the
-    device of y_pred.  On a HIP device with exclusive one-hot 3-D inputs: class maps into csrc/surface.hip; otherwise the CPU restatement."""
-    _check_metric(distance_metric)
+def _kernels_take(t):
+    """a tensor [B, C, D, H, W] that csrc/surface.hip takes: on the device, C <= 64, sides <= 4096"""
+    return t.is_cuda and t.dim() == 5 and t.shape[1] <= 64 and max(t.shape[2:]) <= 4096
+
+
+def _surface_numpy(want, p, g, symmetric, percentile, directed, class_thresholds):
+    """the CPU restatements named in `want` of bool [B, C', *spatial] arrays, as float64 [B, C'] tensors"""
+    out = {"asd": lambda: average_surface_distance_numpy(p, g, symmetric), "hd": lambda: hausdorff_distance_numpy(p, g, percentile, directed),
+           "nsd": lambda: surface_dice_numpy(p, g, class_thresholds)}
+    return tuple(torch.from_numpy(out[w]()) for w in want)
+
+
+def _onehot_surface_metric(want, y_pred, y, include_background, symmetric=True, percentile=None, directed=False, class_thresholds=None):
+    """one surface metric ("asd", "hd" or "nsd") of one-hot [B, C, *spatial] inputs -> float64 [B, C'] on the device of y_pred.  On a HIP
+    device with exclusive one-hot 3-D inputs: class maps into csrc/surface.hip; otherwise the CPU restatement."""
     if y_pred.shape != y.shape:
         raise ValueError(f"y_pred and y should have same shapes, got {tuple(y_pred.shape)} and {tuple(y.shape)}.")
-    Cc = y_pred.shape[1]
-    if (y_pred.is_cuda and y_pred.dim() == 5 and Cc <= 64 and max(y_pred.shape[2:]) <= 4096 and
-            _exclusive_onehot(y_pred) and _exclusive_onehot(y.to(y_pred.device))):
+    if want == "nsd":
+        class_thresholds = _check_thresholds(class_thresholds, y_pred.shape[1] - (0 if include_background else 1))
+    if _kernels_take(y_pred) and _exclusive_onehot(y_pred) and _exclusive_onehot(y.to(y_pred.device)):
         from ..hip import ops
-        return ops.surface_distance(y.to(y_pred.device).argmax(dim=1).to(torch.uint8), pred=y_pred.argmax(dim=1), num_classes=Cc,
-                                    include_background=include_background, symmetric=symmetric)
+        return ops.surface_metrics(y.to(y_pred.device).argmax(dim=1).to(torch.uint8), pred=y_pred.argmax(dim=1), num_classes=y_pred.shape[1],
+                                   include_background=include_background, symmetric=symmetric, percentile=percentile, directed=directed,
+                                   want=(want,), class_thresholds=class_thresholds)[0]
     if not include_background:
         y_pred, y = y_pred[:, 1:], y[:, 1:]
-    asd = average_surface_distance_numpy(y_pred.detach().cpu().numpy().astype(bool), y.detach().cpu().numpy().astype(bool), symmetric)
-    return torch.from_numpy(asd).to(y_pred.device)
+    p, g = y_pred.detach().cpu().numpy().astype(bool), y.detach().cpu().numpy().astype(bool)
+    return _surface_numpy((want,), p, g, symmetric, percentile, directed, class_thresholds)[0].to(y_pred.device)
+
+
+def compute_average_surface_distance(y_pred, y, include_background=False, symmetric=False, distance_metric="euclidean"):
+    """MONAI's compute_average_surface_distance on one-hot [B, C, *spatial] inputs -> float64 [B, C'] (C' = C - 1 without background), on the
+    device of y_pred (_onehot_surface_metric)"""
+    _check_metric(distance_metric)
+    return _onehot_surface_metric("asd", y_pred, y, include_background, symmetric=symmetric)
 
 
 def surface_distance_from_logits(logits, label, num_classes, include_background=True, symmetric=True):
-    """AsDiscrete(argmax, to_onehot) on the logits + AsDiscrete(to_onehot) on the label + SurfaceDistanceMetric, fused: fp64 [B, C'].  On a HIP
-    device (fp32 [B, C, D, H, W] logits): one launch set over logits + labels, no one-hot volume (csrc/surface.hip); on CPU tensors
-    (--infer_cpu) the restatement above.  Label values outside [0, C) belong to no class, as in dice_from_logits."""
-    if (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 5 and logits.shape[1] == num_classes and num_classes <= 64
-            and max(logits.shape[2:]) <= 4096):
-        from ..hip import ops
-        return ops.surface_distance(label.to(logits.device), logits=logits.contiguous(), include_background=include_background, symmetric=symmetric)
-    classes = torch.arange(num_classes, device=logits.device).view(1, -1, *([1] * (logits.dim() - 2)))
-    pred = logits.argmax(dim=1, keepdim=True) == classes
-    lab = label.to(logits.device).reshape(logits.shape[0], 1, *logits.shape[2:]).long() == classes
-    c0 = 0 if include_background else 1
-    asd = average_surface_distance_numpy(pred[:, c0:].cpu().numpy(), lab[:, c0:].cpu().numpy(), symmetric)
-    return torch.from_numpy(asd).to(logits.device)
+    """AsDiscrete(argmax, to_onehot) on the logits + AsDiscrete(to_onehot) on the label + SurfaceDistanceMetric, fused: fp64 [B, C']"""
+    return surface_metrics_from_logits(logits, label, num_classes, include_background=include_background, symmetric=symmetric, want=("asd",))[0]
 
 
 # ------------------------------------------------------------------------------------------ Hausdorff distance (DESIGN.md section 7.5)
@@ -288,35 +296,24 @@ def hausdorff_distance_numpy(pred, gt, percentile=None, directed=False, use_scip
 
 
 def compute_hausdorff_distance(y_pred, y, include_background=False, distance_metric="euclidean", percentile=None, directed=False):
-    """MONAI's compute_hausdorff_distance on one-hot [B, C, *spatial] inputs -> float64 [B, C'] on the device of y_pred.  On a HIP device with
-    exclusive one-hot 3-D inputs: class maps into csrc/surface.hip; otherwise the CPU restatement."""
+    """MONAI's compute_hausdorff_distance on one-hot [B, C, *spatial] inputs -> float64 [B, C'] on the device of y_pred (_onehot_surface_metric)"""
     _check_metric(distance_metric)
     _check_percentile(percentile)
-    if y_pred.shape != y.shape:
-        raise ValueError(f"y_pred and y should have same shapes, got {tuple(y_pred.shape)} and {tuple(y.shape)}.")
-    Cc = y_pred.shape[1]
-    if (y_pred.is_cuda and y_pred.dim() == 5 and Cc <= 64 and max(y_pred.shape[2:]) <= 4096 and
-            _exclusive_onehot(y_pred) and _exclusive_onehot(y.to(y_pred.device))):
-        from ..hip import ops
-        return ops.surface_metrics(y.to(y_pred.device).argmax(dim=1).to(torch.uint8), pred=y_pred.argmax(dim=1), num_classes=Cc,
-                                   include_background=include_background, percentile=percentile, directed=directed, want=("hd",))[0]
-    if not include_background:
-        y_pred, y = y_pred[:, 1:], y[:, 1:]
-    hd = hausdorff_distance_numpy(y_pred.detach().cpu().numpy().astype(bool), y.detach().cpu().numpy().astype(bool), percentile, directed)
-    return torch.from_numpy(hd).to(y_pred.device)
+    return _onehot_surface_metric("hd", y_pred, y, include_background, percentile=percentile, directed=directed)
 
 
 def surface_metrics_from_logits(logits, label, num_classes, include_background=True, symmetric=True, percentile=None, directed=False,
                                 want=("asd", "hd"), class_thresholds=None):
-    """surface_distance_from_logits and the Hausdorff distance of the same argmax, fused: (asd, hd), fp64 [B, C'] each, from ONE launch set on a
-    HIP device (the classify pass and the three distance passes are shared; csrc/surface.hip); on CPU tensors the restatements above.  "nsd" in
-    `want` adds the normalized surface Dice at `class_thresholds` (one per class after include_background) from the same launch set."""
+    """AsDiscrete(argmax, to_onehot) on the logits + AsDiscrete(to_onehot) on the label + the surface metrics named in `want` ("asd": average
+    surface distance, "hd": Hausdorff distance, "nsd": normalized surface Dice at `class_thresholds`, one per class after include_background),
+    fused: a tuple of fp64 [B, C'] in that order.  On a HIP device (fp32 [B, C, D, H, W] logits): ONE launch set over logits + labels, no
+    one-hot volume (csrc/surface.hip); on CPU tensors (--infer_cpu) the restatements above.  Label values outside [0, C) belong to no class,
+    as in dice_from_logits."""
     _check_percentile(percentile)
     want = (want,) if isinstance(want, str) else tuple(want)
     if "nsd" in want:
         class_thresholds = _check_thresholds(class_thresholds, num_classes - (0 if include_background else 1))
-    if (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 5 and logits.shape[1] == num_classes and num_classes <= 64
-            and max(logits.shape[2:]) <= 4096):
+    if _kernels_take(logits) and logits.dtype == torch.float32 and logits.shape[1] == num_classes:
         from ..hip import ops
         return ops.surface_metrics(label.to(logits.device), logits=logits.contiguous(), include_background=include_background, symmetric=symmetric,
                                    percentile=percentile, directed=directed, want=want, class_thresholds=class_thresholds)
@@ -324,10 +321,8 @@ def surface_metrics_from_logits(logits, label, num_classes, include_background=T
     pred = logits.argmax(dim=1, keepdim=True) == classes
     lab = label.to(logits.device).reshape(logits.shape[0], 1, *logits.shape[2:]).long() == classes
     c0 = 0 if include_background else 1
-    p, g = pred[:, c0:].cpu().numpy(), lab[:, c0:].cpu().numpy()
-    out = {"asd": lambda: average_surface_distance_numpy(p, g, symmetric), "hd": lambda: hausdorff_distance_numpy(p, g, percentile, directed),
-           "nsd": lambda: surface_dice_numpy(p, g, class_thresholds)}
-    return tuple(torch.from_numpy(out[w]()).to(logits.device) for w in want)
+    out = _surface_numpy(want, pred[:, c0:].cpu().numpy(), lab[:, c0:].cpu().numpy(), symmetric, percentile, directed, class_thresholds)
+    return tuple(t.to(logits.device) for t in out)
 
 
 def hausdorff_distance_from_logits(logits, label, num_classes, include_background=True, percentile=None, directed=False):
@@ -389,22 +384,10 @@ def surface_dice_numpy(pred, gt, class_thresholds, use_scipy=True):
 
 def compute_surface_dice(y_pred, y, class_thresholds, include_background=False, distance_metric="euclidean", use_subvoxels=False):
     """MONAI's compute_surface_dice on one-hot [B, C, *spatial] inputs -> float64 [B, C'] on the device of y_pred, with the rules of DESIGN.md
-    section 7.9.  On a HIP device with exclusive one-hot 3-D inputs: class maps into csrc/surface.hip; otherwise the CPU restatement."""
+    section 7.9 (_onehot_surface_metric)"""
     _check_metric(distance_metric)
     _check_subvoxels(use_subvoxels)
-    if y_pred.shape != y.shape:
-        raise ValueError(f"y_pred and y should have same shapes, got {tuple(y_pred.shape)} and {tuple(y.shape)}.")
-    Cc = y_pred.shape[1]
-    taus = _check_thresholds(class_thresholds, Cc - (0 if include_background else 1))
-    if (y_pred.is_cuda and y_pred.dim() == 5 and Cc <= 64 and max(y_pred.shape[2:]) <= 4096 and
-            _exclusive_onehot(y_pred) and _exclusive_onehot(y.to(y_pred.device))):
-        from ..hip import ops
-        return ops.surface_metrics(y.to(y_pred.device).argmax(dim=1).to(torch.uint8), pred=y_pred.argmax(dim=1), num_classes=Cc,
-                                   include_background=include_background, want=("nsd",), class_thresholds=taus)[0]
-    if not include_background:
-        y_pred, y = y_pred[:, 1:], y[:, 1:]
-    nsd = surface_dice_numpy(y_pred.detach().cpu().numpy().astype(bool), y.detach().cpu().numpy().astype(bool), taus)
-    return torch.from_numpy(nsd).to(y_pred.device)
+    return _onehot_surface_metric("nsd", y_pred, y, include_background, class_thresholds=class_thresholds)
 
 
 def surface_dice_from_logits(logits, label, num_classes, class_thresholds, include_background=True):

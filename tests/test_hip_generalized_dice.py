@@ -3,7 +3,6 @@ output): DESIGN.md section 7.4, reference utils/training_utils.py:26-33 and tune
 judges are the torch restatement in float64 (training/losses.py, training/metrics.py) and the numpy restatement of
 test_generalized_dice_cpu.py.  The bars are the ones test_hip_training.py applies to the sibling kinds."""
 import argparse
-from functools import partial
 
 import numpy as np
 import pytest
@@ -242,30 +241,11 @@ def test_litmonai_with_the_generalized_criterion_on_the_hip_path():
 def test_evaluate_with_a_generalized_dice_score_on_the_fused_branch():
     """evaluate.test with additional_metrics=[GeneralizedDiceScore]: the fused branch returns the same Dice and surface results as without it,
     and the score equals the one of the one-hot chain on the same logits within 1e-6"""
-    from mi_seg_amd.networks.nets.swin_unetr import SwinUNETR
-    from mi_seg_amd.networks.norms.utils import parse_normalization
     from mi_seg_amd.training import evaluate as E
     from mi_seg_amd.training import metrics as M
-    from mi_seg_amd.training.inferer import sliding_window_inference
-    from mi_seg_amd.utils.detfill import det_input, fill_module_
-    from test_surface_distance_cpu import random_case
+    from surface_common import swin_evaluation
     C = 6
-    norm = partial(parse_normalization, affine=True, num_groups=4, num_styles=2)
-    m = SwinUNETR((32,) * 3, 1, C, feature_size=12, num_heads=(3, 6, 12, 24), vit_norm_name=norm("instance_cond"),
-                  encoder_norm_name=norm("instance_cond"), decoder_norm_name=norm("instance"))
-    fill_module_(m)
-    m = m.to(DEV)
-    loader = []
-    for i in range(3):
-        _, lab = random_case(40 + i, (40, 36, 32), C, B=1)
-        loader.append({"image": det_input(i, (1, 1, 40, 36, 32)), "label": torch.from_numpy(lab)[:, None].float(), "modality": torch.tensor([i % 2])})
-    inferer = partial(sliding_window_inference, roi_size=(32, 32, 32), sw_batch_size=2, predictor=m, overlap=0.5)
-    seen = []
-
-    def on_device(x, modalities=None):
-        out = inferer(x, modalities=modalities)
-        seen.append(out.detach().cpu())
-        return out
+    m, loader, on_device, seen = swin_evaluation(C, volumes=3)
 
     def run(model_inferer, additional):
         res = {}

@@ -5,36 +5,17 @@ than a wave against the CPU restatement, the metric objects on device vs CPU ten
 C ABI's argument checks."""
 import ctypes as C
 import math
-from functools import partial
 
 import numpy as np
 import pytest
 import torch
 
+from surface_common import (DEV, REL, assert_results_match, assert_returns_match, bits_equal as _bits_equal, ops as _ops, swin_device_vs_replayed,
+                            tied_logits as _tied_logits)
 from test_hausdorff_cpu import PERCENTILES, hd_from_lists, oracle_lists
 from test_surface_distance_cpu import onehot, quirk_cases, random_case, same
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-REL = 1e-9
-
-
-def _ops():
-    from mi_seg_amd.hip import ops
-    return ops
-
-
-def _tied_logits(pred, C, seed):
-    """logits whose argmax is `pred` under the first-maximum rule, with exact ties in later channels"""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randint(0, 3, (pred.shape[0], C) + pred.shape[1:], generator=g).float()
-    p = torch.from_numpy(pred)[:, None]
-    top = torch.full_like(x, 5.0)
-    idx = torch.arange(C).view(1, C, 1, 1, 1)
-    tie = torch.randint(0, 2, x.shape, generator=g).bool() & (idx > p)
-    x = torch.where(idx == p, top, torch.where(tie, top, x))
-    assert torch.equal(x.argmax(dim=1), torch.from_numpy(pred))
-    return x
 
 
 def _check_class_maps(pred, gt, Cc, percentiles=PERCENTILES):
@@ -107,11 +88,6 @@ def test_ranks_in_different_coarse_bins(form):
             assert got.item() == expect
 
 
-def _bits_equal(a, b):
-    """torch.equal on the bit patterns: NaNs in the same places count as equal"""
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int64), b.contiguous().view(torch.int64))
-
-
 def test_combined_call_shares_the_passes_bit_for_bit():
     pred, lab = random_case(16, (17, 19, 23), 6)
     logits = _tied_logits(pred, 6, 6).to(DEV)
@@ -168,56 +144,17 @@ def test_onehot_metrics_on_device_equal_the_cpu():
 def test_evaluate_end_to_end_with_all_three_metrics():
     """the evaluation loop over four volumes of both modalities with Dice, surface distance and Hausdorff distance: fused on-device metrics
     (ASD and HD of a batch from one call, the two disagreeing on the background) vs the one-hot chain on the replayed CPU logits"""
-    from mi_seg_amd.networks.nets.swin_unetr import SwinUNETR
-    from mi_seg_amd.networks.norms.utils import parse_normalization
-    from mi_seg_amd.training import evaluate as E
     from mi_seg_amd.training import metrics as M
-    from mi_seg_amd.training.inferer import sliding_window_inference
-    from mi_seg_amd.utils.detfill import det_input, fill_module_
     C = 6
-    norm = partial(parse_normalization, affine=True, num_groups=4, num_styles=2)
-    m = SwinUNETR((32,) * 3, 1, C, feature_size=12, num_heads=(3, 6, 12, 24), vit_norm_name=norm("instance_cond"),
-                  encoder_norm_name=norm("instance_cond"), decoder_norm_name=norm("instance"))
-    fill_module_(m)
-    m = m.to(DEV)
-    loader = []
-    for i in range(4):
-        _, lab = random_case(40 + i, (40, 36, 32), C, B=1)
-        loader.append({"image": det_input(i, (1, 1, 40, 36, 32)), "label": torch.from_numpy(lab)[:, None].float(), "modality": torch.tensor([i % 2])})
-    inferer = partial(sliding_window_inference, roi_size=(32, 32, 32), sw_batch_size=2, predictor=m, overlap=0.5)
-    seen = []
-
-    def on_device(x, modalities=None):
-        out = inferer(x, modalities=modalities)
-        seen.append(out.detach().cpu())
-        return out
-
-    def run(model_inferer):
-        res = {}
-        ret = E.test(m, loader, DEV, M.DiceMetric(include_background=True, reduction="mean_batch", get_not_nans=True),
-                     E.AsDiscrete(to_onehot=C), E.AsDiscrete(argmax=True, to_onehot=C), model_inferer=model_inferer, amp=False,
-                     surface_distance=M.SurfaceDistanceMetric(include_background=True, symmetric=True, reduction="mean_batch", get_not_nans=True),
-                     results=res,
-                     hausdorff_distance=M.HausdorffDistanceMetric(include_background=False, percentile=95, reduction="mean_batch", get_not_nans=True))
-        return ret, res
-
-    ret_dev, res_dev = run(on_device)
-    assert len(seen) == 4 and seen[0].dtype == torch.float32
-    replay = iter(seen)
-    ret_cpu, res_cpu = run(lambda x, modalities=None: next(replay))
+    (ret_dev, res_dev), (ret_cpu, res_cpu) = swin_device_vs_replayed(C, lambda: dict(
+        surface_distance=M.SurfaceDistanceMetric(include_background=True, symmetric=True, reduction="mean_batch", get_not_nans=True),
+        hausdorff_distance=M.HausdorffDistanceMetric(include_background=False, percentile=95, reduction="mean_batch", get_not_nans=True)))
     assert res_dev.keys() == res_cpu.keys() == {"dice_modality", "dice_total", "surface_distance_modality", "surface_distance_total",
                                                 "hausdorff_distance_modality", "hausdorff_distance_total"}
     assert list(res_dev["hausdorff_distance_total"]) == [f"val_total_hausdorff_distance/class{c}" for c in range(1, C)]
     assert "val_modality1/avg" in res_dev["hausdorff_distance_modality"]
-    for part in res_dev:
-        assert res_dev[part].keys() == res_cpu[part].keys()
-        a, b = list(res_dev[part].values()), list(res_cpu[part].values())
-        if part.startswith("dice"):
-            assert a == pytest.approx(b, rel=1e-6, nan_ok=True), part
-        else:
-            same(a, b, rel=REL)
-    assert ret_dev[0] == pytest.approx(ret_cpu[0], rel=1e-6)
-    same([ret_dev[1]], [ret_cpu[1]], rel=REL)
+    assert_results_match(res_dev, res_cpu)
+    assert_returns_match(ret_dev, ret_cpu)
 
 
 def test_abi_rejects_bad_arguments():

@@ -7,42 +7,18 @@ checks.  Every surface-Dice comparison is exact."""
 import ctypes as C
 import itertools
 import math
-from functools import partial
 
 import numpy as np
 import pytest
 import torch
 
+from surface_common import (DEV, assert_results_match, assert_returns_match, bits_equal as _bits_equal, ops as _ops, swin_device_vs_replayed,
+                            tied_logits as _tied_logits)
 from test_hausdorff_cpu import oracle_lists
 from test_surface_dice_cpu import QUIRKS, THRESHOLDS, case, class_taus, exact, nsd_from_lists
-from test_surface_distance_cpu import onehot, random_case, same
+from test_surface_distance_cpu import onehot, random_case
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-REL = 1e-9
-
-
-def _ops():
-    from mi_seg_amd.hip import ops
-    return ops
-
-
-def _tied_logits(pred, C, seed):
-    """logits whose argmax is `pred` under the first-maximum rule, with exact ties in later channels"""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randint(0, 3, (pred.shape[0], C) + pred.shape[1:], generator=g).float()
-    p = torch.from_numpy(pred)[:, None]
-    top = torch.full_like(x, 5.0)
-    idx = torch.arange(C).view(1, C, 1, 1, 1)
-    tie = torch.randint(0, 2, x.shape, generator=g).bool() & (idx > p)
-    x = torch.where(idx == p, top, torch.where(tie, top, x))
-    assert torch.equal(x.argmax(dim=1), torch.from_numpy(pred))
-    return x
-
-
-def _bits_equal(a, b):
-    """torch.equal on the bit patterns: NaNs in the same places count as equal"""
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int64), b.contiguous().view(torch.int64))
 
 
 def _nsd(label, taus, inc, **kw):
@@ -177,24 +153,8 @@ def test_evaluate_end_to_end_with_all_four_metrics():
     """the evaluation loop over four volumes of both modalities with Dice, surface distance, Hausdorff distance and surface Dice: fused
     on-device metrics (ASD, HD and NSD of a batch from one call, the three disagreeing on the background) vs the one-hot chain on the replayed
     CPU logits; the surface-Dice parts exact"""
-    from mi_seg_amd.networks.nets.swin_unetr import SwinUNETR
-    from mi_seg_amd.networks.norms.utils import parse_normalization
-    from mi_seg_amd.training import evaluate as E
     from mi_seg_amd.training import metrics as M
-    from mi_seg_amd.training.inferer import sliding_window_inference
-    from mi_seg_amd.utils.detfill import det_input, fill_module_
     Cc = 6
-    norm = partial(parse_normalization, affine=True, num_groups=4, num_styles=2)
-    m = SwinUNETR((32,) * 3, 1, Cc, feature_size=12, num_heads=(3, 6, 12, 24), vit_norm_name=norm("instance_cond"),
-                  encoder_norm_name=norm("instance_cond"), decoder_norm_name=norm("instance"))
-    fill_module_(m)
-    m = m.to(DEV)
-    loader = []
-    for i in range(4):
-        _, lab = random_case(40 + i, (40, 36, 32), Cc, B=1)
-        loader.append({"image": det_input(i, (1, 1, 40, 36, 32)), "label": torch.from_numpy(lab)[:, None].float(), "modality": torch.tensor([i % 2])})
-    inferer = partial(sliding_window_inference, roi_size=(32, 32, 32), sw_batch_size=2, predictor=m, overlap=0.5)
-    seen = []
     calls = []
     ops = _ops()
     real = ops.surface_metrics
@@ -203,46 +163,22 @@ def test_evaluate_end_to_end_with_all_four_metrics():
         calls.append(tuple(kw.get("want", ())))
         return real(*a, **kw)
 
-    def on_device(x, modalities=None):
-        out = inferer(x, modalities=modalities)
-        seen.append(out.detach().cpu())
-        return out
-
-    def run(model_inferer):
-        res = {}
-        ret = E.test(m, loader, DEV, M.DiceMetric(include_background=True, reduction="mean_batch", get_not_nans=True),
-                     E.AsDiscrete(to_onehot=Cc), E.AsDiscrete(argmax=True, to_onehot=Cc), model_inferer=model_inferer, amp=False,
-                     surface_distance=M.SurfaceDistanceMetric(include_background=True, symmetric=True, reduction="mean_batch", get_not_nans=True),
-                     results=res,
-                     hausdorff_distance=M.HausdorffDistanceMetric(include_background=False, percentile=95, reduction="mean_batch", get_not_nans=True),
-                     surface_dice=M.SurfaceDiceMetric(class_taus(Cc, 0)[1:], include_background=False, reduction="mean_batch", get_not_nans=True))
-        return ret, res
-
     ops.surface_metrics = counted
     try:
-        ret_dev, res_dev = run(on_device)
+        (ret_dev, res_dev), (ret_cpu, res_cpu) = swin_device_vs_replayed(Cc, lambda: dict(
+            surface_distance=M.SurfaceDistanceMetric(include_background=True, symmetric=True, reduction="mean_batch", get_not_nans=True),
+            hausdorff_distance=M.HausdorffDistanceMetric(include_background=False, percentile=95, reduction="mean_batch", get_not_nans=True),
+            surface_dice=M.SurfaceDiceMetric(class_taus(Cc, 0)[1:], include_background=False, reduction="mean_batch", get_not_nans=True)))
     finally:
         ops.surface_metrics = real
-    assert calls == [("asd", "hd", "nsd")] * 4             # ONE call per batch
-    assert len(seen) == 4 and seen[0].dtype == torch.float32
-    replay = iter(seen)
-    ret_cpu, res_cpu = run(lambda x, modalities=None: next(replay))
+    assert calls == [("asd", "hd", "nsd")] * 4             # ONE call per batch on the device, none for the replayed CPU logits
     assert res_dev.keys() == res_cpu.keys() == {"dice_modality", "dice_total", "surface_distance_modality", "surface_distance_total",
                                                 "hausdorff_distance_modality", "hausdorff_distance_total", "surface_dice_modality",
                                                 "surface_dice_total"}
     assert list(res_dev["surface_dice_total"]) == [f"val_total_surface_dice/class{c}" for c in range(1, Cc)]
     assert "val_modality1/avg" in res_dev["surface_dice_modality"]
-    for part in res_dev:
-        assert res_dev[part].keys() == res_cpu[part].keys()
-        a, b = list(res_dev[part].values()), list(res_cpu[part].values())
-        if part.startswith("dice"):
-            assert a == pytest.approx(b, rel=1e-6, nan_ok=True), part
-        elif part.startswith("surface_dice"):
-            exact(a, b)
-        else:
-            same(a, b, rel=REL)
-    assert ret_dev[0] == pytest.approx(ret_cpu[0], rel=1e-6)
-    same([ret_dev[1]], [ret_cpu[1]], rel=REL)
+    assert_results_match(res_dev, res_cpu)
+    assert_returns_match(ret_dev, ret_cpu)
 
 
 def test_evaluate_filtered_path_takes_the_metric():
@@ -296,15 +232,7 @@ def test_evaluate_filtered_path_takes_the_metric():
     assert list(res_dev["surface_dice_total"]) == [f"val_total_surface_dice/class{c}" for c in range(Cc)]
     vals = list(res_dev["surface_dice_total"].values())
     assert len(set(vals)) == Cc and all(0.0 < v < 1.0 for v in vals)
-    for part in res_dev:
-        assert res_dev[part].keys() == res_cpu[part].keys()
-        a, b = list(res_dev[part].values()), list(res_cpu[part].values())
-        if part.startswith("dice"):
-            assert a == pytest.approx(b, rel=1e-6, nan_ok=True), part
-        elif part.startswith("surface_dice"):
-            exact(a, b)
-        else:
-            same(a, b, rel=REL)
+    assert_results_match(res_dev, res_cpu)
 
 
 def test_abi_rejects_bad_arguments():

@@ -3,37 +3,15 @@
 shapes and every rule quirk, against the CPU restatement on a large box with the background class, run-to-run bit equality, the cumulative
 metric objects on device vs CPU tensors, an end-to-end evaluation, and the C ABI's argument checks."""
 import ctypes as C
-from functools import partial
 
 import numpy as np
 import pytest
 import torch
 
+from surface_common import DEV, REL, assert_results_match, assert_returns_match, ops as _ops, swin_device_vs_replayed, tied_logits as _tied_logits
 from test_surface_distance_cpu import oracle_asd, onehot, quirk_cases, random_case, same
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-REL = 1e-9
-
-
-def _ops():
-    from mi_seg_amd.hip import ops
-    return ops
-
-
-def _tied_logits(pred, C, seed):
-    """logits whose argmax is `pred` under torch's first-maximum rule, with exact ties: some channels after pred[v] equal the maximum, so the
-    kernel must take the first maximum to find pred[v]"""
-    g = torch.Generator().manual_seed(seed)
-    B = pred.shape[0]
-    x = torch.randint(0, 3, (B, C) + pred.shape[1:], generator=g).float()
-    p = torch.from_numpy(pred)[:, None]
-    top = torch.full_like(x, 5.0)
-    idx = torch.arange(C).view(1, C, 1, 1, 1)
-    tie = torch.randint(0, 2, x.shape, generator=g).bool() & (idx > p)       # later channels equal to the max: the first one still wins
-    x = torch.where(idx == p, top, torch.where(tie, top, x))
-    assert torch.equal(x.argmax(dim=1), torch.from_numpy(pred))
-    return x
 
 
 @pytest.mark.parametrize("name,pred,gt,expect", quirk_cases(), ids=[c[0] for c in quirk_cases()])
@@ -103,53 +81,13 @@ def test_onehot_metrics_on_device_equal_the_cpu():
 
 def test_evaluate_end_to_end_matches_the_loop_on_cpu_logits():
     """the reference's test() loop over four volumes of both modalities: fused on-device metrics vs the one-hot chain on the CPU logits"""
-    from mi_seg_amd.networks.nets.swin_unetr import SwinUNETR
-    from mi_seg_amd.networks.norms.utils import parse_normalization
-    from mi_seg_amd.training import evaluate as E
     from mi_seg_amd.training import metrics as M
-    from mi_seg_amd.training.inferer import sliding_window_inference
-    from mi_seg_amd.utils.detfill import det_input, fill_module_
-    C = 6
-    norm = partial(parse_normalization, affine=True, num_groups=4, num_styles=2)
-    m = SwinUNETR((32,) * 3, 1, C, feature_size=12, num_heads=(3, 6, 12, 24), vit_norm_name=norm("instance_cond"),
-                  encoder_norm_name=norm("instance_cond"), decoder_norm_name=norm("instance"))
-    fill_module_(m)
-    m = m.to(DEV)
-    loader = []
-    for i in range(4):
-        _, lab = random_case(40 + i, (40, 36, 32), C, B=1)
-        loader.append({"image": det_input(i, (1, 1, 40, 36, 32)), "label": torch.from_numpy(lab)[:, None].float(), "modality": torch.tensor([i % 2])})
-    inferer = partial(sliding_window_inference, roi_size=(32, 32, 32), sw_batch_size=2, predictor=m, overlap=0.5)
-    seen = []
-
-    def on_device(x, modalities=None):
-        out = inferer(x, modalities=modalities)
-        seen.append(out.detach().cpu())
-        return out
-
-    def run(model_inferer):
-        res = {}
-        ret = E.test(m, loader, DEV, M.DiceMetric(include_background=True, reduction="mean_batch", get_not_nans=True),
-                     E.AsDiscrete(to_onehot=C), E.AsDiscrete(argmax=True, to_onehot=C), model_inferer=model_inferer, amp=False,
-                     surface_distance=M.SurfaceDistanceMetric(include_background=True, symmetric=True, reduction="mean_batch", get_not_nans=True),
-                     results=res)
-        return ret, res
-
-    ret_dev, res_dev = run(on_device)
-    assert len(seen) == 4 and seen[0].dtype == torch.float32
-    replay = iter(seen)
-    ret_cpu, res_cpu = run(lambda x, modalities=None: next(replay))
+    (ret_dev, res_dev), (ret_cpu, res_cpu) = swin_device_vs_replayed(6, lambda: dict(
+        surface_distance=M.SurfaceDistanceMetric(include_background=True, symmetric=True, reduction="mean_batch", get_not_nans=True)))
     assert res_dev.keys() == res_cpu.keys() == {"dice_modality", "dice_total", "surface_distance_modality", "surface_distance_total"}
     assert "val_modality1/avg" in res_dev["surface_distance_modality"] and "val_modality0/avg" in res_dev["dice_modality"]
-    for part in res_dev:
-        assert res_dev[part].keys() == res_cpu[part].keys()
-        a, b = list(res_dev[part].values()), list(res_cpu[part].values())
-        if part.startswith("dice"):
-            assert a == pytest.approx(b, rel=1e-6, nan_ok=True), part
-        else:
-            same(a, b, rel=REL)
-    assert ret_dev[0] == pytest.approx(ret_cpu[0], rel=1e-6)
-    same([ret_dev[1]], [ret_cpu[1]], rel=REL)
+    assert_results_match(res_dev, res_cpu)
+    assert_returns_match(ret_dev, ret_cpu)
 
 
 def test_abi_rejects_bad_arguments():
