@@ -816,6 +816,59 @@ typedef struct {
 } miseg_augment_params;
 int miseg_augment_crop(const miseg_augment_params* p, miseg_stream_t stream);
 
+/* miseg_augment_crop plus a free affine resample, gamma contrast and Gaussian noise (MONAI RandAffined / RandAdjustContrastd /
+ * RandGaussianNoised, restated; parity unpinned - DESIGN.md section 7.11; csrc/augment.hip).  A new symbol and new structs:
+ * MISEG_ABI_VERSION stays 16.  Per sample, in this order: crop -> affine resample about the crop centre -> flip 0, 1, 2 -> rot90 (the
+ * gather inverts the last two exactly as miseg_augment_crop does); on the image only: -> gamma -> fma(v, fl(1 + scale), shift), one fused
+ * multiply-add as in miseg_augment_crop -> noise.
+ *   Coordinates, all fp32, every operation rounded on its own (no FMA): q = the pre-flip patch coordinate of the output voxel,
+ *     c = (roi - 1) / 2 per axis, d = q - c (exact), r_a = (m[3a] * d_0 + m[3a+1] * d_1) + m[3a+2] * d_2,
+ *     s_a = (r_a + t[a]) + (origin[a] + c_a)     - a position in the RESIDENT VOLUME, not in the crop: a rotated patch reads real
+ *     neighbouring tissue; only positions outside the volume see padding_mode (BORDER clamps every index; ZEROS contributes 0 / label 0).
+ *   image: trilinear, i = floor(s), f = s - i per axis, seven lerps a + f * (b - a): along W, then H, then D.
+ *   label: nearest, index floor(s + 0.5) per axis (halves round up), the element copied verbatim (1, 4 or 8 bytes).
+ *   A sample whose m is exactly the identity and whose t is exactly 0 takes miseg_augment_crop's integer gather: without gamma and
+ *     noise its output is that call's, bit for bit.
+ *   gamma > 0 (MONAI AdjustContrast, per sample over all channels of the resampled patch): lo = min, range = max - lo,
+ *     v' = powf((v - lo) / (range + 1e-7f), gamma) * range + lo.  min / max: wave shuffles -> LDS -> one integer atomicMax per workgroup on
+ *     an order-preserving uint32 code of the float (the minimum as the maximum of the complemented code) - order independent, so the
+ *     result is bit-reproducible.  `minmax` is the caller's device scratch of MISEG_AUG_AFFINE_SCRATCH_BYTES: ZERO before its first use;
+ *     every call that completes leaves it zero again (the last workgroup of a sample to arrive clears that sample's words).
+ *   noise_std > 0: v += noise_mean + noise_std * z.  z is a pure function of (seed, draw, sample index i, element index e of the sample's
+ *     [C][rd][rh][rw] block), nothing is stored, and sample i's noise does not depend on n:
+ *       key = seed * 0x9E3779B97F4A7C15 + draw * 0xC2B2AE3D27D4EB4F + 0x165667B19E3779F9          (mod 2^64; dropout's host key)
+ *       ks  = mix64(key ^ (i * 0x9E3779B97F4A7C15)),   h = mix64(ks + e * 0xD1342543DE82EF95)
+ *       mix64(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *       u1 = ((h >> 40) + 1) * 2^-24 in (0, 1]   (bits 63..40),      u2 = ((h >> 16) & 0xFFFFFF) * 2^-24 in [0, 1)   (bits 39..16)
+ *       z  = sqrtf(-2 * logf(u1)) * cosf(fl(6.2831855f * u2))        (Box-Muller; the accurate logf / cosf / sqrtf / powf, never the fast forms)
+ *   One launch when no sample has gamma; two otherwise (resample + reduce, then the samples with gamma are finished in place - the
+ *   others were finished by the first launch, so they carry the bits of a call without gamma).  Only enqueues; can be captured.
+ * Refused before any launch: a wrong struct_size, a null image / out_image / samples_host, a label without out_label, a non-finite
+ * m / t / scale / shift / gamma / noise value, a crop that leaves the volume (MISEG_E_BADARG); n outside 1..MISEG_AUG_MAX_SAMPLES,
+ * label_bytes not 1 / 4 / 8, an unknown padding_mode (MISEG_E_UNSUPPORTED); an odd rot_k with rd != rh, a sample with gamma and no
+ * minmax (MISEG_E_BADARG). */
+enum { MISEG_AUG_PAD_BORDER = 0, MISEG_AUG_PAD_ZEROS = 1 };
+#define MISEG_AUG_AFFINE_SCRATCH_BYTES 256     /* uint32 [MISEG_AUG_MAX_SAMPLES][4]: ~code(min), code(max), arrivals, unused */
+typedef struct {
+  int32_t origin[3]; int32_t flip[3]; int32_t rot_k;
+  float m[9];                      /* row-major 3x3: output offsets -> input offsets (a sampling grid) */
+  float t[3];                      /* voxels */
+  float scale, shift;
+  float gamma;                     /* <= 0: off */
+  float noise_mean, noise_std;     /* std <= 0: off */
+} miseg_aug_affine_sample;
+typedef struct {
+  uint32_t struct_size;
+  const float* image; const void* label; int label_bytes;
+  int C, D, H, W, rd, rh, rw, n;
+  float* out_image; void* out_label;
+  const miseg_aug_affine_sample* samples_host;
+  int padding_mode;                /* MISEG_AUG_PAD_* */
+  uint64_t seed, draw;             /* the noise key */
+  uint32_t* minmax;                /* device, MISEG_AUG_AFFINE_SCRATCH_BYTES; may be NULL when no sample has gamma */
+} miseg_augment_affine_params;
+int miseg_augment_affine(const miseg_augment_affine_params* p, miseg_stream_t stream);
+
 /* Dropout / stochastic depth on channels-last rows (the `drop` / `dropout_path_rate` arguments of the reference's Swin stack:
  * networks/blocks/swin_transformer_block.py:90-97,205,247; MONAI Dropout / DropPath semantics): y = x * keep / (1 - p).
  *   rows_per_sample == 0: one Bernoulli(1 - p) draw per ELEMENT (nn.Dropout); > 0: one draw per SAMPLE (DropPath: rows r belong to

@@ -159,6 +159,22 @@ __device__ __forceinline__ uint64_t dropout_step_key(uint64_t key, const uint64_
 __device__ __forceinline__ uint64_t dropout_group_hash(uint64_t k, int64_t row, int cg, int c) { return mix64(k + (uint64_t)(row * cg + (c >> 2)) * 0xD1342543DE82EF95ull); }
 __device__ __forceinline__ bool dropout_keeps(uint64_t h, int c, unsigned thresh) { return (unsigned)((h >> (16 * (c & 3))) & 0xffff) >= thresh; }
 
+// patch coordinate (after rot90 + flips) -> coordinate inside the un-augmented crop.  The forward chain is crop -> flip0 -> flip1 -> flip2 ->
+// rot90^k in the (0, 1) plane; the gather inverts it back to front.  S: miseg_aug_sample or miseg_aug_affine_sample (training.hip, augment.hip).
+template <class S>
+__device__ __forceinline__ void aug_source(const S& a, int rd, int rh, int rw, int i, int j, int k, int& si, int& sj, int& sk) {
+  // torch.rot90(x, k, (0, 1)): k = 1: out[i][j] = in[j][n1 - 1 - i] (n1 = in.size(1) = out.size(0))
+  int pi = i, pj = j;
+  const int kk = a.rot_k & 3;
+  if (kk == 1) { pi = j; pj = rd - 1 - i; }
+  else if (kk == 2) { pi = rd - 1 - i; pj = rh - 1 - j; }
+  else if (kk == 3) { pi = rh - 1 - j; pj = i; }
+  // (rd == rh whenever kk is odd: checked on the host, so the pre-rotation patch has the same extents)
+  si = a.flip[0] ? rd - 1 - pi : pi;
+  sj = a.flip[1] ? rh - 1 - pj : pj;
+  sk = a.flip[2] ? rw - 1 - k : k;
+}
+
 // dropout on attention probabilities (attn_drop): thresh == 0 = off.  The mask is miseg_dropout's over the [windows * heads * n][n] matrix
 struct AttnDrop { unsigned thresh; float scale; uint64_t key; const uint64_t* step_dev; };
 

@@ -579,21 +579,7 @@ struct AugArgs {
   miseg_aug_sample s[MISEG_AUG_MAX_SAMPLES];
 };
 
-// patch coordinate (after rot90 + flips) -> coordinate inside the un-augmented crop.  The forward chain is crop -> flip0 -> flip1 -> flip2 ->
-// rot90^k in the (0, 1) plane; the gather inverts it back to front.
-__device__ __forceinline__ void aug_source(const miseg_aug_sample& a, int rd, int rh, int rw, int i, int j, int k, int& si, int& sj, int& sk) {
-  // torch.rot90(x, k, (0, 1)): k = 1: out[i][j] = in[j][n1 - 1 - i] (n1 = in.size(1) = out.size(0))
-  int pi = i, pj = j;
-  const int kk = a.rot_k & 3;
-  if (kk == 1) { pi = j; pj = rd - 1 - i; }
-  else if (kk == 2) { pi = rd - 1 - i; pj = rh - 1 - j; }
-  else if (kk == 3) { pi = rh - 1 - j; pj = i; }
-  // (rd == rh whenever kk is odd: checked on the host, so the pre-rotation patch has the same extents)
-  si = a.flip[0] ? rd - 1 - pi : pi;
-  sj = a.flip[1] ? rh - 1 - pj : pj;
-  sk = a.flip[2] ? rw - 1 - k : k;
-}
-
+// (aug_source - patch coordinate -> coordinate inside the un-augmented crop - lives in common.h: augment.hip gathers through it too)
 template <class LB>
 __global__ void __launch_bounds__(256) augment_kernel(const float* __restrict__ image, const LB* __restrict__ label, float* __restrict__ oimg, LB* __restrict__ olab, AugArgs a) {
   const int n = blockIdx.z;

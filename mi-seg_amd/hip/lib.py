@@ -163,6 +163,13 @@ AugSample = _struct("AugSample", cname="miseg_aug_sample", fields=[("origin", i3
 Augment = _struct("Augment", cname="miseg_augment_params", fields=[
     ("struct_size", u32), ("image", vp), ("label", vp), ("label_bytes", i32), ("C", i32), ("D", i32), ("H", i32), ("W", i32), ("rd", i32), ("rh", i32),
     ("rw", i32), ("n", i32), ("out_image", vp), ("out_label", vp), ("samples_host", vp)])
+AugAffineSample = _struct("AugAffineSample", cname="miseg_aug_affine_sample", fields=[
+    ("origin", i32 * 3), ("flip", i32 * 3), ("rot_k", i32), ("m", f32 * 9), ("t", f32 * 3), ("scale", f32), ("shift", f32), ("gamma", f32),
+    ("noise_mean", f32), ("noise_std", f32)])
+AugmentAffine = _struct("AugmentAffine", cname="miseg_augment_affine_params", fields=[
+    ("struct_size", u32), ("image", vp), ("label", vp), ("label_bytes", i32), ("C", i32), ("D", i32), ("H", i32), ("W", i32), ("rd", i32), ("rh", i32),
+    ("rw", i32), ("n", i32), ("out_image", vp), ("out_label", vp), ("samples_host", vp), ("padding_mode", i32), ("seed", C.c_uint64), ("draw", C.c_uint64),
+    ("minmax", vp)])
 Resample3d = _struct("Resample3d", cname="miseg_resample3d_params", fields=[
     ("struct_size", u32), ("in", vp), ("out", vp), ("C", i32), ("Di", i32), ("Hi", i32), ("Wi", i32), ("Do", i32), ("Ho", i32), ("Wo", i32),
     ("mode", i32), ("elem_bytes", i32)])
@@ -186,6 +193,9 @@ Ensemble = _struct("Ensemble", cname="miseg_ensemble_params", fields=[
 ENSEMBLE_MEAN_LOGITS, ENSEMBLE_MEAN_PROB, ENSEMBLE_VOTE = 0, 1, 2      # MISEG_ENSEMBLE_*
 ENSEMBLE_KINDS = {"mean_logits": ENSEMBLE_MEAN_LOGITS, "mean_prob": ENSEMBLE_MEAN_PROB, "vote": ENSEMBLE_VOTE}
 AUG_MAX_SAMPLES = 16
+AUG_PAD_BORDER, AUG_PAD_ZEROS = 0, 1                                   # MISEG_AUG_PAD_*
+AUG_PAD_MODES = {"border": AUG_PAD_BORDER, "zeros": AUG_PAD_ZEROS}
+AUG_AFFINE_SCRATCH_BYTES = 256                                         # MISEG_AUG_AFFINE_SCRATCH_BYTES
 LABEL_F32, LABEL_I32, LABEL_I64, LABEL_U8 = 0, 1, 2, 3
 LOSS_DICE_FOCAL, LOSS_DICE_CE, LOSS_GDICE_FOCAL = 0, 1, 2
 GDICE_W_SQUARE, GDICE_W_SIMPLE, GDICE_W_UNIFORM = 0, 1, 2      # MISEG_GDICE_W_* (MONAI w_type / weight_type "square", "simple", "uniform")
@@ -289,6 +299,7 @@ PROTOS = {
     "miseg_opt_step_pack_conv3": (i32, [C.POINTER(OptStep), vp, vp, i32, i32, i32, vp, vp]),
     "miseg_stitch_windows": (i32, [C.POINTER(Stitch), vp]),
     "miseg_augment_crop": (i32, [C.POINTER(Augment), vp]),
+    "miseg_augment_affine": (i32, [C.POINTER(AugmentAffine), vp]),
     "miseg_resample3d": (i32, [C.POINTER(Resample3d), vp]),
     "miseg_label_export_workspace_bytes": (C.c_size_t, [i32, i32, i32]),
     "miseg_label_export": (i32, [C.POINTER(LabelExport), vp]),

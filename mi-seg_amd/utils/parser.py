@@ -1,5 +1,6 @@
 """Command-line surface of MI-Seg (reference utils/parser.py:5-150): same flags, types and defaults, expressed as tables
-(plus --infer_mode / --infer_sigma_scale / --infer_padding_mode, whose defaults are what the reference gets from MONAI)."""
+(plus --infer_mode / --infer_sigma_scale / --infer_padding_mode, whose defaults are what the reference gets from MONAI, and the
+rotation / zoom / gamma / noise flags of the device augmenter, all off by default)."""
 from argparse import ArgumentParser
 
 _T = "store_true"
@@ -68,6 +69,16 @@ DATA_ARGS = {
         ("--patches_training_sample", dict(default=1, type=int)),
         ("--randFlipd_prob", dict(default=0.2, type=float)), ("--randRotate90d_prob", dict(default=0.2, type=float)),
         ("--randScaleIntensityd_prob", dict(default=0.1, type=float)), ("--randShiftIntensityd_prob", dict(default=0.1, type=float)),
+        # not flags of the reference: free rotation / zoom, gamma contrast and Gaussian noise on the device augmenter (data/augment.py), all off
+        ("--randAffined_prob", dict(default=0.0, type=float)),
+        ("--rotate_range", dict(default=[0.0, 0.0, 0.0], type=float, nargs="+", help="radians per axis (one value, or one per axis): drawn U(-r, r)")),
+        ("--scale_range", dict(default=[0.0, 0.0, 0.0], type=float, nargs="+", help="zoom factor 1 + U(-s, s) per axis")),
+        ("--translate_range", dict(default=[0.0, 0.0, 0.0], type=float, nargs="+", help="voxels per axis: drawn U(-t, t)")),
+        ("--affine_padding_mode", dict(default="border", type=str, choices=("border", "zeros"), help="what a resampled patch reads outside the volume")),
+        ("--randAdjustContrastd_prob", dict(default=0.0, type=float)),
+        ("--gamma_range", dict(default=[0.5, 4.5], type=float, nargs=2, help="gamma of RandAdjustContrastd: drawn U(low, high)")),
+        ("--randGaussianNoised_prob", dict(default=0.0, type=float)),
+        ("--noise_std", dict(default=0.1, type=float, help="RandGaussianNoised: the std of a sample is drawn U(0, noise_std)")),
         ("--use_normal_dataset", dict(action=_T)), ("--cache_num", dict(default=24, type=int)), ("--loader_workers", dict(default=8, type=int)),
         ("--batch_size", dict(default=1, type=int)), ("--num_workers", dict(default=8, type=int)),
     ],
