@@ -511,12 +511,48 @@ typedef struct {
 int miseg_space_to_channel(const miseg_s2c_params* p, miseg_stream_t stream);
 int miseg_channel_to_space(const miseg_s2c_params* p, miseg_stream_t stream);
 
+/* ---- plans of the network ends (patch embedding, one- to four-channel stem convolution, output head) ----
+ * miseg_<call>_plan(&params, &plan) tells what miseg_<call>(&params, stream) will launch; each launcher dispatches on exactly this plan,
+ * and a problem the call refuses gets the same error code from the plan.  Pointers are only tested for NULL and alignment, so a host may
+ * ask with stand-ins for buffers it has not allocated.  Host only: touches no device.  (New symbols: MISEG_ABI_VERSION stays 16.) */
+#define MISEG_NE_NONE 0                  /* no launch (head_bwd: dx or dw is NULL) */
+#define MISEG_NE_STEM_FWD_GENERIC 1      /* thread = voxel: Cin 2..4, ragged Cout, misaligned y */
+#define MISEG_NE_STEM_FWD_BRICK 2        /* Cin 1, Cout % 8 == 0 <= 64, 4x4x16 bricks, persistent workgroups (cap 4096) */
+#define MISEG_NE_STEM_FWD_MFMA 3         /* bf16, Cin 1, Cout 48, matrix cores (cap 2048) */
+#define MISEG_NE_STEM_WGRAD_GENERIC 4    /* one 8x8x8 brick per workgroup, fp32 atomics */
+#define MISEG_NE_STEM_WGRAD_BRICK 5      /* Cin 1, persistent workgroups (cap 512), fp32 atomics */
+#define MISEG_NE_STEM_WGRAD_MFMA 6       /* bf16, Cin 1, Cout 48, matrix cores (cap 512); partial sums with a workspace and >= 16 workgroups */
+#define MISEG_NE_PATCH_FWD 7             /* the one forward kernel; idx32 tells its item arithmetic */
+#define MISEG_NE_PATCH_BWD_GENERIC 8     /* 1024 coarse voxels per workgroup, fp32 atomics */
+#define MISEG_NE_PATCH_BWD_TEAM 9        /* Cout a whole number of 16-byte vectors, aligned dy; workgroups x Cin; partial sums as above */
+#define MISEG_NE_HEAD_FWD_SCALAR 10      /* thread = voxel, element loads */
+#define MISEG_NE_HEAD_FWD_TILE 11        /* 256-voxel tiles, 16-byte loads, persistent workgroups (cap 1152) */
+#define MISEG_NE_HEAD_DX_SCALAR 12
+#define MISEG_NE_HEAD_DX_TEAM 13         /* lane = (voxel, 16-byte channel vector); idx32 tells its item arithmetic */
+#define MISEG_NE_HEAD_DX_TILE 14         /* bf16, Cout <= 8, S % 256 == 0, Cin <= 256: 256-voxel tiles (cap 1152) */
+#define MISEG_NE_HEAD_DW_GENERIC 15      /* 2048 voxels per workgroup */
+#define MISEG_NE_HEAD_DW_TEAM 16         /* lane = (row, channel vector); one pass per 8 output channels */
+#define MISEG_NE_HEAD_DW_MFMA 17         /* bf16, Cin 48, S % 256 == 0, matrix cores (cap 512) */
+typedef struct {
+  int32_t kernel;                  /* MISEG_NE_* */
+  int32_t workgroups;              /* gridDim.x of the launch (of each pass) */
+  int32_t workgroups_y;            /* gridDim.y: Cin for MISEG_NE_PATCH_BWD_TEAM, else 1 */
+  int32_t per_workgroup;           /* items one workgroup takes per trip of its loop: 1 brick or tile, 256 thread items, or its block of rows */
+  int64_t items;                   /* bricks, tiles, thread items or rows of the whole problem: > workgroups * per_workgroup means the loops wrap */
+  int32_t passes;                  /* launches of this kernel (MISEG_NE_HEAD_DW_TEAM: ceil(Cout / 8)), 0 for MISEG_NE_NONE */
+  int32_t partial;                 /* 1: per-workgroup partial sums in `workspace` and a reduce launch (a fixed order of summation); 0: fp32 atomics or no sums */
+  int32_t idx32;                   /* 1: 32-bit item arithmetic (MISEG_NE_PATCH_FWD, MISEG_NE_HEAD_DX_TEAM), else 0 */
+  int32_t pad_;
+} miseg_net_end_launch;
+typedef struct { miseg_net_end_launch dx, dw; } miseg_head_bwd_plan_info;
+
 /* PatchEmbed Conv3d(k2,s2)+bias with Cin input channels given as NCDHW fp32 (the network input)
  * (networks/blocks/patch_embedding.py:167-169,204).  w: fp32 [Cout][Cin][2][2][2]. */
 typedef struct {
   const float* x; void* y; int64_t ldy; const float* w; const float* bias;
   int B, Cin, D, H, W, Cout, dtype;  /* D,H,W: input grid (even) */
 } miseg_patch_embed_params;
+int miseg_patch_embed_fwd_plan(const miseg_patch_embed_params* p, miseg_net_end_launch* plan);
 int miseg_patch_embed_fwd(const miseg_patch_embed_params* p, miseg_stream_t stream);
 typedef struct {
   const float* x; const void* dy; int64_t lddy; float* dw; float* dbias;   /* accumulated */
@@ -525,6 +561,7 @@ typedef struct {
                       * fp32 atomics from every workgroup onto the 9 * Cout outputs (46 of 53 us on the headline patch) */
 } miseg_patch_embed_bwd_params;
 size_t miseg_patch_embed_bwd_workspace_bytes(const miseg_patch_embed_bwd_params* p);
+int miseg_patch_embed_bwd_plan(const miseg_patch_embed_bwd_params* p, miseg_net_end_launch* plan);
 int miseg_patch_embed_bwd(const miseg_patch_embed_bwd_params* p, miseg_stream_t stream);
 
 /* First encoder conv: 3x3x3, Cin in {1..4} NCDHW fp32 input -> channels-last Cout (dynunet_block.py:55-64 with
@@ -533,6 +570,7 @@ typedef struct {
   const float* x; void* y; int64_t ldy; const float* w;
   int B, Cin, D, H, W, Cout, dtype;
 } miseg_conv3_thin_params;
+int miseg_conv3_thin_fwd_plan(const miseg_conv3_thin_params* p, miseg_net_end_launch* plan);
 int miseg_conv3_thin_fwd(const miseg_conv3_thin_params* p, miseg_stream_t stream);
 typedef struct {
   const float* x; const void* dy; int64_t lddy; float* dw;
@@ -541,6 +579,7 @@ typedef struct {
                       * small launch instead of fp32 atomics from every workgroup onto the 27 * Cout outputs */
 } miseg_conv3_thin_wgrad_params;
 size_t miseg_conv3_thin_wgrad_workspace_bytes(const miseg_conv3_thin_wgrad_params* p);
+int miseg_conv3_thin_wgrad_plan(const miseg_conv3_thin_wgrad_params* p, miseg_net_end_launch* plan);
 int miseg_conv3_thin_wgrad(const miseg_conv3_thin_wgrad_params* p, miseg_stream_t stream);
 
 /* Network input (NCDHW fp32, Cin <= 8 image channels) -> channels-last rows of CP channels (CP = 4 for fp32, 8 for bf16:
@@ -588,11 +627,13 @@ typedef struct {
   const void* x; int64_t ldx; float* y; const float* w; const float* bias;
   int B, S, Cin, Cout, dtype;
 } miseg_head_params;
+int miseg_head_fwd_plan(const miseg_head_params* p, miseg_net_end_launch* plan);
 int miseg_head_fwd(const miseg_head_params* p, miseg_stream_t stream);
 typedef struct {
   const void* x; int64_t ldx; const float* dy; void* dx; int64_t lddx; const float* w; float* dw; float* dbias;
   int B, S, Cin, Cout, dtype;
 } miseg_head_bwd_params;
+int miseg_head_bwd_plan(const miseg_head_bwd_params* p, miseg_head_bwd_plan_info* plan);
 int miseg_head_bwd(const miseg_head_bwd_params* p, miseg_stream_t stream);
 
 /* im2col for 3x3x3/pad 1 on small grids (<= 6^3): col[v][tap][ci]; and its adjoint col2im (dst zero-filled by

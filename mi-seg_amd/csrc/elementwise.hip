@@ -1511,19 +1511,43 @@ static int s2c_common(const miseg_s2c_params* p, hipStream_t s, bool gather) {
 extern "C" int miseg_space_to_channel(const miseg_s2c_params* p, miseg_stream_t s) { return s2c_common(p, (hipStream_t)s, true); }
 extern "C" int miseg_channel_to_space(const miseg_s2c_params* p, miseg_stream_t s) { return s2c_common(p, (hipStream_t)s, false); }
 
-extern "C" int miseg_patch_embed_fwd(const miseg_patch_embed_params* p, miseg_stream_t s_) {
-  hipStream_t s = (hipStream_t)s_;
+// ----------------------------------------------------------------------------- the network ends: one plan per launch
+// Each launcher below dispatches on the plan its miseg_*_plan entry point returns (host only): the predicates exist once.
+static inline int ne_vec(int dtype) { return dtype == MISEG_F32 ? 4 : 8; }      // Vec16<T>::N
+static inline miseg_net_end_launch ne_launch(int kernel, int64_t workgroups, int per_workgroup, int64_t items) {
+  miseg_net_end_launch l{};
+  l.kernel = kernel; l.workgroups = (int)workgroups; l.workgroups_y = 1; l.per_workgroup = per_workgroup; l.items = items; l.passes = 1;
+  return l;
+}
+#define NE_DTYPE(p) MISEG_REQUIRE((p)->dtype == MISEG_F32 || (p)->dtype == MISEG_BF16, MISEG_E_BADARG, "unknown dtype %d", (p)->dtype)
+static inline int stem_bricks(int B, int D, int H, int W) { return B * cdiv(D, miseg::SB_D) * cdiv(H, miseg::SB_H) * cdiv(W, miseg::SB_W); }
+
+static int patch_embed_fwd_plan(const miseg_patch_embed_params* p, miseg_net_end_launch* pl) {
   MISEG_REQUIRE(p && p->x && p->y && p->w, MISEG_E_BADARG, "patch_embed_fwd: null pointer");
   MISEG_REQUIRE(p->D % 2 == 0 && p->H % 2 == 0 && p->W % 2 == 0, MISEG_E_BADARG, "patch_embed_fwd: grid %dx%dx%d must be even (pad on host)", p->D, p->H, p->W);
   MISEG_REQUIRE(p->Cin * 8 * p->Cout <= 12000, MISEG_E_UNSUPPORTED, "patch_embed_fwd: Cin*8*Cout too large");
+  NE_DTYPE(p);
+  const int64_t tot = (int64_t)p->B * (p->D / 2) * (p->H / 2) * (p->W / 2) * ((p->Cout + 7) / 8);
+  // (grid sweep, round 5: 2592 = 1296 workgroups 15.2 us, 864: 17.7, 648: 20.7 - the kernel is its instruction count, not its launch shape)
+  *pl = ne_launch(MISEG_NE_PATCH_FWD, ew_grid(tot), 256, tot);
+  pl->idx32 = tot + 256 * 8192 < (1LL << 31) && (int64_t)p->B * p->Cin * p->D * p->H * p->W < (1LL << 31);
+  return MISEG_OK;
+}
+extern "C" int miseg_patch_embed_fwd_plan(const miseg_patch_embed_params* p, miseg_net_end_launch* plan) {
+  MISEG_REQUIRE(plan, MISEG_E_BADARG, "patch_embed_fwd_plan: null pointer");
+  return patch_embed_fwd_plan(p, plan);
+}
+
+extern "C" int miseg_patch_embed_fwd(const miseg_patch_embed_params* p, miseg_stream_t s_) {
+  hipStream_t s = (hipStream_t)s_;
+  miseg_net_end_launch pl;
+  if (int rc = patch_embed_fwd_plan(p, &pl)) return rc;
   DT(p, {
-    const int64_t tot = (int64_t)p->B * (p->D / 2) * (p->H / 2) * (p->W / 2) * ((p->Cout + 7) / 8);
     size_t sh = ((size_t)p->Cin * 8 * p->Cout + p->Cout) * sizeof(float);
-    // (grid sweep, round 5: 2592 = 1296 workgroups 15.2 us, 864: 17.7, 648: 20.7 - the kernel is its instruction count, not its launch shape)
-    if (tot + 256 * 8192 < (1LL << 31) && (int64_t)p->B * p->Cin * p->D * p->H * p->W < (1LL << 31))
-      patch_embed_fwd_kernel<T, unsigned><<<ew_grid(tot), 256, sh, s>>>(p->x, (T*)p->y, p->ldy, p->w, p->bias, p->B, p->Cin, p->D, p->H, p->W, p->Cout);
+    if (pl.idx32)
+      patch_embed_fwd_kernel<T, unsigned><<<pl.workgroups, 256, sh, s>>>(p->x, (T*)p->y, p->ldy, p->w, p->bias, p->B, p->Cin, p->D, p->H, p->W, p->Cout);
     else
-      patch_embed_fwd_kernel<T><<<ew_grid(tot), 256, sh, s>>>(p->x, (T*)p->y, p->ldy, p->w, p->bias, p->B, p->Cin, p->D, p->H, p->W, p->Cout);
+      patch_embed_fwd_kernel<T><<<pl.workgroups, 256, sh, s>>>(p->x, (T*)p->y, p->ldy, p->w, p->bias, p->B, p->Cin, p->D, p->H, p->W, p->Cout);
     MISEG_LAUNCH_CHECK("patch_embed_fwd");
   });
 }
@@ -1533,56 +1557,91 @@ extern "C" size_t miseg_patch_embed_bwd_workspace_bytes(const miseg_patch_embed_
   return (size_t)256 * p->Cin * 9 * p->Cout * sizeof(float);       // at most 256 workgroups per input channel
 }
 
-extern "C" int miseg_patch_embed_bwd(const miseg_patch_embed_bwd_params* p, miseg_stream_t s_) {
-  hipStream_t s = (hipStream_t)s_;
+static int patch_embed_bwd_plan(const miseg_patch_embed_bwd_params* p, miseg_net_end_launch* pl) {
   MISEG_REQUIRE(p && p->x && p->dy && p->dw, MISEG_E_BADARG, "patch_embed_bwd: null pointer");
   MISEG_REQUIRE(p->Cout * (p->Cin * 8 + 1) <= 2048, MISEG_E_UNSUPPORTED, "patch_embed_bwd: Cout*(8Cin+1) > 2048");
+  NE_DTYPE(p);
+  const int64_t nv = (int64_t)p->B * (p->D / 2) * (p->H / 2) * (p->W / 2);
+  const int N = ne_vec(p->dtype), tx_n = p->Cout / N;
+  if (p->Cout % N == 0 && p->lddy % N == 0 && al16(p->dy) && tx_n >= 1 && tx_n <= 64) {
+    const int ty_n = 256 / tx_n;
+    int rpb = (int)((nv + 255) / 256);
+    if (rpb < 4 * ty_n) rpb = 4 * ty_n;
+    *pl = ne_launch(MISEG_NE_PATCH_BWD_TEAM, cdiv(nv, rpb), rpb, nv);
+    pl->workgroups_y = p->Cin;
+    pl->partial = p->workspace && pl->workgroups >= 16;
+  } else
+    *pl = ne_launch(MISEG_NE_PATCH_BWD_GENERIC, cdiv(nv, 1024), 1024, nv);
+  return MISEG_OK;
+}
+extern "C" int miseg_patch_embed_bwd_plan(const miseg_patch_embed_bwd_params* p, miseg_net_end_launch* plan) {
+  MISEG_REQUIRE(plan, MISEG_E_BADARG, "patch_embed_bwd_plan: null pointer");
+  return patch_embed_bwd_plan(p, plan);
+}
+
+extern "C" int miseg_patch_embed_bwd(const miseg_patch_embed_bwd_params* p, miseg_stream_t s_) {
+  hipStream_t s = (hipStream_t)s_;
+  miseg_net_end_launch pl;
+  if (int rc = patch_embed_bwd_plan(p, &pl)) return rc;
   DT(p, {
-    const int64_t nv = (int64_t)p->B * (p->D / 2) * (p->H / 2) * (p->W / 2);
     constexpr int N = Vec16<T>::N;
-    const int tx_n = p->Cout / N;
-    if (p->Cout % N == 0 && p->lddy % N == 0 && al16(p->dy) && tx_n >= 1 && tx_n <= 64) {
-      const int ty_n = 256 / tx_n;
-      int rpb = (int)((nv + 255) / 256);
-      if (rpb < 4 * ty_n) rpb = 4 * ty_n;
+    if (pl.kernel == MISEG_NE_PATCH_BWD_TEAM) {
+      const int tx_n = p->Cout / N, ty_n = 256 / tx_n, rpb = pl.per_workgroup, nblk = pl.workgroups;
       const size_t sh = (size_t)ty_n * 9 * tx_n * N * sizeof(float);
       hipFuncSetAttribute((const void*)patch_embed_bwd_team_kernel<T, N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-      const int nblk = cdiv(nv, rpb);
-      float* part = (p->workspace && nblk >= 16) ? (float*)p->workspace : nullptr;
-      patch_embed_bwd_team_kernel<T, N><<<dim3(nblk, p->Cin), 256, sh, s>>>(p->x, (const T*)p->dy, p->lddy, p->dw, p->dbias, p->B, p->Cin, p->D, p->H, p->W,
-                                                                            p->Cout, rpb, part);
+      float* part = pl.partial ? (float*)p->workspace : nullptr;
+      patch_embed_bwd_team_kernel<T, N><<<dim3(nblk, pl.workgroups_y), 256, sh, s>>>(p->x, (const T*)p->dy, p->lddy, p->dw, p->dbias, p->B, p->Cin, p->D, p->H, p->W,
+                                                                                   p->Cout, rpb, part);
       if (part) patch_embed_bwd_reduce_kernel<<<dim3(cdiv(9 * p->Cout, 32), p->Cin), 256, 0, s>>>(part, p->dw, p->dbias, p->Cin, p->Cout, nblk);
     } else {
-      const int vpb = 1024;
+      const int vpb = pl.per_workgroup;
       size_t sh = ((size_t)64 * (p->Cin * 8 + 1) + 64 * p->Cout) * sizeof(float);
-      patch_embed_bwd_kernel<T><<<cdiv(nv, vpb), 256, sh, s>>>(p->x, (const T*)p->dy, p->lddy, p->dw, p->dbias, p->B, p->Cin, p->D, p->H, p->W, p->Cout, vpb);
+      patch_embed_bwd_kernel<T><<<pl.workgroups, 256, sh, s>>>(p->x, (const T*)p->dy, p->lddy, p->dw, p->dbias, p->B, p->Cin, p->D, p->H, p->W, p->Cout, vpb);
     }
     MISEG_LAUNCH_CHECK("patch_embed_bwd");
   });
 }
 
-extern "C" int miseg_conv3_thin_fwd(const miseg_conv3_thin_params* p, miseg_stream_t s_) {
-  hipStream_t s = (hipStream_t)s_;
+static int conv3_thin_fwd_plan(const miseg_conv3_thin_params* p, miseg_net_end_launch* pl) {
   MISEG_REQUIRE(p && p->x && p->y && p->w, MISEG_E_BADARG, "conv3_thin_fwd: null pointer");
   MISEG_REQUIRE(p->Cin >= 1 && p->Cin <= 4 && p->Cin * 27 * p->Cout <= 15000, MISEG_E_UNSUPPORTED, "conv3_thin_fwd: Cin %d Cout %d", p->Cin, p->Cout);
-  DT(p, {
+  NE_DTYPE(p);
+  const int nbricks = stem_bricks(p->B, p->D, p->H, p->W);
+  if (p->dtype == MISEG_BF16 && p->Cin == 1 && p->Cout == 48 && p->ldy % 4 == 0 && ((uintptr_t)p->y & 7) == 0)      // matrix-core form (see conv3_stem_fwd_mfma_kernel)
+    *pl = ne_launch(MISEG_NE_STEM_FWD_MFMA, nbricks < 2048 ? nbricks : 2048, 1, nbricks);
+  else if (p->Cin == 1 && p->Cout % 8 == 0 && p->Cout <= 64 && p->ldy % 8 == 0 && al16(p->y))       // brick kernel (see conv3_stem_fwd_kernel)
+    *pl = ne_launch(MISEG_NE_STEM_FWD_BRICK, nbricks < 4096 ? nbricks : 4096, 1, nbricks);
+  else {
     const int64_t nv = (int64_t)p->B * p->D * p->H * p->W;
+    *pl = ne_launch(MISEG_NE_STEM_FWD_GENERIC, ew_grid(nv), 256, nv);
+  }
+  return MISEG_OK;
+}
+extern "C" int miseg_conv3_thin_fwd_plan(const miseg_conv3_thin_params* p, miseg_net_end_launch* plan) {
+  MISEG_REQUIRE(plan, MISEG_E_BADARG, "conv3_thin_fwd_plan: null pointer");
+  return conv3_thin_fwd_plan(p, plan);
+}
+
+extern "C" int miseg_conv3_thin_fwd(const miseg_conv3_thin_params* p, miseg_stream_t s_) {
+  hipStream_t s = (hipStream_t)s_;
+  miseg_net_end_launch pl;
+  if (int rc = conv3_thin_fwd_plan(p, &pl)) return rc;
+  DT(p, {
     if constexpr (std::is_same<T, bf16>::value) {
-      if (p->Cin == 1 && p->Cout == 48 && p->ldy % 4 == 0 && ((uintptr_t)p->y & 7) == 0) {           // matrix-core form (see conv3_stem_fwd_mfma_kernel)
-        const int nbricks = p->B * cdiv(p->D, miseg::SB_D) * cdiv(p->H, miseg::SB_H) * cdiv(p->W, miseg::SB_W);
-        conv3_stem_fwd_mfma_kernel<<<nbricks < 2048 ? nbricks : 2048, 256, 0, s>>>(p->x, (bf16*)p->y, p->ldy, p->w, p->B, p->D, p->H, p->W, nbricks);
+      if (pl.kernel == MISEG_NE_STEM_FWD_MFMA) {
+        conv3_stem_fwd_mfma_kernel<<<pl.workgroups, 256, 0, s>>>(p->x, (bf16*)p->y, p->ldy, p->w, p->B, p->D, p->H, p->W, (int)pl.items);
         MISEG_LAUNCH_CHECK("conv3_stem_fwd_mfma");
         return MISEG_OK;
       }
     }
-    if (p->Cin == 1 && p->Cout % 8 == 0 && p->Cout <= 64 && p->ldy % 8 == 0 && al16(p->y)) {       // brick kernel (see conv3_stem_fwd_kernel)
-      const int nbricks = p->B * cdiv(p->D, miseg::SB_D) * cdiv(p->H, miseg::SB_H) * cdiv(p->W, miseg::SB_W);
-      conv3_stem_fwd_kernel<T><<<nbricks < 4096 ? nbricks : 4096, 256, 0, s>>>(p->x, (T*)p->y, p->ldy, p->w, p->B, p->D, p->H, p->W, p->Cout, nbricks);
+    if (pl.kernel == MISEG_NE_STEM_FWD_BRICK) {
+      conv3_stem_fwd_kernel<T><<<pl.workgroups, 256, 0, s>>>(p->x, (T*)p->y, p->ldy, p->w, p->B, p->D, p->H, p->W, p->Cout, (int)pl.items);
       MISEG_LAUNCH_CHECK("conv3_stem_fwd");
       return MISEG_OK;
     }
+    MISEG_REQUIRE(pl.kernel == MISEG_NE_STEM_FWD_GENERIC, MISEG_E_BADARG, "conv3_thin_fwd: plan names kernel %d", pl.kernel);
     size_t sh = (size_t)p->Cin * 27 * p->Cout * sizeof(float);
-    conv3_thin_fwd_kernel<T><<<ew_grid(nv), 256, sh, s>>>(p->x, (T*)p->y, p->ldy, p->w, p->B, p->Cin, p->D, p->H, p->W, p->Cout);
+    conv3_thin_fwd_kernel<T><<<pl.workgroups, 256, sh, s>>>(p->x, (T*)p->y, p->ldy, p->w, p->B, p->Cin, p->D, p->H, p->W, p->Cout);
     MISEG_LAUNCH_CHECK("conv3_thin_fwd");
   });
 }
@@ -1591,36 +1650,55 @@ extern "C" size_t miseg_conv3_thin_wgrad_workspace_bytes(const miseg_conv3_thin_
   return (p && p->dtype == MISEG_BF16 && p->Cin == 1 && p->Cout == 48) ? (size_t)512 * 48 * 27 * sizeof(float) : 0;      // the matrix-core form only
 }
 
-extern "C" int miseg_conv3_thin_wgrad(const miseg_conv3_thin_wgrad_params* p, miseg_stream_t s_) {
-  hipStream_t s = (hipStream_t)s_;
+static int conv3_thin_wgrad_plan(const miseg_conv3_thin_wgrad_params* p, miseg_net_end_launch* pl) {
   MISEG_REQUIRE(p && p->x && p->dy && p->dw, MISEG_E_BADARG, "conv3_thin_wgrad: null pointer");
   MISEG_REQUIRE(p->Cin >= 1 && p->Cin <= 4 && p->Cout <= 64, MISEG_E_UNSUPPORTED, "conv3_thin_wgrad: Cin %d Cout %d", p->Cin, p->Cout);
+  NE_DTYPE(p);
+  const int VN = ne_vec(p->dtype);
+  const int nbricks = stem_bricks(p->B, p->D, p->H, p->W);
+  if (p->dtype == MISEG_BF16 && p->Cin == 1 && p->Cout == 48 && p->lddy % 8 == 0 && al16(p->dy)) {      // matrix-core form (see conv3_stem_wgrad_mfma_kernel)
+    *pl = ne_launch(MISEG_NE_STEM_WGRAD_MFMA, nbricks < 512 ? nbricks : 512, 1, nbricks);
+    pl->partial = p->workspace && pl->workgroups >= 16;
+  } else if (p->Cin == 1 && p->Cout % 8 == 0 && p->Cout % VN == 0 && p->Cout / 8 * 36 <= 256 && p->lddy % VN == 0 && al16(p->dy))   // see conv3_stem_wgrad_kernel
+    *pl = ne_launch(MISEG_NE_STEM_WGRAD_BRICK, nbricks < 512 ? nbricks : 512, 1, nbricks);
+  else {
+    const int nb = p->B * cdiv(p->D, 8) * cdiv(p->H, 8) * cdiv(p->W, 8);
+    *pl = ne_launch(MISEG_NE_STEM_WGRAD_GENERIC, nb, 1, nb);
+  }
+  return MISEG_OK;
+}
+extern "C" int miseg_conv3_thin_wgrad_plan(const miseg_conv3_thin_wgrad_params* p, miseg_net_end_launch* plan) {
+  MISEG_REQUIRE(plan, MISEG_E_BADARG, "conv3_thin_wgrad_plan: null pointer");
+  return conv3_thin_wgrad_plan(p, plan);
+}
+
+extern "C" int miseg_conv3_thin_wgrad(const miseg_conv3_thin_wgrad_params* p, miseg_stream_t s_) {
+  hipStream_t s = (hipStream_t)s_;
+  miseg_net_end_launch pl;
+  if (int rc = conv3_thin_wgrad_plan(p, &pl)) return rc;
   DT(p, {
-    constexpr int VN = Vec16<T>::N;
     if constexpr (std::is_same<T, bf16>::value) {
-      if (p->Cin == 1 && p->Cout == 48 && p->lddy % 8 == 0 && al16(p->dy)) {      // matrix-core form (see conv3_stem_wgrad_mfma_kernel)
-        const int nbricks = p->B * cdiv(p->D, miseg::SB_D) * cdiv(p->H, miseg::SB_H) * cdiv(p->W, miseg::SB_W);
-        const int nblk = nbricks < 512 ? nbricks : 512;
-        float* part = (p->workspace && nblk >= 16) ? (float*)p->workspace : nullptr;
-        conv3_stem_wgrad_mfma_kernel<<<nblk, 256, 0, s>>>(p->x, (const bf16*)p->dy, p->lddy, p->dw, p->B, p->D, p->H, p->W, nbricks, part);
+      if (pl.kernel == MISEG_NE_STEM_WGRAD_MFMA) {
+        const int nblk = pl.workgroups;
+        float* part = pl.partial ? (float*)p->workspace : nullptr;
+        conv3_stem_wgrad_mfma_kernel<<<nblk, 256, 0, s>>>(p->x, (const bf16*)p->dy, p->lddy, p->dw, p->B, p->D, p->H, p->W, (int)pl.items, part);
         if (part) partial_sum_add_kernel<<<cdiv(48 * 27, 32), 256, 0, s>>>(part, p->dw, 48 * 27, nblk);
         MISEG_LAUNCH_CHECK("conv3_stem_wgrad_mfma");
         return MISEG_OK;
       }
     }
-    if (p->Cin == 1 && p->Cout % 8 == 0 && p->Cout % VN == 0 && p->Cout / 8 * 36 <= 256 && p->lddy % VN == 0 && al16(p->dy)) {   // see conv3_stem_wgrad_kernel
-      const int nbricks = p->B * cdiv(p->D, miseg::SB_D) * cdiv(p->H, miseg::SB_H) * cdiv(p->W, miseg::SB_W);
+    if (pl.kernel == MISEG_NE_STEM_WGRAD_BRICK) {
       size_t sh = 2608 + (size_t)256 * p->Cout * sizeof(T);
       if (sh < 256 * 24 * 4) sh = 256 * 24 * 4;
       (void)hipFuncSetAttribute((const void*)conv3_stem_wgrad_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-      conv3_stem_wgrad_kernel<T><<<nbricks < 512 ? nbricks : 512, 256, sh, s>>>(p->x, (const T*)p->dy, p->lddy, p->dw, p->B, p->D, p->H, p->W, p->Cout, nbricks);
+      conv3_stem_wgrad_kernel<T><<<pl.workgroups, 256, sh, s>>>(p->x, (const T*)p->dy, p->lddy, p->dw, p->B, p->D, p->H, p->W, p->Cout, (int)pl.items);
       MISEG_LAUNCH_CHECK("conv3_stem_wgrad");
       return MISEG_OK;
     }
-    const int nb = p->B * cdiv(p->D, 8) * cdiv(p->H, 8) * cdiv(p->W, 8);
+    MISEG_REQUIRE(pl.kernel == MISEG_NE_STEM_WGRAD_GENERIC, MISEG_E_BADARG, "conv3_thin_wgrad: plan names kernel %d", pl.kernel);
     size_t sh = ((size_t)1000 + 512 * p->Cout) * sizeof(float);
     hipFuncSetAttribute((const void*)conv3_thin_wgrad_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    conv3_thin_wgrad_kernel<T><<<nb, 256, sh, s>>>(p->x, (const T*)p->dy, p->lddy, p->dw, p->B, p->Cin, p->D, p->H, p->W, p->Cout);
+    conv3_thin_wgrad_kernel<T><<<pl.workgroups, 256, sh, s>>>(p->x, (const T*)p->dy, p->lddy, p->dw, p->B, p->Cin, p->D, p->H, p->W, p->Cout);
     MISEG_LAUNCH_CHECK("conv3_thin_wgrad");
   });
 }
@@ -1630,68 +1708,110 @@ extern "C" int miseg_conv3_thin_wgrad(const miseg_conv3_thin_wgrad_params* p, mi
 // 36.5 / 65.8, **1152 / 494: 32.6 / 62.8**, 864: 37.0 / 63.1, 576: 47.6 / 63.4, 3456: 33.8 / 82; weight gradient at 256 / 864: + 10 / + 2.5 us
 static constexpr int HEAD_GRID_CAP = 1152, HEAD_DW_GRID_CAP = 512;
 
-extern "C" int miseg_head_fwd(const miseg_head_params* p, miseg_stream_t s_) {
-  hipStream_t s = (hipStream_t)s_;
+static int head_fwd_plan(const miseg_head_params* p, miseg_net_end_launch* pl) {
   MISEG_REQUIRE(p && p->x && p->y && p->w, MISEG_E_BADARG, "head_fwd: null pointer");
   MISEG_REQUIRE(p->Cout <= 16 && p->Cin * p->Cout <= 8192, MISEG_E_UNSUPPORTED, "head_fwd: Cout %d (max 16)", p->Cout);
+  NE_DTYPE(p);
+  const int N = ne_vec(p->dtype);
+  const int64_t nv = (int64_t)p->B * p->S;
+  if (p->Cin % N == 0 && p->ldx % N == 0 && al16(p->x)) {
+    const int64_t ntiles = (nv + 255) / 256;
+    *pl = ne_launch(MISEG_NE_HEAD_FWD_TILE, balanced_grid(ntiles, HEAD_GRID_CAP), 1, ntiles);
+  } else
+    *pl = ne_launch(MISEG_NE_HEAD_FWD_SCALAR, ew_grid(nv), 256, nv);
+  return MISEG_OK;
+}
+extern "C" int miseg_head_fwd_plan(const miseg_head_params* p, miseg_net_end_launch* plan) {
+  MISEG_REQUIRE(plan, MISEG_E_BADARG, "head_fwd_plan: null pointer");
+  return head_fwd_plan(p, plan);
+}
+
+extern "C" int miseg_head_fwd(const miseg_head_params* p, miseg_stream_t s_) {
+  hipStream_t s = (hipStream_t)s_;
+  miseg_net_end_launch pl;
+  if (int rc = head_fwd_plan(p, &pl)) return rc;
   DT(p, {
     size_t sh = ((size_t)p->Cin * p->Cout + p->Cout) * sizeof(float);
     constexpr int N = Vec16<T>::N;
-    if (p->Cin % N == 0 && p->ldx % N == 0 && al16(p->x)) {
-      const int64_t nv = (int64_t)p->B * p->S;
+    if (pl.kernel == MISEG_NE_HEAD_FWD_TILE) {
       const size_t sh2 = (size_t)((p->Cout * p->Cin + p->Cout + 3) & ~3) * 4 + (size_t)256 * (p->Cin * sizeof(T) + 16);
-      const int grid = balanced_grid((nv + 255) / 256, HEAD_GRID_CAP);
       hipFuncSetAttribute((const void*)head_fwd_tile_kernel<T, N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh2);
-      head_fwd_tile_kernel<T, N><<<grid, 256, sh2, s>>>((const T*)p->x, p->ldx, p->y, p->w, p->bias, p->B, p->S, p->Cin, p->Cout);
+      head_fwd_tile_kernel<T, N><<<pl.workgroups, 256, sh2, s>>>((const T*)p->x, p->ldx, p->y, p->w, p->bias, p->B, p->S, p->Cin, p->Cout);
     } else
-      head_fwd_kernel<T, 1><<<ew_grid((int64_t)p->B * p->S), 256, sh, s>>>((const T*)p->x, p->ldx, p->y, p->w, p->bias, p->B, p->S, p->Cin, p->Cout);
+      head_fwd_kernel<T, 1><<<pl.workgroups, 256, sh, s>>>((const T*)p->x, p->ldx, p->y, p->w, p->bias, p->B, p->S, p->Cin, p->Cout);
     MISEG_LAUNCH_CHECK("head_fwd");
   });
 }
 
-extern "C" int miseg_head_bwd(const miseg_head_bwd_params* p, miseg_stream_t s_) {
-  hipStream_t s = (hipStream_t)s_;
+static int head_bwd_plan(const miseg_head_bwd_params* p, miseg_head_bwd_plan_info* pl) {
   MISEG_REQUIRE(p && p->x && p->dy && p->w, MISEG_E_BADARG, "head_bwd: null pointer");
   MISEG_REQUIRE(p->Cout <= 16 && p->Cout * (p->Cin + 1) <= 1024, MISEG_E_UNSUPPORTED, "head_bwd: Cout %d Cin %d", p->Cout, p->Cin);
+  NE_DTYPE(p);
+  const int64_t nv = (int64_t)p->B * p->S;
+  const int N = ne_vec(p->dtype);
+  pl->dx = pl->dw = miseg_net_end_launch{};      // MISEG_NE_NONE
+  if (p->dx) {
+    if (p->Cin % N == 0 && p->lddx % N == 0 && al16(p->dx) && p->Cout <= 8 && p->S % 256 == 0 && p->Cin / N <= 32 && N == 8)
+      pl->dx = ne_launch(MISEG_NE_HEAD_DX_TILE, balanced_grid(nv / 256, HEAD_GRID_CAP), 1, nv / 256);
+    else if (p->Cin % N == 0 && p->lddx % N == 0 && al16(p->dx)) {
+      const int64_t items = nv * (p->Cin / N);
+      pl->dx = ne_launch(MISEG_NE_HEAD_DX_TEAM, ew_grid(items), 256, items);
+      pl->dx.idx32 = items < (1LL << 29);      // 32-bit item arithmetic (see s2c_kernel)
+    } else
+      pl->dx = ne_launch(MISEG_NE_HEAD_DX_SCALAR, ew_grid(nv), 256, nv);
+  }
+  if (p->dw) {
+    const int tx_n = p->Cin / N;
+    if (p->dtype == MISEG_BF16 && p->Cin == 48 && p->Cout <= 16 && p->S % 256 == 0 && p->ldx % 8 == 0 && al16(p->x) && al16(p->dy))
+      pl->dw = ne_launch(MISEG_NE_HEAD_DW_MFMA, balanced_grid(nv / 256, HEAD_DW_GRID_CAP), 1, nv / 256);
+    else if (p->Cin % N == 0 && p->ldx % N == 0 && al16(p->x) && tx_n >= 1 && tx_n <= 64) {
+      const int ty_n = 256 / tx_n;
+      int rpb = (int)((nv + 2047) / 2048);
+      if (rpb < 4 * ty_n) rpb = 4 * ty_n;
+      pl->dw = ne_launch(MISEG_NE_HEAD_DW_TEAM, cdiv(nv, rpb), rpb, nv);
+      pl->dw.passes = (p->Cout + 7) / 8;      // 8 output channels per launch
+    } else
+      pl->dw = ne_launch(MISEG_NE_HEAD_DW_GENERIC, cdiv(nv, 2048), 2048, nv);
+  }
+  return MISEG_OK;
+}
+extern "C" int miseg_head_bwd_plan(const miseg_head_bwd_params* p, miseg_head_bwd_plan_info* plan) {
+  MISEG_REQUIRE(plan, MISEG_E_BADARG, "head_bwd_plan: null pointer");
+  return head_bwd_plan(p, plan);
+}
+
+extern "C" int miseg_head_bwd(const miseg_head_bwd_params* p, miseg_stream_t s_) {
+  hipStream_t s = (hipStream_t)s_;
+  miseg_head_bwd_plan_info pl;
+  if (int rc = head_bwd_plan(p, &pl)) return rc;
   DT(p, {
-    const int64_t nv = (int64_t)p->B * p->S;
     constexpr int N = Vec16<T>::N;
-    if (p->dx) {
+    if (pl.dx.kernel != MISEG_NE_NONE) {
       size_t sh = (size_t)p->Cin * p->Cout * sizeof(float);
-      if (p->Cin % N == 0 && p->lddx % N == 0 && al16(p->dx) && p->Cout <= 8 && p->S % 256 == 0 && p->Cin / N <= 32 && N == 8) {
-        const int64_t ntiles = nv / 256;
-        head_bwd_dx_tile_kernel<T, N><<<balanced_grid(ntiles, HEAD_GRID_CAP), 256, 0, s>>>(p->dy, (T*)p->dx, p->lddx, p->w, p->S, p->Cin, p->Cout, ntiles);
-      } else if (p->Cin % N == 0 && p->lddx % N == 0 && al16(p->dx))
-        if (nv * (p->Cin / N) < (1LL << 29))      // 32-bit item arithmetic (see s2c_kernel)
-          head_bwd_dx_team_kernel<T, N, unsigned><<<ew_grid(nv * (p->Cin / N)), 256, sh, s>>>(p->dy, (T*)p->dx, p->lddx, p->w, p->B, p->S, p->Cin, p->Cout);
+      if (pl.dx.kernel == MISEG_NE_HEAD_DX_TILE)
+        head_bwd_dx_tile_kernel<T, N><<<pl.dx.workgroups, 256, 0, s>>>(p->dy, (T*)p->dx, p->lddx, p->w, p->S, p->Cin, p->Cout, pl.dx.items);
+      else if (pl.dx.kernel == MISEG_NE_HEAD_DX_TEAM)
+        if (pl.dx.idx32)
+          head_bwd_dx_team_kernel<T, N, unsigned><<<pl.dx.workgroups, 256, sh, s>>>(p->dy, (T*)p->dx, p->lddx, p->w, p->B, p->S, p->Cin, p->Cout);
         else
-          head_bwd_dx_team_kernel<T, N><<<ew_grid(nv * (p->Cin / N)), 256, sh, s>>>(p->dy, (T*)p->dx, p->lddx, p->w, p->B, p->S, p->Cin, p->Cout);
+          head_bwd_dx_team_kernel<T, N><<<pl.dx.workgroups, 256, sh, s>>>(p->dy, (T*)p->dx, p->lddx, p->w, p->B, p->S, p->Cin, p->Cout);
       else
-        head_bwd_dx_kernel<T, 1><<<ew_grid(nv), 256, sh, s>>>(p->dy, (T*)p->dx, p->lddx, p->w, p->B, p->S, p->Cin, p->Cout);
+        head_bwd_dx_kernel<T, 1><<<pl.dx.workgroups, 256, sh, s>>>(p->dy, (T*)p->dx, p->lddx, p->w, p->B, p->S, p->Cin, p->Cout);
     }
-    bool dw_done = false;
     if constexpr (std::is_same<T, bf16>::value) {
-      if (p->dw && p->Cin == 48 && p->Cout <= 16 && p->S % 256 == 0 && p->ldx % 8 == 0 && al16(p->x) && al16(p->dy)) {
-        const int64_t ntiles = nv / 256;
-        head_bwd_dw_mfma_kernel<<<balanced_grid(ntiles, HEAD_DW_GRID_CAP), 256, 0, s>>>((const bf16*)p->x, p->ldx, p->dy, p->dw, p->dbias, p->S, p->Cout, ntiles);
-        dw_done = true;
-      }
+      if (pl.dw.kernel == MISEG_NE_HEAD_DW_MFMA)
+        head_bwd_dw_mfma_kernel<<<pl.dw.workgroups, 256, 0, s>>>((const bf16*)p->x, p->ldx, p->dy, p->dw, p->dbias, p->S, p->Cout, pl.dw.items);
     }
-    if (p->dw && !dw_done) {
-      const int tx_n = p->Cin / N;
-      if (p->Cin % N == 0 && p->ldx % N == 0 && al16(p->x) && tx_n >= 1 && tx_n <= 64) {
-        const int ty_n = 256 / tx_n;
-        int rpb = (int)((nv + 2047) / 2048);
-        if (rpb < 4 * ty_n) rpb = 4 * ty_n;
-        const size_t sh = (size_t)ty_n * 8 * tx_n * N * sizeof(float);
-        hipFuncSetAttribute((const void*)head_bwd_dw_team_kernel<T, N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        for (int co0 = 0; co0 < p->Cout; co0 += 8)
-          head_bwd_dw_team_kernel<T, N><<<cdiv(nv, rpb), 256, sh, s>>>((const T*)p->x, p->ldx, p->dy, p->dw, p->dbias, p->B, p->S, p->Cin, p->Cout, co0, rpb);
-      } else {
-        const int vpb = 2048;
-        size_t sh = ((size_t)64 * (p->Cin + 1) + (size_t)p->Cout * 64) * sizeof(float);
-        head_bwd_dw_kernel<T><<<cdiv(nv, vpb), 256, sh, s>>>((const T*)p->x, p->ldx, p->dy, p->dw, p->dbias, p->B, p->S, p->Cin, p->Cout, vpb);
-      }
+    if (pl.dw.kernel == MISEG_NE_HEAD_DW_TEAM) {
+      const int tx_n = p->Cin / N, ty_n = 256 / tx_n, rpb = pl.dw.per_workgroup;
+      const size_t sh = (size_t)ty_n * 8 * tx_n * N * sizeof(float);
+      hipFuncSetAttribute((const void*)head_bwd_dw_team_kernel<T, N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+      for (int pass = 0; pass < pl.dw.passes; ++pass)
+        head_bwd_dw_team_kernel<T, N><<<pl.dw.workgroups, 256, sh, s>>>((const T*)p->x, p->ldx, p->dy, p->dw, p->dbias, p->B, p->S, p->Cin, p->Cout, 8 * pass, rpb);
+    } else if (pl.dw.kernel == MISEG_NE_HEAD_DW_GENERIC) {
+      const int vpb = pl.dw.per_workgroup;
+      size_t sh = ((size_t)64 * (p->Cin + 1) + (size_t)p->Cout * 64) * sizeof(float);
+      head_bwd_dw_kernel<T><<<pl.dw.workgroups, 256, sh, s>>>((const T*)p->x, p->ldx, p->dy, p->dw, p->dbias, p->B, p->S, p->Cin, p->Cout, vpb);
     }
     MISEG_LAUNCH_CHECK("head_bwd");
   });

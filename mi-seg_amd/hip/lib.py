@@ -126,6 +126,21 @@ HeadBwd = _struct("HeadBwd", cname="miseg_head_bwd_params", fields=[("x", vp), (
                               ("B", i32), ("S", i32), ("Cin", i32), ("Cout", i32), ("dtype", i32)])
 Im2col3 = _struct("Im2col3", cname="miseg_im2col3_params", fields=[("src", vp), ("lds", i64), ("dst", vp), ("ldd", i64), ("B", i32), ("D", i32), ("H", i32), ("W", i32),
                               ("C", i32), ("dtype", i32)])
+# miseg_net_end_launch.kernel (MISEG_NE_*): what the network-end launchers run, as their plans report it
+NE_NONE, NE_STEM_FWD_GENERIC, NE_STEM_FWD_BRICK, NE_STEM_FWD_MFMA, NE_STEM_WGRAD_GENERIC, NE_STEM_WGRAD_BRICK, NE_STEM_WGRAD_MFMA = 0, 1, 2, 3, 4, 5, 6
+NE_PATCH_FWD, NE_PATCH_BWD_GENERIC, NE_PATCH_BWD_TEAM, NE_HEAD_FWD_SCALAR, NE_HEAD_FWD_TILE = 7, 8, 9, 10, 11
+NE_HEAD_DX_SCALAR, NE_HEAD_DX_TEAM, NE_HEAD_DX_TILE, NE_HEAD_DW_GENERIC, NE_HEAD_DW_TEAM, NE_HEAD_DW_MFMA = 12, 13, 14, 15, 16, 17
+NE_KERNELS = {      # plan call -> the kernels it can name
+    "miseg_conv3_thin_fwd_plan": (NE_STEM_FWD_GENERIC, NE_STEM_FWD_BRICK, NE_STEM_FWD_MFMA),
+    "miseg_conv3_thin_wgrad_plan": (NE_STEM_WGRAD_GENERIC, NE_STEM_WGRAD_BRICK, NE_STEM_WGRAD_MFMA),
+    "miseg_patch_embed_fwd_plan": (NE_PATCH_FWD,),
+    "miseg_patch_embed_bwd_plan": (NE_PATCH_BWD_GENERIC, NE_PATCH_BWD_TEAM),
+    "miseg_head_fwd_plan": (NE_HEAD_FWD_SCALAR, NE_HEAD_FWD_TILE),
+    "miseg_head_bwd_plan": (NE_NONE, NE_HEAD_DX_SCALAR, NE_HEAD_DX_TEAM, NE_HEAD_DX_TILE, NE_HEAD_DW_GENERIC, NE_HEAD_DW_TEAM, NE_HEAD_DW_MFMA),
+}
+NetEndLaunch = _struct("NetEndLaunch", cname="miseg_net_end_launch", fields=[("kernel", i32), ("workgroups", i32), ("workgroups_y", i32), ("per_workgroup", i32),
+                                                                            ("items", i64), ("passes", i32), ("partial", i32), ("idx32", i32), ("pad_", i32)])
+HeadBwdPlan = _struct("HeadBwdPlan", cname="miseg_head_bwd_plan_info", fields=[("dx", NetEndLaunch), ("dw", NetEndLaunch)])
 
 u32, u64p = C.c_uint32, C.POINTER(C.c_uint64)
 Mlp = _struct("Mlp", cname="miseg_mlp_params", fields=[("struct_size", u32), ("M", i32), ("C", i32), ("HID", i32), ("dtype", i32), ("x", vp), ("ldx", i64),
@@ -264,13 +279,19 @@ PROTOS = {
     "miseg_gelu_bwd": (i32, [C.POINTER(GeluBwd), vp]),
     "miseg_space_to_channel": (i32, [C.POINTER(S2C), vp]),
     "miseg_channel_to_space": (i32, [C.POINTER(S2C), vp]),
+    "miseg_patch_embed_fwd_plan": (i32, [C.POINTER(PatchEmbed), C.POINTER(NetEndLaunch)]),
     "miseg_patch_embed_fwd": (i32, [C.POINTER(PatchEmbed), vp]),
     "miseg_patch_embed_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(PatchEmbedBwd)]),
+    "miseg_patch_embed_bwd_plan": (i32, [C.POINTER(PatchEmbedBwd), C.POINTER(NetEndLaunch)]),
     "miseg_patch_embed_bwd": (i32, [C.POINTER(PatchEmbedBwd), vp]),
+    "miseg_conv3_thin_fwd_plan": (i32, [C.POINTER(Conv3Thin), C.POINTER(NetEndLaunch)]),
     "miseg_conv3_thin_fwd": (i32, [C.POINTER(Conv3Thin), vp]),
     "miseg_conv3_thin_wgrad_workspace_bytes": (C.c_size_t, [C.POINTER(Conv3ThinWgrad)]),
+    "miseg_conv3_thin_wgrad_plan": (i32, [C.POINTER(Conv3ThinWgrad), C.POINTER(NetEndLaunch)]),
     "miseg_conv3_thin_wgrad": (i32, [C.POINTER(Conv3ThinWgrad), vp]),
+    "miseg_head_fwd_plan": (i32, [C.POINTER(Head), C.POINTER(NetEndLaunch)]),
     "miseg_head_fwd": (i32, [C.POINTER(Head), vp]),
+    "miseg_head_bwd_plan": (i32, [C.POINTER(HeadBwd), C.POINTER(HeadBwdPlan)]),
     "miseg_head_bwd": (i32, [C.POINTER(HeadBwd), vp]),
     "miseg_im2col3": (i32, [C.POINTER(Im2col3), vp]),
     "miseg_col2im3": (i32, [C.POINTER(Im2col3), vp]),
