@@ -1008,9 +1008,11 @@ static constexpr int WG_CB = 48;   // channel block (3 MFMA tiles) on both the o
 #ifdef MISEG_WGRAD_STAMPS
 __device__ unsigned long long miseg_wg_stamps[8];   // debug build only (scripts/debug_wgrad_stamps.py): summed s_memrealtime ticks
 #define WG_STAMP(var) const unsigned long long var = __builtin_amdgcn_s_memrealtime()
+#define WG_CYCLES(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
 #define WG_STAMP_ADD(i, a, b) do { if (tid == 0) atomicAdd(&miseg_wg_stamps[i], (b) - (a)); } while (0)
 #else
 #define WG_STAMP(var)
+#define WG_CYCLES(var)
 #define WG_STAMP_ADD(i, a, b)
 #endif
 
@@ -1172,21 +1174,36 @@ __device__ __forceinline__ void conv3_wgrad_body(const T* __restrict__ x, int64_
       if constexpr (PIPED) pitem(j); else gitem(j);
     }
   };
+  // The MFMA pipe idles while the image is written (a quarter of a brick's time on the 96^3 layers), so the stores carry as little as they
+  // can: items are moved as four dwords (a select on bf16x8 is lowered element by element), an item every lane has needs no guard, and a
+  // wave all of whose items lie inside the volume - every wave of an interior brick - stores them as they are, without the selects.
+  typedef uint32_t __attribute__((ext_vector_type(4))) U4;
   auto lstore = [&]() {
-    VT zero;
+    constexpr uint32_t all_items = (NXI + NDI == 32) ? 0xffffffffu : ((1u << (NXI + NDI)) - 1u);
+    uint32_t want = all_items;      // the items this lane has at all
+    if (tid + (NXI - 1) * WG_THREADS >= HROWS * GPR) want &= ~(1u << (NXI - 1));
+    if (tid + (NDI - 1) * WG_THREADS >= NVOX * GPR) want &= ~(1u << (NXI + NDI - 1));
+    const bool whole = __builtin_amdgcn_ballot_w64(vmask != want) == 0;      // (wave-uniform)
+    auto put_all = [&](auto select) {
+      auto put = [&](char* dst, const VT& v, int bit, bool guard, int idx, int count) {
+        U4 u = __builtin_bit_cast(U4, v);
+        if constexpr (decltype(select)::value) u = (vmask >> bit) & 1 ? u : U4{0u, 0u, 0u, 0u};
+        if (!guard || idx < count) *reinterpret_cast<U4*>(dst) = u;
+      };
 #pragma unroll
-    for (int e = 0; e < KPC; ++e) zero[e] = from_f32<T>(0.f);
+      for (int i = 0; i < NXI; ++i) {
+        const int idx = tid + i * WG_THREADS;
+        put(lx + (idx / GPR) * rowb + (idx % GPR) * 16, rx[i], i, (i + 1) * WG_THREADS > HROWS * GPR, idx, HROWS * GPR);
+      }
 #pragma unroll
-    for (int i = 0; i < NXI; ++i) {
-      const int idx = tid + i * WG_THREADS;
-      if (idx < HROWS * GPR) *reinterpret_cast<VT*>(lx + (idx / GPR) * rowb + (idx % GPR) * 16) = (vmask >> i) & 1 ? rx[i] : zero;
-    }
-#pragma unroll
-    for (int i = 0; i < NDI; ++i) {
-      const int idx = tid + i * WG_THREADS;
-      if (idx < NVOX * GPR) *reinterpret_cast<VT*>(ld + (idx / GPR) * rowb + (idx % GPR) * 16) = (vmask >> (NXI + i)) & 1 ? rd[i] : zero;
-    }
+      for (int i = 0; i < NDI; ++i) {
+        const int idx = tid + i * WG_THREADS;
+        put(ld + (idx / GPR) * rowb + (idx % GPR) * 16, rd[i], NXI + i, (i + 1) * WG_THREADS > NVOX * GPR, idx, NVOX * GPR);
+      }
+    };
+    if (whole) put_all(std::false_type{}); else put_all(std::true_type{});
   };
+  static_assert((NXI - 1) * WG_THREADS < HROWS * GPR && (NDI - 1) * WG_THREADS < NVOX * GPR, "only the last item of each kind may be partial");
   static_assert(NXI + NDI <= 32, "validity mask is one 32-bit word");
   // which bricks this workgroup walks.  Workgroups are dealt to the 8 XCDs round-robin and every XCD has its own L2: with
   // xcd_map (nsplit % 8 == 0, first workgroup of the layer on XCD 0) XCD k takes the k-th contiguous eighth of the bricks, so the
@@ -1279,6 +1296,7 @@ __device__ __forceinline__ void conv3_wgrad_body(const T* __restrict__ x, int64_
     }
     WG_STAMP(t_k0);
     WG_STAMP_ADD(0, t_s0, t_k0);
+    WG_CYCLES(c_k0);
     if constexpr (std::is_same<T, bf16>::value) {
       // k-step = 32 voxels = 4 h-rows x 8 w at one depth; MFMA k-group fq <-> h-row, element j <-> w
       const int qq = fi >> 2, p4 = (fi & 3) * 4;
@@ -1320,6 +1338,16 @@ __device__ __forceinline__ void conv3_wgrad_body(const T* __restrict__ x, int64_
 #pragma unroll
           for (int t = 0; t < WG_TPW; ++t) {
             const int slot = ks * WG_TPW + t, nx = slot + 2;
+            // ONE counted wait per slot.  Its fragments were requested two slots ago; what the slot before requested - 6 reads, 12 where
+            // it also carried the next k-step's dy fragments - stays in flight.  Left to itself the compiler waits in front of each of
+            // the slot's first three MFMAs, behind the two reads it has just issued there: three gaps of read, read, wait (12 cycles of
+            // issue against the 8 a 16-cycle MFMA leaves free).  (s_waitcnt immediates: lgkmcnt in bits 11:8, vmcnt and expcnt at
+            // their maxima = not waited for.)  Pinning each MFMA in front of the reads that follow it in the source as well (a
+            // sched_barrier between them) measured slower: 9090 against 8850 cycles per brick.
+            if (slot + 1 >= NSLOT) __builtin_amdgcn_s_waitcnt(0xC07F);
+            else if ((slot + 1) % WG_TPW == 0) __builtin_amdgcn_s_waitcnt(0xCC7F);
+            else __builtin_amdgcn_s_waitcnt(0xC67F);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 0; i < 9; ++i) {
               const int mt = i / 3, nt = i - 3 * mt;
@@ -1394,7 +1422,9 @@ __device__ __forceinline__ void conv3_wgrad_body(const T* __restrict__ x, int64_
       }
     }
     WG_STAMP(t_k1);
+    WG_CYCLES(c_k1);
     WG_STAMP_ADD(1, t_k0, t_k1);
+    WG_STAMP_ADD(7, c_k0, c_k1);      // the k-loop in shader cycles: over slot 1 (100 MHz ticks), the clock the loop ran at
     WG_STAMP_ADD(3, t_k1 - 1, t_k1);
   }
   WG_STAMP(t_e0);

@@ -18,9 +18,12 @@ for S, Cin, Cout in [(96, 48, 48), (96, 96, 48), (48, 48, 48), (24, 96, 96), (12
     t0 = torch.cuda.Event(enable_timing=True); t1 = torch.cuda.Event(enable_timing=True)
     t0.record(); ops.conv3_wgrad(x, dy); t1.record(); torch.cuda.synchronize()
     lib.miseg_debug_wgrad_stamps(buf)
-    stage, kloop, epi, bricks, gwait, lst, vmw = [buf[i] for i in range(7)]
+    stage, kloop, epi, bricks, gwait, lst, vmw, kcyc = [buf[i] for i in range(8)]
     tot = stage + kloop + epi
-    print(f"{S}^3 {Cin}->{Cout}: {t0.elapsed_time(t1)*1e3:7.1f} us (both kernels) | per brick: staging {10*stage/bricks:6.0f} ns (barrier {10*gwait/bricks:5.0f}, lds store {10*lst/bricks:5.0f} of which vmcnt wait {10*vmw/bricks:5.0f}, load issue {10*(stage-gwait-lst)/bricks:5.0f}) k-loop {10*kloop/bricks:6.0f} ns | "
+    if not bricks:      # (the 3^3 / 6^3 layers take the tiny-volume kernel: no stamps)
+        print(f"{S}^3 {Cin}->{Cout}: {t0.elapsed_time(t1)*1e3:7.1f} us, no brick kernel")
+        continue
+    print(f"{S}^3 {Cin}->{Cout}: {t0.elapsed_time(t1)*1e3:7.1f} us (both kernels) | per brick: staging {10*stage/bricks:6.0f} ns (barrier {10*gwait/bricks:5.0f}, lds store {10*lst/bricks:5.0f} of which vmcnt wait {10*vmw/bricks:5.0f}, load issue {10*(stage-gwait-lst)/bricks:5.0f}) k-loop {10*kloop/bricks:6.0f} ns = {kcyc/bricks:6.0f} cycles at {kcyc/max(kloop, 1)/10:4.2f} GHz | "
           f"share staging {100*stage/tot:4.1f}% k-loop {100*kloop/tot:4.1f}% epilogue {100*epi/tot:4.1f}%  bricks {bricks}")
 
 # the grouped launch of a C-Swin-UNETR step (every 3^3 conv of 48^3 and below)
@@ -41,4 +44,7 @@ for name, ls in sets.items():
     lib.miseg_debug_wgrad_stamps(buf)
     stage, kloop, epi, bricks, gwait, lst, vmw = [buf[i] for i in range(7)]
     tot = stage + kloop + epi
+    if not tot:
+        print(f"group {name:5s}: {t0.elapsed_time(t1)*1e3:7.1f} us, no brick kernel")
+        continue
     print(f"group {name:5s}: {t0.elapsed_time(t1)*1e3:7.1f} us (both kernels) | workgroup-time sum {10*tot/1e3:8.1f} us = {10*tot/1e3/256:6.1f} us per CU | staging {100*stage/tot:4.1f}% k-loop {100*kloop/tot:4.1f}% epilogue {100*epi/tot:4.1f}%  bricks {bricks}")
