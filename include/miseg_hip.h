@@ -813,6 +813,57 @@ typedef struct { int64_t off; int32_t param_index, pad_; } miseg_opt_pack_map;
 int miseg_opt_step_pack_conv3(const miseg_opt_step_params* p, const miseg_pack_conv3_desc* descs_dev, const miseg_opt_pack_map* map_dev, int n, int total_tiles,
                               int dtype, int64_t* pack_state, miseg_stream_t stream);
 
+/* Gradient clipping and the non-finite step guard of the fused optimiser (Lightning's Trainer(gradient_clip_val, gradient_clip_algorithm,
+ * track_grad_norm), which the reference's train.py takes through Trainer.add_argparse_args; new symbols: MISEG_ABI_VERSION stays 16).
+ *
+ * miseg_grad_norm: the global L2 norm of the gradient arena over the parameters with used[i] != 0, in two launches and without atomics.
+ *   1. one workgroup per 4096-element block of the descriptor table (the table of miseg_opt_step over ALL parameters: used[] is indexed by the
+ *      descriptor) squares and sums its elements in double - per thread its 16 elements in ascending order, then a shuffle tree over the 64
+ *      lanes, then the four waves in order - and stores the block's partial; a block of an unused parameter reads nothing and stores 0.
+ *   2. one workgroup of 16 waves: a tensor's partials are added by one wave (which one does not matter to the sum): lane l adds partials
+ *      l, l + 64, ... in ascending order, then the shuffle tree (offsets 32, 16, .., 1); thread t then adds the tensor sums t, t + 1024, ...
+ *      in ascending order, the shuffle tree again, and thread 0 adds the 16 wave sums in ascending order.  The order depends on the table
+ *      alone: equal bits every run.
+ * The launch fills `record`:  norm = (float)sqrt(S);  coef = fminf(1, max_norm / (norm + 1e-6f)), every operation rounded in fp32
+ * (torch.nn.utils.clip_grad_norm_) in MISEG_CLIP_NORM mode, 1 otherwise;  finite = isfinite(norm);  skip = skip_nonfinite && !finite;  and the
+ * running counters seen (+1 per call), clipped (+1 when coef < 1), skipped (+1 when skip) - the caller zeroes the record once.
+ * per_param (optional, fp32 [ndesc]): every tensor's own L2 norm, 0 for an unused one.  used: optional (NULL = every parameter).
+ * workspace: miseg_grad_norm_workspace_bytes(total_blocks, ndesc) bytes, 8-byte aligned.  max_norm is read in MISEG_CLIP_NORM mode only.
+ *
+ * miseg_opt_step_clipped / miseg_opt_step_pack_conv3_clipped: miseg_opt_step / miseg_opt_step_pack_conv3 on the clipped gradient
+ *   MISEG_CLIP_NORM : g' = g * rec->coef, the product rounded on its own (never contracted into the update's multiply-adds): the result is
+ *                     bit-identical to the plain step on gradients multiplied by coef beforehand;  clip_value is ignored
+ *   MISEG_CLIP_VALUE: g' = g < -clip_value ? -clip_value : (g > clip_value ? clip_value : g)  (a NaN stays a NaN, as in torch.clamp)
+ *   MISEG_CLIP_NONE : g' = g (the guard alone)
+ * The gradient arena itself is never written.  With rec_dev->skip set every workgroup returns before its first store: parameters, moments,
+ * conv packs, steps, params_version and pack_state keep their bits.  rec_dev may be NULL only in MISEG_CLIP_VALUE mode (no guard).
+ * Refused before any launch: a wrong struct_size, a null pointer, an unknown mode, a max_norm / clip_value that is not finite or <= 0,
+ * MISEG_CLIP_NORM or MISEG_CLIP_NONE without a record. */
+enum { MISEG_CLIP_NONE = 0, MISEG_CLIP_NORM = 1, MISEG_CLIP_VALUE = 2 };
+typedef struct {
+  float norm, coef;
+  int32_t finite, skip;
+  uint32_t seen, clipped, skipped, reserved;
+} miseg_grad_clip_record;
+typedef struct {
+  uint32_t struct_size;
+  int mode;                        /* MISEG_CLIP_* */
+  const miseg_opt_desc* descs_dev; int ndesc, total_blocks;
+  const float* grad;
+  const int32_t* used;
+  float max_norm;
+  int skip_nonfinite;
+  void* workspace;
+  miseg_grad_clip_record* record;
+  float* per_param;
+} miseg_grad_norm_params;
+size_t miseg_grad_norm_workspace_bytes(int total_blocks, int ndesc);
+int miseg_grad_norm(const miseg_grad_norm_params* p, miseg_stream_t stream);
+int miseg_opt_step_clipped(const miseg_opt_step_params* p, const miseg_grad_clip_record* rec_dev, int mode, float clip_value, miseg_stream_t stream);
+int miseg_opt_step_pack_conv3_clipped(const miseg_opt_step_params* p, const miseg_pack_conv3_desc* descs_dev, const miseg_opt_pack_map* map_dev, int n,
+                                      int total_tiles, int dtype, int64_t* pack_state, const miseg_grad_clip_record* rec_dev, int mode, float clip_value,
+                                      miseg_stream_t stream);
+
 /* Sliding-window stitching (MONAI sliding_window_inference, mode="constant", as used at lightning_monai.py:86-93,187): every window's logits
  * stay resident (win: fp32 [nd*nh*nw][C][rd][rh][rw], window (id, ih, iw) at index (id*nh + ih)*nw + iw, origin (start_d[id], start_h[ih],
  * start_w[iw]); 700 windows x 6 x 96^3 = 14.9 GB of the 288), and ONE gather pass writes out[c][d][h][w] = (sum over the windows covering the

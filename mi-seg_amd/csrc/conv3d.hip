@@ -794,9 +794,11 @@ __device__ __forceinline__ void fwd96_pack_dummies(int gpt, T* pack, int chunk, 
 // state slots at the same element offsets of the flat arena - and the packs are written from the new values: the separate refresh pass of
 // the next step (a second read of the 55 M conv weights, 440 MB moved) is gone.
 struct OptTile { const float* g; float* m; float* v; OptHyper h; };      // g / m / v: already offset to this parameter's slot
-template <class T, bool OPT = false>
+// CLIP (miseg_opt_step_pack_conv3_clipped): the update runs on opt_clip(clip_mode, clip_c, gradient) (opt_math.h)
+template <class T, bool OPT = false, bool CLIP = false>
 __device__ __forceinline__ void pack_conv3_tile(typename std::conditional<OPT, float, const float>::type* __restrict__ w, T* __restrict__ fwd, T* __restrict__ bwd, int Cin,
-                                                int Cout, int CinP, int CoutP, int Cin16, int Cout16, int fwd_gpt, int bwd_gpt, int bx, int by, const OptTile* ot = nullptr) {
+                                                int Cout, int CinP, int CoutP, int Cin16, int Cout16, int fwd_gpt, int bwd_gpt, int bx, int by, const OptTile* ot = nullptr,
+                                                int clip_mode = 0, float clip_c = 1.f) {
   const bool fwd_planar = fwd_gpt != 0, bwd_planar = bwd_gpt != 0;      // groups per chunk of the planar pack's K side, 0 = row-major pack
   typedef typename Vec16<T>::type VT;
   constexpr int KPC = Vec16<T>::N, NG = PK_T / KPC;
@@ -842,7 +844,7 @@ __device__ __forceinline__ void pack_conv3_tile(typename std::conditional<OPT, f
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float we = v[k][e], me = m4[k][e], ve = v4[k][e];
-          opt_update(ot->h, we, g4[k][e], me, ve);
+          opt_update(ot->h, we, CLIP ? opt_clip(clip_mode, clip_c, g4[k][e]) : g4[k][e], me, ve);
           v[k][e] = we; m4[k][e] = me; v4[k][e] = ve;
         }
         if (ok[k]) {
@@ -873,7 +875,7 @@ __device__ __forceinline__ void pack_conv3_tile(typename std::conditional<OPT, f
         wv = w[off];
         if constexpr (OPT) {
           float me = ot->m[off], ve = ot->h.kind != MISEG_OPT_SGD_NESTEROV ? ot->v[off] : 0.f;
-          opt_update(ot->h, wv, ot->g[off], me, ve);
+          opt_update(ot->h, wv, CLIP ? opt_clip(clip_mode, clip_c, ot->g[off]) : ot->g[off], me, ve);
           w[off] = wv;
           ot->m[off] = me;
           if (ot->h.kind != MISEG_OPT_SGD_NESTEROV) ot->v[off] = ve;
@@ -961,15 +963,22 @@ __global__ void __launch_bounds__(256) pack_conv3_batch_kernel(const miseg_pack_
 
 // one optimiser step on every 3x3x3 weight of the table + its packs (miseg_opt_step_pack_conv3).  Same tile walk as the refresh kernel above;
 // a tensor without a gradient this step (used[] == 0) is left alone - weights, state and packs.
-template <class T>
+// CLIP: a skipped step (rec->skip) returns before any store - weights, state and packs keep their bits
+template <class T, bool CLIP>
 __global__ void __launch_bounds__(256) opt_pack_conv3_batch_kernel(const miseg_pack_conv3_desc* __restrict__ descs, const miseg_opt_pack_map* __restrict__ map, int n,
                                                                       int total_tiles, int pad_min, int kind, const float* __restrict__ grad, float* __restrict__ s1,
                                                                       float* __restrict__ s2, const int32_t* __restrict__ used, const int32_t* __restrict__ steps, float lr,
-                                                                      float b1, float b2, float eps, float wd, float mom, const float* __restrict__ lr_dev) {
+                                                                      float b1, float b2, float eps, float wd, float mom, const float* __restrict__ lr_dev,
+                                                                      const miseg_grad_clip_record* __restrict__ rec, int clip_mode, float clip_value) {
   constexpr int KPC = Vec16<T>::N;
   constexpr int NS = 128;
   __shared__ int s_tile0[NS];
   __shared__ OptTile s_ot;
+  float clip_c = clip_value;      // the bound of value mode, the record's coefficient of norm mode
+  if constexpr (CLIP) {
+    if (rec && rec->skip) return;
+    if (clip_mode == MISEG_CLIP_NORM) clip_c = rec->coef;
+  }
   const bool in_lds = n <= NS;
   if (in_lds) {
     for (int i = threadIdx.x; i < n; i += 256) s_tile0[i] = descs[i].tile0;
@@ -991,8 +1000,9 @@ __global__ void __launch_bounds__(256) opt_pack_conv3_batch_kernel(const miseg_p
     __syncthreads();      // the LDS tile (and s_ot) of the previous iteration has been read
     if (threadIdx.x == 0) s_ot = OptTile{grad + mp.off, s1 + mp.off, s2 ? s2 + mp.off : nullptr, opt_hyper(kind, steps[mp.param_index] + 1, lr, b1, b2, eps, wd, mom)};
     __syncthreads();
-    pack_conv3_tile<T, true>(const_cast<float*>(d.w), (T*)d.fwd_pack, (T*)d.bwd_pack, d.Cin, d.Cout, CinP, CoutP, (d.Cin + 15) / 16 * 16, (d.Cout + 15) / 16 * 16,
-                             kf ? conv3_gpt(d.Cin, (int)sizeof(T), pad_min) : 0, kb ? conv3_gpt(d.Cout, (int)sizeof(T), pad_min) : 0, t % tci, t / tci, &s_ot);
+    pack_conv3_tile<T, true, CLIP>(const_cast<float*>(d.w), (T*)d.fwd_pack, (T*)d.bwd_pack, d.Cin, d.Cout, CinP, CoutP, (d.Cin + 15) / 16 * 16, (d.Cout + 15) / 16 * 16,
+                                   kf ? conv3_gpt(d.Cin, (int)sizeof(T), pad_min) : 0, kb ? conv3_gpt(d.Cout, (int)sizeof(T), pad_min) : 0, t % tci, t / tci, &s_ot,
+                                   clip_mode, clip_c);
   }
 }
 
@@ -2149,9 +2159,9 @@ extern "C" int miseg_pack_conv3_batch(const miseg_pack_conv3_desc* descs, int n,
   });
 }
 
-extern "C" int miseg_opt_step_pack_conv3(const miseg_opt_step_params* p, const miseg_pack_conv3_desc* descs, const miseg_opt_pack_map* map, int n, int total_tiles,
-                                         int dtype, int64_t* pack_state, miseg_stream_t s_) {
-  hipStream_t s = (hipStream_t)s_;
+// miseg_opt_step_pack_conv3 (clipped == false: rec / mode / clip_value unused) and miseg_opt_step_pack_conv3_clipped
+static int opt_step_pack_conv3_launch(const miseg_opt_step_params* p, const miseg_pack_conv3_desc* descs, const miseg_opt_pack_map* map, int n, int total_tiles,
+                                      int dtype, int64_t* pack_state, bool clipped, const miseg_grad_clip_record* rec, int mode, float clip_value, hipStream_t s) {
   MISEG_REQUIRE(p && p->struct_size == sizeof(miseg_opt_step_params), MISEG_E_BADARG, "opt_step_pack_conv3: struct_size %u != %zu", p ? p->struct_size : 0u,
                 sizeof(miseg_opt_step_params));
   MISEG_REQUIRE(descs && map && n > 0 && total_tiles > 0 && p->grad && p->state1 && p->steps, MISEG_E_BADARG, "opt_step_pack_conv3: null pointer / empty table");
@@ -2161,15 +2171,33 @@ extern "C" int miseg_opt_step_pack_conv3(const miseg_opt_step_params* p, const m
   const int rc = dispatch_dtype(dtype, [&](auto* tag) -> int {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
     const int cap = 2048;      // (7 loads + 3 stores of 16 bytes per thread and tile in flight: more workgroups than the refresh kernel's 512)
-    opt_pack_conv3_batch_kernel<T><<<total_tiles < cap ? total_tiles : cap, 256, 0, s>>>(descs, map, n, total_tiles, conv3_pad_min_bytes(), p->kind, p->grad, p->state1,
-                                                                                         p->kind == MISEG_OPT_SGD_NESTEROV ? nullptr : p->state2, p->used, p->steps, p->lr,
-                                                                                         p->beta1, p->beta2, p->eps, p->weight_decay, p->momentum, p->lr_dev);
+    const int grid = total_tiles < cap ? total_tiles : cap;
+    float* s2 = p->kind == MISEG_OPT_SGD_NESTEROV ? nullptr : p->state2;
+    if (clipped)
+      opt_pack_conv3_batch_kernel<T, true><<<grid, 256, 0, s>>>(descs, map, n, total_tiles, conv3_pad_min_bytes(), p->kind, p->grad, p->state1, s2, p->used, p->steps, p->lr,
+                                                               p->beta1, p->beta2, p->eps, p->weight_decay, p->momentum, p->lr_dev, rec, mode, clip_value);
+    else
+      opt_pack_conv3_batch_kernel<T, false><<<grid, 256, 0, s>>>(descs, map, n, total_tiles, conv3_pad_min_bytes(), p->kind, p->grad, p->state1, s2, p->used, p->steps, p->lr,
+                                                                p->beta1, p->beta2, p->eps, p->weight_decay, p->momentum, p->lr_dev, nullptr, MISEG_CLIP_NONE, 0.f);
     MISEG_LAUNCH_CHECK("opt_step_pack_conv3");
     return MISEG_OK;
   });
   if (rc != MISEG_OK) return rc;
-  if (p->count_n > 0) return opt_count_launch(p->used, p->steps, p->count_n, p->params_version, pack_state, s);
+  if (p->count_n > 0) return opt_count_launch(p->used, p->steps, p->count_n, p->params_version, pack_state, s, clipped ? rec : nullptr);
   return MISEG_OK;
+}
+
+extern "C" int miseg_opt_step_pack_conv3(const miseg_opt_step_params* p, const miseg_pack_conv3_desc* descs, const miseg_opt_pack_map* map, int n, int total_tiles,
+                                         int dtype, int64_t* pack_state, miseg_stream_t s_) {
+  return opt_step_pack_conv3_launch(p, descs, map, n, total_tiles, dtype, pack_state, false, nullptr, MISEG_CLIP_NONE, 0.f, (hipStream_t)s_);
+}
+
+extern "C" int miseg_opt_step_pack_conv3_clipped(const miseg_opt_step_params* p, const miseg_pack_conv3_desc* descs, const miseg_opt_pack_map* map, int n,
+                                                 int total_tiles, int dtype, int64_t* pack_state, const miseg_grad_clip_record* rec, int mode, float clip_value,
+                                                 miseg_stream_t s_) {
+  const int rc = opt_clip_check(rec, mode, clip_value, "opt_step_pack_conv3_clipped");
+  if (rc != MISEG_OK) return rc;
+  return opt_step_pack_conv3_launch(p, descs, map, n, total_tiles, dtype, pack_state, true, rec, mode, clip_value, (hipStream_t)s_);
 }
 
 static void wgrad_plan(int B, int D, int H, int W, int Cin, int Cout, int wbd, int* ncob, int* ncib, int* nsplit, int max_wg = 0) {

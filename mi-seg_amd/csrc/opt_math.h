@@ -41,8 +41,27 @@ __device__ __forceinline__ void opt_update(const OptHyper& h, float& w, float g,
   }
 }
 
+// Gradient clipping in front of the update (miseg_opt_step_clipped / miseg_opt_step_pack_conv3_clipped): c = the record's coefficient
+// (MISEG_CLIP_NORM) or the bound (MISEG_CLIP_VALUE).  The scaled gradient is a value of its own, rounded once: the empty asm keeps the
+// compiler from contracting the product into opt_update's multiply-adds, so the step equals the plain step on a gradient that was
+// multiplied by the same coefficient beforehand, bit for bit.  The clamp keeps a NaN (both comparisons are false), like torch.clamp.
+__device__ __forceinline__ float opt_clip(int mode, float c, float g) {
+  if (mode == MISEG_CLIP_NORM) {
+    float r = __fmul_rn(g, c);
+    asm("" : "+v"(r));
+    return r;
+  }
+  if (mode == MISEG_CLIP_VALUE) return g < -c ? -c : (g > c ? c : g);
+  return g;
+}
+
 // steps[i] += used[i], parameter version += 1 (training.hip); `pack_state` (optional): state[0] of a versioned pack table whose packs were
-// written from the new parameters by the launch in front of this one - it then holds the new version and the next refresh launch finds it current
-int opt_count_launch(const int32_t* used, int32_t* steps, int n, int64_t* params_version, int64_t* pack_state, hipStream_t s);
+// written from the new parameters by the launch in front of this one - it then holds the new version and the next refresh launch finds it current.
+// `rec` (optional): the clip record of this step - a skipped step (rec->skip) counts nothing and bumps nothing
+int opt_count_launch(const int32_t* used, int32_t* steps, int n, int64_t* params_version, int64_t* pack_state, hipStream_t s,
+                     const miseg_grad_clip_record* rec = nullptr);
+
+// argument checks shared by the two clipped entry points (training.hip); MISEG_OK or MISEG_E_BADARG with the error text set
+int opt_clip_check(const miseg_grad_clip_record* rec, int mode, float clip_value, const char* what);
 
 }  // namespace miseg

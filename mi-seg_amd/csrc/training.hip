@@ -391,9 +391,18 @@ static __global__ void dice_finalize_kernel(const unsigned long long* __restrict
 // ------------------------------------------------------------------------------------------------ optimiser
 constexpr int OPT_BLOCK = 4096;     // elements per workgroup (256 threads x 4 float4)
 
-static __global__ void __launch_bounds__(256) opt_step_kernel(const miseg_opt_desc* __restrict__ descs, int ndesc, int kind, const float* __restrict__ grad, float* __restrict__ s1,
-                                                            float* __restrict__ s2, const int32_t* __restrict__ used, int32_t* __restrict__ steps, float lr, float b1, float b2,
-                                                            float eps, float wd, float mom, const float* __restrict__ lr_dev, const int32_t* __restrict__ index) {
+// CLIP (miseg_opt_step_clipped): the update runs on opt_clip(gradient) and a skipped step (rec->skip) returns before any store; the plain
+// instantiation never looks at rec / clip_mode / clip_value
+template <bool CLIP>
+__global__ void __launch_bounds__(256) opt_step_kernel(const miseg_opt_desc* __restrict__ descs, int ndesc, int kind, const float* __restrict__ grad, float* __restrict__ s1,
+                                                     float* __restrict__ s2, const int32_t* __restrict__ used, int32_t* __restrict__ steps, float lr, float b1, float b2,
+                                                     float eps, float wd, float mom, const float* __restrict__ lr_dev, const int32_t* __restrict__ index,
+                                                     const miseg_grad_clip_record* __restrict__ rec, int clip_mode, float clip_value) {
+  float clip_c = clip_value;      // the bound of value mode, the record's coefficient of norm mode
+  if constexpr (CLIP) {
+    if (rec && rec->skip) return;
+    if (clip_mode == MISEG_CLIP_NORM) clip_c = rec->coef;
+  }
   // descriptor of this workgroup: the last one with block0 <= blockIdx.x
   int lo = 0, hi = ndesc - 1;
   while (lo < hi) {
@@ -435,7 +444,7 @@ static __global__ void __launch_bounds__(256) opt_step_kernel(const miseg_opt_de
       }
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) opt_update(hy, pv[k], gv[k], mv[k], vv[k]);
+    for (int k = 0; k < 4; ++k) opt_update(hy, pv[k], CLIP ? opt_clip(clip_mode, clip_c, gv[k]) : gv[k], mv[k], vv[k]);
     if (vec && cnt == 4) {
       f32x4 tp, tm, tv;
 #pragma unroll
@@ -452,12 +461,139 @@ static __global__ void __launch_bounds__(256) opt_step_kernel(const miseg_opt_de
 }
 
 static __global__ void opt_count_kernel(const int32_t* __restrict__ used, int32_t* __restrict__ steps, int n, int64_t* __restrict__ params_version,
-                                        int64_t* __restrict__ pack_state) {
+                                        int64_t* __restrict__ pack_state, const miseg_grad_clip_record* __restrict__ rec) {
+  if (rec && rec->skip) return;      // a skipped step (non-finite gradient) is no update: no count, no version
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n && (!used || used[i])) steps[i] += 1;
   if (i == 0 && params_version) {
     *params_version += 1;      // the parameters changed: the versioned refresh kernels re-lay-out their copies
     if (pack_state) pack_state[0] = *params_version;      // ... except the packs the fused launch in front of this one has just written (opt_math.h)
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ gradient norm (miseg_grad_norm)
+// fixed shuffle tree over the 64 lanes of a wave (offsets 32, 16, .., 1): lane 0 holds the sum
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
+// Launch 1: opt_step_kernel's geometry (one workgroup per 4096-element block of the table) over the gradient arena alone.  Squares and sums
+// in double: a thread's 16 elements in ascending order, the shuffle tree, the four waves in order through LDS; one plain store per block.
+static __global__ void __launch_bounds__(256) grad_sqsum_kernel(const miseg_opt_desc* __restrict__ descs, int ndesc, const float* __restrict__ grad,
+                                                              const int32_t* __restrict__ used, double* __restrict__ part) {
+  __shared__ double s_wave[4];
+  int lo = 0, hi = ndesc - 1;
+  while (lo < hi) {      // the last descriptor with block0 <= blockIdx.x
+    const int mid = (lo + hi + 1) >> 1;
+    if (descs[mid].block0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+  }
+  if (used && !used[lo]) {      // `grad is None`: the slot is not read (it may hold anything) and adds nothing
+    if (threadIdx.x == 0) part[blockIdx.x] = 0.0;
+    return;
+  }
+  const miseg_opt_desc d = descs[lo];
+  const float* gp = grad + d.off;
+  const int e0 = ((int)blockIdx.x - d.block0) * OPT_BLOCK;
+  const bool vec = (((uintptr_t)gp) & 15) == 0;
+  f32x4 g[4];
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {      // (all four loads in flight before the first add)
+    const int e = e0 + (it * 256 + threadIdx.x) * 4;
+    const int cnt = d.n - e;
+    if (vec && cnt >= 4) {
+      g[it] = *reinterpret_cast<const f32x4*>(gp + e);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) g[it][k] = k < cnt ? gp[e + k] : 0.f;
+    }
+  }
+  double acc = 0.0;
+#pragma unroll
+  for (int it = 0; it < 4; ++it)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc += (double)g[it][k] * (double)g[it][k];
+  acc = wave_sum_f64(acc);
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+}
+
+// Launch 2, one workgroup of 16 waves (the order is written out in miseg_hip.h): per-tensor sums into dsum, then their sum, then the record.
+constexpr int GN_THREADS = 1024, GN_WAVES = GN_THREADS / 64, GN_UNROLL = 4, GN_DEPTH = 16;
+constexpr int GN_LDS_DESCS = 2048;      // block0 of this many descriptors is staged in LDS (one coalesced read instead of two dependent loads per tensor)
+
+static __global__ void __launch_bounds__(GN_THREADS) grad_norm_finish_kernel(const miseg_opt_desc* __restrict__ descs, int ndesc, int total_blocks,
+                                                                           const double* __restrict__ part, double* __restrict__ dsum, int mode, float max_norm,
+                                                                           int skip_nonfinite, miseg_grad_clip_record* __restrict__ rec, float* __restrict__ per_param) {
+  __shared__ int s_block0[GN_LDS_DESCS + 1];
+  __shared__ double s_wave[GN_WAVES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bool in_lds = ndesc <= GN_LDS_DESCS;
+  if (in_lds) {
+    for (int i = tid; i <= ndesc; i += GN_THREADS) s_block0[i] = i < ndesc ? descs[i].block0 : total_blocks;
+    __syncthreads();
+  }
+  // A wave takes GN_UNROLL tensors at a time and has the first partial of each in flight before it adds anything: one tensor per round was a
+  // chain of 17 dependent memory round trips per wave on the headline net's 265 tensors (29.7 us for 120 KB of partials).  Which wave adds a
+  // tensor does not change its sum: lane l adds the tensor's partials l, l + 64, ... in ascending order, then the shuffle tree.
+  for (int i0 = wave * GN_UNROLL; i0 < ndesc; i0 += GN_WAVES * GN_UNROLL) {
+    int b0[GN_UNROLL], b1[GN_UNROLL];
+    double acc[GN_UNROLL];
+#pragma unroll
+    for (int u = 0; u < GN_UNROLL; ++u) {
+      const int i = i0 + u;
+      b0[u] = b1[u] = 0;
+      if (i < ndesc) {
+        b0[u] = in_lds ? s_block0[i] : descs[i].block0;
+        b1[u] = in_lds ? s_block0[i + 1] : (i + 1 < ndesc ? descs[i + 1].block0 : total_blocks);
+        b1[u] = b1[u] < total_blocks ? b1[u] : total_blocks;      // (a table that disagrees with total_blocks reads no partial outside the workspace)
+      }
+      acc[u] = b0[u] + lane < b1[u] ? part[b0[u] + lane] : 0.0;
+    }
+    // the rest of a large tensor (the headline net's largest has 3888 partials, 61 a lane): GN_DEPTH loads in flight, added in ascending
+    // order (a partial is >= 0, so the + 0.0 of a lane that ran out changes no bit)
+#pragma unroll
+    for (int u = 0; u < GN_UNROLL; ++u)
+      for (int b = b0[u] + lane + 64; b < b1[u]; b += 64 * GN_DEPTH) {
+        double v[GN_DEPTH];
+#pragma unroll
+        for (int k = 0; k < GN_DEPTH; ++k) v[k] = b + 64 * k < b1[u] ? part[b + 64 * k] : 0.0;
+#pragma unroll
+        for (int k = 0; k < GN_DEPTH; ++k) acc[u] += v[k];
+      }
+#pragma unroll
+    for (int u = 0; u < GN_UNROLL; ++u) acc[u] = wave_sum_f64(acc[u]);
+    if (lane == 0) {
+#pragma unroll
+      for (int u = 0; u < GN_UNROLL; ++u)
+        if (i0 + u < ndesc) {
+          dsum[i0 + u] = acc[u];
+          if (per_param) per_param[i0 + u] = (float)sqrt(acc[u]);
+        }
+    }
+  }
+  __syncthreads();      // (dsum was written by this workgroup: visible to it after the barrier)
+  double acc = 0.0;
+  for (int i = tid; i < ndesc; i += GN_THREADS) acc += dsum[i];
+  acc = wave_sum_f64(acc);
+  if (lane == 0) s_wave[wave] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    double S = 0.0;
+    for (int w = 0; w < GN_WAVES; ++w) S += s_wave[w];
+    const float norm = (float)sqrt(S);
+    const float coef = mode == MISEG_CLIP_NORM ? fminf(1.f, __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f))) : 1.f;
+    const int finite = isfinite(norm) ? 1 : 0, skip = (skip_nonfinite && !finite) ? 1 : 0;
+    rec->norm = norm;
+    rec->coef = coef;
+    rec->finite = finite;
+    rec->skip = skip;
+    rec->seen += 1u;
+    rec->clipped += coef < 1.f ? 1u : 0u;
+    rec->skipped += skip ? 1u : 0u;
+    rec->reserved = 0u;
   }
 }
 
@@ -829,28 +965,75 @@ extern "C" int miseg_dice_metric(const miseg_dice_metric_params* p, miseg_stream
   });
 }
 
-extern "C" int miseg_opt_step(const miseg_opt_step_params* p, miseg_stream_t s_) {
-  hipStream_t s = (hipStream_t)s_;
+// miseg_opt_step (clipped == false: rec / mode / clip_value unused) and miseg_opt_step_clipped
+static int opt_step_launch(const miseg_opt_step_params* p, bool clipped, const miseg_grad_clip_record* rec, int mode, float clip_value, hipStream_t s) {
   MISEG_REQUIRE(p && p->struct_size == sizeof(miseg_opt_step_params), MISEG_E_BADARG, "opt_step: struct_size %u != %zu", p ? p->struct_size : 0u,
                 sizeof(miseg_opt_step_params));
   MISEG_REQUIRE(p->descs_dev && p->grad && p->state1 && p->steps && p->ndesc > 0 && p->total_blocks > 0, MISEG_E_BADARG, "opt_step: null pointer / empty table");
   MISEG_REQUIRE(p->kind == MISEG_OPT_ADAMW || p->kind == MISEG_OPT_ADAM || p->kind == MISEG_OPT_SGD_NESTEROV, MISEG_E_BADARG, "opt_step: kind %d", p->kind);
   MISEG_REQUIRE(p->kind == MISEG_OPT_SGD_NESTEROV || p->state2, MISEG_E_BADARG, "opt_step: Adam needs state2");
-  opt_step_kernel<<<p->total_blocks, 256, 0, s>>>(p->descs_dev, p->ndesc, p->kind, p->grad, p->state1, p->kind == MISEG_OPT_SGD_NESTEROV ? nullptr : p->state2, p->used,
-                                                 p->steps, p->lr, p->beta1, p->beta2, p->eps, p->weight_decay, p->momentum, p->lr_dev, p->index);
+  MISEG_REQUIRE(p->index || p->count_n < 0 || p->count_n == p->ndesc, MISEG_E_BADARG, "opt_step: count_n %d without an index table", p->count_n);
+  float* s2 = p->kind == MISEG_OPT_SGD_NESTEROV ? nullptr : p->state2;
+  if (clipped)
+    opt_step_kernel<true><<<p->total_blocks, 256, 0, s>>>(p->descs_dev, p->ndesc, p->kind, p->grad, p->state1, s2, p->used, p->steps, p->lr, p->beta1, p->beta2, p->eps,
+                                                         p->weight_decay, p->momentum, p->lr_dev, p->index, rec, mode, clip_value);
+  else
+    opt_step_kernel<false><<<p->total_blocks, 256, 0, s>>>(p->descs_dev, p->ndesc, p->kind, p->grad, p->state1, s2, p->used, p->steps, p->lr, p->beta1, p->beta2, p->eps,
+                                                          p->weight_decay, p->momentum, p->lr_dev, p->index, nullptr, MISEG_CLIP_NONE, 0.f);
   MISEG_LAUNCH_CHECK("opt_step");
   const int cn = p->count_n < 0 ? p->ndesc : p->count_n;
-  MISEG_REQUIRE(p->index || p->count_n < 0 || p->count_n == p->ndesc, MISEG_E_BADARG, "opt_step: count_n %d without an index table", p->count_n);
   if (cn > 0) {
-    const int rc = opt_count_launch(p->used, p->steps, cn, p->params_version, nullptr, s);
+    const int rc = opt_count_launch(p->used, p->steps, cn, p->params_version, nullptr, s, clipped ? rec : nullptr);
     if (rc != MISEG_OK) return rc;
   }
   return MISEG_OK;
 }
 
-int miseg::opt_count_launch(const int32_t* used, int32_t* steps, int n, int64_t* params_version, int64_t* pack_state, hipStream_t s) {
-  opt_count_kernel<<<cdiv(n, 256), 256, 0, s>>>(used, steps, n, params_version, pack_state);
+extern "C" int miseg_opt_step(const miseg_opt_step_params* p, miseg_stream_t s_) {
+  return opt_step_launch(p, false, nullptr, MISEG_CLIP_NONE, 0.f, (hipStream_t)s_);
+}
+
+int miseg::opt_clip_check(const miseg_grad_clip_record* rec, int mode, float clip_value, const char* what) {
+  MISEG_REQUIRE(mode == MISEG_CLIP_NONE || mode == MISEG_CLIP_NORM || mode == MISEG_CLIP_VALUE, MISEG_E_BADARG, "%s: clip mode %d", what, mode);
+  MISEG_REQUIRE(rec || mode == MISEG_CLIP_VALUE, MISEG_E_BADARG, "%s: clip mode %d needs the record miseg_grad_norm fills", what, mode);
+  MISEG_REQUIRE(mode != MISEG_CLIP_VALUE || (isfinite(clip_value) && clip_value > 0.f), MISEG_E_BADARG, "%s: clip_value %g must be finite and > 0", what,
+                (double)clip_value);
+  return MISEG_OK;
+}
+
+extern "C" int miseg_opt_step_clipped(const miseg_opt_step_params* p, const miseg_grad_clip_record* rec, int mode, float clip_value, miseg_stream_t s_) {
+  const int rc = opt_clip_check(rec, mode, clip_value, "opt_step_clipped");
+  if (rc != MISEG_OK) return rc;
+  return opt_step_launch(p, true, rec, mode, clip_value, (hipStream_t)s_);
+}
+
+int miseg::opt_count_launch(const int32_t* used, int32_t* steps, int n, int64_t* params_version, int64_t* pack_state, hipStream_t s,
+                            const miseg_grad_clip_record* rec) {
+  opt_count_kernel<<<cdiv(n, 256), 256, 0, s>>>(used, steps, n, params_version, pack_state, rec);
   MISEG_LAUNCH_CHECK("opt_count");
+  return MISEG_OK;
+}
+
+extern "C" size_t miseg_grad_norm_workspace_bytes(int total_blocks, int ndesc) {
+  if (total_blocks <= 0 || ndesc <= 0) return 0;
+  return ((size_t)total_blocks + (size_t)ndesc) * sizeof(double);      // the blocks' partials, then the tensors' sums
+}
+
+extern "C" int miseg_grad_norm(const miseg_grad_norm_params* p, miseg_stream_t s_) {
+  hipStream_t s = (hipStream_t)s_;
+  MISEG_REQUIRE(p && p->struct_size == sizeof(miseg_grad_norm_params), MISEG_E_BADARG, "grad_norm: struct_size %u != %zu", p ? p->struct_size : 0u,
+                sizeof(miseg_grad_norm_params));
+  MISEG_REQUIRE(p->descs_dev && p->grad && p->workspace && p->record && p->ndesc > 0 && p->total_blocks > 0, MISEG_E_BADARG, "grad_norm: null pointer / empty table");
+  MISEG_REQUIRE((((uintptr_t)p->workspace) & 7) == 0, MISEG_E_BADARG, "grad_norm: the workspace must be 8-byte aligned");
+  MISEG_REQUIRE(p->mode == MISEG_CLIP_NONE || p->mode == MISEG_CLIP_NORM || p->mode == MISEG_CLIP_VALUE, MISEG_E_BADARG, "grad_norm: clip mode %d", p->mode);
+  MISEG_REQUIRE(p->mode != MISEG_CLIP_NORM || (isfinite(p->max_norm) && p->max_norm > 0.f), MISEG_E_BADARG, "grad_norm: max_norm %g must be finite and > 0",
+                (double)p->max_norm);
+  double* part = (double*)p->workspace;
+  grad_sqsum_kernel<<<p->total_blocks, 256, 0, s>>>(p->descs_dev, p->ndesc, p->grad, p->used, part);
+  MISEG_LAUNCH_CHECK("grad_sqsum");
+  grad_norm_finish_kernel<<<1, GN_THREADS, 0, s>>>(p->descs_dev, p->ndesc, p->total_blocks, part, part + p->total_blocks, p->mode, p->max_norm,
+                                                  p->skip_nonfinite ? 1 : 0, p->record, p->per_param);
+  MISEG_LAUNCH_CHECK("grad_norm_finish");
   return MISEG_OK;
 }
 

@@ -170,6 +170,14 @@ OptStep = _struct("OptStep", cname="miseg_opt_step_params", fields=[
     ("struct_size", u32), ("kind", i32), ("descs_dev", vp), ("ndesc", i32), ("total_blocks", i32), ("grad", vp), ("state1", vp), ("state2", vp),
     ("used", vp), ("steps", vp), ("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("weight_decay", f32), ("momentum", f32), ("lr_dev", vp), ("params_version", vp),
     ("index", vp), ("count_n", i32)])
+GradClipRecord = _struct("GradClipRecord", cname="miseg_grad_clip_record", fields=[
+    ("norm", f32), ("coef", f32), ("finite", C.c_int32), ("skip", C.c_int32), ("seen", C.c_uint32), ("clipped", C.c_uint32), ("skipped", C.c_uint32),
+    ("reserved", C.c_uint32)])
+GradNorm = _struct("GradNorm", cname="miseg_grad_norm_params", fields=[
+    ("struct_size", C.c_uint32), ("mode", i32), ("descs_dev", vp), ("ndesc", i32), ("total_blocks", i32), ("grad", vp), ("used", vp), ("max_norm", f32),
+    ("skip_nonfinite", i32), ("workspace", vp), ("record", vp), ("per_param", vp)])
+CLIP_NONE, CLIP_NORM, CLIP_VALUE = 0, 1, 2                             # MISEG_CLIP_*
+CLIP_MODES = {"norm": CLIP_NORM, "value": CLIP_VALUE}
 Stitch = _struct("Stitch", cname="miseg_stitch_params", fields=[
     ("struct_size", u32), ("win", vp), ("out", vp), ("count", vp), ("C", i32), ("D", i32), ("H", i32), ("W", i32), ("rd", i32), ("rh", i32), ("rw", i32),
     ("nd", i32), ("nh", i32), ("nw", i32), ("start_d", vp), ("start_h", vp), ("start_w", vp), ("d_begin", i32), ("d_count", i32),
@@ -318,6 +326,10 @@ PROTOS = {
     "miseg_surface_dice": (i32, [C.POINTER(SurfaceDice), vp]),
     "miseg_opt_step": (i32, [C.POINTER(OptStep), vp]),
     "miseg_opt_step_pack_conv3": (i32, [C.POINTER(OptStep), vp, vp, i32, i32, i32, vp, vp]),
+    "miseg_grad_norm_workspace_bytes": (C.c_size_t, [i32, i32]),
+    "miseg_grad_norm": (i32, [C.POINTER(GradNorm), vp]),
+    "miseg_opt_step_clipped": (i32, [C.POINTER(OptStep), vp, i32, f32, vp]),
+    "miseg_opt_step_pack_conv3_clipped": (i32, [C.POINTER(OptStep), vp, vp, i32, i32, i32, vp, vp, i32, f32, vp]),
     "miseg_stitch_windows": (i32, [C.POINTER(Stitch), vp]),
     "miseg_augment_crop": (i32, [C.POINTER(Augment), vp]),
     "miseg_augment_affine": (i32, [C.POINTER(AugmentAffine), vp]),

@@ -145,7 +145,11 @@ class LitMonai(_Base):
         from ..training.optim import ArenaOptimizer
         if self.optim_name not in ("adam", "adamw", "sgd"):
             raise ValueError("Optimization {} not implemented, please chose another optimizer.".format(self.optim_name))
-        return ArenaOptimizer(arena, kind=self.optim_name, lr=self.learning_rate, weight_decay=self.reg_weight, momentum=self.momentum)
+        # (the Trainer arguments of utils/parser.py::TRAINER_ARGS arrive as attributes through **kwargs; absent: everything off)
+        d = self.__dict__
+        return ArenaOptimizer(arena, kind=self.optim_name, lr=self.learning_rate, weight_decay=self.reg_weight, momentum=self.momentum,
+                              gradient_clip_val=d.get("gradient_clip_val"), gradient_clip_algorithm=d.get("gradient_clip_algorithm") or "norm",
+                              skip_nonfinite=bool(d.get("skip_nonfinite_steps")), track_grad_norm=d.get("track_grad_norm", -1))
 
     def configure_optimizers(self):
         if self.optim_name == "adam":

@@ -393,13 +393,19 @@ class GraphedTrainStep:
         # opt-in (MISEG_EARLY_OPT=1): measured SLOWER on the headline net - 138.1 / 137.3 patches/s against 140.1 / 139.1 with the one-launch
         # step behind the pass (same box): 1.2 GB of optimiser traffic beside the end-of-pass grouped launches lengthens the tail by more than
         # the 0.28 ms it takes off the chain (the same finding as the tiny-volume weight gradients on the branch, hip/ops.py::conv3_wgrad)
-        self.early_optimizer = bool(os.environ.get("MISEG_EARLY_OPT"))
+        # (ignored with gradient clipping / the non-finite guard on: the early launch would run before the step's gradient norm exists)
+        self.early_optimizer = bool(os.environ.get("MISEG_EARLY_OPT")) and not optimizer.clipping
         if optimizer.lr_dev is None:
             optimizer.lr_dev = torch.tensor([optimizer.lr], dtype=torch.float32, device=dev)
 
     def set_lr(self, lr):
         self.opt.lr = float(lr)
         self.opt.lr_dev.fill_(float(lr))
+
+    @property
+    def grad_norm(self):
+        """the optimiser's static device scalar: global L2 norm of the last replay's gradient before clipping (ArenaOptimizer.grad_norm)"""
+        return self.opt.grad_norm
 
     def _run(self, host, optimise):
         # round 5, opt-in (self.early_optimizer): the parameters whose gradients are final when the main chain of the backward pass ends (the

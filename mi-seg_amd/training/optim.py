@@ -16,10 +16,48 @@ from ..hip import ops
 KINDS = {"adamw": L.OPT_ADAMW, "adam": L.OPT_ADAM, "sgd": L.OPT_SGD_NESTEROV}
 
 
+def clip_options(gradient_clip_val=None, gradient_clip_algorithm="norm", skip_nonfinite=False, track_grad_norm=False):
+    """(MISEG_CLIP_* mode, clip value, guard on, tracking on) of ArenaOptimizer's clipping arguments; ValueError for what they do not allow.
+    track_grad_norm also takes the command line's spelling: -1 = off, 2 = the L2 norm (the only norm the kernel forms)."""
+    if gradient_clip_algorithm not in L.CLIP_MODES:
+        raise ValueError("gradient_clip_algorithm {!r}: 'norm' or 'value'".format(gradient_clip_algorithm))
+    val = None if gradient_clip_val is None else float(gradient_clip_val)
+    if val is not None and not (0.0 < val < float("inf")):
+        raise ValueError("gradient_clip_val {!r} must be finite and > 0 (None: no clipping)".format(gradient_clip_val))
+    if isinstance(track_grad_norm, bool) or track_grad_norm is None:
+        track = bool(track_grad_norm)
+    elif track_grad_norm in (-1, 2):
+        track = track_grad_norm == 2
+    else:
+        raise ValueError("track_grad_norm {!r}: only the L2 norm (2 / True) is computed; -1 / False turns it off".format(track_grad_norm))
+    return (L.CLIP_NONE if val is None else L.CLIP_MODES[gradient_clip_algorithm]), (0.0 if val is None else val), bool(skip_nonfinite), track
+
+
 class ArenaOptimizer:
-    def __init__(self, arena, kind="adamw", lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, momentum=0.99):
+    """The optimiser of the module docstring.  Its step controls beyond the hyper-parameters are gradient clipping and the non-finite guard
+    (Lightning's Trainer(gradient_clip_val, gradient_clip_algorithm, track_grad_norm)), all off by default - the step then issues exactly the
+    launches it always did:
+
+      gradient_clip_val, gradient_clip_algorithm="norm"   every gradient is scaled by min(1, clip / (global L2 norm + 1e-6)): torch's clip_grad_norm_
+      gradient_clip_val, gradient_clip_algorithm="value"  every gradient element is clamped to [-clip, clip]: torch's clip_grad_value_
+      skip_nonfinite                                      a step whose gradient norm is inf or NaN changes nothing (weights, moments, packs, step counts)
+      track_grad_norm                                     the norm (and `grad_norms`, one per parameter) is computed even when nothing else needs it
+
+    The norm is two launches over the arena in front of the update (miseg_grad_norm), its result stays on the device (`clip_record`, `grad_norm`)
+    and the update kernels read it there: no host read, so the step is capturable.  Unlike torch, which clips in place, the arena is NOT modified:
+    `p.grad` shows the unclipped gradient after the step.  Under data parallelism step() runs behind the all-reduce, so every rank computes the
+    same norm from the same bytes."""
+
+    def __init__(self, arena, kind="adamw", lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, momentum=0.99, gradient_clip_val=None,
+                 gradient_clip_algorithm="norm", skip_nonfinite=False, track_grad_norm=False):
         if kind not in KINDS:
             raise ValueError("Optimization {} not implemented, please chose another optimizer.".format(kind))
+        self.clip_mode, self.clip_val, self.skip_nonfinite, self.track_grad_norm = clip_options(gradient_clip_val, gradient_clip_algorithm, skip_nonfinite,
+                                                                                               track_grad_norm)
+        # which launches the options add: the norm in front (norm clipping, the guard, tracking) and the clipped forms of the update (all but tracking)
+        self._need_norm = self.clip_mode == L.CLIP_NORM or self.skip_nonfinite or self.track_grad_norm
+        self._clipped = self.clip_mode != L.CLIP_NONE or self.skip_nonfinite
+        self._rec = self._norm_ws = self.grad_norms = None
         self.arena, self.kind = arena, kind
         self.lr, self.betas, self.eps, self.weight_decay, self.momentum = float(lr), betas, float(eps), float(weight_decay), float(momentum)
         dev = arena.flat.device
@@ -43,6 +81,58 @@ class ArenaOptimizer:
         self._early = None          # (table, index, blocks, n) of the parameters updated by step_early(), and of the rest
         self._late = None
         self._early_done = False
+
+    @property
+    def clipping(self):
+        """True when any of clipping / the guard / norm tracking is on (the step then starts with the norm launches or ends in the clipped kernels)"""
+        return self._need_norm or self._clipped
+
+    def _clip_buffers(self):
+        """the 32-byte record (miseg_grad_clip_record, zeroed once: its counters run on), the norm workspace and the per-parameter norms.  Allocated
+        ONCE: a captured hipGraph holds their addresses."""
+        if self._rec is None and self.clipping:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ArenaOptimizer.prepare() must run before a step with clipping is captured (it allocates the clip record)")
+            dev = self.state1.device
+            self._rec = torch.zeros(C.sizeof(L.GradClipRecord) // 4, dtype=torch.int32, device=dev)
+            if self._need_norm:
+                n = len(self.arena.params)
+                self._norm_ws = torch.empty(L.load().miseg_grad_norm_workspace_bytes(self._blocks, n) // 8, dtype=torch.float64, device=dev)
+                if self.track_grad_norm:
+                    self.grad_norms = torch.zeros(n, dtype=torch.float32, device=dev)
+        return self._rec
+
+    @property
+    def clip_record(self):
+        """the device record of the last step (int32 [8] over miseg_grad_clip_record: norm, coef as float bits, finite, skip, seen, clipped, skipped)"""
+        return self._clip_buffers()
+
+    @property
+    def grad_norm(self):
+        """global L2 norm of the last step's gradient BEFORE clipping: a 0-dim fp32 device view of the record (no sync; static under graph replay)"""
+        if not self._need_norm:
+            raise ValueError("no gradient norm is computed: turn on norm clipping, skip_nonfinite or track_grad_norm")
+        return self._clip_buffers()[:1].view(torch.float32)[0]
+
+    def clip_stats(self):
+        """the record read back once (one device-to-host copy): norm, coef, finite, seen, clipped, skipped"""
+        if not self.clipping:
+            raise ValueError("clipping, the non-finite guard and norm tracking are all off")
+        r = self._clip_buffers().cpu()
+        f = r[:2].view(torch.float32)
+        return {"norm": float(f[0]), "coef": float(f[1]), "finite": int(r[2]), "seen": int(r[4]), "clipped": int(r[5]), "skipped": int(r[6])}
+
+    def _launch_norm(self):
+        n = len(self.arena.params)
+        p = L.GradNorm(C.sizeof(L.GradNorm), self.clip_mode, self._table.data_ptr(), n, self._blocks, self.arena.flat.data_ptr(), self.used.data_ptr(),
+                       self.clip_val if self.clip_mode == L.CLIP_NORM else 0.0, int(self.skip_nonfinite), self._norm_ws.data_ptr(), self._rec.data_ptr(),
+                       self.grad_norms.data_ptr() if self.grad_norms is not None else None)
+        ops._call("miseg_grad_norm", p)
+
+    def _clip_extra(self):
+        """(record, mode, value): the trailing arguments of the clipped entry points; value mode without the guard reads no record"""
+        rec = self._rec.data_ptr() if (self.clip_mode != L.CLIP_VALUE or self.skip_nonfinite) else None
+        return (C.c_void_p(rec), self.clip_mode, C.c_float(self.clip_val if self.clip_mode != L.CLIP_NONE else 0.0))
 
     def _subset_table(self, sel):
         """(descriptor table, index, blocks, count) of the arena parameters `sel` (a list of indices) on the device"""
@@ -86,6 +176,7 @@ class ArenaOptimizer:
     def prepare(self):
         """build (and upload) the launch tables now - call before capturing a step that contains `step()` into a hipGraph"""
         self._fused_tables()
+        self._clip_buffers()
 
     def _launch_pack(self, tabs, lr, count_n):
         _, maps, (ptab, n, tiles) = tabs
@@ -95,13 +186,21 @@ class ArenaOptimizer:
                       self.lr if lr is None else float(lr), self.betas[0], self.betas[1], self.eps, self.weight_decay, self.momentum,
                       self.lr_dev.data_ptr() if self.lr_dev is not None else None, a.params_version_ptr(), None, count_n)
         state = a._ver(3)[1]
+        if self._clipped:
+            L.check(L.load().miseg_opt_step_pack_conv3_clipped(C.byref(p), C.c_void_p(ptab.data_ptr()), C.c_void_p(maps.data_ptr()), n, tiles,
+                                                               L.F32 if a.dtype == torch.float32 else L.BF16, state, *self._clip_extra(), ops._stream()),
+                    "opt_step_pack_conv3_clipped")
+            return
         L.check(L.load().miseg_opt_step_pack_conv3(C.byref(p), C.c_void_p(ptab.data_ptr()), C.c_void_p(maps.data_ptr()), n, tiles,
                                                    L.F32 if a.dtype == torch.float32 else L.BF16, state, ops._stream()), "opt_step_pack_conv3")
 
     def split_early(self, early_params):
         """Two launches per step: `early_params` (parameters whose gradients are final before the end of the backward pass: what
         ParamArena.inline_final_params reports after a step) are updated by step_early() - which the caller may issue on a side stream beside the
-        rest of the pass - and all the others by step().  Same arithmetic, same result as the one-launch step (each parameter is touched once)."""
+        rest of the pass - and all the others by step().  Same arithmetic, same result as the one-launch step (each parameter is touched once).
+        Refused with clipping or the guard on: the early launch runs before the gradient norm of the step exists."""
+        if self.clipping:
+            raise ValueError("split_early: gradient clipping / skip_nonfinite / track_grad_norm need the whole gradient before the first update")
         ids = {id(p) for p in early_params}
         # (tables a captured hipGraph points at by raw address must never be freed: an unchanged set keeps its tables - a second capture, of
         # another modality set, asks again - and replaced ones are retired, not dropped)
@@ -134,7 +233,10 @@ class ArenaOptimizer:
                       self.lr if lr is None else float(lr), self.betas[0], self.betas[1], self.eps, self.weight_decay, self.momentum,
                       self.lr_dev.data_ptr() if self.lr_dev is not None else None, self.arena.params_version_ptr(),
                       index.data_ptr() if index is not None else None, count_n)
-        ops._call("miseg_opt_step", p)
+        if self._clipped:
+            ops._call("miseg_opt_step_clipped", p, extra=self._clip_extra())
+        else:
+            ops._call("miseg_opt_step", p)
 
     def step_early(self, lr=None):
         """the first launch of a split step (split_early): the `used` flags must be on the device already (set_used_from_arena / a captured
@@ -165,6 +267,10 @@ class ArenaOptimizer:
             else:
                 self.set_used_from_arena()
         fused = self._fused_tables()
+        if self.clipping:             # the norm of the whole gradient first (two launches); the update kernels read its record on the device
+            self._clip_buffers()
+            if self._need_norm:
+                self._launch_norm()
         if self._early_done:          # the early launch of this step is out: the rest, then the step counts of ALL parameters and the version bump
             self._launch(self._late, lr, len(self.arena.params))
             self._early_done = False

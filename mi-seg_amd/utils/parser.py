@@ -94,6 +94,18 @@ TUNE_ARGS = {
     ],
 }
 
+# The reference's train.py takes every pytorch_lightning.Trainer argument (Trainer.add_argparse_args); these are the ones the fused optimiser
+# (training/optim.py::ArenaOptimizer) carries out on the device.  A table of its own that no other add_* function adds: a script that also adds
+# Lightning's own Trainer arguments would otherwise define them twice.  --skip_nonfinite_steps is the only flag Lightning does not have.
+TRAINER_ARGS = {
+    "trainer": [
+        ("--gradient_clip_val", dict(default=None, type=float, help="clip gradients to this global norm / absolute value (default: no clipping)")),
+        ("--gradient_clip_algorithm", dict(default="norm", type=str, choices=("norm", "value"))),
+        ("--track_grad_norm", dict(default=-1, type=int, choices=(-1, 2), help="2: compute the gradients' L2 norm every step for logging; -1: off")),
+        ("--skip_nonfinite_steps", dict(action=_T, help="an optimisation step whose gradient norm is inf or NaN changes nothing")),
+    ],
+}
+
 
 def _add(parser: ArgumentParser, table):
     for group_name, entries in table.items():
@@ -113,3 +125,7 @@ def add_data_argparse_args(parser: ArgumentParser):
 
 def add_tune_argparse_args(parser: ArgumentParser):
     return _add(parser, TUNE_ARGS)
+
+
+def add_trainer_argparse_args(parser: ArgumentParser):
+    return _add(parser, TRAINER_ARGS)
