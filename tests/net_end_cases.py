@@ -1,4 +1,4 @@
-"""The case table of the network-end kernels (csrc/elementwise.hip: the one- to four-channel stem convolution, the patch embedding, the
+"""The case table of the network-end kernels (csrc/net_end.hip: the one- to four-channel stem convolution, the patch embedding, the
 output head): one row per launch form, operand layout and loop condition, each with the kernel its plan must name.  Two files run it:
 tests/test_net_end_plan_cpu.py through the host-only plans with stand-in addresses, tests/test_hip_net_end_forms.py on the card - the GPU file
 runs exactly the rows the CPU file pinned.  No torch here: shapes, layouts, expectations and the ctypes params of a row.

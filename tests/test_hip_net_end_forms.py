@@ -1,6 +1,6 @@
-"""Launch forms and operand layouts of the kernels at the two ends of every network (csrc/elementwise.hip): the stem convolution
+"""Launch forms and operand layouts of the kernels at the two ends of every network (csrc/net_end.hip): the stem convolution
 (miseg_conv3_thin_fwd / _wgrad), the patch embedding (miseg_patch_embed_fwd / _bwd), the output head (miseg_head_fwd / _bwd) and the public
-im2col3 / col2im3.
+im2col3 / col2im3 (csrc/elementwise.hip).
 
 The rows are tests/net_end_cases.py, the table tests/test_net_end_plan_cpu.py pins on the host-only plans: every row goes through
 `ops._call` with its ctypes struct (leading dimensions and bases chosen freely), and BEFORE the launch the plan of these very params must

@@ -1,5 +1,5 @@
 """The host-only plans of the network-end launchers (miseg_conv3_thin_fwd_plan, miseg_conv3_thin_wgrad_plan, miseg_patch_embed_fwd_plan,
-miseg_patch_embed_bwd_plan, miseg_head_fwd_plan, miseg_head_bwd_plan; csrc/elementwise.hip): the launchers dispatch on them, so the kernel a
+miseg_patch_embed_bwd_plan, miseg_head_fwd_plan, miseg_head_bwd_plan; csrc/net_end.hip): the launchers dispatch on them, so the kernel a
 shape reaches is pinned here without a card.  The table is tests/net_end_cases.py - the rows tests/test_hip_net_end_forms.py launches - run
 with stand-in addresses (aligned 1 << 12, or 8 bytes into a 16-byte unit): every row asserts the kernel, the partial-sum flag, the passes and,
 where the row is there for a wrapping loop, items > workgroups x items per trip.  Every kernel value of every plan appears in a row.
