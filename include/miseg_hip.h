@@ -412,6 +412,31 @@ int miseg_conv3_wgrad(const miseg_conv3_wgrad_params* p, miseg_stream_t stream);
  * params is ignored; one shared buffer of miseg_conv3_wgrad_group_workspace_bytes is passed instead (may be NULL when that is 0). */
 size_t miseg_conv3_wgrad_group_workspace_bytes(const miseg_conv3_wgrad_params* layers, int n);
 int miseg_conv3_wgrad_group(const miseg_conv3_wgrad_params* layers, int n, void* workspace, miseg_stream_t stream);
+/* ABI 16 (new symbols): the whole FORM of a weight-gradient launch - a superset of the plan; the slab, narrow, tiny and grouped launchers
+ * dispatch on exactly this struct.  Host only.  miseg_conv3_wgrad_form: the launch miseg_conv3_wgrad(p) makes.
+ * miseg_conv3_wgrad_group_form: forms[i] is what miseg_conv3_wgrad_group(layers, n, ..) does with layers[i] (n entries; every layer runs in
+ * the slab kernels there; plan.workspace_bytes is the layer's share of the group's buffer). */
+typedef struct {
+  miseg_conv3_wgrad_plan_info plan;
+  int32_t brick_depth;             /* slab kernels: 2 (fp32) / 4 (bf16); NARROW 4; TINY 0 */
+  int32_t piped;                   /* slab kernels: 1 = the software-pipelined loop (bf16, whole 48-channel blocks, aligned, a whole brick per axis) */
+  int32_t vec_x, vec_dy;           /* 16-byte aligned base and whole vectors per row */
+  int32_t nbricks;                 /* bricks of brick_depth x 8 x 8 voxels over the batch */
+  int32_t ncob, ncib;              /* slab kernels: 48-channel blocks on the output / input side */
+  int32_t nsplit;                  /* slab kernels: brick ranges = partial slabs per channel-block pair */
+  int32_t bricks_per_workgroup;    /* slab kernels / NARROW: the most bricks one workgroup walks (> 1: its brick loop goes round) */
+  int32_t direct;                  /* slab kernels: 0 = slabs + reduce launch; 1 = direct epilogue adding to dw; 2 = direct epilogue storing */
+  int32_t fill;                    /* 1 = dw is zero-filled first (slab route, accumulate 0) */
+  int32_t reduce_groups, spg;      /* slab route: split groups of the reduce launch, splits per group (groups > 1: fp32 atomics) */
+  int32_t narrow_nco, narrow_nci;  /* NARROW: conv3_wgrad_narrow_kernel<NCO, NCI> (16-channel tiles a side); else 0 */
+  int32_t tiny_s;                  /* TINY: conv3_wgrad_tiny_kernel<S> (3 / 6); else 0 */
+  int32_t workgroups;              /* workgroups (grouped: units) of this layer in the main launch */
+  int32_t walk;                    /* grouped: 1 = the grid this layer runs in is capped (descs[0].max_workgroups) and walks its units */
+  int32_t grid_workgroups;         /* grouped: workgroups of that grid; single launch: = workgroups */
+  int32_t group_target;            /* grouped: bricks per workgroup the group aimed at; else 0 */
+} miseg_conv3_wgrad_form_info;
+int miseg_conv3_wgrad_form(const miseg_conv3_wgrad_params* p, miseg_conv3_wgrad_form_info* form);
+int miseg_conv3_wgrad_group_form(const miseg_conv3_wgrad_params* layers, int n, miseg_conv3_wgrad_form_info* forms);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused 3D (shifted-)window attention core: zero pad -> cyclic roll -> window partition -> per-head

@@ -1698,18 +1698,18 @@ static int wgrad_narrow_workgroups(const miseg_conv3_wgrad_params* p) {
   if (p->max_workgroups > 0 && p->max_workgroups < wg) wg = p->max_workgroups;      // background form
   return wg;
 }
-static int conv3_wgrad_narrow_launch(const miseg_conv3_wgrad_params* p, hipStream_t s) {
+static int conv3_wgrad_narrow_launch(const miseg_conv3_wgrad_params* p, const miseg_conv3_wgrad_form_info& f, hipStream_t s) {
   ConvGeom g{p->B, p->D, p->H, p->W, cdiv(p->D, 4), cdiv(p->H, BH), cdiv(p->W, BW)};
-  const int wg = wgrad_narrow_workgroups(p);
+  const int wg = f.workgroups;
   const size_t lds = (size_t)6 * HH * HW * (p->Cin * 2 + 16) + (size_t)4 * BH * BW * (p->Cout * 2 + 16);
 #define NARROW_LAUNCH(A, B_)                                                                                                              \
   do {                                                                                                                                    \
     MISEG_SET_SMEM((conv3_wgrad_narrow_kernel<A, B_>), lds);                                                                                \
     conv3_wgrad_narrow_kernel<A, B_><<<wg, WG_THREADS, lds, s>>>((const bf16*)p->x, p->ldx, (const bf16*)p->dy, p->lddy, (float*)p->workspace, g); \
   } while (0)
-  if (p->Cout == 16 && p->Cin == 16) NARROW_LAUNCH(1, 1);
-  else if (p->Cout == 16) NARROW_LAUNCH(1, 2);
-  else if (p->Cin == 16) NARROW_LAUNCH(2, 1);
+  if (f.narrow_nco == 1 && f.narrow_nci == 1) NARROW_LAUNCH(1, 1);
+  else if (f.narrow_nco == 1) NARROW_LAUNCH(1, 2);
+  else if (f.narrow_nci == 1) NARROW_LAUNCH(2, 1);
   else NARROW_LAUNCH(2, 2);
 #undef NARROW_LAUNCH
   const int n = 27 * p->Cout * p->Cin;
@@ -1824,10 +1824,10 @@ static bool wgrad_tiny(const miseg_conv3_wgrad_params* p) {
   return p->dtype == MISEG_BF16 && p->D == p->H && p->H == p->W && (p->D == 3 || p->D == 6) && p->B >= 1 && p->B <= 64 && p->Cin % 16 == 0 &&
          p->Cout % 48 == 0 && ((uintptr_t)p->x % 16 == 0) && ((uintptr_t)p->dy % 16 == 0) && p->ldx % 8 == 0 && p->lddy % 8 == 0;
 }
-static int conv3_wgrad_tiny_launch(const miseg_conv3_wgrad_params* p, hipStream_t s) {
+static int conv3_wgrad_tiny_launch(const miseg_conv3_wgrad_params* p, const miseg_conv3_wgrad_form_info& f, hipStream_t s) {
   const dim3 grid(p->Cin / 16, p->Cout / 48);
   const int add = p->accumulate == 1 ? 1 : 0;      // 0 / 2 (a slot known to hold zeros): plain stores
-  if (p->D == 3)
+  if (f.tiny_s == 3)
     conv3_wgrad_tiny_kernel<3><<<grid, 256, 0, s>>>((const bf16*)p->x, p->ldx, (const bf16*)p->dy, p->lddy, p->dw, p->B, p->Cin, p->Cout, add);
   else
     conv3_wgrad_tiny_kernel<6><<<grid, 256, 0, s>>>((const bf16*)p->x, p->ldx, (const bf16*)p->dy, p->lddy, p->dw, p->B, p->Cin, p->Cout, add);
@@ -2212,20 +2212,67 @@ static void wgrad_plan(int B, int D, int H, int W, int Cin, int Cout, int wbd, i
   *nsplit = ns;
 }
 
-// THE plan of a weight-gradient launch: miseg_conv3_wgrad dispatches on it, miseg_conv3_wgrad_plan returns it (host only)
-static int conv3_wgrad_plan(const miseg_conv3_wgrad_params* p, miseg_conv3_wgrad_plan_info* pl) {
+static bool wgrad_piped(const miseg_conv3_wgrad_params* p, int wbd, bool vec_x, bool vec_dy) {
+  const int esz = p->dtype == MISEG_F32 ? 4 : 2;
+  const int64_t span = (int64_t)(wbd + 2) * p->H * p->W * (p->ldx > p->lddy ? p->ldx : p->lddy) * (int64_t)esz;   // 32-bit item offsets
+  // (round 5: the last brick along an axis may be partial; every axis holds at least one whole brick, so a brick's first interior voxel -
+  // what an invalid item reads instead - is inside the volume)
+  return p->dtype == MISEG_BF16 && vec_x && vec_dy && p->Cin % WG_CB == 0 && p->Cout % WG_CB == 0 && p->D >= wbd && p->H >= BH && p->W >= BW &&
+         span < ((int64_t)1 << 31);
+}
+
+// what a slab-kernel launch of one layer does once its split count is known (single launch: wgrad_plan, grouped: wgrad_group_plan);
+// reduce_cap: (co, ci-block) tiles x split groups the reduce launch aims at
+static void wgrad_slab_form(const miseg_conv3_wgrad_params* p, int wbd, int ncob, int ncib, int nsplit, int reduce_cap, miseg_conv3_wgrad_form_info* f) {
+  const int kpc = p->dtype == MISEG_F32 ? 4 : 8;
+  f->brick_depth = wbd;
+  f->vec_x = ((uintptr_t)p->x % 16 == 0) && (p->ldx % kpc == 0);
+  f->vec_dy = ((uintptr_t)p->dy % 16 == 0) && (p->lddy % kpc == 0);
+  f->piped = wgrad_piped(p, wbd, f->vec_x, f->vec_dy);
+  f->nbricks = p->B * cdiv(p->D, wbd) * cdiv(p->H, BH) * cdiv(p->W, BW);
+  f->ncob = ncob; f->ncib = ncib; f->nsplit = nsplit;
+  f->bricks_per_workgroup = cdiv(f->nbricks, nsplit);
+  f->direct = nsplit == 1 ? (p->accumulate == 1 ? 1 : 2) : 0;     // a single producer per element: no slabs, no second launch
+  f->workgroups = f->grid_workgroups = ncob * ncib * nsplit;
+  if (!f->direct) {
+    f->fill = !p->accumulate;
+    const int tiles = p->Cout * ncib;
+    int groups = cdiv(reduce_cap, tiles);
+    if (groups > nsplit) groups = nsplit;
+    f->spg = cdiv(nsplit, groups);
+    f->reduce_groups = cdiv(nsplit, f->spg);
+  }
+}
+
+// THE form of a weight-gradient launch: miseg_conv3_wgrad dispatches on it, miseg_conv3_wgrad_form returns it and miseg_conv3_wgrad_plan
+// its public part (host only)
+static int conv3_wgrad_form(const miseg_conv3_wgrad_params* p, miseg_conv3_wgrad_form_info* f) {
   MISEG_REQUIRE(p->B > 0 && p->D > 0 && p->H > 0 && p->W > 0 && p->Cin > 0 && p->Cout > 0, MISEG_E_BADARG, "conv3_wgrad: bad shape");
   MISEG_REQUIRE(p->dtype == MISEG_F32 || p->dtype == MISEG_BF16, MISEG_E_BADARG, "conv3_wgrad: dtype %d", p->dtype);
-  *pl = miseg_conv3_wgrad_plan_info{};
+  *f = miseg_conv3_wgrad_form_info{};
+  miseg_conv3_wgrad_plan_info* pl = &f->plan;
   if (p->dtype == MISEG_F32) pl->kernel = MISEG_CONV3_WGRAD_F32;
   else if (wgrad_narrow(p)) pl->kernel = MISEG_CONV3_WGRAD_NARROW;
   else if (wgrad_tiny(p)) pl->kernel = MISEG_CONV3_WGRAD_TINY;
   else pl->kernel = MISEG_CONV3_WGRAD_BF16;
   if (pl->kernel == MISEG_CONV3_WGRAD_NARROW) {      // one slab per workgroup
-    pl->workspace_bytes = (size_t)wgrad_narrow_workgroups(p) * 27 * p->Cin * p->Cout * sizeof(float);
-  } else if (pl->kernel != MISEG_CONV3_WGRAD_TINY) {      // the slab kernels (conv3_wgrad_launch: fp32 bricks of depth 2, bf16 of depth 4)
+    f->brick_depth = 4;
+    f->vec_x = f->vec_dy = 1;
+    f->nbricks = p->B * cdiv(p->D, 4) * cdiv(p->H, BH) * cdiv(p->W, BW);
+    f->workgroups = f->grid_workgroups = wgrad_narrow_workgroups(p);
+    f->bricks_per_workgroup = cdiv(f->nbricks, f->workgroups);
+    f->narrow_nco = p->Cout / 16;
+    f->narrow_nci = p->Cin / 16;
+    pl->workspace_bytes = (size_t)f->workgroups * 27 * p->Cin * p->Cout * sizeof(float);
+  } else if (pl->kernel == MISEG_CONV3_WGRAD_TINY) {
+    f->vec_x = f->vec_dy = 1;
+    f->tiny_s = p->D;
+    f->workgroups = f->grid_workgroups = (p->Cin / 16) * (p->Cout / 48);
+  } else {      // the slab kernels: fp32 bricks of depth 2, bf16 of depth 4
+    const int wbd = p->dtype == MISEG_F32 ? 2 : 4;
     int ncob, ncib, ns;
-    wgrad_plan(p->B, p->D, p->H, p->W, p->Cin, p->Cout, p->dtype == MISEG_F32 ? 2 : 4, &ncob, &ncib, &ns, p->max_workgroups);
+    wgrad_plan(p->B, p->D, p->H, p->W, p->Cin, p->Cout, wbd, &ncob, &ncib, &ns, p->max_workgroups);
+    wgrad_slab_form(p, wbd, ncob, ncib, ns, 2048, f);
     pl->workspace_bytes = (size_t)ncob * ncib * ns * 27 * WG_CB * WG_CB * sizeof(float);
   }
   return MISEG_OK;
@@ -2233,34 +2280,31 @@ static int conv3_wgrad_plan(const miseg_conv3_wgrad_params* p, miseg_conv3_wgrad
 
 extern "C" int miseg_conv3_wgrad_plan(const miseg_conv3_wgrad_params* p, miseg_conv3_wgrad_plan_info* plan) {
   MISEG_REQUIRE(p && plan, MISEG_E_BADARG, "conv3_wgrad_plan: null pointer");
-  return conv3_wgrad_plan(p, plan);
+  miseg_conv3_wgrad_form_info f;
+  if (const int rc = conv3_wgrad_form(p, &f)) return rc;
+  *plan = f.plan;
+  return MISEG_OK;
+}
+
+extern "C" int miseg_conv3_wgrad_form(const miseg_conv3_wgrad_params* p, miseg_conv3_wgrad_form_info* form) {
+  MISEG_REQUIRE(p && form, MISEG_E_BADARG, "conv3_wgrad_form: null pointer");
+  return conv3_wgrad_form(p, form);
 }
 
 template <class T, int WBD>
-static bool wgrad_piped(const miseg_conv3_wgrad_params* p, bool vec_x, bool vec_dy) {
-  const int64_t span = (int64_t)(WBD + 2) * p->H * p->W * (p->ldx > p->lddy ? p->ldx : p->lddy) * (int64_t)sizeof(T);   // 32-bit item offsets
-  // (round 5: the last brick along an axis may be partial; every axis holds at least one whole brick, so a brick's first interior voxel -
-  // what an invalid item reads instead - is inside the volume)
-  return std::is_same<T, bf16>::value && vec_x && vec_dy && p->Cin % WG_CB == 0 && p->Cout % WG_CB == 0 && p->D >= WBD && p->H >= BH && p->W >= BW &&
-         span < ((int64_t)1 << 31);
-}
-
-template <class T, int WBD>
-static int conv3_wgrad_launch(const miseg_conv3_wgrad_params* p, hipStream_t s) {
-  constexpr int KPC = Vec16<T>::N;
-  int ncob, ncib, nsplit;
-  wgrad_plan(p->B, p->D, p->H, p->W, p->Cin, p->Cout, WBD, &ncob, &ncib, &nsplit, p->max_workgroups);
+static int conv3_wgrad_launch(const miseg_conv3_wgrad_params* p, const miseg_conv3_wgrad_form_info& f, hipStream_t s) {
+  const int ncib = f.ncib, nsplit = f.nsplit, direct = f.direct;
   ConvGeom g{p->B, p->D, p->H, p->W, cdiv(p->D, WBD), cdiv(p->H, BH), cdiv(p->W, BW)};
   const int rowb = WG_CB * (int)sizeof(T) + 16;
   const size_t lds = (size_t)((WBD + 2) * HH * HW + WBD * BH * BW) * rowb;
-  const bool vec_x = ((uintptr_t)p->x % 16 == 0) && (p->ldx % KPC == 0);
-  const bool vec_dy = ((uintptr_t)p->dy % 16 == 0) && (p->lddy % KPC == 0);
-  const int direct = nsplit == 1 ? (p->accumulate == 1 ? 1 : 2) : 0;     // a single producer per element: no slabs, no second launch
-  dim3 grid(nsplit, ncob * ncib);
-  if (wgrad_piped<T, WBD>(p, vec_x, vec_dy)) {
-    hipFuncSetAttribute((const void*)conv3_wgrad_kernel<T, WBD, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    conv3_wgrad_kernel<T, WBD, true><<<grid, WG_THREADS, lds, s>>>((const T*)p->x, p->ldx, (const T*)p->dy, p->lddy, (float*)p->workspace, p->dw, g, p->Cin, p->Cout,
-                                                                   ncib, nsplit, rowb, vec_x, vec_dy, direct);
+  const bool vec_x = f.vec_x != 0, vec_dy = f.vec_dy != 0;
+  dim3 grid(nsplit, f.ncob * ncib);
+  if (f.piped) {
+    if constexpr (std::is_same<T, bf16>::value) {
+      hipFuncSetAttribute((const void*)conv3_wgrad_kernel<T, WBD, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      conv3_wgrad_kernel<T, WBD, true><<<grid, WG_THREADS, lds, s>>>((const T*)p->x, p->ldx, (const T*)p->dy, p->lddy, (float*)p->workspace, p->dw, g, p->Cin, p->Cout,
+                                                                     ncib, nsplit, rowb, vec_x, vec_dy, direct);
+    }
   } else {
     hipFuncSetAttribute((const void*)conv3_wgrad_kernel<T, WBD, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     conv3_wgrad_kernel<T, WBD, false><<<grid, WG_THREADS, lds, s>>>((const T*)p->x, p->ldx, (const T*)p->dy, p->lddy, (float*)p->workspace, p->dw, g, p->Cin, p->Cout,
@@ -2268,13 +2312,8 @@ static int conv3_wgrad_launch(const miseg_conv3_wgrad_params* p, hipStream_t s) 
   }
   if (!direct) {
     const int64_t total = (int64_t)p->Cout * p->Cin * 27;
-    if (!p->accumulate) MISEG_REQUIRE(fill_words_async(p->dw, 0, (size_t)total, s) == hipSuccess, MISEG_E_LAUNCH, "conv3_wgrad: fill");
-    const int tiles = p->Cout * ncib;
-    int groups = cdiv(2048, tiles);
-    if (groups > nsplit) groups = nsplit;
-    const int spg = cdiv(nsplit, groups);
-    groups = cdiv(nsplit, spg);
-    conv3_wgrad_reduce_kernel<<<dim3(tiles, groups), 256, 0, s>>>((const float*)p->workspace, p->dw, p->Cin, p->Cout, ncib, nsplit, spg);
+    if (f.fill) MISEG_REQUIRE(fill_words_async(p->dw, 0, (size_t)total, s) == hipSuccess, MISEG_E_LAUNCH, "conv3_wgrad: fill");
+    conv3_wgrad_reduce_kernel<<<dim3(p->Cout * ncib, f.reduce_groups), 256, 0, s>>>((const float*)p->workspace, p->dw, p->Cin, p->Cout, ncib, nsplit, f.spg);
   }
   MISEG_LAUNCH_CHECK("conv3_wgrad");
   return MISEG_OK;
@@ -2310,36 +2349,71 @@ static void wgrad_group_plan(const miseg_conv3_wgrad_params* p, int wbd, int tar
   *nsplit = ns;
 }
 
-static size_t wgrad_group_slab_floats(const miseg_conv3_wgrad_params* p, int wbd, int target) {
-  int ncob, ncib, nsplit;
-  wgrad_group_plan(p, wbd, target, &ncob, &ncib, &nsplit);
-  return nsplit == 1 ? 0 : (size_t)ncob * ncib * nsplit * 27 * WG_CB * WG_CB;
+// THE form of a grouped launch, layer by layer in the caller's order: conv3_wgrad_group_launch dispatches on it,
+// miseg_conv3_wgrad_group_form returns it, miseg_conv3_wgrad_group_workspace_bytes sums its workspace shares (host only)
+static void conv3_wgrad_group_form(const miseg_conv3_wgrad_params* descs, int n, miseg_conv3_wgrad_form_info* forms) {
+  const int wbd = descs[0].dtype == MISEG_BF16 ? 4 : 2;
+  const int target = wgrad_group_target(descs, n, wbd);
+  int nwg[2] = {0, 0};      // units of the pipelined grid and of the other
+  for (int i = 0; i < n; ++i) {
+    miseg_conv3_wgrad_form_info* f = forms + i;
+    *f = miseg_conv3_wgrad_form_info{};
+    f->plan.kernel = descs[0].dtype == MISEG_BF16 ? MISEG_CONV3_WGRAD_BF16 : MISEG_CONV3_WGRAD_F32;
+    int ncob, ncib, nsplit;
+    wgrad_group_plan(descs + i, wbd, target, &ncob, &ncib, &nsplit);
+    wgrad_slab_form(descs + i, wbd, ncob, ncib, nsplit, 512, f);     // the layers of the group fill the chip together: few split groups each (fewer atomics)
+    f->plan.workspace_bytes = f->direct ? 0 : (size_t)ncob * ncib * nsplit * 27 * WG_CB * WG_CB * sizeof(float);
+    f->group_target = target;
+    nwg[f->piped ? 0 : 1] += f->workgroups;
+  }
+  const int cap = descs[0].max_workgroups;      // > 0: background form (see the kernel)
+  for (int i = 0; i < n; ++i) {
+    const int units = nwg[forms[i].piped ? 0 : 1];
+    forms[i].walk = cap > 0 && cap < units;
+    forms[i].grid_workgroups = forms[i].walk ? cap : units;
+  }
 }
 
 extern "C" size_t miseg_conv3_wgrad_group_workspace_bytes(const miseg_conv3_wgrad_params* descs, int n) {
-  if (!descs || n <= 0) return 0;
-  const int wbd = descs[0].dtype == MISEG_BF16 ? 4 : 2;
-  const int target = wgrad_group_target(descs, n, wbd);
+  if (!descs || n <= 0 || n > WG_GROUP_MAX) return 0;
+  miseg_conv3_wgrad_form_info forms[WG_GROUP_MAX];
+  conv3_wgrad_group_form(descs, n, forms);
   size_t total = 0;
-  for (int i = 0; i < n; ++i) total += wgrad_group_slab_floats(descs + i, wbd, target);
-  return total * sizeof(float);
+  for (int i = 0; i < n; ++i) total += forms[i].plan.workspace_bytes;
+  return total;
+}
+
+static int conv3_wgrad_group_check(const miseg_conv3_wgrad_params* descs, int n) {
+  MISEG_REQUIRE(descs && n > 0 && n <= WG_GROUP_MAX, MISEG_E_BADARG, "conv3_wgrad_group: 1..%d layers per launch", WG_GROUP_MAX);
+  for (int i = 0; i < n; ++i) {
+    const miseg_conv3_wgrad_params* p = descs + i;
+    MISEG_REQUIRE(p->x && p->dy && p->dw, MISEG_E_BADARG, "conv3_wgrad_group: null pointer in layer %d", i);
+    MISEG_REQUIRE(p->B > 0 && p->D > 0 && p->H > 0 && p->W > 0 && p->Cin > 0 && p->Cout > 0, MISEG_E_BADARG, "conv3_wgrad_group: bad shape in layer %d", i);
+    MISEG_REQUIRE(p->dtype == descs[0].dtype, MISEG_E_BADARG, "conv3_wgrad_group: mixed dtypes");
+  }
+  MISEG_REQUIRE(descs[0].dtype == MISEG_F32 || descs[0].dtype == MISEG_BF16, MISEG_E_BADARG, "conv3_wgrad_group: dtype %d", descs[0].dtype);
+  return MISEG_OK;
+}
+
+extern "C" int miseg_conv3_wgrad_group_form(const miseg_conv3_wgrad_params* descs, int n, miseg_conv3_wgrad_form_info* forms) {
+  MISEG_REQUIRE(forms, MISEG_E_BADARG, "conv3_wgrad_group_form: null pointer");
+  if (const int rc = conv3_wgrad_group_check(descs, n)) return rc;
+  conv3_wgrad_group_form(descs, n, forms);
+  return MISEG_OK;
 }
 
 template <class T, int WBD>
 static int conv3_wgrad_group_launch(const miseg_conv3_wgrad_params* descs, int n, float* workspace, hipStream_t s) {
-  constexpr int KPC = Vec16<T>::N;
   const int rowb = WG_CB * (int)sizeof(T) + 16;
   const size_t lds = (size_t)((WBD + 2) * HH * HW + WBD * BH * BW) * rowb;
-  const int target = wgrad_group_target(descs, n, WBD);
+  miseg_conv3_wgrad_form_info forms[WG_GROUP_MAX];
+  conv3_wgrad_group_form(descs, n, forms);
   // longest workgroups first
   int order[WG_GROUP_MAX];
   int weight[WG_GROUP_MAX];
   for (int i = 0; i < n; ++i) {
-    int ncob, ncib, nsplit;
-    wgrad_group_plan(descs + i, WBD, target, &ncob, &ncib, &nsplit);
-    const int nbricks = descs[i].B * cdiv(descs[i].D, WBD) * cdiv(descs[i].H, BH) * cdiv(descs[i].W, BW);
     order[i] = i;
-    weight[i] = cdiv(nbricks, nsplit) * 8 - (descs[i].D < WBD ? 4 : 0) - (descs[i].H <= 4 ? 2 : 0);
+    weight[i] = forms[i].bricks_per_workgroup * 8 - (descs[i].D < WBD ? 4 : 0) - (descs[i].H <= 4 ? 2 : 0);
   }
   for (int i = 1; i < n; ++i)
     for (int j = i; j > 0 && weight[order[j]] > weight[order[j - 1]]; --j) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
@@ -2349,38 +2423,32 @@ static int conv3_wgrad_group_launch(const miseg_conv3_wgrad_params* descs, int n
   size_t off = 0;
   for (int k = 0; k < n; ++k) {
     const miseg_conv3_wgrad_params* p = descs + order[k];
+    const miseg_conv3_wgrad_form_info& f = forms[order[k]];
     WgradLayer& L = grp.l[k];
-    int ncob, ncib, nsplit;
-    wgrad_group_plan(p, WBD, target, &ncob, &ncib, &nsplit);
     L.x = p->x; L.dy = p->dy; L.dw = p->dw; L.ldx = p->ldx; L.lddy = p->lddy;
     L.g = ConvGeom{p->B, p->D, p->H, p->W, cdiv(p->D, WBD), cdiv(p->H, BH), cdiv(p->W, BW)};
-    L.Cin = p->Cin; L.Cout = p->Cout; L.ncib = ncib; L.nsplit = nsplit;
-    const int direct = nsplit == 1 ? (p->accumulate == 1 ? 1 : 2) : 0;
-    const bool vec_x = ((uintptr_t)p->x % 16 == 0) && (p->ldx % KPC == 0);
-    const bool vec_dy = ((uintptr_t)p->dy % 16 == 0) && (p->lddy % KPC == 0);
-    L.flags = (vec_x ? 1 : 0) | (vec_dy ? 2 : 0) | (direct << 2) | (wgrad_piped<T, WBD>(p, vec_x, vec_dy) ? 16 : 0);
+    L.Cin = p->Cin; L.Cout = p->Cout; L.ncib = f.ncib; L.nsplit = f.nsplit;
+    L.flags = (f.vec_x ? 1 : 0) | (f.vec_dy ? 2 : 0) | (f.direct << 2) | (f.piped ? 16 : 0);
     L.wg0 = wg;
-    wg += ncob * ncib * nsplit;
+    wg += f.workgroups;
     L.slabs = workspace + off;
     L.tiles = 0; L.groups = 0; L.spg = 0; L.rb0 = rb;
-    if (!direct) {
-      off += (size_t)ncob * ncib * nsplit * 27 * WG_CB * WG_CB;
-      if (!p->accumulate)
+    if (!f.direct) {
+      off += f.plan.workspace_bytes / sizeof(float);
+      if (f.fill)
         MISEG_REQUIRE(fill_words_async(p->dw, 0, (size_t)p->Cout * p->Cin * 27, s) == hipSuccess, MISEG_E_LAUNCH, "conv3_wgrad_group: fill");
-      L.tiles = p->Cout * ncib;
-      int groups = cdiv(512, L.tiles);     // the layers of the group fill the chip together: few split groups each (fewer atomics)
-      if (groups > nsplit) groups = nsplit;
-      L.spg = cdiv(nsplit, groups);
-      L.groups = cdiv(nsplit, L.spg);
+      L.tiles = p->Cout * f.ncib;
+      L.spg = f.spg;
+      L.groups = f.reduce_groups;
       rb += L.tiles * L.groups;
     }
   }
-  const int cap = descs[0].max_workgroups;      // > 0: background form (see the kernel)
   // the pipelined layers and the others: one grid each (same descriptors, workgroups renumbered; the reduce launch walks `grp`)
   for (int form = 0; form < 2; ++form) {
     WgradGroup sub;
     sub.n = 0;
-    int nwg = 0;
+    int nwg = 0, grid = 0;
+    bool walk = false;
     for (int k = 0; k < n; ++k) {
       if ((((grp.l[k].flags >> 4) & 1) != 0) != (form == 0)) continue;
       WgradLayer& L = sub.l[sub.n++];
@@ -2388,10 +2456,10 @@ static int conv3_wgrad_group_launch(const miseg_conv3_wgrad_params* descs, int n
       const int units = (k + 1 < n ? grp.l[k + 1].wg0 : wg) - grp.l[k].wg0;
       L.wg0 = nwg;
       nwg += units;
+      walk = forms[order[k]].walk != 0;      // (one answer per grid)
+      grid = forms[order[k]].grid_workgroups;
     }
     if (!sub.n) continue;
-    const bool walk = cap > 0 && cap < nwg;
-    const int grid = walk ? cap : nwg;
 #define MISEG_WG_GROUP_LAUNCH(PIPED_, WALK_)                                                                                                       \
     do {                                                                                                                                           \
       hipFuncSetAttribute((const void*)conv3_wgrad_group_kernel<T, WBD, PIPED_, WALK_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);      \
@@ -2420,28 +2488,21 @@ extern "C" int miseg_debug_wgrad_stamps(unsigned long long* out) {   // read and
 #endif
 
 extern "C" int miseg_conv3_wgrad_group(const miseg_conv3_wgrad_params* descs, int n, void* workspace, miseg_stream_t s_) {
-  MISEG_REQUIRE(descs && n > 0 && n <= WG_GROUP_MAX, MISEG_E_BADARG, "conv3_wgrad_group: 1..%d layers per launch", WG_GROUP_MAX);
-  for (int i = 0; i < n; ++i) {
-    const miseg_conv3_wgrad_params* p = descs + i;
-    MISEG_REQUIRE(p->x && p->dy && p->dw, MISEG_E_BADARG, "conv3_wgrad_group: null pointer in layer %d", i);
-    MISEG_REQUIRE(p->B > 0 && p->D > 0 && p->H > 0 && p->W > 0 && p->Cin > 0 && p->Cout > 0, MISEG_E_BADARG, "conv3_wgrad_group: bad shape in layer %d", i);
-    MISEG_REQUIRE(p->dtype == descs[0].dtype, MISEG_E_BADARG, "conv3_wgrad_group: mixed dtypes");
-  }
+  if (const int rc = conv3_wgrad_group_check(descs, n)) return rc;
   MISEG_REQUIRE(workspace || miseg_conv3_wgrad_group_workspace_bytes(descs, n) == 0, MISEG_E_BADARG, "conv3_wgrad_group: workspace missing");
   if (descs[0].dtype == MISEG_F32) return conv3_wgrad_group_launch<float, 2>(descs, n, (float*)workspace, (hipStream_t)s_);
-  if (descs[0].dtype == MISEG_BF16) return conv3_wgrad_group_launch<bf16, 4>(descs, n, (float*)workspace, (hipStream_t)s_);
-  return set_error(MISEG_E_BADARG, "conv3_wgrad_group: dtype %d", descs[0].dtype);
+  return conv3_wgrad_group_launch<bf16, 4>(descs, n, (float*)workspace, (hipStream_t)s_);
 }
 
 extern "C" int miseg_conv3_wgrad(const miseg_conv3_wgrad_params* p, miseg_stream_t s_) {
   MISEG_REQUIRE(p && p->x && p->dy && p->dw, MISEG_E_BADARG, "conv3_wgrad: null pointer");
-  miseg_conv3_wgrad_plan_info pl;
-  if (const int rc = conv3_wgrad_plan(p, &pl)) return rc;
-  MISEG_REQUIRE(!pl.workspace_bytes || p->workspace, MISEG_E_BADARG, "conv3_wgrad: workspace required (miseg_conv3_wgrad_plan_info.workspace_bytes)");
-  switch (pl.kernel) {
-    case MISEG_CONV3_WGRAD_F32: return conv3_wgrad_launch<float, 2>(p, (hipStream_t)s_);
-    case MISEG_CONV3_WGRAD_NARROW: return conv3_wgrad_narrow_launch(p, (hipStream_t)s_);
-    case MISEG_CONV3_WGRAD_TINY: return conv3_wgrad_tiny_launch(p, (hipStream_t)s_);
-    default: return conv3_wgrad_launch<bf16, 4>(p, (hipStream_t)s_);
+  miseg_conv3_wgrad_form_info f;
+  if (const int rc = conv3_wgrad_form(p, &f)) return rc;
+  MISEG_REQUIRE(!f.plan.workspace_bytes || p->workspace, MISEG_E_BADARG, "conv3_wgrad: workspace required (miseg_conv3_wgrad_plan_info.workspace_bytes)");
+  switch (f.plan.kernel) {
+    case MISEG_CONV3_WGRAD_F32: return conv3_wgrad_launch<float, 2>(p, f, (hipStream_t)s_);
+    case MISEG_CONV3_WGRAD_NARROW: return conv3_wgrad_narrow_launch(p, f, (hipStream_t)s_);
+    case MISEG_CONV3_WGRAD_TINY: return conv3_wgrad_tiny_launch(p, f, (hipStream_t)s_);
+    default: return conv3_wgrad_launch<bf16, 4>(p, f, (hipStream_t)s_);
   }
 }

@@ -84,6 +84,11 @@ Conv3Plan = _struct("Conv3Plan", cname="miseg_conv3_plan_info", fields=[("kernel
                                   ("sc", i32), ("s2c", i32), ("fs", i32), ("defer_slabs", i32)])
 CONV3_WGRAD_F32, CONV3_WGRAD_NARROW, CONV3_WGRAD_TINY, CONV3_WGRAD_BF16 = 0, 1, 2, 3      # miseg_conv3_wgrad_plan_info.kernel
 Conv3WgradPlan = _struct("Conv3WgradPlan", cname="miseg_conv3_wgrad_plan_info", fields=[("kernel", i32), ("pad_", i32), ("workspace_bytes", C.c_size_t)])
+# the whole launch form of a weight gradient (host only): what the launchers dispatch on, a superset of the plan
+Conv3WgradForm = _struct("Conv3WgradForm", cname="miseg_conv3_wgrad_form_info", fields=[
+    ("plan", Conv3WgradPlan), ("brick_depth", i32), ("piped", i32), ("vec_x", i32), ("vec_dy", i32), ("nbricks", i32), ("ncob", i32), ("ncib", i32), ("nsplit", i32),
+    ("bricks_per_workgroup", i32), ("direct", i32), ("fill", i32), ("reduce_groups", i32), ("spg", i32), ("narrow_nco", i32), ("narrow_nci", i32), ("tiny_s", i32),
+    ("workgroups", i32), ("walk", i32), ("grid_workgroups", i32), ("group_target", i32)])
 Winattn = _struct("Winattn", cname="miseg_winattn_params", fields=[("qkv", vp), ("ldq", i64), ("out", vp), ("ldo", i64), ("qkv_bias", vp), ("bias_table", vp),
                               ("lse", vp), ("B", i32), ("D", i32), ("H", i32), ("W", i32), ("C", i32), ("heads", i32),
                               ("dtype", i32), ("wd", i32), ("wh", i32), ("ww", i32), ("sd", i32), ("sh", i32), ("sw", i32),
@@ -266,6 +271,8 @@ PROTOS = {
     "miseg_colsum_batch": (i32, [vp, i32, i32, vp]),
     "miseg_conv3_fwd_plan": (i32, [C.POINTER(Conv3), C.POINTER(Conv3Plan)]),
     "miseg_conv3_fwd": (i32, [C.POINTER(Conv3), vp]),
+    "miseg_conv3_wgrad_form": (i32, [C.POINTER(Conv3Wgrad), C.POINTER(Conv3WgradForm)]),
+    "miseg_conv3_wgrad_group_form": (i32, [C.POINTER(Conv3Wgrad), i32, C.POINTER(Conv3WgradForm)]),
     "miseg_pack_conv3_elems": (C.c_size_t, [i32, i32, i32, i32]),
     "miseg_pack_conv3_tiles": (i32, [i32, i32, i32]),
     "miseg_pack_conv3_weight": (i32, [C.POINTER(PackConv3), vp]),
