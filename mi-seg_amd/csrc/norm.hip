@@ -72,7 +72,14 @@ template <class T, int VEC> struct RowVec {
       *reinterpret_cast<typename Vec16<T>::type*>(p) = t;
     }
   }
+  __device__ __forceinline__ float get(int i) const { return v[i]; }
 };
+
+// one value's share of a channel's (sum, sum of squares)
+__device__ __forceinline__ void stat_term(float v, float& s, float& q) {
+  s += v;
+  q = fmaf(v, v, q);
+}
 
 // Statistics buffers hold NORM_R replicas of the fp64 (sum, sum of squares) pairs: double [NORM_R][B][C][2].  A block adds
 // its partial sums to replica (chunk mod NORM_R): with one row, the ~900 blocks of a 96^3 tensor queue on 96 addresses and
@@ -117,13 +124,155 @@ __device__ __forceinline__ void gather_stat(double* sums, const double* __restri
 }
 
 // mean and 1/sqrt(var + eps) of one channel; the variance is formed in fp64 (cancellation), the root in fp32
-__device__ __forceinline__ void mean_rstd(const double* sums2, double invS, float eps, float& m, float& rs) {
-  const double mu = sums2[0] * invS;
-  double var = fma(sums2[1], invS, -mu * mu);
+__device__ __forceinline__ void mean_rstd(double sum, double sumsq, double invS, float eps, float& m, float& rs) {
+  const double mu = sum * invS;
+  double var = fma(sumsq, invS, -mu * mu);
   if (var < 0.0) var = 0.0;
   m = (float)mu;
   rs = 1.0f / sqrtf((float)var + eps);
 }
+
+// ---------------------------------------------------------------------------------------------------
+// The instance-norm arithmetic.  Every forward and backward kernel below is built from these pieces, so the scale / shift, the
+// pre-activation and with them the LeakyReLU's sign are the same expressions, in the same order, in the forward and the backward pass.
+// ---------------------------------------------------------------------------------------------------
+struct StylePtrs {
+  const float* gamma[MISEG_MAX_STYLES];
+  const float* beta[MISEG_MAX_STYLES];
+};
+struct StyleGradPtrs {
+  float* dgamma[MISEG_MAX_STYLES];
+  float* dbeta[MISEG_MAX_STYLES];
+};
+
+// A workgroup keeps its tile's per-channel pairs of sums in LDS in one of two layouts:
+//   gathered (gather_stat):  [col][2] with col = t * VEC + i                      the streaming kernels, the forward statistics of the fused backward
+//   totals (fused_totals):   sum k of element i of channel vector t at [(k * VEC + i) * tx_n + t], sum 0 shared by all norms of the kernel
+// LaneSums is one lane's view of either: element i has s[i * step] and q[i * step].
+struct LaneSums {
+  const double* s;
+  const double* q;
+  int step;
+};
+template <int VEC> __device__ __forceinline__ LaneSums gathered_sums(const double* sums, int tx) { return {sums + tx * VEC * 2, sums + tx * VEC * 2 + 1, 2}; }
+template <int VEC> __device__ __forceinline__ LaneSums total_sums(const double* tot, int k, int tx, int tx_n) { return {tot + tx, tot + k * VEC * tx_n + tx, tx_n}; }
+
+// per-lane coefficients of one norm: y = fma(x, sc, sh), xhat = (x - m) * rs
+template <int VEC> struct NormCoef {
+  float m[VEC], rs[VEC], sc[VEC], sh[VEC];
+  // first half: request the style's affine values (sc, sh hold gamma, beta until finish()).  The fused kernels issue this before the statistics
+  // are gathered, so that it is in flight with the rows.  Dead lanes of a ragged tile read the last channel vector (VEC divides C): one clamp
+  // per lane keeps the VEC addresses consecutive.
+  __device__ __forceinline__ void affine(const float* g, const float* b, int ch0, int C) {
+    const int ch = min(ch0, C - VEC);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) sc[i] = g ? g[ch + i] : 1.f;      // (one loop per row: each null test then guards VEC loads, not one)
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) sh[i] = b ? b[ch + i] : 0.f;
+  }
+  __device__ __forceinline__ void finish(const LaneSums& st, double invS, float eps) {
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+      mean_rstd(st.s[i * st.step], st.q[i * st.step], invS, eps, m[i], rs[i]);
+      sc[i] = rs[i] * sc[i];
+      sh[i] = sh[i] - m[i] * sc[i];
+    }
+  }
+  __device__ __forceinline__ void fill(const LaneSums& st, double invS, float eps, const float* g, const float* b, int ch0, int C) {
+    affine(g, b, ch0, C);
+    finish(st, invS, eps);
+  }
+  __device__ __forceinline__ void identity() {      // a residual that is added as it is
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) { m[i] = 0.f; rs[i] = 1.f; sc[i] = 1.f; sh[i] = 0.f; }
+  }
+};
+
+// what enters the activation: of one norm, and of the residual pair y = LeakyReLU(norm_a(xa) + norm_b(xb))
+template <int VEC> __device__ __forceinline__ float preact(const NormCoef<VEC>& c, int i, float x) { return fmaf(x, c.sc[i], c.sh[i]); }
+template <int VEC> __device__ __forceinline__ float pair_preact(const NormCoef<VEC>& ca, const NormCoef<VEC>& cb, int i, float xa, float xb) {
+  float o = preact(ca, i, xa);
+  o += preact(cb, i, xb);
+  return o;
+}
+
+// the LeakyReLU's backward on one row g of the incoming gradient: out = g where the activation's input was positive, g * slope elsewhere
+// (out may be g's own values).  sign(i) is anything with that input's sign: the stored output y (a residual that the kernel does not see
+// entered the activation) or the pre-activation recomputed from the inputs - one tensor less to read.  The caller chooses between the two
+// per ROW: inside the element loop that test was a scalar branch per element - 40 instructions per element, 3.8 us for 7 rows of a fused launch.
+template <int VEC, class GRow, class Sign> __device__ __forceinline__ void leaky_mask(float (&out)[VEC], const GRow& g, Sign sign, float slope) {
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) {
+    const float gi = g.get(i);
+    out[i] = sign(i) > 0.f ? gi : gi * slope;
+  }
+}
+
+// backward sums of one row: q += g * xhat (sum g itself is shared by the norms of a pair and added by the kernel)
+template <int VEC, class Row> __device__ __forceinline__ void bwd_sum_term(const NormCoef<VEC>& c, const float (&g)[VEC], const Row& x, float* q) {
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) q[i] = fmaf(g[i], (x.get(i) - c.m[i]) * c.rs[i], q[i]);
+}
+// the sample's mean of g, and of g * xhat, from the backward sums (a pair shares the first: both norms see the same g)
+template <int VEC> __device__ __forceinline__ void bwd_mean_g(const LaneSums& d, double invS, float (&a)[VEC]) {
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) a[i] = (float)(d.s[i * d.step] * invS);
+}
+template <int VEC> __device__ __forceinline__ void bwd_mean_gxhat(const LaneSums& d, double invS, float (&bq)[VEC]) {
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) bq[i] = (float)(d.q[i * d.step] * invS);
+}
+template <int VEC> __device__ __forceinline__ float input_grad(const NormCoef<VEC>& c, int i, float g, float x, float a, float bq) {
+  return c.sc[i] * (g - a - (x - c.m[i]) * c.rs[i] * bq);
+}
+
+// where column e of a workgroup's tile has its channel and its two sums, in the two layouts of LaneSums.  cv0: the tile's first channel vector;
+// k: which of the totals holds this norm's g * xhat
+template <int VEC> struct GatheredCols {
+  int cv0;
+  __device__ __forceinline__ void operator()(int e, int& ch, int& is, int& iq) const {
+    ch = cv0 * VEC + e;
+    is = 2 * e;
+    iq = 2 * e + 1;
+  }
+};
+template <int VEC> struct TotalCols {
+  int cv0, tx_n, k;
+  __device__ __forceinline__ void operator()(int e, int& ch, int& is, int& iq) const {
+    const int i = e / tx_n, t = e - i * tx_n;
+    ch = (cv0 + t) * VEC + i;
+    is = e;
+    iq = k * VEC * tx_n + e;
+  }
+};
+// the affine gradients of one (sample, channel tile) of one norm: dgamma += sum g * xhat, dbeta += sum g
+template <class Cols> __device__ __forceinline__ void add_affine_grads(const StyleGradPtrs& gp, int st, const double* sums, int ncols, int C, Cols cols) {
+  float* dg = gp.dgamma[st];
+  float* db = gp.dbeta[st];
+  for (int e = threadIdx.x; e < ncols; e += NORM_THREADS) {
+    int ch, is, iq;
+    cols(e, ch, is, iq);
+    if (ch < C) {
+      if (dg) atomicAdd(dg + ch, (float)sums[iq]);
+      if (db) atomicAdd(db + ch, (float)sums[is]);
+    }
+  }
+}
+
+// the row of a 1x1x1 convolution of a ONE-channel image (the stem block's shortcut), which is never stored: row[c] = round(r1x[row] * r1w[c]),
+// formed exactly as the rank-1 GEMM would have rounded it
+template <class T, int VEC> struct Rank1Row {
+  float w[VEC];
+  __device__ __forceinline__ void load(const T* r1w, int ch0, int C) {      // r1w == nullptr: no such shortcut
+    const int ch = min(ch0, C - VEC);      // (dead lanes: as NormCoef::affine)
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) w[i] = r1w ? to_f32(r1w[ch + i]) : 0.f;
+  }
+  __device__ __forceinline__ void form(float xs, RowVec<T, VEC>& row) const {
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) row.v[i] = to_f32(from_f32<T>(xs * w[i]));
+  }
+};
 
 // ---------------------------------------------------------------------------------------------------
 // stats: stat[b][c] += (sum x, sum x^2) over this block's rows      grid (chunks, B, ctiles)
@@ -149,13 +298,13 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_stats_kernel(const T* _
 #pragma unroll
       for (int u = 0; u < 4; ++u)
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) { s[i] += v[u].v[i]; q[i] = fmaf(v[u].v[i], v[u].v[i], q[i]); }
+        for (int i = 0; i < VEC; ++i) stat_term(v[u].v[i], s[i], q[i]);
     }
     for (; r < r1; r += ty_n) {
       RowVec<T, VEC> v;
       v.load(xb + (int64_t)r * ldx + c * VEC);
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) { s[i] += v.v[i]; q[i] = fmaf(v.v[i], v.v[i], q[i]); }
+      for (int i = 0; i < VEC; ++i) stat_term(v.v[i], s[i], q[i]);
     }
   }
   block_reduce_to_stat<VEC>(red, s, q, tx, ty, tx_n, ty_n, c0, C, stat + ((int64_t)(chunk % NORM_R) * gridDim.y + b) * C * 2);
@@ -217,19 +366,13 @@ __global__ void __launch_bounds__(NORM_THREADS) slabs_to_out_stats_kernel(const 
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
         o.v[i] = to_f32(from_f32<T>(a[i]));      // statistics of the stored (rounded) values, as miseg_instnorm_stats would read them
-        s[i] += o.v[i];
-        q[i] = fmaf(o.v[i], o.v[i], q[i]);
+        stat_term(o.v[i], s[i], q[i]);
       }
       o.store(y + row * ldy + c * VEC);
     }
   }
   if (stat) block_reduce_to_stat<VEC>(red, s, q, tx, ty, tx_n, ty_n, c0, C, stat + ((int64_t)(chunk % NORM_R) * gridDim.y + b) * C * 2);
 }
-
-struct StylePtrs {
-  const float* gamma[MISEG_MAX_STYLES];
-  const float* beta[MISEG_MAX_STYLES];
-};
 
 template <class T, int VEC>
 __global__ void __launch_bounds__(NORM_THREADS) instnorm_apply_kernel(const T* __restrict__ x, int64_t ldx, const T* __restrict__ res, int64_t ldres,
@@ -240,7 +383,7 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_apply_kernel(const T* _
   // rstat != nullptr: `res` is the RAW input of a second (shortcut) instance norm with its own statistics / affine rows and is
   // normalised on the fly: y = act(norm(x) + norm_r(res)) in one pass (UnetResBlock with a 1x1x1 shortcut conv, dynunet_block.py:118-124)
   // r1x != nullptr (with rstat, res == nullptr): that raw input is the 1x1x1 convolution of a ONE-channel image (the stem block) and is
-  // not stored at all: res[row][c] = round(r1x[row] * r1w[c]), formed here exactly as the rank-1 GEMM would have rounded it
+  // not stored at all (Rank1Row)
   extern __shared__ __attribute__((aligned(16))) double sums[];
   const int b = blockIdx.y, chunk = blockIdx.x;
   const int tx = threadIdx.x % tx_n, ty = threadIdx.x / tx_n;
@@ -251,55 +394,27 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_apply_kernel(const T* _
   if (ty >= ty_n || c >= cv) return;
   const int r0 = chunk * rpb, r1 = min(S, r0 + rpb);
   const int st = styles ? styles[b] : 0;
-  const float* g = sp.gamma[st];
-  const float* be = sp.beta[st];
   const int64_t boff = (int64_t)b * S;
   const double invS = 1.0 / S;
-  float sc[VEC], sh[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) {
-    const int ch = c * VEC + i;
-    float m, rs;
-    mean_rstd(sums + (tx * VEC + i) * 2, invS, eps, m, rs);
-    const float gg = g ? g[ch] : 1.f, bb = be ? be[ch] : 0.f;
-    sc[i] = rs * gg;
-    sh[i] = bb - m * sc[i];
-  }
-  float rsc[VEC], rsh[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) { rsc[i] = 1.f; rsh[i] = 0.f; }
-  if (rstat) {
-    const float* rg = rsp.gamma[st];
-    const float* rb = rsp.beta[st];
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) {
-      const int ch = c * VEC + i;
-      float m, rs;
-      mean_rstd(rsums + (tx * VEC + i) * 2, invS, eps, m, rs);
-      rsc[i] = rs * (rg ? rg[ch] : 1.f);
-      rsh[i] = (rb ? rb[ch] : 0.f) - m * rsc[i];
-    }
-  }
-  float r1wv[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) r1wv[i] = r1x ? to_f32(r1w[c * VEC + i]) : 0.f;
+  NormCoef<VEC> cx, cr;
+  cx.fill(gathered_sums<VEC>(sums, tx), invS, eps, sp.gamma[st], sp.beta[st], c * VEC, C);
+  if (rstat) cr.fill(gathered_sums<VEC>(rsums, tx), invS, eps, rsp.gamma[st], rsp.beta[st], c * VEC, C);
+  else cr.identity();
+  Rank1Row<T, VEC> rank1;
+  rank1.load(r1x ? r1w : nullptr, c * VEC, C);
 #pragma unroll 4
   for (int r = r0 + ty; r < r1; r += ty_n) {
     RowVec<T, VEC> v, o;
     v.load(x + (boff + r) * ldx + c * VEC);
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) o.v[i] = fmaf(v.v[i], sc[i], sh[i]);
     if (res || r1x) {
       RowVec<T, VEC> rr;
-      if (res) {
-        rr.load(res + (boff + r) * ldres + c * VEC);
-      } else {
-        const float xs = to_f32(r1x[(boff + r) * ldr1x]);
+      if (res) rr.load(res + (boff + r) * ldres + c * VEC);
+      else rank1.form(to_f32(r1x[(boff + r) * ldr1x]), rr);
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) rr.v[i] = to_f32(from_f32<T>(xs * r1wv[i]));
-      }
+      for (int i = 0; i < VEC; ++i) o.v[i] = pair_preact(cx, cr, i, v.v[i], rr.v[i]);
+    } else {
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) o.v[i] += fmaf(rr.v[i], rsc[i], rsh[i]);
+      for (int i = 0; i < VEC; ++i) o.v[i] = preact(cx, i, v.v[i]);
     }
     if (act == MISEG_ACT_LEAKY) {
 #pragma unroll
@@ -325,22 +440,12 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_bwd_reduce_kernel(const
   const int64_t boff = (int64_t)b * S;
   const int c = c0 + tx;
   gather_stat(sums, stat, (int64_t)gridDim.y * C * 2, b, C, c0 * VEC, tx_n * VEC);
-  float s[VEC], q[VEC], m[VEC], rs[VEC];
-  const double invS = 1.0 / S;
+  const int st = styles ? styles[b] : 0;
+  NormCoef<VEC> cf;      // (its sc / sh: only to recompute the activation's sign)
+  cf.fill(gathered_sums<VEC>(sums, tx), 1.0 / S, eps, sp.gamma[st], sp.beta[st], c * VEC, C);
+  float s[VEC], q[VEC];
 #pragma unroll
-  for (int i = 0; i < VEC; ++i) { s[i] = q[i] = 0.f; mean_rstd(sums + (tx * VEC + i) * 2, invS, eps, m[i], rs[i]); }
-  float zsc[VEC], zsh[VEC];     // the forward's scale / shift (instnorm_apply_kernel): only to recompute the activation's sign
-  {
-    const int st = styles ? styles[b] : 0;
-    const float* gz = sp.gamma[st];
-    const float* bz = sp.beta[st];
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) {
-      const int ch = c * VEC + i;
-      zsc[i] = rs[i] * ((gz && c < cv) ? gz[ch] : 1.f);
-      zsh[i] = ((bz && c < cv) ? bz[ch] : 0.f) - m[i] * zsc[i];
-    }
-  }
+  for (int i = 0; i < VEC; ++i) s[i] = q[i] = 0.f;
   __syncthreads();
   if (ty < ty_n && c < cv) {
 #pragma unroll 4
@@ -352,27 +457,18 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_bwd_reduce_kernel(const
         if (yact) {
           RowVec<T, VEC> yv;
           yv.load(yact + (boff + r) * ldy + c * VEC);
-#pragma unroll
-          for (int i = 0; i < VEC; ++i) g.v[i] = yv.v[i] > 0.f ? g.v[i] : g.v[i] * slope;
-        } else {   // no residual went into the activation: its sign is the sign of the forward's fma(x, sc, sh), recomputed from x
-#pragma unroll
-          for (int i = 0; i < VEC; ++i) g.v[i] = fmaf(xv.v[i], zsc[i], zsh[i]) > 0.f ? g.v[i] : g.v[i] * slope;
+          leaky_mask(g.v, g, [&](int i) { return yv.v[i]; }, slope);
+        } else {
+          leaky_mask(g.v, g, [&](int i) { return preact(cf, i, xv.v[i]); }, slope);
         }
       }
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) {
-        s[i] += g.v[i];
-        q[i] = fmaf(g.v[i], (xv.v[i] - m[i]) * rs[i], q[i]);
-      }
+      for (int i = 0; i < VEC; ++i) s[i] += g.v[i];
+      bwd_sum_term(cf, g.v, xv, q);
     }
   }
   block_reduce_to_stat<VEC>(red, s, q, tx, ty, tx_n, ty_n, c0, C, dstat + ((int64_t)(chunk % NORM_R) * gridDim.y + b) * C * 2);
 }
-
-struct StyleGradPtrs {
-  float* dgamma[MISEG_MAX_STYLES];
-  float* dbeta[MISEG_MAX_STYLES];
-};
 
 template <class T, int VEC>
 __global__ void __launch_bounds__(NORM_THREADS) instnorm_bwd_apply_kernel(const T* __restrict__ dy, int64_t lddy, const T* __restrict__ yact, int64_t ldy,
@@ -388,37 +484,17 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_bwd_apply_kernel(const 
   double* dsums = sums + 2 * tx_n * VEC;
   gather_stat(sums, stat, (int64_t)gridDim.y * C * 2, b, C, blockIdx.z * tx_n * VEC, tx_n * VEC);
   gather_stat(dsums, dstat, (int64_t)gridDim.y * C * 2, b, C, blockIdx.z * tx_n * VEC, tx_n * VEC);
-  if (chunk == 0) {   // the affine gradients of this (sample, channel tile): dgamma = sum dz*xhat, dbeta = sum dz
-    const int st0 = styles ? styles[b] : 0;
-    for (int e = threadIdx.x; e < tx_n * VEC; e += NORM_THREADS) {
-      const int ch = blockIdx.z * tx_n * VEC + e;
-      if (ch < C) {
-        if (gp.dgamma[st0]) atomicAdd(gp.dgamma[st0] + ch, (float)dsums[2 * e + 1]);
-        if (gp.dbeta[st0]) atomicAdd(gp.dbeta[st0] + ch, (float)dsums[2 * e]);
-      }
-    }
-  }
+  const int st = styles ? styles[b] : 0;
+  if (chunk == 0) add_affine_grads(gp, st, dsums, tx_n * VEC, C, GatheredCols<VEC>{(int)blockIdx.z * tx_n});
   if (ty >= ty_n || c >= cv) return;
   const int r0 = chunk * rpb, r1 = min(S, r0 + rpb);
-  const int st = styles ? styles[b] : 0;
-  const float* g = sp.gamma[st];
   const int64_t boff = (int64_t)b * S;
   const double invS = 1.0 / S;
-  float m[VEC], rs[VEC], sc[VEC], a[VEC], bq[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) {
-    const int ch = c * VEC + i;
-    mean_rstd(sums + (tx * VEC + i) * 2, invS, eps, m[i], rs[i]);
-    sc[i] = rs[i] * (g ? g[ch] : 1.f);
-    a[i] = (float)(dsums[(tx * VEC + i) * 2] * invS);
-    bq[i] = (float)(dsums[(tx * VEC + i) * 2 + 1] * invS);
-  }
-  float zsc[VEC], zsh[VEC];
-  {
-    const float* bz = sp.beta[st];
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) { zsc[i] = sc[i]; zsh[i] = (bz ? bz[c * VEC + i] : 0.f) - m[i] * sc[i]; }
-  }
+  NormCoef<VEC> cf;
+  cf.fill(gathered_sums<VEC>(sums, tx), invS, eps, sp.gamma[st], sp.beta[st], c * VEC, C);
+  float a[VEC], bq[VEC];
+  bwd_mean_g(gathered_sums<VEC>(dsums, tx), invS, a);
+  bwd_mean_gxhat(gathered_sums<VEC>(dsums, tx), invS, bq);
 #pragma unroll 4
   for (int r = r0 + ty; r < r1; r += ty_n) {
     RowVec<T, VEC> gv, xv, o;
@@ -428,19 +504,14 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_bwd_apply_kernel(const 
       if (yact) {
         RowVec<T, VEC> yv;
         yv.load(yact + (boff + r) * ldy + c * VEC);
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) gv.v[i] = yv.v[i] > 0.f ? gv.v[i] : gv.v[i] * slope;
+        leaky_mask(gv.v, gv, [&](int i) { return yv.v[i]; }, slope);
       } else {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) gv.v[i] = fmaf(xv.v[i], zsc[i], zsh[i]) > 0.f ? gv.v[i] : gv.v[i] * slope;
+        leaky_mask(gv.v, gv, [&](int i) { return preact(cf, i, xv.v[i]); }, slope);
       }
     }
     if (dres) gv.store(dres + (boff + r) * lddres + c * VEC);
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) {
-      const float xh = (xv.v[i] - m[i]) * rs[i];
-      o.v[i] = sc[i] * (gv.v[i] - a[i] - xh * bq[i]);
-    }
+    for (int i = 0; i < VEC; ++i) o.v[i] = input_grad(cf, i, gv.v[i], xv.v[i], a[i], bq[i]);
     if (gadd) {
       RowVec<T, VEC> ga;
       ga.load(gadd + (boff + r) * ldgadd + c * VEC);
@@ -451,52 +522,9 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_bwd_apply_kernel(const 
   }
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Small tensors (the deep stages: <= 512 rows per sample): statistics and normalisation in ONE launch, one workgroup per
-// (sample, tile of tx_n channel vectors) that walks all rows twice (the second pass hits L1/L2).  A launch costs ~4 us
-// on this chip whatever it does, so the 2 + 2 launches of forward + backward become 1 + 1.
-// ---------------------------------------------------------------------------------------------------
-// per-column totals of two per-thread vectors over the ty rows of the workgroup -> tot[(tx * VEC + i) * 2 + which] (double)
-template <int VEC>
-__device__ __forceinline__ void team_totals(float* red, double* tot, const float* s, const float* q, int tx, int ty, int tx_n, int ty_n) {
-  if (ty < ty_n) {
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) {
-      red[(ty * 2 + 0) * tx_n * VEC + tx * VEC + i] = s[i];
-      red[(ty * 2 + 1) * tx_n * VEC + tx * VEC + i] = q[i];
-    }
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < 2 * tx_n * VEC; e += NORM_THREADS) {
-    const int which = e / (tx_n * VEC), col = e % (tx_n * VEC);
-    double acc = 0.0;
-    for (int y = 0; y < ty_n; ++y) acc += (double)red[(y * 2 + which) * tx_n * VEC + col];
-    tot[col * 2 + which] = acc;
-  }
-  __syncthreads();
-}
-
 // ---- backward of y = LeakyReLU(norm_a(xa) + norm_b(xb)) (instnorm_apply_kernel with rstat): both norms see the same activation-
 // masked gradient g, so ONE reduction pass yields sum g, sum g*xhat_a, sum g*xhat_b and ONE apply pass writes both input gradients
 // (10 passes over the tensor instead of the 13 of two chained norm backwards, no `dres` tensor, two launches instead of four).
-// the pre-activation of the residual norm pair exactly as instnorm_apply_kernel forms it (same operations in the same order: the
-// recomputed sign must be the sign the forward pass saw)
-__device__ __forceinline__ float pair_preact(float xa, float sca, float sha, float xb, float scb, float shb) {
-  float o = fmaf(xa, sca, sha);
-  o += fmaf(xb, scb, shb);
-  return o;
-}
-__device__ __forceinline__ void pair_preact_coeffs(const StylePtrs& spa, const StylePtrs& spb, int st, int ch, float ma, float rsa, float mb, float rsb,
-                                                   float& sca, float& sha, float& scb, float& shb) {
-  const float* ga = spa.gamma[st];
-  const float* ba = spa.beta[st];
-  const float* gb = spb.gamma[st];
-  const float* bb = spb.beta[st];
-  sca = rsa * (ga ? ga[ch] : 1.f);
-  sha = (ba ? ba[ch] : 0.f) - ma * sca;
-  scb = rsb * (gb ? gb[ch] : 1.f);
-  shb = (bb ? bb[ch] : 0.f) - mb * scb;
-}
 
 template <class T, int VEC>
 __global__ void __launch_bounds__(NORM_THREADS) instnorm_pair_bwd_reduce_kernel(const T* __restrict__ dy, int64_t lddy, const T* __restrict__ yact, int64_t ldy,
@@ -506,9 +534,9 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_pair_bwd_reduce_kernel(
                                                                                 float slope, double* __restrict__ dstat_a, double* __restrict__ dstat_b,
                                                                                 const int32_t* __restrict__ styles, StylePtrs spa, StylePtrs spb,
                                                                                 const T* __restrict__ r1x, int64_t ldr1x, const T* __restrict__ r1w) {
-  // r1x != nullptr: xb is not stored - xb[row][c] = round(r1x[row] * r1w[c]) (see instnorm_apply_kernel)
-  // yact == nullptr: the LeakyReLU's sign is recomputed from the two inputs with the forward pass's own expression (instnorm_apply_kernel:
-  // fmaf(xa, sc_a, sh_a) + fmaf(xb, sc_b, sh_b), identical operands) - one tensor less to read in both passes
+  // r1x != nullptr: xb is not stored (Rank1Row)
+  // yact == nullptr: the LeakyReLU's sign is recomputed from the two inputs (pair_preact, as the forward formed it) - one tensor less to
+  // read in both passes
   extern __shared__ __attribute__((aligned(16))) float red[];
   double* sums_a = reinterpret_cast<double*>(red);   // prologue only; the reductions reuse the space after a barrier
   double* sums_b = sums_a + 2 * tx_n * VEC;
@@ -519,20 +547,16 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_pair_bwd_reduce_kernel(
   const int c = c0 + tx;
   gather_stat(sums_a, stat_a, (int64_t)gridDim.y * C * 2, b, C, c0 * VEC, tx_n * VEC);
   gather_stat(sums_b, stat_b, (int64_t)gridDim.y * C * 2, b, C, c0 * VEC, tx_n * VEC);
-  float s[VEC], qa[VEC], qb[VEC], ma[VEC], rsa[VEC], mb[VEC], rsb[VEC], zsa[VEC], zha[VEC], zsb[VEC], zhb[VEC];
   const double invS = 1.0 / S;
   const int st = styles ? styles[b] : 0;
+  NormCoef<VEC> ca, cb;
+  ca.fill(gathered_sums<VEC>(sums_a, tx), invS, eps, spa.gamma[st], spa.beta[st], c * VEC, C);
+  cb.fill(gathered_sums<VEC>(sums_b, tx), invS, eps, spb.gamma[st], spb.beta[st], c * VEC, C);
+  Rank1Row<T, VEC> rank1;
+  rank1.load(r1x ? r1w : nullptr, c * VEC, C);
+  float s[VEC], qa[VEC], qb[VEC];
 #pragma unroll
-  for (int i = 0; i < VEC; ++i) {
-    s[i] = qa[i] = qb[i] = 0.f;
-    mean_rstd(sums_a + (tx * VEC + i) * 2, invS, eps, ma[i], rsa[i]);
-    mean_rstd(sums_b + (tx * VEC + i) * 2, invS, eps, mb[i], rsb[i]);
-    const int ch = min(c * VEC + i, C - 1);
-    pair_preact_coeffs(spa, spb, st, ch, ma[i], rsa[i], mb[i], rsb[i], zsa[i], zha[i], zsb[i], zhb[i]);
-  }
-  float r1wv[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) r1wv[i] = r1x ? to_f32(r1w[min(c * VEC + i, C - 1)]) : 0.f;
+  for (int i = 0; i < VEC; ++i) s[i] = qa[i] = qb[i] = 0.f;
   __syncthreads();
   if (ty < ty_n && c < cv) {
 #pragma unroll 4
@@ -541,21 +565,15 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_pair_bwd_reduce_kernel(
       g.load(dy + (boff + r) * lddy + c * VEC);
       if (yact) yv.load(yact + (boff + r) * ldy + c * VEC);
       va.load(xa + (boff + r) * ldxa + c * VEC);
-      if (r1x) {
-        const float xs = to_f32(r1x[(boff + r) * ldr1x]);
+      if (r1x) rank1.form(to_f32(r1x[(boff + r) * ldr1x]), vb);
+      else vb.load(xb + (boff + r) * ldxb + c * VEC);
+      // (a select per element, not a branch per row: with the branch the compiler keeps two copies of the unrolled loop's registers - 138
+      // against 111 for fp32 lanes, one wave per SIMD less)
+      leaky_mask(g.v, g, [&](int i) { return yact ? yv.v[i] : pair_preact(ca, cb, i, va.v[i], vb.v[i]); }, slope);
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) vb.v[i] = to_f32(from_f32<T>(xs * r1wv[i]));
-      } else {
-        vb.load(xb + (boff + r) * ldxb + c * VEC);
-      }
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) {
-        const float pre = yact ? yv.v[i] : pair_preact(va.v[i], zsa[i], zha[i], vb.v[i], zsb[i], zhb[i]);
-        const float gi = pre > 0.f ? g.v[i] : g.v[i] * slope;
-        s[i] += gi;
-        qa[i] = fmaf(gi, (va.v[i] - ma[i]) * rsa[i], qa[i]);
-        qb[i] = fmaf(gi, (vb.v[i] - mb[i]) * rsb[i], qb[i]);
-      }
+      for (int i = 0; i < VEC; ++i) s[i] += g.v[i];
+      bwd_sum_term(ca, g.v, va, qa);
+      bwd_sum_term(cb, g.v, vb, qb);
     }
   }
   block_reduce_to_stat<VEC>(red, s, qa, tx, ty, tx_n, ty_n, c0, C, dstat_a + ((int64_t)(chunk % NORM_R) * gridDim.y + b) * C * 2);
@@ -589,16 +607,9 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_pair_bwd_apply_kernel(c
   gather_stat(da, dstat_a, (int64_t)gridDim.y * C * 2, b, C, blockIdx.z * tx_n * VEC, tx_n * VEC);
   gather_stat(db, dstat_b, (int64_t)gridDim.y * C * 2, b, C, blockIdx.z * tx_n * VEC, tx_n * VEC);
   const int st = styles ? styles[b] : 0;
-  if (chunk == 0) {   // the affine gradients of this (sample, channel tile), both norms
-    for (int e = threadIdx.x; e < tx_n * VEC; e += NORM_THREADS) {
-      const int ch = blockIdx.z * tx_n * VEC + e;
-      if (ch < C) {
-        if (gpa.dgamma[st]) atomicAdd(gpa.dgamma[st] + ch, (float)da[2 * e + 1]);
-        if (gpa.dbeta[st]) atomicAdd(gpa.dbeta[st] + ch, (float)da[2 * e]);
-        if (gpb.dgamma[st]) atomicAdd(gpb.dgamma[st] + ch, (float)db[2 * e + 1]);
-        if (gpb.dbeta[st]) atomicAdd(gpb.dbeta[st] + ch, (float)db[2 * e]);
-      }
-    }
+  if (chunk == 0) {
+    add_affine_grads(gpa, st, da, tx_n * VEC, C, GatheredCols<VEC>{(int)blockIdx.z * tx_n});
+    add_affine_grads(gpb, st, db, tx_n * VEC, C, GatheredCols<VEC>{(int)blockIdx.z * tx_n});
   }
   const bool live = ty < ty_n && c < cv;
   if (!live && !r1x) return;
@@ -609,56 +620,45 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_pair_bwd_apply_kernel(c
 #pragma unroll
   for (int i = 0; i < VEC; ++i) dwacc[i] = 0.0;
   if (live) {
-  const int r0 = chunk * rpb, r1 = min(S, r0 + rpb);
-  const float* ga = spa.gamma[st];
-  const float* gb = spb.gamma[st];
-  const int64_t boff = (int64_t)b * S;
-  const double invS = 1.0 / S;
-  float ma[VEC], rsa[VEC], sca[VEC], aa[VEC], bqa[VEC], mb[VEC], rsb[VEC], scb[VEC], bqb[VEC], zsa[VEC], zha[VEC], zsb[VEC], zhb[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) {
-    const int ch = c * VEC + i;
-    mean_rstd(sa + (tx * VEC + i) * 2, invS, eps, ma[i], rsa[i]);
-    mean_rstd(sb + (tx * VEC + i) * 2, invS, eps, mb[i], rsb[i]);
-    sca[i] = rsa[i] * (ga ? ga[ch] : 1.f);
-    scb[i] = rsb[i] * (gb ? gb[ch] : 1.f);
-    pair_preact_coeffs(spa, spb, st, ch, ma[i], rsa[i], mb[i], rsb[i], zsa[i], zha[i], zsb[i], zhb[i]);
-    aa[i] = (float)(da[(tx * VEC + i) * 2] * invS);          // mean of g: the same for both norms
-    bqa[i] = (float)(da[(tx * VEC + i) * 2 + 1] * invS);
-    bqb[i] = (float)(db[(tx * VEC + i) * 2 + 1] * invS);
-  }
-  float r1wv[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) r1wv[i] = r1x ? to_f32(r1w[c * VEC + i]) : 0.f;
+    const int r0 = chunk * rpb, r1 = min(S, r0 + rpb);
+    const int64_t boff = (int64_t)b * S;
+    const double invS = 1.0 / S;
+    NormCoef<VEC> ca, cb;
+    ca.fill(gathered_sums<VEC>(sa, tx), invS, eps, spa.gamma[st], spa.beta[st], c * VEC, C);
+    cb.fill(gathered_sums<VEC>(sb, tx), invS, eps, spb.gamma[st], spb.beta[st], c * VEC, C);
+    float aa[VEC], bqa[VEC], bqb[VEC];
+    bwd_mean_g(gathered_sums<VEC>(da, tx), invS, aa);
+    bwd_mean_gxhat(gathered_sums<VEC>(da, tx), invS, bqa);
+    bwd_mean_gxhat(gathered_sums<VEC>(db, tx), invS, bqb);
+    Rank1Row<T, VEC> rank1;
+    rank1.load(r1x ? r1w : nullptr, c * VEC, C);
 #pragma unroll 4
-  for (int r = r0 + ty; r < r1; r += ty_n) {
-    RowVec<T, VEC> g, yv, va, vb, oa, ob;
-    g.load(dy + (boff + r) * lddy + c * VEC);
-    if (yact) yv.load(yact + (boff + r) * ldy + c * VEC);
-    va.load(xa + (boff + r) * ldxa + c * VEC);
-    float xs = 0.f;
-    if (r1x) {
-      xs = to_f32(r1x[(boff + r) * ldr1x]);
+    for (int r = r0 + ty; r < r1; r += ty_n) {
+      RowVec<T, VEC> g, yv, va, vb, oa, ob;
+      g.load(dy + (boff + r) * lddy + c * VEC);
+      if (yact) yv.load(yact + (boff + r) * ldy + c * VEC);
+      va.load(xa + (boff + r) * ldxa + c * VEC);
+      float xs = 0.f;
+      if (r1x) {
+        xs = to_f32(r1x[(boff + r) * ldr1x]);
+        rank1.form(xs, vb);
+      } else {
+        vb.load(xb + (boff + r) * ldxb + c * VEC);
+      }
+      leaky_mask(g.v, g, [&](int i) { return yact ? yv.v[i] : pair_preact(ca, cb, i, va.v[i], vb.v[i]); }, slope);      // (as in the reduce kernel)
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) vb.v[i] = to_f32(from_f32<T>(xs * r1wv[i]));
-    } else {
-      vb.load(xb + (boff + r) * ldxb + c * VEC);
-    }
+      for (int i = 0; i < VEC; ++i) {
+        oa.v[i] = input_grad(ca, i, g.v[i], va.v[i], aa[i], bqa[i]);
+        ob.v[i] = input_grad(cb, i, g.v[i], vb.v[i], aa[i], bqb[i]);
+      }
+      oa.store(dxa + (boff + r) * lddxa + c * VEC);
+      if (r1x) {
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) {
-      const float pre = yact ? yv.v[i] : pair_preact(va.v[i], zsa[i], zha[i], vb.v[i], zsb[i], zhb[i]);
-      const float gi = pre > 0.f ? g.v[i] : g.v[i] * slope;
-      oa.v[i] = sca[i] * (gi - aa[i] - (va.v[i] - ma[i]) * rsa[i] * bqa[i]);
-      ob.v[i] = scb[i] * (gi - aa[i] - (vb.v[i] - mb[i]) * rsb[i] * bqb[i]);
+        for (int i = 0; i < VEC; ++i) dwacc[i] = fma((double)to_f32(from_f32<T>(ob.v[i])), (double)xs, dwacc[i]);
+      } else {
+        ob.store(dxb + (boff + r) * lddxb + c * VEC);
+      }
     }
-    oa.store(dxa + (boff + r) * lddxa + c * VEC);
-    if (r1x) {
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) dwacc[i] = fma((double)to_f32(from_f32<T>(ob.v[i])), (double)xs, dwacc[i]);
-    } else {
-      ob.store(dxb + (boff + r) * lddxb + c * VEC);
-    }
-  }
   }
   if (r1x) {     // every thread of the workgroup is here: column sums of dwacc over ty, one fp32 atomic per channel and workgroup
     float* redf = reinterpret_cast<float*>(sums);
@@ -687,8 +687,7 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_pair_bwd_apply_kernel(c
 // two launches with an fp64-atomic hand-off between them (8 + 8 us).
 // ---------------------------------------------------------------------------------------------------
 static constexpr int FUSED_MAXR = 8;
-static constexpr int NORM_FUSED_MAX_ROWS_HW = FUSED_MAXR * NORM_THREADS;
-#define NORM_FUSED_MAX_ROWS NORM_FUSED_MAX_ROWS_HW
+static constexpr int NORM_FUSED_MAX_ROWS = FUSED_MAXR * NORM_THREADS;
 
 template <class T, int VEC> struct PRow {       // one row's VEC channels of a lane as loaded (packed: VEC * sizeof(T) bytes, one load)
   typedef T raw_t __attribute__((ext_vector_type(VEC)));
@@ -758,6 +757,15 @@ template <int VEC> __device__ __forceinline__ void add_floats(const float* __res
     for (int j = 0; j < VEC; ++j) a[j] += p[j];
   }
 }
+// row = round(sum of this lane's elements of `nslabs` fp32 partial slabs): the output of a split convolution, formed by its consumer
+template <class T, int VEC> __device__ __forceinline__ void sum_slabs(PRow<T, VEC>& row, const float* __restrict__ p, int nslabs, int64_t slab_stride) {
+  float a[VEC];
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) a[i] = 0.f;
+  for (int k = 0; k < nslabs; ++k) add_floats<VEC>(p + k * slab_stride, a);
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) row.set(i, a[i]);
+}
 
 // SLABS: the input is still the `nslabs` fp32 partial slabs [B * S][C] of a split convolution (miseg_conv3_params.defer_slabs): a lane sums
 // its elements, rounds them to T - that IS the convolution's output, written to x for the backward pass - and goes on as below.  One launch
@@ -777,30 +785,15 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_fused_fwd_kernel(T* __r
   const int64_t boff = (int64_t)b * S;
   // (style id and affine rows are requested first: they are in flight with the rows)
   const int st = styles ? styles[b] : 0;
-  float gam[VEC], bet[VEC];
-  {
-    const float* g = sp.gamma[st];
-    const float* be = sp.beta[st];
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) {
-      const int ch = min(c * VEC + i, C - 1);
-      gam[i] = g ? g[ch] : 1.f;
-      bet[i] = be ? be[ch] : 0.f;
-    }
-  }
+  NormCoef<VEC> cf;
+  cf.affine(sp.gamma[st], sp.beta[st], c * VEC, C);
   PRow<T, VEC> xr[FUSED_MAXR], rr[FUSED_MAXR];
   if constexpr (SLABS) {
 #pragma unroll
     for (int u = 0; u < FUSED_MAXR; ++u) {
       const int r = ty + u * ty_n;
       if (live && r < S) {
-        float a[VEC];
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) a[i] = 0.f;
-        const float* sp0 = slabs + (boff + r) * (int64_t)C + c * VEC;
-        for (int k = 0; k < nslabs; ++k) add_floats<VEC>(sp0 + k * slab_stride, a);
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) xr[u].set(i, a[i]);
+        sum_slabs(xr[u], slabs + (boff + r) * (int64_t)C + c * VEC, nslabs, slab_stride);
         xr[u].store(x + (boff + r) * ldx + c * VEC);
       }
     }
@@ -825,7 +818,7 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_fused_fwd_kernel(T* __r
   for (int u = 0; u < FUSED_MAXR; ++u) {
     if (live && ty + u * ty_n < S) {
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) { const float v = xr[u].get(i); sq[i] += v; sq[VEC + i] = fmaf(v, v, sq[VEC + i]); }
+      for (int i = 0; i < VEC; ++i) stat_term(xr[u].get(i), sq[i], sq[VEC + i]);
     }
   }
   fused_totals<2 * VEC>(sq, red, tot, tx_n);      // tot[(which * VEC + i) * tx_n + tx]
@@ -836,23 +829,14 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_fused_fwd_kernel(T* __r
     if (ch < C) stat[((int64_t)b * C + ch) * 2 + which] = tot[e];
   }
   if (!live) return;
-  const double invS = 1.0 / S;
-  float sc[VEC], sh[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) {
-    const double two[2] = {tot[i * tx_n + tx], tot[(VEC + i) * tx_n + tx]};
-    float m, rs;
-    mean_rstd(two, invS, eps, m, rs);
-    sc[i] = rs * gam[i];
-    sh[i] = bet[i] - m * sc[i];
-  }
+  cf.finish(total_sums<VEC>(tot, 1, tx, tx_n), 1.0 / S, eps);
 #pragma unroll
   for (int u = 0; u < FUSED_MAXR; ++u) {
     const int r = ty + u * ty_n;
     if (r < S) {
       float v[VEC];
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) v[i] = fmaf(xr[u].get(i), sc[i], sh[i]);
+      for (int i = 0; i < VEC; ++i) v[i] = preact(cf, i, xr[u].get(i));
       if (res) {
 #pragma unroll
         for (int i = 0; i < VEC; ++i) v[i] += rr[u].get(i);
@@ -891,34 +875,16 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_fused_bwd_kernel(const 
   NSTAMP(0);
   // style id, affine rows and all row loads first: nothing below depends on them until the statistics have arrived as well
   const int st = styles ? styles[b] : 0;
-  float gam[VEC], bet[VEC];
-  {
-    const float* gz = sp.gamma[st];
-    const float* bz = sp.beta[st];
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) {
-      const int ch = min(c * VEC + i, C - 1);
-      gam[i] = gz ? gz[ch] : 1.f;
-      bet[i] = (bz && masked && !yact) ? bz[ch] : 0.f;
-    }
-  }
-  PRow<T, VEC> gr[FUSED_MAXR], xr[FUSED_MAXR], yr[FUSED_MAXR];
   const bool from_y = masked && yact;      // a residual entered the activation: its sign comes from the stored output
+  NormCoef<VEC> cf;
+  cf.affine(sp.gamma[st], (masked && !yact) ? sp.beta[st] : nullptr, c * VEC, C);      // (the shift: only to recompute the activation's sign)
+  PRow<T, VEC> gr[FUSED_MAXR], xr[FUSED_MAXR], yr[FUSED_MAXR];
 #pragma unroll
   for (int u = 0; u < FUSED_MAXR; ++u) {
     const int r = ty + u * ty_n;
     if (live && r < S) {
-      if constexpr (SLABS) {
-        float a[VEC];
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) a[i] = 0.f;
-        const float* sp0 = slabs + (boff + r) * (int64_t)C + c * VEC;
-        for (int k = 0; k < nslabs; ++k) add_floats<VEC>(sp0 + k * slab_stride, a);
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) gr[u].set(i, a[i]);
-      } else {
-        gr[u].load(dy + (boff + r) * lddy + c * VEC);
-      }
+      if constexpr (SLABS) sum_slabs(gr[u], slabs + (boff + r) * (int64_t)C + c * VEC, nslabs, slab_stride);
+      else gr[u].load(dy + (boff + r) * lddy + c * VEC);
       xr[u].load(x + (boff + r) * ldx + c * VEC);
       if (from_y) yr[u].load(yact + (boff + r) * ldy + c * VEC);
     }
@@ -927,24 +893,16 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_fused_bwd_kernel(const 
   gather_stat(sums, stat, (int64_t)gridDim.y * C * 2, b, C, blockIdx.x * tx_n * VEC, tx_n * VEC);
   NSTAMP(2);
   const double invS = 1.0 / S;
-  float m[VEC], rs[VEC], sc[VEC], zsh[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) {
-    mean_rstd(sums + (tx * VEC + i) * 2, invS, eps, m[i], rs[i]);
-    sc[i] = rs[i] * gam[i];
-    zsh[i] = bet[i] - m[i] * sc[i];      // the forward's shift: without a residual the activation's sign is the sign of fma(x, sc, zsh)
-  }
-  // the activation-masked gradient of row u; evaluated in both passes (three instructions per element) rather than stored.  The mode
-  // tests are per ROW: inside the element loop they were a scalar branch per element - 40 instructions per element, 3.8 us for 7 rows
+  cf.finish(gathered_sums<VEC>(sums, tx), invS, eps);
+  // the activation-masked gradient of row u; evaluated in both passes (three instructions per element) rather than stored
   auto gmask = [&](int u, float (&gm)[VEC]) {
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) gm[i] = gr[u].get(i);
     if (from_y) {
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) gm[i] = yr[u].get(i) > 0.f ? gm[i] : gm[i] * slope;
+      leaky_mask(gm, gr[u], [&](int i) { return yr[u].get(i); }, slope);
     } else if (masked) {
+      leaky_mask(gm, gr[u], [&](int i) { return preact(cf, i, xr[u].get(i)); }, slope);
+    } else {
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) gm[i] = fmaf(xr[u].get(i), sc[i], zsh[i]) > 0.f ? gm[i] : gm[i] * slope;
+      for (int i = 0; i < VEC; ++i) gm[i] = gr[u].get(i);
     }
   };
   float sq[2 * VEC];
@@ -956,31 +914,19 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_fused_bwd_kernel(const 
       float gm[VEC];
       gmask(u, gm);
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) {
-        sq[i] += gm[i];
-        sq[VEC + i] = fmaf(gm[i], (xr[u].get(i) - m[i]) * rs[i], sq[VEC + i]);
-      }
+      for (int i = 0; i < VEC; ++i) sq[i] += gm[i];
+      bwd_sum_term(cf, gm, xr[u], sq + VEC);
     }
   }
   NSTAMP(3);
   fused_totals<2 * VEC>(sq, red, tot, tx_n);
   NSTAMP(4);
-  for (int e = threadIdx.x; e < VEC * tx_n; e += NORM_THREADS) {      // the affine gradients of this (sample, channel tile)
-    const int i = e / tx_n, t = e - i * tx_n;
-    const int ch = (blockIdx.x * tx_n + t) * VEC + i;
-    if (ch < C) {
-      if (gp.dgamma[st]) atomicAdd(gp.dgamma[st] + ch, (float)tot[(VEC + i) * tx_n + t]);
-      if (gp.dbeta[st]) atomicAdd(gp.dbeta[st] + ch, (float)tot[i * tx_n + t]);
-    }
-  }
+  add_affine_grads(gp, st, tot, tx_n * VEC, C, TotalCols<VEC>{(int)blockIdx.x * tx_n, tx_n, 1});
   NSTAMP(5);
   if (!live) return;
   float a[VEC], bq[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) {
-    a[i] = (float)(tot[i * tx_n + tx] * invS);
-    bq[i] = (float)(tot[(VEC + i) * tx_n + tx] * invS);
-  }
+  bwd_mean_g(total_sums<VEC>(tot, 1, tx, tx_n), invS, a);
+  bwd_mean_gxhat(total_sums<VEC>(tot, 1, tx, tx_n), invS, bq);
 #pragma unroll
   for (int u = 0; u < FUSED_MAXR; ++u) {
     const int r = ty + u * ty_n;
@@ -994,7 +940,7 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_fused_bwd_kernel(const 
         dr.store(dres + (boff + r) * lddres + c * VEC);
       }
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) v[i] = sc[i] * (gm[i] - a[i] - (xr[u].get(i) - m[i]) * rs[i] * bq[i]);
+      for (int i = 0; i < VEC; ++i) v[i] = input_grad(cf, i, gm[i], xr[u].get(i), a[i], bq[i]);
       if (gadd) {
         PRow<T, VEC> ga;
         ga.load(gadd + (boff + r) * ldgadd + c * VEC);
@@ -1030,21 +976,9 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_pair_fused_bwd_kernel(c
   const int64_t boff = (int64_t)b * S;
   // style id + affine rows first (in flight with the rows)
   const int st = styles ? styles[b] : 0;
-  float gma[VEC], bta[VEC], gmb[VEC], btb[VEC];
-  {
-    const float* ga = spa.gamma[st];
-    const float* ba = spa.beta[st];
-    const float* gb = spb.gamma[st];
-    const float* bb = spb.beta[st];
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) {
-      const int ch = min(c * VEC + i, C - 1);
-      gma[i] = ga ? ga[ch] : 1.f;
-      bta[i] = ba ? ba[ch] : 0.f;
-      gmb[i] = gb ? gb[ch] : 1.f;
-      btb[i] = bb ? bb[ch] : 0.f;
-    }
-  }
+  NormCoef<VEC> ca, cb;
+  ca.affine(spa.gamma[st], spa.beta[st], c * VEC, C);
+  cb.affine(spb.gamma[st], spb.beta[st], c * VEC, C);
   PRow<T, VEC> gr[FUSED_MAXR], ar[FUSED_MAXR], br[FUSED_MAXR], yr[FUSED_MAXR];
 #pragma unroll
   for (int u = 0; u < FUSED_MAXR; ++u) {
@@ -1059,27 +993,11 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_pair_fused_bwd_kernel(c
   gather_stat(sums_a, stat_a, (int64_t)gridDim.y * C * 2, b, C, blockIdx.x * tx_n * VEC, tx_n * VEC);
   gather_stat(sums_b, stat_b, (int64_t)gridDim.y * C * 2, b, C, blockIdx.x * tx_n * VEC, tx_n * VEC);
   const double invS = 1.0 / S;
-  float ma[VEC], rsa[VEC], mb[VEC], rsb[VEC], sca[VEC], scb[VEC], zha[VEC], zhb[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) {
-    mean_rstd(sums_a + (tx * VEC + i) * 2, invS, eps, ma[i], rsa[i]);
-    mean_rstd(sums_b + (tx * VEC + i) * 2, invS, eps, mb[i], rsb[i]);
-    sca[i] = rsa[i] * gma[i];      // the expressions of pair_preact_coeffs (instnorm_apply_kernel's scale / shift): the recomputed sign
-    zha[i] = bta[i] - ma[i] * sca[i];      // must be the sign the forward pass saw
-    scb[i] = rsb[i] * gmb[i];
-    zhb[i] = btb[i] - mb[i] * scb[i];
-  }
-  auto gmask = [&](int u, float (&gm)[VEC]) {      // (mode test per row, not per element: see instnorm_fused_bwd_kernel)
-    if (yact) {
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) { const float g = gr[u].get(i); gm[i] = yr[u].get(i) > 0.f ? g : g * slope; }
-    } else {
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) {
-        const float g = gr[u].get(i);
-        gm[i] = pair_preact(ar[u].get(i), sca[i], zha[i], br[u].get(i), scb[i], zhb[i]) > 0.f ? g : g * slope;
-      }
-    }
+  ca.finish(gathered_sums<VEC>(sums_a, tx), invS, eps);
+  cb.finish(gathered_sums<VEC>(sums_b, tx), invS, eps);
+  auto gmask = [&](int u, float (&gm)[VEC]) {
+    if (yact) leaky_mask(gm, gr[u], [&](int i) { return yr[u].get(i); }, slope);
+    else leaky_mask(gm, gr[u], [&](int i) { return pair_preact(ca, cb, i, ar[u].get(i), br[u].get(i)); }, slope);
   };
   float sq[3 * VEC];
 #pragma unroll
@@ -1090,32 +1008,19 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_pair_fused_bwd_kernel(c
       float gm[VEC];
       gmask(u, gm);
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) {
-        sq[i] += gm[i];
-        sq[VEC + i] = fmaf(gm[i], (ar[u].get(i) - ma[i]) * rsa[i], sq[VEC + i]);
-        sq[2 * VEC + i] = fmaf(gm[i], (br[u].get(i) - mb[i]) * rsb[i], sq[2 * VEC + i]);
-      }
+      for (int i = 0; i < VEC; ++i) sq[i] += gm[i];
+      bwd_sum_term(ca, gm, ar[u], sq + VEC);
+      bwd_sum_term(cb, gm, br[u], sq + 2 * VEC);
     }
   }
   fused_totals<3 * VEC>(sq, red, tot, tx_n);
-  for (int e = threadIdx.x; e < VEC * tx_n; e += NORM_THREADS) {
-    const int i = e / tx_n, t = e - i * tx_n;
-    const int ch = (blockIdx.x * tx_n + t) * VEC + i;
-    if (ch < C) {
-      if (gpa.dgamma[st]) atomicAdd(gpa.dgamma[st] + ch, (float)tot[(VEC + i) * tx_n + t]);
-      if (gpa.dbeta[st]) atomicAdd(gpa.dbeta[st] + ch, (float)tot[i * tx_n + t]);
-      if (gpb.dgamma[st]) atomicAdd(gpb.dgamma[st] + ch, (float)tot[(2 * VEC + i) * tx_n + t]);
-      if (gpb.dbeta[st]) atomicAdd(gpb.dbeta[st] + ch, (float)tot[i * tx_n + t]);
-    }
-  }
+  add_affine_grads(gpa, st, tot, tx_n * VEC, C, TotalCols<VEC>{(int)blockIdx.x * tx_n, tx_n, 1});
+  add_affine_grads(gpb, st, tot, tx_n * VEC, C, TotalCols<VEC>{(int)blockIdx.x * tx_n, tx_n, 2});
   if (!live) return;
   float aa[VEC], bqa[VEC], bqb[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) {
-    aa[i] = (float)(tot[i * tx_n + tx] * invS);
-    bqa[i] = (float)(tot[(VEC + i) * tx_n + tx] * invS);
-    bqb[i] = (float)(tot[(2 * VEC + i) * tx_n + tx] * invS);
-  }
+  bwd_mean_g(total_sums<VEC>(tot, 1, tx, tx_n), invS, aa);
+  bwd_mean_gxhat(total_sums<VEC>(tot, 1, tx, tx_n), invS, bqa);
+  bwd_mean_gxhat(total_sums<VEC>(tot, 2, tx, tx_n), invS, bqb);
 #pragma unroll
   for (int u = 0; u < FUSED_MAXR; ++u) {
     const int r = ty + u * ty_n;
@@ -1125,8 +1030,8 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_pair_fused_bwd_kernel(c
       gmask(u, gm);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
-        oa.set(i, sca[i] * (gm[i] - aa[i] - (ar[u].get(i) - ma[i]) * rsa[i] * bqa[i]));
-        ob.set(i, scb[i] * (gm[i] - aa[i] - (br[u].get(i) - mb[i]) * rsb[i] * bqb[i]));
+        oa.set(i, input_grad(ca, i, gm[i], ar[u].get(i), aa[i], bqa[i]));
+        ob.set(i, input_grad(cb, i, gm[i], br[u].get(i), aa[i], bqb[i]));
       }
       oa.store(dxa + (boff + r) * lddxa + c * VEC);
       ob.store(dxb + (boff + r) * lddxb + c * VEC);
@@ -1158,17 +1063,48 @@ static FusedGeom fused_geom(int S, int C, bool vec_ok, int vecN) {
   g.cv = C / g.vec;
   return g;
 }
-// launch `KERNEL<T, vec>` for the lane width the geometry chose (bf16: 8 / 4 / 2 / 1 channels, fp32: 4 / 2 / 1)
-#define FUSED_DISPATCH(GEOM, LAUNCH)                          \
-  do {                                                        \
-    if ((GEOM).vec == 8) { if constexpr (V >= 8) { LAUNCH(8); } } \
-    else if ((GEOM).vec == 4) { if constexpr (V >= 4) { LAUNCH(4); } } \
-    else if ((GEOM).vec == 2) { LAUNCH(2); }                  \
-    else { LAUNCH(1); }                                       \
-  } while (0)
+
+// calls f(std::integral_constant<int, vec>) for the lane width the geometry chose, so that every kernel's launch is written once.  HALVINGS:
+// the widths of the register-resident kernels (bf16: 8 / 4 / 2 / 1 channels, fp32: 4 / 2 / 1); otherwise V or 1 (the streaming kernels).
+template <int V, bool HALVINGS, class F> static void for_lane_width(int vec, F&& f) {
+  if constexpr (V == 1) f(std::integral_constant<int, 1>{});
+  else if (vec == V) f(std::integral_constant<int, V>{});
+  else for_lane_width<HALVINGS ? V / 2 : 1, HALVINGS>(vec, f);
+}
+// the same for a kernel's bool template parameter
+template <class F> static void for_flag(bool on, F&& f) {
+  if (on) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// LDS bytes of the three kinds of launch; nstat: how many (sum, sum of squares) sets the prologue gathers
+static size_t reduce_smem(const NormGeom& g, int nstat) {      // block_reduce_to_stat's floats, which reuse the prologue's doubles: the larger of the two
+  const size_t red = (size_t)g.ty * 2 * g.tx * g.vec * sizeof(float), pro = (size_t)nstat * 2 * g.tx * g.vec * sizeof(double);
+  return red > pro ? red : pro;
+}
+static size_t apply_smem(const NormGeom& g, int nstat, bool rank1 = false) {      // rank1: no smaller than the floats of the weight gradient's reduction
+  const size_t pro = (size_t)nstat * 2 * g.tx * g.vec * sizeof(double), r1 = (size_t)NORM_THREADS * g.vec * sizeof(float);
+  return (rank1 && pro < r1) ? r1 : pro;
+}
 static size_t fused_smem(const FusedGeom& g, int nsum, int nstat) {      // red + tot + gathered statistics
   return (size_t)(NORM_THREADS / 16) * nsum * g.vec * g.tx * sizeof(float) + (size_t)nsum * g.vec * g.tx * sizeof(double) +
          (size_t)nstat * 2 * g.vec * g.tx * sizeof(double);
+}
+
+template <class P> static void fill_style_rows(P* (&dst)[MISEG_MAX_STYLES], P* const (&src)[MISEG_MAX_STYLES], int num_styles) {
+  for (int s = 0; s < MISEG_MAX_STYLES; ++s) dst[s] = s < num_styles ? src[s] : nullptr;
+}
+static StylePtrs style_ptrs(const float* const (&gamma)[MISEG_MAX_STYLES], const float* const (&beta)[MISEG_MAX_STYLES], int num_styles) {
+  StylePtrs sp;
+  fill_style_rows(sp.gamma, gamma, num_styles);
+  fill_style_rows(sp.beta, beta, num_styles);
+  return sp;
+}
+static StyleGradPtrs style_grad_ptrs(float* const (&dgamma)[MISEG_MAX_STYLES], float* const (&dbeta)[MISEG_MAX_STYLES], int num_styles) {
+  StyleGradPtrs gp;
+  fill_style_rows(gp.dgamma, dgamma, num_styles);
+  fill_style_rows(gp.dbeta, dbeta, num_styles);
+  return gp;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1273,12 +1209,11 @@ int slabs_to_out_stats(const float* slabs, int nslabs, void* y, int64_t ldy, con
     g.rpb = g.ty * (per < 1 ? 1 : per > 8 ? 8 : per);
     g.chunks = cdiv(S, g.rpb);
     dim3 grid(g.chunks, B, g.ctiles);
-    const size_t sh = (size_t)g.ty * 2 * g.tx * g.vec * sizeof(float);
     const int64_t stride = (int64_t)B * S * C;
-    if (g.vec == 1)
-      slabs_to_out_stats_kernel<T, 1><<<grid, NORM_THREADS, sh, stream>>>(slabs, nslabs, stride, (T*)y, ldy, (const T*)res, ldres, S, C, g.cv, g.tx, g.ty, g.rpb, stat);
-    else
-      slabs_to_out_stats_kernel<T, V><<<grid, NORM_THREADS, sh, stream>>>(slabs, nslabs, stride, (T*)y, ldy, (const T*)res, ldres, S, C, g.cv, g.tx, g.ty, g.rpb, stat);
+    for_lane_width<V, false>(g.vec, [&](auto w) {
+      slabs_to_out_stats_kernel<T, decltype(w)::value><<<grid, NORM_THREADS, reduce_smem(g, 0), stream>>>(slabs, nslabs, stride, (T*)y, ldy, (const T*)res, ldres, S, C,
+                                                                                                        g.cv, g.tx, g.ty, g.rpb, stat);
+    });
     MISEG_LAUNCH_CHECK("slabs_to_out_stats");
     return MISEG_OK;
   });
@@ -1301,9 +1236,10 @@ extern "C" int miseg_instnorm_stats(const miseg_instnorm_stats_params* p, miseg_
     constexpr int V = Vec16<T>::N;
     NormGeom g = norm_geom(p->S, p->C, aligned16(p->x) && p->ldx % V == 0, V, 256);
     dim3 grid(g.chunks, p->B, g.ctiles);
-    size_t sh = (size_t)g.ty * 2 * g.tx * g.vec * sizeof(float);
-    if (g.vec == 1) instnorm_stats_kernel<T, 1><<<grid, NORM_THREADS, sh, stream>>>((const T*)p->x, p->ldx, p->S, p->C, g.cv, g.tx, g.ty, g.rpb, (double*)p->stat);
-    else instnorm_stats_kernel<T, V><<<grid, NORM_THREADS, sh, stream>>>((const T*)p->x, p->ldx, p->S, p->C, g.cv, g.tx, g.ty, g.rpb, (double*)p->stat);
+    for_lane_width<V, false>(g.vec, [&](auto w) {
+      instnorm_stats_kernel<T, decltype(w)::value><<<grid, NORM_THREADS, reduce_smem(g, 0), stream>>>((const T*)p->x, p->ldx, p->S, p->C, g.cv, g.tx, g.ty, g.rpb,
+                                                                                                    (double*)p->stat);
+    });
     MISEG_LAUNCH_CHECK("instnorm_stats");
     return MISEG_OK;
   });
@@ -1322,23 +1258,14 @@ extern "C" int miseg_instnorm_apply(const miseg_instnorm_apply_params* p, miseg_
     const int64_t ldor = p->ldx | p->ldy | (p->res ? p->ldres : 0);
     const bool al = aligned16(p->x) && aligned16(p->y) && (!p->res || aligned16(p->res)) && ldor % V == 0;
     NormGeom g = norm_geom(p->S, p->C, al, V);
-    StylePtrs sp;
-    for (int s = 0; s < MISEG_MAX_STYLES; ++s) { sp.gamma[s] = s < p->num_styles ? p->gamma[s] : nullptr; sp.beta[s] = s < p->num_styles ? p->beta[s] : nullptr; }
-    StylePtrs rsp;
-    for (int s = 0; s < MISEG_MAX_STYLES; ++s) {
-      rsp.gamma[s] = (p->res_stat && s < p->num_styles) ? p->res_gamma[s] : nullptr;
-      rsp.beta[s] = (p->res_stat && s < p->num_styles) ? p->res_beta[s] : nullptr;
-    }
+    const StylePtrs sp = style_ptrs(p->gamma, p->beta, p->num_styles);
+    const StylePtrs rsp = style_ptrs(p->res_gamma, p->res_beta, p->res_stat ? p->num_styles : 0);
     dim3 grid(g.chunks, p->B, g.ctiles);
-    const size_t shd = (size_t)4 * g.tx * g.vec * sizeof(double);
-    if (g.vec == 1)
-      instnorm_apply_kernel<T, 1><<<grid, NORM_THREADS, shd, stream>>>((const T*)p->x, p->ldx, (const T*)p->res, p->ldres, (T*)p->y, p->ldy, p->S, p->C, g.cv, g.tx,
-                                                                      g.ty, g.rpb, (const double*)p->stat, p->eps, p->styles, sp, p->act, p->slope,
-                                                                      (const double*)p->res_stat, rsp, (const T*)p->r1x, p->ldr1x, (const T*)p->r1w);
-    else
-      instnorm_apply_kernel<T, V><<<grid, NORM_THREADS, shd, stream>>>((const T*)p->x, p->ldx, (const T*)p->res, p->ldres, (T*)p->y, p->ldy, p->S, p->C, g.cv, g.tx,
-                                                                      g.ty, g.rpb, (const double*)p->stat, p->eps, p->styles, sp, p->act, p->slope,
-                                                                      (const double*)p->res_stat, rsp, (const T*)p->r1x, p->ldr1x, (const T*)p->r1w);
+    for_lane_width<V, false>(g.vec, [&](auto w) {
+      instnorm_apply_kernel<T, decltype(w)::value><<<grid, NORM_THREADS, apply_smem(g, 2), stream>>>(
+          (const T*)p->x, p->ldx, (const T*)p->res, p->ldres, (T*)p->y, p->ldy, p->S, p->C, g.cv, g.tx, g.ty, g.rpb, (const double*)p->stat, p->eps, p->styles, sp,
+          p->act, p->slope, (const double*)p->res_stat, rsp, (const T*)p->r1x, p->ldr1x, (const T*)p->r1w);
+    });
     MISEG_LAUNCH_CHECK("instnorm_apply");
     return MISEG_OK;
   });
@@ -1369,20 +1296,15 @@ static int instnorm_fwd_impl(const miseg_instnorm_apply_params* p, const float* 
     const int64_t ldor = p->ldx | p->ldy | (p->res ? p->ldres : 0) | (slabs ? p->C : 0);
     const bool al = aligned16(p->x) && aligned16(p->y) && (!p->res || aligned16(p->res)) && ldor % V == 0 && (!slabs || (aligned16(slabs) && slab_stride % 4 == 0));
     const FusedGeom g = fused_geom(p->S, p->C, al, V);
-    StylePtrs sp;
-    for (int s = 0; s < MISEG_MAX_STYLES; ++s) { sp.gamma[s] = s < p->num_styles ? p->gamma[s] : nullptr; sp.beta[s] = s < p->num_styles ? p->beta[s] : nullptr; }
+    const StylePtrs sp = style_ptrs(p->gamma, p->beta, p->num_styles);
     dim3 grid(cdiv(g.cv, g.tx), p->B);
-    const size_t sh = fused_smem(g, 2, 0);
-#define FWD_LAUNCH(VV)                                                                                                                                       \
-    if (slabs)                                                                                                                                               \
-      instnorm_fused_fwd_kernel<T, VV, true><<<grid, NORM_THREADS, sh, stream>>>((T*)p->x, p->ldx, (const T*)p->res, p->ldres, (T*)p->y, p->ldy, p->S, p->C, g.cv, \
-                                                                                 g.tx, g.ty, (double*)p->stat, p->eps, p->styles, sp, p->act, p->slope, slabs,       \
-                                                                                 nslabs, slab_stride);                                                               \
-    else                                                                                                                                                     \
-      instnorm_fused_fwd_kernel<T, VV, false><<<grid, NORM_THREADS, sh, stream>>>((T*)p->x, p->ldx, (const T*)p->res, p->ldres, (T*)p->y, p->ldy, p->S, p->C, g.cv, \
-                                                                                  g.tx, g.ty, (double*)p->stat, p->eps, p->styles, sp, p->act, p->slope)
-    FUSED_DISPATCH(g, FWD_LAUNCH);
-#undef FWD_LAUNCH
+    for_lane_width<V, true>(g.vec, [&](auto w) {
+      for_flag(slabs != nullptr, [&](auto from_slabs) {
+        instnorm_fused_fwd_kernel<T, decltype(w)::value, decltype(from_slabs)::value><<<grid, NORM_THREADS, fused_smem(g, 2, 0), stream>>>(
+            (T*)p->x, p->ldx, (const T*)p->res, p->ldres, (T*)p->y, p->ldy, p->S, p->C, g.cv, g.tx, g.ty, (double*)p->stat, p->eps, p->styles, sp, p->act, p->slope,
+            slabs, nslabs, slab_stride);
+      });
+    });
     MISEG_LAUNCH_CHECK("instnorm_fwd");
     return MISEG_OK;
   });
@@ -1414,49 +1336,34 @@ static int instnorm_bwd_impl(const miseg_instnorm_bwd_params* p, const float* sl
     const bool al = (slabs ? aligned16(slabs) && slab_stride % 4 == 0 : aligned16(p->dy)) && aligned16(p->x) && aligned16(p->dx) && (!p->act || aligned16(p->y)) &&
                     (!p->dres || aligned16(p->dres)) && (!p->gadd || aligned16(p->gadd)) && ldor % V == 0;
     NormGeom g = norm_geom(p->S, p->C, al, V);
-    StylePtrs sp;
-    StyleGradPtrs gp;
-    for (int s = 0; s < MISEG_MAX_STYLES; ++s) {
-      sp.gamma[s] = s < p->num_styles ? p->gamma[s] : nullptr;
-      sp.beta[s] = s < p->num_styles ? p->beta[s] : nullptr;
-      gp.dgamma[s] = s < p->num_styles ? p->dgamma[s] : nullptr;
-      gp.dbeta[s] = s < p->num_styles ? p->dbeta[s] : nullptr;
-    }
+    const StylePtrs sp = style_ptrs(p->gamma, p->beta, p->num_styles);
+    const StyleGradPtrs gp = style_grad_ptrs(p->dgamma, p->dbeta, p->num_styles);
     if (p->S <= NORM_FUSED_MAX_ROWS && !apply_only) {
       const FusedGeom f = fused_geom(p->S, p->C, al, V);
       dim3 fgrid(cdiv(f.cv, f.tx), p->B);
-      const size_t fsh = fused_smem(f, 2, 1);
-#define FBWD_LAUNCH(VV)                                                                                                                                      \
-      if (slabs)                                                                                                                                             \
-        instnorm_fused_bwd_kernel<T, VV, true><<<fgrid, NORM_THREADS, fsh, stream>>>((const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->x, p->ldx,         \
-                                                                                     (T*)p->dx, p->lddx, (T*)p->dres, p->lddres, p->S, p->C, f.cv, f.tx, f.ty,        \
-                                                                                     (const double*)p->stat, p->eps, p->styles, sp, gp, p->act, p->slope,             \
-                                                                                     (const T*)p->gadd, p->ldgadd, slabs, nslabs, slab_stride);                      \
-      else                                                                                                                                                   \
-        instnorm_fused_bwd_kernel<T, VV, false><<<fgrid, NORM_THREADS, fsh, stream>>>((const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->x, p->ldx,        \
-                                                                                      (T*)p->dx, p->lddx, (T*)p->dres, p->lddres, p->S, p->C, f.cv, f.tx, f.ty,       \
-                                                                                      (const double*)p->stat, p->eps, p->styles, sp, gp, p->act, p->slope,            \
-                                                                                      (const T*)p->gadd, p->ldgadd)
-      FUSED_DISPATCH(f, FBWD_LAUNCH);
-#undef FBWD_LAUNCH
+      for_lane_width<V, true>(f.vec, [&](auto w) {
+        for_flag(slabs != nullptr, [&](auto from_slabs) {
+          instnorm_fused_bwd_kernel<T, decltype(w)::value, decltype(from_slabs)::value><<<fgrid, NORM_THREADS, fused_smem(f, 2, 1), stream>>>(
+              (const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->x, p->ldx, (T*)p->dx, p->lddx, (T*)p->dres, p->lddres, p->S, p->C, f.cv, f.tx, f.ty,
+              (const double*)p->stat, p->eps, p->styles, sp, gp, p->act, p->slope, (const T*)p->gadd, p->ldgadd, slabs, nslabs, slab_stride);
+        });
+      });
       MISEG_LAUNCH_CHECK("instnorm_bwd");
       return MISEG_OK;
     }
     dim3 grid(g.chunks, p->B, g.ctiles);
-    size_t sh = (size_t)g.ty * 2 * g.tx * g.vec * sizeof(float);
-    if (sh < (size_t)2 * g.tx * g.vec * sizeof(double)) sh = (size_t)2 * g.tx * g.vec * sizeof(double);
-    const size_t shd = (size_t)4 * g.tx * g.vec * sizeof(double);
     const double* stat = (const double*)p->stat;
     double* dstat = (double*)p->dstat;
-#define BWD_LAUNCH(VV)                                                                                                                                          \
-    if (!apply_only)                                                                                                                                           \
-      instnorm_bwd_reduce_kernel<T, VV><<<grid, NORM_THREADS, sh, stream>>>((const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->x, p->ldx, p->S, p->C,  \
-                                                                             g.cv, g.tx, g.ty, g.rpb, stat, p->eps, p->act, p->slope, dstat, p->styles, sp);             \
-    instnorm_bwd_apply_kernel<T, VV><<<grid, NORM_THREADS, shd, stream>>>((const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->x, p->ldx, (T*)p->dx,    \
-                                                                         p->lddx, (T*)p->dres, p->lddres, p->S, p->C, g.cv, g.tx, g.ty, g.rpb, stat, p->eps, p->styles, \
-                                                                         sp, p->act, p->slope, dstat, gp, (const T*)p->gadd, p->ldgadd);
-    if (g.vec == 1) { BWD_LAUNCH(1) } else { BWD_LAUNCH(V) }
-#undef BWD_LAUNCH
+    for_lane_width<V, false>(g.vec, [&](auto w) {
+      constexpr int W = decltype(w)::value;
+      if (!apply_only)
+        instnorm_bwd_reduce_kernel<T, W><<<grid, NORM_THREADS, reduce_smem(g, 1), stream>>>((const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->x, p->ldx, p->S,
+                                                                                           p->C, g.cv, g.tx, g.ty, g.rpb, stat, p->eps, p->act, p->slope, dstat, p->styles,
+                                                                                           sp);
+      instnorm_bwd_apply_kernel<T, W><<<grid, NORM_THREADS, apply_smem(g, 2), stream>>>((const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->x, p->ldx, (T*)p->dx,
+                                                                                       p->lddx, (T*)p->dres, p->lddres, p->S, p->C, g.cv, g.tx, g.ty, g.rpb, stat, p->eps,
+                                                                                       p->styles, sp, p->act, p->slope, dstat, gp, (const T*)p->gadd, p->ldgadd);
+    });
     MISEG_LAUNCH_CHECK("instnorm_bwd");
     return MISEG_OK;
   });
@@ -1483,17 +1390,13 @@ extern "C" int miseg_instnorm_bwd_reduce(const miseg_instnorm_bwd_params* p, mis
     constexpr int V = Vec16<T>::N;
     const bool al = aligned16(p->dy) && aligned16(p->x) && (p->lddy | p->ldx) % V == 0;
     NormGeom g = norm_geom(p->S, p->C, al, V);
-    StylePtrs sp;
-    for (int s = 0; s < MISEG_MAX_STYLES; ++s) { sp.gamma[s] = nullptr; sp.beta[s] = nullptr; }
+    const StylePtrs sp = style_ptrs(p->gamma, p->beta, 0);      // no activation: nothing reads the affine rows
     dim3 grid(g.chunks, p->B, g.ctiles);
-    size_t sh = (size_t)g.ty * 2 * g.tx * g.vec * sizeof(float);
-    if (sh < (size_t)2 * g.tx * g.vec * sizeof(double)) sh = (size_t)2 * g.tx * g.vec * sizeof(double);
-    if (g.vec == 1)
-      instnorm_bwd_reduce_kernel<T, 1><<<grid, NORM_THREADS, sh, stream>>>((const T*)p->dy, p->lddy, nullptr, 0, (const T*)p->x, p->ldx, p->S, p->C, g.cv, g.tx, g.ty,
-                                                                           g.rpb, (const double*)p->stat, p->eps, MISEG_ACT_NONE, 0.f, (double*)p->dstat, nullptr, sp);
-    else
-      instnorm_bwd_reduce_kernel<T, V><<<grid, NORM_THREADS, sh, stream>>>((const T*)p->dy, p->lddy, nullptr, 0, (const T*)p->x, p->ldx, p->S, p->C, g.cv, g.tx, g.ty,
-                                                                           g.rpb, (const double*)p->stat, p->eps, MISEG_ACT_NONE, 0.f, (double*)p->dstat, nullptr, sp);
+    for_lane_width<V, false>(g.vec, [&](auto w) {
+      instnorm_bwd_reduce_kernel<T, decltype(w)::value><<<grid, NORM_THREADS, reduce_smem(g, 1), stream>>>(
+          (const T*)p->dy, p->lddy, nullptr, 0, (const T*)p->x, p->ldx, p->S, p->C, g.cv, g.tx, g.ty, g.rpb, (const double*)p->stat, p->eps, MISEG_ACT_NONE, 0.f,
+          (double*)p->dstat, nullptr, sp);
+    });
     MISEG_LAUNCH_CHECK("instnorm_bwd_reduce");
     return MISEG_OK;
   });
@@ -1512,48 +1415,31 @@ extern "C" int miseg_instnorm_pair_bwd(const miseg_instnorm_pair_bwd_params* p, 
     const bool al = aligned16(p->dy) && (!p->y || aligned16(p->y)) && aligned16(p->xa) && (!p->xb || (aligned16(p->xb) && aligned16(p->dxb))) && aligned16(p->dxa) &&
                     ldor % V == 0 && (!p->r1x || p->C % V == 0);
     NormGeom g = norm_geom(p->S, p->C, al, V);
-    StylePtrs spa, spb;
-    StyleGradPtrs gpa, gpb;
-    for (int s = 0; s < MISEG_MAX_STYLES; ++s) {
-      const bool on = s < p->num_styles;
-      spa.gamma[s] = on ? p->gamma_a[s] : nullptr; spa.beta[s] = on ? p->beta_a[s] : nullptr;      // betas: only read when y is absent
-      spb.gamma[s] = on ? p->gamma_b[s] : nullptr; spb.beta[s] = on ? p->beta_b[s] : nullptr;
-      gpa.dgamma[s] = on ? p->dgamma_a[s] : nullptr; gpa.dbeta[s] = on ? p->dbeta_a[s] : nullptr;
-      gpb.dgamma[s] = on ? p->dgamma_b[s] : nullptr; gpb.dbeta[s] = on ? p->dbeta_b[s] : nullptr;
-    }
+    const StylePtrs spa = style_ptrs(p->gamma_a, p->beta_a, p->num_styles), spb = style_ptrs(p->gamma_b, p->beta_b, p->num_styles);      // betas: only read when y is absent
+    const StyleGradPtrs gpa = style_grad_ptrs(p->dgamma_a, p->dbeta_a, p->num_styles), gpb = style_grad_ptrs(p->dgamma_b, p->dbeta_b, p->num_styles);
     if (!p->r1x && p->S <= NORM_FUSED_MAX_ROWS) {      // small tensors: one register-resident launch
       const FusedGeom f = fused_geom(p->S, p->C, al, V);
       dim3 fgrid(cdiv(f.cv, f.tx), p->B);
-      const size_t fsh = fused_smem(f, 3, 2);
-#define PFBWD_LAUNCH(VV)                                                                                                                                     \
-      instnorm_pair_fused_bwd_kernel<T, VV><<<fgrid, NORM_THREADS, fsh, stream>>>((const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->xa, p->ldxa,         \
-                                                                                  (const T*)p->xb, p->ldxb, (T*)p->dxa, p->lddxa, (T*)p->dxb, p->lddxb, p->S, p->C,  \
-                                                                                  f.cv, f.tx, f.ty, (const double*)p->stat_a, (const double*)p->stat_b, p->eps,   \
-                                                                                  p->styles, spa, spb, p->slope, gpa, gpb)
-      FUSED_DISPATCH(f, PFBWD_LAUNCH);
-#undef PFBWD_LAUNCH
+      for_lane_width<V, true>(f.vec, [&](auto w) {
+        instnorm_pair_fused_bwd_kernel<T, decltype(w)::value><<<fgrid, NORM_THREADS, fused_smem(f, 3, 2), stream>>>(
+            (const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->xa, p->ldxa, (const T*)p->xb, p->ldxb, (T*)p->dxa, p->lddxa, (T*)p->dxb, p->lddxb, p->S, p->C,
+            f.cv, f.tx, f.ty, (const double*)p->stat_a, (const double*)p->stat_b, p->eps, p->styles, spa, spb, p->slope, gpa, gpb);
+      });
       MISEG_LAUNCH_CHECK("instnorm_pair_bwd");
       return MISEG_OK;
     }
     dim3 grid(g.chunks, p->B, g.ctiles);
-    size_t sh = (size_t)g.ty * 2 * g.tx * g.vec * sizeof(float);
-    if (sh < (size_t)4 * g.tx * g.vec * sizeof(double)) sh = (size_t)4 * g.tx * g.vec * sizeof(double);
-    size_t shd = (size_t)8 * g.tx * g.vec * sizeof(double);
-    if (p->r1x && shd < (size_t)NORM_THREADS * g.vec * sizeof(float)) shd = (size_t)NORM_THREADS * g.vec * sizeof(float);
-#define PAIR_LAUNCH(VV)                                                                                                                                          \
-    instnorm_pair_bwd_reduce_kernel<T, VV><<<grid, NORM_THREADS, sh, stream>>>((const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->xa, p->ldxa,         \
-                                                                               (const T*)p->xb, p->ldxb, p->S, p->C, g.cv, g.tx, g.ty, g.rpb,                    \
-                                                                               (const double*)p->stat_a, (const double*)p->stat_b, p->eps, p->slope,            \
-                                                                               (double*)p->dstat_a, (double*)p->dstat_b, p->styles, spa, spb,                   \
-                                                                               (const T*)p->r1x, p->ldr1x, (const T*)p->r1w);                                   \
-    instnorm_pair_bwd_apply_kernel<T, VV><<<grid, NORM_THREADS, shd, stream>>>((const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->xa, p->ldxa,         \
-                                                                               (const T*)p->xb, p->ldxb, (T*)p->dxa, p->lddxa, (T*)p->dxb, p->lddxb, p->S, p->C, \
-                                                                               g.cv, g.tx, g.ty, g.rpb, (const double*)p->stat_a, (const double*)p->stat_b,     \
-                                                                               p->eps, p->styles, spa, spb, p->slope, (const double*)p->dstat_a,               \
-                                                                               (const double*)p->dstat_b, gpa, gpb, (const T*)p->r1x, p->ldr1x,                 \
-                                                                               (const T*)p->r1w, p->r1dw);
-    if (g.vec == 1) { PAIR_LAUNCH(1) } else { PAIR_LAUNCH(V) }
-#undef PAIR_LAUNCH
+    for_lane_width<V, false>(g.vec, [&](auto w) {
+      constexpr int W = decltype(w)::value;
+      instnorm_pair_bwd_reduce_kernel<T, W><<<grid, NORM_THREADS, reduce_smem(g, 2), stream>>>(
+          (const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->xa, p->ldxa, (const T*)p->xb, p->ldxb, p->S, p->C, g.cv, g.tx, g.ty, g.rpb,
+          (const double*)p->stat_a, (const double*)p->stat_b, p->eps, p->slope, (double*)p->dstat_a, (double*)p->dstat_b, p->styles, spa, spb, (const T*)p->r1x,
+          p->ldr1x, (const T*)p->r1w);
+      instnorm_pair_bwd_apply_kernel<T, W><<<grid, NORM_THREADS, apply_smem(g, 4, p->r1x != nullptr), stream>>>(
+          (const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->xa, p->ldxa, (const T*)p->xb, p->ldxb, (T*)p->dxa, p->lddxa, (T*)p->dxb, p->lddxb, p->S, p->C,
+          g.cv, g.tx, g.ty, g.rpb, (const double*)p->stat_a, (const double*)p->stat_b, p->eps, p->styles, spa, spb, p->slope, (const double*)p->dstat_a,
+          (const double*)p->dstat_b, gpa, gpb, (const T*)p->r1x, p->ldr1x, (const T*)p->r1w, p->r1dw);
+    });
     MISEG_LAUNCH_CHECK("instnorm_pair_bwd");
     return MISEG_OK;
   });
