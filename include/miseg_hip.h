@@ -267,6 +267,43 @@ int miseg_gemm_tn_fuses_colsum(const miseg_gemm_params* p);   /* 1: this TN prod
 size_t miseg_gemm_workspace_bytes(const miseg_gemm_params* p);
 int miseg_gemm(const miseg_gemm_params* p, miseg_stream_t stream);
 
+/* What miseg_gemm(p) does with these params - the launch dispatches on exactly this plan, and the seven question entry points above read
+ * their answers from it.  Pointers are only tested for NULL and alignment, so a host may ask with stand-ins for buffers it has not
+ * allocated yet (`workspace` is not looked at).  Host only: touches no device.  Returns what miseg_gemm would return for a refused launch
+ * (kernel == MISEG_GEMM_NONE then); the fuses_* / tn_fuses_colsum answers, and for a TN product of the streaming path splits and
+ * workspace_bytes, are filled either way.  (A new symbol and struct: MISEG_ABI_VERSION stays 16.) */
+#define MISEG_GEMM_NONE 0
+#define MISEG_GEMM_NT_RANK1 1           /* K == 1 */
+#define MISEG_GEMM_NT_RANK1_STAT 2      /* ... with the statistics of its output */
+#define MISEG_GEMM_NT_SMALL 3           /* bf16, M <= 2048: <mtw, ntw, gelu, stat, anorm> */
+#define MISEG_GEMM_NT_STREAM 4          /* bf16, M >= 4096, weight resident in LDS: <k16, gelu, nch, stat, scat, anorm> */
+#define MISEG_GEMM_NT_GENERIC 5         /* <nt> */
+#define MISEG_GEMM_TN_STREAM 6          /* bf16 -> fp32 token streams: wm x wn waves of 48 x 48, partial tiles per split */
+#define MISEG_GEMM_TN_GENERIC 7
+#define MISEG_GEMM_OUT_STORE 0
+#define MISEG_GEMM_OUT_ACCUMULATE 1
+#define MISEG_GEMM_OUT_ATOMIC 2
+typedef struct {
+  int32_t kernel;                        /* MISEG_GEMM_* */
+  int32_t mtw, ntw;                      /* NT small: 16-row / 16-column tiles per wave */
+  int32_t k16, nch;                      /* NT stream: K / 16, column tiles per accumulator chunk */
+  int32_t gelu, stat, scat, anorm;       /* NT small / stream: stat 0 none, 1 forward statistics, 2 norm-backward sums */
+  int32_t nt;                            /* NT generic: column tiles per workgroup */
+  int32_t wm, wn;                        /* TN stream */
+  int32_t grid_x, grid_y, grid_z;
+  int32_t row_tiles;                     /* NT small: workgroup rows (grid_x = row_tiles * col_groups) */
+  int32_t col_groups, cols_per_group;    /* NT small / stream: column groups of the grid and the columns of one */
+  int32_t splits, k_per_split;           /* generic kernels and TN stream: parts of the K range and the length of one */
+  int32_t out_mode;                      /* MISEG_GEMM_OUT_* */
+  int32_t zero_fill;                     /* 1: C is zero-filled first (before the atomics that meet in it) */
+  int32_t reduce_groups, reduce_blocks;  /* TN stream: grid y / x of the sum over the partial tiles (0: no such launch) */
+  int32_t al_a, al_b;                    /* A / B rows may be read as 16-byte vectors */
+  int32_t fuses_stat, fuses_anorm, fuses_bstat, fuses_scatter, tn_fuses_colsum;      /* what the entry points of these names answer */
+  size_t lds_bytes;                      /* dynamic LDS of the launch */
+  size_t workspace_bytes;                /* what miseg_gemm_workspace_bytes answers */
+} miseg_gemm_plan_info;
+int miseg_gemm_plan(const miseg_gemm_params* p, miseg_gemm_plan_info* plan);
+
 /* up to MISEG_GEMM_GROUP independent TN problems C[M][N] += A[K][M]^T B[K][N] (fp32 C, accumulate mode) in ONE launch: the weight
  * gradients of the deep stages are a few dozen workgroups each; the host queues them during the backward pass and issues them
  * together.  `descs` is a HOST array (copied into the kernel arguments). */

@@ -548,7 +548,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_stream_kernel(const bf16* __re
 // MTW x NTW MFMA tiles per workgroup.  The kernel is bound by the operand traffic L2 -> CU, not by a latency chain (a software-pipelined
 // K loop with unconditional, clamped loads was SLOWER: 216 x 768 x 3072 18.8 -> 20.3 us, it over-fetches two batches per wave): 32 x 32
 // outputs read 64 operand rows per k-step for 4 MFMAs where 16 x 32 read 48 for 2 (216 x 768 x 3072: 20.2 -> 14.2 us, 216 x 768 x 768:
-// 8.4 -> 6.4), 32 x 64 read 96 for 8 (216 x 2304 x 768: 12.8 -> 8.9).  scripts/bench_gemm.py small, MISEG_GEMM_SMALL_TILE.
+// 8.4 -> 6.4), 32 x 64 read 96 for 8 (216 x 2304 x 768: 12.8 -> 8.9).  scripts/bench_gemm.py small; the tile rule is nt_small_tile below.
 // Round 5 (the deep Swin stages, 1,728 / 216 tokens of ONE sample): STAT = 1 - instance-norm statistics of the rounded output in the epilogue
 // (proj + residual, fc2 + residual: the consumer norm then has no statistics pass); STAT = 2 - the backward sums (sum q, sum q * xhat) of
 // the norm whose output gradient this GEMM produces; ANORM - A is the raw input of an instance norm, normalised as it is loaded (scale /
@@ -1080,58 +1080,219 @@ static bool tn_stream_plan(const miseg_gemm_params* p, TnStreamPlan* pl) {
   return true;
 }
 
-// the small-M kernel (M <= 2048 rows of one sample) takes the same folds (gemm_nt_small_kernel)
-static bool nt_small_ok(const miseg_gemm_params* p) {
-  if (!p || p->ta || p->tb || p->dtype != MISEG_BF16 || p->out_dtype != MISEG_BF16) return false;
-  const bool al_a = ((uintptr_t)p->A % 16 == 0) && (p->lda % 8 == 0), al_b = ((uintptr_t)p->B % 16 == 0) && (p->ldb % 8 == 0);
-  const bool epi_vec_ok = (!p->res || (((uintptr_t)p->res % 8 == 0) && p->ldres % 4 == 0)) && (!p->epi_mode || (((uintptr_t)p->aux % 8 == 0) && p->ldaux % 4 == 0));
-  return p->split_k <= 1 && !p->accumulate && p->M <= 2048 && p->M >= 16 && p->K % 32 == 0 && p->N % 16 == 0 && al_a && al_b && ((uintptr_t)p->C % 8 == 0) &&
-         p->ldc % 4 == 0 && epi_vec_ok && !p->scat_cout;
+// ------------------------------------------------------------------------------------------------ the plan of one miseg_gemm launch
+// Host only.  Every predicate, grid and LDS size of miseg_gemm is written here, once; the launchers below read the plan and compute nothing.
+static bool vec_rows(const void* ptr, int64_t ld, unsigned bytes, int elems) { return (uintptr_t)ptr % bytes == 0 && ld % elems == 0; }
+static bool one_of(int v, std::initializer_list<int> set) {
+  for (int s : set) if (v == s) return true;
+  return false;
 }
-extern "C" int miseg_gemm_fuses_stat(const miseg_gemm_params* p) {
-  if (p && !p->ta && !p->tb && p->dtype == p->out_dtype && p->K == 1) {      // the rank-1 kernel (stem shortcut), either dtype
-    const int n16 = p->dtype == MISEG_BF16 ? 8 : 4;
-    return p->split_k <= 1 && !p->accumulate && p->act == MISEG_ACT_NONE && !p->res && !p->epi_mode && p->N % n16 == 0 && p->N <= 128 &&
-           ((uintptr_t)p->C % 16 == 0) && p->ldc % n16 == 0 && !p->scat_cout;
+static int rank1_stat_blocks(int M, int N, int n16) {      // callers hold N % n16 == 0 and N <= 128
+  const int sb = cdiv(M, 256 / (N / n16));
+  return sb > 2048 ? 2048 : sb;
+}
+// column groups of the streaming NT kernel: the smallest divisor d of the N / 16 column tiles that brings the grid to >= 300 workgroups
+static int nt_stream_groups(int blocks, int N) {
+  const int tiles = N / 16;
+  for (int d = 1; d <= tiles; ++d)
+    if (tiles % d == 0 && blocks * d >= 300) return d;
+  return tiles;
+}
+// tile of the small-M kernel: the largest that still leaves >= 140 workgroups (sweep over the deep-stage / ViT shapes in the kernel's
+// comment: with fewer the launch is one workgroup's K loop long; beyond, the smaller tile only adds operand traffic); a grid of at most 256
+// workgroups - one round on the 256 CUs - beats a finer tile that needs a second, partly empty round (216 x 768 -> 3072: 32 x 64 tiles = 336
+// workgroups 11.6 us, 64 x 48 tiles = 256 workgroups 9.0 us; 216 x 768 -> 2304: 32 x 64 = 252 workgroups 7.6 us, 64 x 48 = 192: 8.9): the
+// candidate with the most workgroups <= 256 wins when it has >= 140, else the first rule
+static void nt_small_tile(int M, int N, int* mtw, int* ntw) {
+  static const int cand[6][2] = {{4, 3}, {2, 4}, {2, 2}, {2, 1}, {1, 2}, {1, 1}};
+  int best = -1;
+  int64_t best_wg = 0;
+  for (int c = 0; c < 6; ++c) {
+    const int a_ = cand[c][0], b_ = cand[c][1];
+    if (N % (16 * b_) != 0 || (a_ >= 2 && M <= 16 * (a_ / 2))) continue;
+    const int64_t wg = (int64_t)cdiv(M, 16 * a_) * (N / (16 * b_));
+    if (wg >= 140 && wg <= 256 && wg > best_wg) { best = c; best_wg = wg; }
   }
-  if (!p || p->ta || p->tb || p->dtype != MISEG_BF16 || p->out_dtype != MISEG_BF16) return 0;
-  if (nt_small_ok(p) && p->act == MISEG_ACT_NONE && !p->an.stat) return 1;      // the small-M kernel: any N (round 5)
-  const size_t lds = (size_t)p->N * (p->K * 2 + 16) + (size_t)p->N * 4;
-  const bool al_a = ((uintptr_t)p->A % 16 == 0) && (p->lda % 8 == 0), al_b = ((uintptr_t)p->B % 16 == 0) && (p->ldb % 8 == 0);
-  const bool epi_vec_ok = (!p->res || (((uintptr_t)p->res % 8 == 0) && p->ldres % 4 == 0)) && (!p->epi_mode || (((uintptr_t)p->aux % 8 == 0) && p->ldaux % 4 == 0));
-  return p->split_k <= 1 && !p->accumulate && p->act == MISEG_ACT_NONE && (p->K == 48 || p->K == 96 || p->K == 192) && p->N % 16 == 0 && p->N <= 96 &&
-         p->M >= 4096 && lds <= 96 * 1024 && al_a && al_b && ((uintptr_t)p->C % 8 == 0) && p->ldc % 4 == 0 && epi_vec_ok;
+  *mtw = *ntw = 1;
+  if (best >= 0) { *mtw = cand[best][0]; *ntw = cand[best][1]; return; }
+  for (int c = 1; c < 6; ++c) {
+    const int a_ = cand[c][0], b_ = cand[c][1];
+    if (N % (16 * b_) != 0 || (a_ == 2 && M <= 16)) continue;
+    *mtw = a_; *ntw = b_;
+    if ((int64_t)cdiv(M, 16 * a_) * (N / (16 * b_)) >= 140) break;
+  }
 }
 
-// the streaming NT kernel with the consumer-side norm fold (ANORM): Swin qkv / fc1 at the high-resolution stages
-static bool nt_stream_common_ok(const miseg_gemm_params* p) {
-  if (!p || p->ta || p->tb || p->dtype != MISEG_BF16 || p->out_dtype != MISEG_BF16) return false;
-  const bool al_a = ((uintptr_t)p->A % 16 == 0) && (p->lda % 8 == 0), al_b = ((uintptr_t)p->B % 16 == 0) && (p->ldb % 8 == 0);
-  const bool epi_vec_ok = (!p->res || (((uintptr_t)p->res % 8 == 0) && p->ldres % 4 == 0)) && (!p->epi_mode || (((uintptr_t)p->aux % 8 == 0) && p->ldaux % 4 == 0));
-  return p->split_k <= 1 && !p->accumulate && p->N % 16 == 0 && p->M >= 4096 && al_a && al_b && ((uintptr_t)p->C % 8 == 0) && p->ldc % 4 == 0 && epi_vec_ok &&
-         !p->scat_cout;
-}
-extern "C" int miseg_gemm_fuses_anorm(const miseg_gemm_params* p) {
-  if (nt_small_ok(p) && !p->stat && p->K <= 384 && p->an.num_styles >= 1 && p->an.num_styles <= MISEG_MAX_STYLES &&
-      (!p->an_out || (((uintptr_t)p->an_out % 16) == 0 && p->ld_an_out % 8 == 0)))
-    return 1;
-  if (!nt_stream_common_ok(p) || !(p->K == 48 || p->K == 96) || p->stat) return 0;
-  if (p->an.num_styles < 1 || p->an.num_styles > MISEG_MAX_STYLES) return 0;
-  if (p->an_out && (((uintptr_t)p->an_out % 16) != 0 || p->ld_an_out % 8 != 0)) return 0;
-  const size_t lds = (size_t)p->N * (p->K * 2 + 16) + (size_t)p->N * 4;
-  return lds <= 96 * 1024;
-}
-// ... with the norm-backward sums of its output (STAT == 2): the data-gradient GEMMs behind qkv / fc1
-extern "C" int miseg_gemm_fuses_bstat(const miseg_gemm_params* p) {
-  if (nt_small_ok(p) && p->act == MISEG_ACT_NONE && !p->epi_mode && !p->an.stat && p->bs_x && ((uintptr_t)p->bs_x % 8) == 0 && p->ld_bs_x % 4 == 0 && p->N <= 384) return 1;
-  if (!nt_stream_common_ok(p) || p->act != MISEG_ACT_NONE || p->epi_mode || p->an.stat) return 0;
+#define GEMM_REFUSE(code, ...) return say ? set_error((code), __VA_ARGS__) : (code)
+
+// say: a refusal leaves its text for miseg_last_error (the question entry points ask quietly)
+static int gemm_plan(const miseg_gemm_params* p, miseg_gemm_plan_info* pl, bool say) {
+  *pl = miseg_gemm_plan_info{};
+  if (!p) GEMM_REFUSE(MISEG_E_BADARG, "gemm: null pointer");
+  const int M = p->M, N = p->N, K = p->K;
+  const bool nt = !p->ta && !p->tb, tn = p->ta == 1 && p->tb == 1;
+  const bool same = p->dtype == p->out_dtype, bf = p->dtype == MISEG_BF16 && p->out_dtype == MISEG_BF16;
+  const int n16 = p->dtype == MISEG_BF16 ? 8 : 4;      // elements of a 16-byte vector of the operands
+
+  // ---- what the shape and the operands allow, whatever is requested (the fuses_* answers).  Alignment, each written once:
+  pl->al_a = vec_rows(p->A, p->lda, 16, n16);
+  pl->al_b = vec_rows(p->B, p->ldb, 16, n16);
+  const bool c_vec = vec_rows(p->C, p->ldc, 8, 4);      // the 8-byte stores of a bf16 epilogue
+  const bool epi_vec = (!p->res || vec_rows(p->res, p->ldres, 8, 4)) && (!p->epi_mode || vec_rows(p->aux, p->ldaux, 8, 4));
+  const bool an_ok = p->an.num_styles >= 1 && p->an.num_styles <= MISEG_MAX_STYLES && (!p->an_out || vec_rows(p->an_out, p->ld_an_out, 16, 8));
+  const bool bsx_ok = p->bs_x && vec_rows(p->bs_x, p->ld_bs_x, 8, 4);
+  const bool unsplit = p->split_k <= 1 && !p->accumulate, no_act = p->act == MISEG_ACT_NONE;
+  const size_t wlds = (size_t)N * (K * 2 + 16) + (size_t)N * 4;      // the whole weight and bias in LDS (streaming NT kernel)
+  const bool wlds_ok = wlds <= 96 * 1024;
+  // the two bf16 kernels with vector epilogues share this much
+  const bool bf_vec = nt && bf && unsplit && N % 16 == 0 && pl->al_a && pl->al_b && c_vec && epi_vec;
+  const bool small_launch = bf_vec && M <= 2048 && K % 32 == 0;
+  const bool stream_rows = bf_vec && M >= 4096;
+  const bool stream_launch = stream_rows && wlds_ok && one_of(K, {48, 96, 144, 192, 288, 384});
+  const bool rank1_launch = nt && same && K == 1 && !p->accumulate && no_act && !p->res && !p->epi_mode && N % n16 == 0 && vec_rows(p->C, p->ldc, 16, n16);
+  // Where the answers are narrower than the launcher (the parent's, kept):
+  const bool small_fuse = small_launch && M >= 16 && !p->scat_cout;      // (1) the small kernel runs M < 16, but no fold rides on it
+  const bool rank1_fuse = rank1_launch && p->split_k <= 1 && N <= 128 && !p->scat_cout;      // (2) rank-1 runs split_k > 1 (moot at K = 1) and N > 128
+  const bool stream_fuse = stream_rows && !p->scat_cout;      // (3) fuses_stat alone does not look at scat_cout on the streaming path
+  if (nt && same && K == 1) pl->fuses_stat = rank1_fuse;
+  else if (nt && bf)
+    pl->fuses_stat = (small_fuse && no_act && !p->an.stat) || (stream_rows && wlds_ok && no_act && one_of(K, {48, 96, 192}) && N <= 96);
+  pl->fuses_anorm = (small_fuse && !p->stat && K <= 384 && an_ok) || (stream_fuse && one_of(K, {48, 96}) && !p->stat && an_ok && wlds_ok);
   // (K = 384, the fc1 data gradient of the 96-channel stage: its operand fragments fill the register file - 156 bytes of scratch per lane with
   // the sums beside them - and it keeps the reduction launch)
-  if (!(p->K == 144 || p->K == 288 || p->K == 48 || p->K == 96 || p->K == 192) || !(p->N == 48 || p->N == 96)) return 0;
-  if (!p->bs_x || ((uintptr_t)p->bs_x % 8) != 0 || p->ld_bs_x % 4 != 0) return 0;
-  const size_t lds = (size_t)p->N * (p->K * 2 + 16) + (size_t)p->N * 4;
-  return lds <= 96 * 1024;
+  pl->fuses_bstat = no_act && !p->epi_mode && !p->an.stat && bsx_ok &&
+                    ((small_fuse && N <= 384) || (stream_fuse && one_of(K, {48, 96, 144, 192, 288}) && one_of(N, {48, 96}) && wlds_ok));
+  pl->fuses_scatter = stream_rows && p->scat_cout > 0 && no_act && !p->res && !p->epi_mode && !p->stat && one_of(K, {48, 96}) && N == 8 * p->scat_cout &&
+                      p->scat_cout % 4 == 0 && p->scat_d > 0 && p->scat_h > 0 && p->scat_w > 0 && M % (p->scat_d * p->scat_h * p->scat_w) == 0 && wlds_ok;
+  TnStreamPlan ts;
+  if (M > 0 && N > 0 && tn_stream_plan(p, &ts)) {      // its whole form: miseg_gemm_tn_splits and miseg_gemm_workspace_bytes ask before a launch
+    pl->tn_fuses_colsum = 1;
+    pl->wm = ts.wm; pl->wn = ts.wn; pl->grid_x = ts.gx; pl->grid_y = ts.gy; pl->grid_z = pl->splits = ts.splits; pl->k_per_split = ts.tps;
+    pl->lds_bytes = (size_t)2 * 64 * (ts.wm * 48 * 2 + ts.wn * 48 * 2 + 32);
+    if (ts.splits > 1) pl->workspace_bytes = (size_t)ts.splits * M * N * sizeof(float);
+  }
+
+  // ---- the launch, refusals in miseg_gemm's order
+  if (!p->A || !p->B || !p->C) GEMM_REFUSE(MISEG_E_BADARG, "gemm: null pointer");
+  if (!(M > 0 && N > 0 && K > 0)) GEMM_REFUSE(MISEG_E_BADARG, "gemm: bad shape M=%d N=%d K=%d", M, N, K);
+  if (!(no_act || p->act == MISEG_ACT_GELU)) GEMM_REFUSE(MISEG_E_UNSUPPORTED, "gemm: act %d", p->act);
+  const bool f32out = p->out_dtype == MISEG_F32;
+  if (!(bf || (p->dtype == MISEG_F32 && f32out) || (p->dtype == MISEG_BF16 && f32out))) GEMM_REFUSE(MISEG_E_BADARG, "gemm: dtype %d -> %d", p->dtype, p->out_dtype);
+  int split = p->split_k > 1 ? p->split_k : 1;
+  if (split > 1 && !f32out) GEMM_REFUSE(MISEG_E_BADARG, "gemm: split_k needs fp32 output");
+  if (p->accumulate && !f32out) GEMM_REFUSE(MISEG_E_BADARG, "gemm: accumulate needs fp32 output");
+  const bool bstat = p->stat && p->stat_mode == 2;
+  if (p->an.stat && !pl->fuses_anorm) GEMM_REFUSE(MISEG_E_UNSUPPORTED, "gemm: folded instance norm on this shape / path (ask miseg_gemm_fuses_anorm first)");
+  if (bstat && !pl->fuses_bstat) GEMM_REFUSE(MISEG_E_UNSUPPORTED, "gemm: norm-backward sums on this shape / path (ask miseg_gemm_fuses_bstat first)");
+  if (p->stat && p->stat_mode != 0 && p->stat_mode != 2) GEMM_REFUSE(MISEG_E_BADARG, "gemm: stat_mode %d", p->stat_mode);
+  if (p->scat_cout && !pl->fuses_scatter) GEMM_REFUSE(MISEG_E_UNSUPPORTED, "gemm: scattered (transposed-conv) store on this shape / path (ask miseg_gemm_fuses_scatter first)");
+  if (p->stat && !bstat && !pl->fuses_stat) GEMM_REFUSE(MISEG_E_UNSUPPORTED, "gemm: fused statistics on this shape / path (ask miseg_gemm_fuses_stat first)");
+  const int accumulate = p->accumulate ? MISEG_GEMM_OUT_ACCUMULATE : MISEG_GEMM_OUT_STORE;
+  pl->grid_y = pl->grid_z = 1;
+
+  if (tn) {
+    if (p->bias || !no_act) GEMM_REFUSE(MISEG_E_UNSUPPORTED, "gemm TN: no bias/act epilogue");
+    if (pl->tn_fuses_colsum) {      // tall token streams (see gemm_tn_stream_kernel); K is the token count here
+      pl->kernel = MISEG_GEMM_TN_STREAM;
+      pl->grid_y = ts.gy; pl->grid_z = ts.splits;
+      pl->out_mode = accumulate;
+      if (ts.splits > 1 && !p->defer_reduce) {      // the sum over the partial tiles follows; more than one group of splits meets in atomics
+        pl->reduce_groups = cdiv(ts.splits, TN_RG);
+        pl->reduce_blocks = cdiv(M * (N / 4), 256);
+        pl->zero_fill = pl->reduce_groups > 1 && !p->accumulate;
+      }
+      return MISEG_OK;
+    }
+    if (p->tn_colsum) GEMM_REFUSE(MISEG_E_UNSUPPORTED, "gemm TN: column sums ride on the streaming path only (ask miseg_gemm_tn_fuses_colsum first)");
+    if (p->split_k == 0) {      // auto: enough workgroups for the chip, >= 512 reduction rows each
+      const int tiles = cdiv(M, 64) * cdiv(N, 64);
+      split = cdiv(K, 512);
+      if (split > 1024 / tiles) split = 1024 / tiles;
+      if (split < 1) split = 1;
+    }
+    const int bk = p->dtype == MISEG_BF16 ? 128 : 64;
+    pl->kernel = MISEG_GEMM_TN_GENERIC;
+    pl->k_per_split = cdiv(cdiv(K, split), bk) * bk;
+    pl->splits = cdiv(K, pl->k_per_split);
+    pl->out_mode = pl->splits > 1 ? MISEG_GEMM_OUT_ATOMIC : accumulate;
+    pl->zero_fill = pl->splits > 1 && !p->accumulate;
+    pl->grid_x = cdiv(M, 64); pl->grid_y = cdiv(N, 64); pl->grid_z = pl->splits;
+    return MISEG_OK;
+  }
+  if (!nt) GEMM_REFUSE(MISEG_E_UNSUPPORTED, "gemm: only NT (ta=tb=0) and TN (ta=tb=1) are implemented");
+
+  if ((p->res || p->epi_mode) && (split > 1 || p->accumulate)) GEMM_REFUSE(MISEG_E_BADARG, "gemm: residual / auxiliary epilogue with split_k or accumulate");
+  if (p->epi_mode && !p->aux) GEMM_REFUSE(MISEG_E_BADARG, "gemm: epi_mode %d needs aux", p->epi_mode);
+  pl->k_per_split = cdiv(cdiv(K, split), 8 * n16) * 8 * n16;
+  pl->splits = cdiv(K, pl->k_per_split);
+  if (pl->splits > 1 && !no_act) GEMM_REFUSE(MISEG_E_BADARG, "gemm: activation with split_k");
+  if (rank1_launch) {      // the stem shortcut, either dtype
+    pl->kernel = p->stat ? MISEG_GEMM_NT_RANK1_STAT : MISEG_GEMM_NT_RANK1;
+    const int64_t blocks = ((int64_t)M * (N / n16) + 255) / 256;
+    pl->grid_x = p->stat ? rank1_stat_blocks(M, N, n16) : (int)(blocks > 8192 ? 8192 : blocks);
+    return MISEG_OK;
+  }
+  if (small_launch || stream_launch) {
+    pl->gelu = p->act == MISEG_ACT_GELU;
+    pl->stat = !p->stat ? 0 : bstat ? 2 : 1;
+    pl->scat = p->scat_cout != 0;
+    pl->anorm = p->an.stat != nullptr;      // no statistics with it (fuses_anorm)
+  }
+  if (small_launch) {      // deep-stage linears (see gemm_nt_small_kernel)
+    pl->kernel = MISEG_GEMM_NT_SMALL;
+    nt_small_tile(M, N, &pl->mtw, &pl->ntw);
+    pl->row_tiles = cdiv(M, 16 * pl->mtw);
+    pl->cols_per_group = 16 * pl->ntw;
+    pl->col_groups = N / pl->cols_per_group;
+    pl->grid_x = pl->row_tiles * pl->col_groups;
+    return MISEG_OK;
+  }
+  if (stream_launch) {      // tall-skinny (see gemm_nt_stream_kernel); a requested fold has been answered yes above, on this path
+    pl->kernel = MISEG_GEMM_NT_STREAM;
+    pl->k16 = K / 16;
+    // column tiles per accumulator chunk: the long rows' A fragments fill the registers, and the sums of a stat launch sit beside them
+    pl->nch = pl->stat == 1 ? 6 : pl->stat == 2 ? (K >= 288 ? 3 : 6) : K >= 384 ? 3 : K >= 288 ? 6 : 12;
+    const int cap = wlds > 80 * 1024 ? 256 : 512;      // (a weight of more than 80 KB leaves one workgroup per CU)
+    const int blocks = cdiv(cdiv(M, 32), 4);
+    pl->grid_x = blocks > cap ? cap : blocks;
+    int ns = pl->scat ? 1 : nt_stream_groups(pl->grid_x, N);
+    if (pl->stat == 2) {      // one accumulator chunk per column group (the sums are indexed by the chunk's tile)
+      while (N / ns > 16 * pl->nch) ++ns;
+      while ((N / 16) % ns) ++ns;
+    }
+    pl->grid_y = pl->col_groups = ns;
+    const int nper = pl->cols_per_group = N / ns;
+    pl->lds_bytes = (size_t)nper * (K * 2 + 16) + (size_t)nper * 4 * (pl->stat == 2 ? 3 : 1) + (pl->anorm ? (size_t)2 * K * 4 : 0);
+    const size_t sums = (size_t)2 * nper * 65 * sizeof(float);      // the statistics meet in LDS after the row loop
+    if (pl->stat && pl->lds_bytes < sums) pl->lds_bytes = sums;
+    return MISEG_OK;
+  }
+  pl->kernel = MISEG_GEMM_NT_GENERIC;
+  pl->nt = (N % 64 == 0) ? 4 : (N % 48 == 0) ? 3 : (N <= 16) ? 1 : (N <= 32) ? 2 : (N <= 48) ? 3 : 4;
+  // (4) the mode is the requested split_k's, the fill the rounded split's: split_k > 1 over a K of one stage adds to an unfilled C
+  pl->out_mode = p->split_k > 1 ? MISEG_GEMM_OUT_ATOMIC : accumulate;
+  pl->zero_fill = pl->splits > 1 && !p->accumulate;
+  pl->grid_x = cdiv(M, 128); pl->grid_y = cdiv(N, 16 * pl->nt); pl->grid_z = pl->splits;
+  return MISEG_OK;
 }
+#undef GEMM_REFUSE
+
+extern "C" int miseg_gemm_plan(const miseg_gemm_params* p, miseg_gemm_plan_info* plan) {
+  MISEG_REQUIRE(plan, MISEG_E_BADARG, "gemm_plan: null plan");
+  return gemm_plan(p, plan, true);
+}
+static miseg_gemm_plan_info gemm_asked(const miseg_gemm_params* p) {
+  miseg_gemm_plan_info pl;
+  (void)gemm_plan(p, &pl, false);
+  return pl;
+}
+extern "C" int miseg_gemm_fuses_stat(const miseg_gemm_params* p) { return gemm_asked(p).fuses_stat; }
+extern "C" int miseg_gemm_fuses_anorm(const miseg_gemm_params* p) { return gemm_asked(p).fuses_anorm; }
+extern "C" int miseg_gemm_fuses_bstat(const miseg_gemm_params* p) { return gemm_asked(p).fuses_bstat; }
+extern "C" int miseg_gemm_fuses_scatter(const miseg_gemm_params* p) { return gemm_asked(p).fuses_scatter; }
+extern "C" int miseg_gemm_tn_fuses_colsum(const miseg_gemm_params* p) { return gemm_asked(p).tn_fuses_colsum; }
+extern "C" int miseg_gemm_tn_splits(const miseg_gemm_params* p) { const miseg_gemm_plan_info pl = gemm_asked(p); return pl.tn_fuses_colsum ? pl.splits : 0; }
+extern "C" size_t miseg_gemm_workspace_bytes(const miseg_gemm_params* p) { return gemm_asked(p).workspace_bytes; }
 
 extern "C" int miseg_rank1_stats(const void* x, int64_t ldx, const void* w, int64_t ldw, int M, int N, int dtype, void* stat, miseg_stream_t stream_) {
   hipStream_t s = (hipStream_t)stream_;
@@ -1140,323 +1301,128 @@ extern "C" int miseg_rank1_stats(const void* x, int64_t ldx, const void* w, int6
     typedef typename std::remove_pointer<decltype(tag)>::type T;
     constexpr int N16 = Vec16<T>::N;
     MISEG_REQUIRE(N % N16 == 0, MISEG_E_UNSUPPORTED, "rank1_stats: N %d is not a multiple of %d", N, N16);
-    int sb = cdiv(M, 256 / (N / N16));
-    if (sb > 2048) sb = 2048;
-    gemm_nt_k1_stat_kernel<T><<<sb, 256, 0, s>>>((const T*)x, ldx, (const T*)w, ldw, (T*)nullptr, 0, M, N, nullptr, (double*)stat);
+    gemm_nt_k1_stat_kernel<T><<<rank1_stat_blocks(M, N, N16), 256, 0, s>>>((const T*)x, ldx, (const T*)w, ldw, (T*)nullptr, 0, M, N, nullptr, (double*)stat);
     MISEG_LAUNCH_CHECK("rank1_stats");
     return MISEG_OK;
   });
 }
 
-extern "C" int miseg_gemm_fuses_scatter(const miseg_gemm_params* p) {
-  if (!p || p->ta || p->tb || p->dtype != MISEG_BF16 || p->out_dtype != MISEG_BF16 || p->scat_cout <= 0) return 0;
-  const size_t lds = (size_t)p->N * (p->K * 2 + 16) + (size_t)p->N * 4;
-  const bool al_a = ((uintptr_t)p->A % 16 == 0) && (p->lda % 8 == 0), al_b = ((uintptr_t)p->B % 16 == 0) && (p->ldb % 8 == 0);
-  return p->split_k <= 1 && !p->accumulate && p->act == MISEG_ACT_NONE && !p->res && !p->epi_mode && !p->stat && (p->K == 48 || p->K == 96) &&
-         p->N == 8 * p->scat_cout && p->scat_cout % 4 == 0 && p->N % 16 == 0 && p->scat_d > 0 && p->scat_h > 0 && p->scat_w > 0 &&
-         p->M % (p->scat_d * p->scat_h * p->scat_w) == 0 && p->M >= 4096 && lds <= 96 * 1024 && al_a && al_b && ((uintptr_t)p->C % 8 == 0) && p->ldc % 4 == 0;
+// ------------------------------------------------------------------------------------------------ the launchers: they read the plan
+static int gemm_zero_c(const miseg_gemm_params* p, hipStream_t s) {      // atomics need a zeroed destination
+  if (p->ldc == p->N) { if (fill_words_async(p->C, 0, (size_t)p->M * p->N, s) != hipSuccess) return set_error(MISEG_E_LAUNCH, "gemm: memset"); }
+  else if (fill_words_2d_async(p->C, (size_t)p->ldc, 0, (size_t)p->N, (size_t)p->M, s) != hipSuccess) return set_error(MISEG_E_LAUNCH, "gemm: memset2d");
+  return MISEG_OK;
 }
 
-extern "C" size_t miseg_gemm_workspace_bytes(const miseg_gemm_params* p) {
-  TnStreamPlan pl;
-  if (!p || !tn_stream_plan(p, &pl) || pl.splits <= 1) return 0;
-  return (size_t)pl.splits * p->M * p->N * sizeof(float);
+#define GEMM_BF16_ARGS (const bf16*)p->A, p->lda, (const bf16*)p->B, p->ldb, (bf16*)p->C, p->ldc, p->M, p->N
+
+// every gemm_nt_small_kernel<MTW, NTW, GELU, STAT, ANORM> a plan reaches: the six tiles of nt_small_tile, each with six epilogues - plain and
+// the folded norm with and without GELU, the forward statistics and the norm-backward sums without
+#define NT_SMALL_EPILOGUES(X, m_, n_) \
+  X(m_, n_, false, 0, false) X(m_, n_, true, 0, false) X(m_, n_, false, 0, true) X(m_, n_, true, 0, true) X(m_, n_, false, 1, false) X(m_, n_, false, 2, false)
+#define NT_SMALL_FORMS(X) \
+  NT_SMALL_EPILOGUES(X, 4, 3) NT_SMALL_EPILOGUES(X, 2, 4) NT_SMALL_EPILOGUES(X, 2, 2) NT_SMALL_EPILOGUES(X, 2, 1) NT_SMALL_EPILOGUES(X, 1, 2) NT_SMALL_EPILOGUES(X, 1, 1)
+static int launch_nt_small(const miseg_gemm_params* p, const miseg_gemm_plan_info& pl, const Epi& epi, hipStream_t s) {
+#define SM_FORM(m_, n_, g_, st_, an_)                                                                                \
+  if (pl.mtw == m_ && pl.ntw == n_ && pl.gelu == g_ && pl.stat == st_ && pl.anorm == an_) {                          \
+    gemm_nt_small_kernel<m_, n_, g_, st_, an_><<<pl.grid_x, 256, 0, s>>>(GEMM_BF16_ARGS, p->K, epi, pl.row_tiles); \
+    return MISEG_OK;                                                                                                 \
+  }
+  NT_SMALL_FORMS(SM_FORM)
+#undef SM_FORM
+  return set_error(MISEG_E_UNSUPPORTED, "gemm: no small-M kernel <%d, %d, gelu %d, stat %d, anorm %d>", pl.mtw, pl.ntw, pl.gelu, pl.stat, pl.anorm);
 }
 
-extern "C" int miseg_gemm_fuses_stat(const miseg_gemm_params* p);
-extern "C" int miseg_gemm_fuses_scatter(const miseg_gemm_params* p);
-extern "C" int miseg_gemm_fuses_anorm(const miseg_gemm_params* p);
-extern "C" int miseg_gemm_fuses_bstat(const miseg_gemm_params* p);
+// every gemm_nt_stream_kernel<K16, GELU, NCH, STAT, SCAT, ANORM> a plan reaches: plain (six K, with and without GELU), the folded norm,
+// forward statistics, norm-backward sums, the scattered store
+#define NT_STREAM_FORMS(X)                                                                                                                   \
+  X(3, false, 12, 0, false, false) X(3, true, 12, 0, false, false) X(6, false, 12, 0, false, false) X(6, true, 12, 0, false, false)            \
+  X(9, false, 12, 0, false, false) X(9, true, 12, 0, false, false) X(12, false, 12, 0, false, false) X(12, true, 12, 0, false, false)          \
+  X(18, false, 6, 0, false, false) X(18, true, 6, 0, false, false) X(24, false, 3, 0, false, false) X(24, true, 3, 0, false, false)            \
+  X(3, false, 12, 0, false, true) X(3, true, 12, 0, false, true) X(6, false, 12, 0, false, true) X(6, true, 12, 0, false, true)                \
+  X(3, false, 6, 1, false, false) X(6, false, 6, 1, false, false) X(12, false, 6, 1, false, false)                                             \
+  X(3, false, 6, 2, false, false) X(6, false, 6, 2, false, false) X(9, false, 6, 2, false, false) X(12, false, 6, 2, false, false) X(18, false, 3, 2, false, false) \
+  X(3, false, 12, 0, true, false) X(6, false, 12, 0, true, false)
+static int launch_nt_stream(const miseg_gemm_params* p, const miseg_gemm_plan_info& pl, const Epi& epi, hipStream_t s) {
+#define ST_FORM(k16_, g_, nch_, st_, sc_, an_)                                                                                               \
+  if (pl.k16 == k16_ && pl.gelu == g_ && pl.nch == nch_ && pl.stat == st_ && pl.scat == sc_ && pl.anorm == an_) {                             \
+    (void)hipFuncSetAttribute((const void*)gemm_nt_stream_kernel<k16_, g_, nch_, st_, sc_, an_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes); \
+    gemm_nt_stream_kernel<k16_, g_, nch_, st_, sc_, an_><<<dim3(pl.grid_x, pl.grid_y), 256, pl.lds_bytes, s>>>(GEMM_BF16_ARGS, epi, pl.cols_per_group); \
+    return MISEG_OK;                                                                                                                         \
+  }
+  NT_STREAM_FORMS(ST_FORM)
+#undef ST_FORM
+  return set_error(MISEG_E_UNSUPPORTED, "gemm: no streaming kernel <%d, gelu %d, %d, stat %d, scat %d, anorm %d>", pl.k16, pl.gelu, pl.nch, pl.stat, pl.scat, pl.anorm);
+}
+#undef GEMM_BF16_ARGS
 
-// column groups of the streaming NT kernel: the smallest divisor d of the N / 16 column tiles that brings the grid to >= 300 workgroups
-static int nt_stream_groups(int blocks, int N) {
-  const int tiles = N / 16;
-  for (int d = 1; d <= tiles; ++d)
-    if (tiles % d == 0 && blocks * d >= 300) return d;
-  return tiles;
+static int launch_tn_stream(const miseg_gemm_params* p, const miseg_gemm_plan_info& pl, hipStream_t s) {
+  MISEG_REQUIRE(pl.splits == 1 || p->workspace, MISEG_E_BADARG, "gemm: workspace required (miseg_gemm_workspace_bytes)");
+  float* partial = pl.splits > 1 ? (float*)p->workspace : nullptr;
+  hipFuncSetAttribute((const void*)gemm_tn_stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
+  gemm_tn_stream_kernel<<<dim3(pl.grid_x, pl.grid_y, pl.grid_z), 256, pl.lds_bytes, s>>>((const bf16*)p->A, p->lda, (const bf16*)p->B, p->ldb, (float*)p->C, p->ldc, p->M, p->N,
+                                                                                        p->K, pl.wm, pl.wn, pl.k_per_split, pl.out_mode, partial, p->tn_colsum);
+  if (pl.reduce_groups) {
+    if (pl.zero_fill) { const int rc = gemm_zero_c(p, s); if (rc != MISEG_OK) return rc; }
+    gemm_tn_partial_reduce_kernel<<<dim3(pl.reduce_blocks, pl.reduce_groups), 256, 0, s>>>(partial, (float*)p->C, p->ldc, p->M, p->N, pl.splits, p->accumulate);
+  }
+  return MISEG_OK;
 }
 
+// the kernels of either dtype pair: rank-1 (T == TO) and the two generic ones
 template <class T, class TO>
-static int launch_gemm(const miseg_gemm_params* p, hipStream_t s) {
-  constexpr int N16 = Vec16<T>::N;
-  const bool al_a = ((uintptr_t)p->A % 16 == 0) && (p->lda % N16 == 0);
-  const bool al_b = ((uintptr_t)p->B % 16 == 0) && (p->ldb % N16 == 0);
-  int split = p->split_k > 1 ? p->split_k : 1;
-  const bool f32out = std::is_same<TO, float>::value;
-  if (split > 1 && !f32out) return set_error(MISEG_E_BADARG, "gemm: split_k needs fp32 output");
-  if (p->accumulate && !f32out) return set_error(MISEG_E_BADARG, "gemm: accumulate needs fp32 output");
-  int mode = split > 1 ? 2 : (p->accumulate ? 1 : 0);
-  Epi epi{p->bias, p->act, p->res, p->ldres, p->aux, p->ldaux, p->epi_mode, (double*)p->stat, p->scat_d, p->scat_h, p->scat_w, p->scat_cout};
-  epi.bx = p->bs_x; epi.ldbx = p->ld_bs_x; epi.bstat_in = (const double*)p->bs_stat; epi.beps = p->bs_eps;
-  epi.an_stat = (const double*)p->an.stat; epi.an_styles = p->an.styles; epi.an_eps = p->an.eps; epi.an_out = p->an_out; epi.ld_an_out = p->ld_an_out;
-  for (int i = 0; i < MISEG_MAX_STYLES; ++i) { epi.an_gamma[i] = i < p->an.num_styles ? p->an.gamma[i] : nullptr; epi.an_beta[i] = i < p->an.num_styles ? p->an.beta[i] : nullptr; }
-  const bool bstat = p->stat && p->stat_mode == 2;
-  if (p->an.stat && !miseg_gemm_fuses_anorm(p)) return set_error(MISEG_E_UNSUPPORTED, "gemm: folded instance norm on this shape / path (ask miseg_gemm_fuses_anorm first)");
-  if (bstat && !miseg_gemm_fuses_bstat(p)) return set_error(MISEG_E_UNSUPPORTED, "gemm: norm-backward sums on this shape / path (ask miseg_gemm_fuses_bstat first)");
-  if (p->stat && p->stat_mode != 0 && p->stat_mode != 2) return set_error(MISEG_E_BADARG, "gemm: stat_mode %d", p->stat_mode);
-  const bool epi_vec_ok = (!p->res || (((uintptr_t)p->res % 8 == 0) && p->ldres % 4 == 0)) && (!p->epi_mode || (((uintptr_t)p->aux % 8 == 0) && p->ldaux % 4 == 0));
-  if (p->scat_cout && !miseg_gemm_fuses_scatter(p)) return set_error(MISEG_E_UNSUPPORTED, "gemm: scattered (transposed-conv) store on this shape / path (ask miseg_gemm_fuses_scatter first)");
-  if (p->stat && !bstat && !miseg_gemm_fuses_stat(p)) return set_error(MISEG_E_UNSUPPORTED, "gemm: fused statistics on this shape / path (ask miseg_gemm_fuses_stat first)");
-  if (p->ta == 0 && p->tb == 0) {
-    if ((p->res || p->epi_mode) && (split > 1 || p->accumulate)) return set_error(MISEG_E_BADARG, "gemm: residual / auxiliary epilogue with split_k or accumulate");
-    if (p->epi_mode && !p->aux) return set_error(MISEG_E_BADARG, "gemm: epi_mode %d needs aux", p->epi_mode);
-    const int kstage = 8 * N16;
-    int kps = cdiv(cdiv(p->K, split), kstage) * kstage;
-    split = cdiv(p->K, kps);
-    if (split > 1 && !p->accumulate) {
-      // atomics need a zeroed destination
-      if (p->ldc == p->N) { if (fill_words_async(p->C, 0, (size_t)p->M * p->N, s) != hipSuccess) return set_error(MISEG_E_LAUNCH, "gemm: memset"); }
-      else if (fill_words_2d_async(p->C, (size_t)p->ldc, 0, (size_t)p->N, (size_t)p->M, s) != hipSuccess) return set_error(MISEG_E_LAUNCH, "gemm: memset2d");
+static int launch_gemm_typed(const miseg_gemm_params* p, const miseg_gemm_plan_info& pl, const Epi& epi, hipStream_t s) {
+  if (pl.zero_fill) { const int rc = gemm_zero_c(p, s); if (rc != MISEG_OK) return rc; }
+  const dim3 grid(pl.grid_x, pl.grid_y, pl.grid_z);
+  if constexpr (std::is_same<T, TO>::value) {
+    if (pl.kernel == MISEG_GEMM_NT_RANK1_STAT) {
+      gemm_nt_k1_stat_kernel<T><<<grid, 256, 0, s>>>((const T*)p->A, p->lda, (const T*)p->B, p->ldb, (T*)p->C, p->ldc, p->M, p->N, p->bias, (double*)p->stat);
+      return MISEG_OK;
     }
-    if (split > 1 && p->act != MISEG_ACT_NONE) return set_error(MISEG_E_BADARG, "gemm: activation with split_k");
-    if (split > 1 && p->act != MISEG_ACT_NONE) return set_error(MISEG_E_BADARG, "gemm: activation with split_k");
-    if constexpr (std::is_same<T, TO>::value) {
-      if (p->K == 1 && split == 1 && !p->accumulate && p->act == MISEG_ACT_NONE && !p->res && !p->epi_mode && p->N % N16 == 0 && ((uintptr_t)p->C % 16 == 0) &&
-          p->ldc % N16 == 0) {
-        if (p->stat) {
-          int sb = cdiv(p->M, 256 / (p->N / N16));
-          if (sb > 2048) sb = 2048;
-          gemm_nt_k1_stat_kernel<T><<<sb, 256, 0, s>>>((const T*)p->A, p->lda, (const T*)p->B, p->ldb, (T*)p->C, p->ldc, p->M, p->N, p->bias, (double*)p->stat);
-          MISEG_LAUNCH_CHECK("gemm_nt_k1(stat)");
-          return MISEG_OK;
-        }
-        int64_t blocks = ((int64_t)p->M * (p->N / N16) + 255) / 256;
-        if (blocks > 8192) blocks = 8192;
-        gemm_nt_k1_kernel<T><<<(int)blocks, 256, 0, s>>>((const T*)p->A, p->lda, (const T*)p->B, p->ldb, (T*)p->C, p->ldc, p->M, p->N, p->bias);
-        MISEG_LAUNCH_CHECK("gemm_nt_k1");
-        return MISEG_OK;
-      }
+    if (pl.kernel == MISEG_GEMM_NT_RANK1) {
+      gemm_nt_k1_kernel<T><<<grid, 256, 0, s>>>((const T*)p->A, p->lda, (const T*)p->B, p->ldb, (T*)p->C, p->ldc, p->M, p->N, p->bias);
+      return MISEG_OK;
     }
-    if constexpr (std::is_same<T, bf16>::value && std::is_same<TO, bf16>::value) {
-      // deep-stage linears (see gemm_nt_small_kernel)
-      if (split == 1 && !p->accumulate && p->M <= 2048 && p->K % 32 == 0 && p->N % 16 == 0 && al_a && al_b && ((uintptr_t)p->C % 8 == 0) && p->ldc % 4 == 0 && epi_vec_ok) {
-        // the largest tile that still leaves >= 140 workgroups (sweep over the deep-stage / ViT shapes in the kernel's comment: with fewer
-        // the launch is one workgroup's K loop long; beyond, the smaller tile only adds operand traffic)
-        // round 4: a grid of at most 256 workgroups - one round on the 256 CUs - beats a finer tile that needs a second, partly empty round
-        // (216 x 768 -> 3072: 32 x 64 tiles = 336 workgroups 11.6 us, 64 x 48 tiles = 256 workgroups 9.0 us; 216 x 768 -> 2304: 32 x 64 = 252
-        // workgroups 7.6 us, 64 x 48 = 192: 8.9): the candidate with the most workgroups <= 256 wins when it has >= 140, else the rule above
-        int mtw = 1, ntw = 1;
-        {
-          static const int cand[6][2] = {{4, 3}, {2, 4}, {2, 2}, {2, 1}, {1, 2}, {1, 1}};
-          int best = -1;
-          int64_t best_wg = 0;
-          for (int c = 0; c < 6; ++c) {
-            const int a_ = cand[c][0], b_ = cand[c][1];
-            if (p->N % (16 * b_) != 0 || (a_ >= 2 && p->M <= 16 * (a_ / 2))) continue;
-            const int64_t wg = (int64_t)cdiv(p->M, 16 * a_) * (p->N / (16 * b_));
-            if (wg >= 140 && wg <= 256 && wg > best_wg) { best = c; best_wg = wg; }
-          }
-          if (best >= 0) { mtw = cand[best][0]; ntw = cand[best][1]; }
-          else {
-            for (int c = 1; c < 6; ++c) {
-              const int a_ = cand[c][0], b_ = cand[c][1];
-              if (p->N % (16 * b_) != 0 || (a_ == 2 && p->M <= 16)) continue;
-              mtw = a_; ntw = b_;
-              if ((int64_t)cdiv(p->M, 16 * a_) * (p->N / (16 * b_)) >= 140) break;
-            }
-          }
-        }
-        const int gm = cdiv(p->M, 16 * mtw);
-        dim3 grid(gm * (p->N / (16 * ntw)));
-        const bool ge = p->act == MISEG_ACT_GELU;
-        const int smode = p->an.stat ? 3 : !p->stat ? 0 : bstat ? 2 : 1;      // 3: folded norm on the A side (no statistics with it)
-#define SM_ARGS (const bf16*)p->A, p->lda, (const bf16*)p->B, p->ldb, (bf16*)p->C, p->ldc, p->M, p->N, p->K, epi, gm
-#define SM_LAUNCH(m_, n_)                                                                                                                       \
-  do {                                                                                                                                          \
-    if (smode == 3) { if (ge) gemm_nt_small_kernel<m_, n_, true, 0, true><<<grid, 256, 0, s>>>(SM_ARGS); else gemm_nt_small_kernel<m_, n_, false, 0, true><<<grid, 256, 0, s>>>(SM_ARGS); } \
-    else if (smode == 2) gemm_nt_small_kernel<m_, n_, false, 2><<<grid, 256, 0, s>>>(SM_ARGS);                                                  \
-    else if (smode == 1) gemm_nt_small_kernel<m_, n_, false, 1><<<grid, 256, 0, s>>>(SM_ARGS);                                                  \
-    else if (ge) gemm_nt_small_kernel<m_, n_, true><<<grid, 256, 0, s>>>(SM_ARGS);                                                              \
-    else gemm_nt_small_kernel<m_, n_, false><<<grid, 256, 0, s>>>(SM_ARGS);                                                                     \
-  } while (0)
-        if (mtw == 4) SM_LAUNCH(4, 3);
-        else if (mtw == 2) { if (ntw == 4) SM_LAUNCH(2, 4); else if (ntw == 2) SM_LAUNCH(2, 2); else SM_LAUNCH(2, 1); }
-        else { if (ntw == 4) SM_LAUNCH(1, 4); else if (ntw == 2) SM_LAUNCH(1, 2); else SM_LAUNCH(1, 1); }
-#undef SM_LAUNCH
-#undef SM_ARGS
-        MISEG_LAUNCH_CHECK("gemm_nt_small");
-        return MISEG_OK;
-      }
-      // tall-skinny streaming path (see gemm_nt_stream_kernel)
-      const size_t lds = (size_t)p->N * (p->K * 2 + 16) + (size_t)p->N * 4;
-      const bool st_ok = split == 1 && !p->accumulate && (p->K == 48 || p->K == 96 || p->K == 192 || p->K == 144 || p->K == 288 || p->K == 384) && p->N % 16 == 0 && p->M >= 4096 && lds <= 96 * 1024 &&
-                         al_a && al_b && ((uintptr_t)p->C % 8 == 0) && p->ldc % 4 == 0 && epi_vec_ok;
-      const bool stat_ok = st_ok && p->act == MISEG_ACT_NONE && p->N <= 96 && (p->K == 48 || p->K == 96 || p->K == 192);
-      if (p->stat && !bstat && !stat_ok) return set_error(MISEG_E_UNSUPPORTED, "gemm: fused statistics on this shape / path (ask miseg_gemm_fuses_stat first)");
-      if (p->an.stat) {          // miseg_gemm_fuses_anorm held: K in {48, 96}; the norm's apply pass rides in the operand load
-        const int mtiles = cdiv(p->M, 32);
-        int blocks = cdiv(mtiles, 4);
-        const int cap = lds > 80 * 1024 ? 256 : 512;
-        if (blocks > cap) blocks = cap;
-        const int ns = nt_stream_groups(blocks, p->N), nper = p->N / ns;
-        const size_t ldsa = (size_t)nper * (p->K * 2 + 16) + (size_t)nper * 4 + (size_t)2 * p->K * 4;
-#define AN_CASE(k16, g)                                                                                                                       \
-  (void)hipFuncSetAttribute((const void*)gemm_nt_stream_kernel<k16, g, 12, 0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsa); \
-  gemm_nt_stream_kernel<k16, g, 12, 0, false, true><<<dim3(blocks, ns), 256, ldsa, s>>>((const bf16*)p->A, p->lda, (const bf16*)p->B, p->ldb, (bf16*)p->C, p->ldc, p->M, p->N, epi, nper)
-        const bool ge = p->act == MISEG_ACT_GELU;
-        if (p->K == 48) { if (ge) { AN_CASE(3, true); } else { AN_CASE(3, false); } }
-        else { if (ge) { AN_CASE(6, true); } else { AN_CASE(6, false); } }
-#undef AN_CASE
-        MISEG_LAUNCH_CHECK("gemm_nt_stream(anorm)");
-        return MISEG_OK;
-      }
-      if (bstat) {               // miseg_gemm_fuses_bstat held: N in {48, 96}; the norm-backward reduction rides in the epilogue
-        const int mtiles = cdiv(p->M, 32);
-        int blocks = cdiv(mtiles, 4);
-        if (blocks > 512) blocks = 512;
-        const int nch = p->K >= 288 ? 3 : 6;      // (the long rows' A fragments fill the registers: fewer accumulator tiles beside the sums)
-        int ns = nt_stream_groups(blocks, p->N);
-        while (p->N / ns > 16 * nch) ++ns;          // one accumulator chunk per column group (the sums are indexed by the chunk's tile)
-        while ((p->N / 16) % ns) ++ns;
-        const int nper = p->N / ns;
-        size_t ldsb = (size_t)nper * (p->K * 2 + 16) + (size_t)nper * 4 * 3;
-        if (ldsb < (size_t)2 * nper * 65 * sizeof(float)) ldsb = (size_t)2 * nper * 65 * sizeof(float);
-#define BS_CASE(k16, nch_)                                                                                                                      \
-  (void)hipFuncSetAttribute((const void*)gemm_nt_stream_kernel<k16, false, nch_, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb); \
-  gemm_nt_stream_kernel<k16, false, nch_, 2><<<dim3(blocks, ns), 256, ldsb, s>>>((const bf16*)p->A, p->lda, (const bf16*)p->B, p->ldb, (bf16*)p->C, p->ldc, p->M, p->N, epi, nper)
-        switch (p->K) {
-          case 48: BS_CASE(3, 6); break;
-          case 96: BS_CASE(6, 6); break;
-          case 192: BS_CASE(12, 6); break;
-          case 144: BS_CASE(9, 6); break;
-          default: BS_CASE(18, 3); break;
-        }
-#undef BS_CASE
-        MISEG_LAUNCH_CHECK("gemm_nt_stream(bstat)");
-        return MISEG_OK;
-      }
-      if (p->scat_cout) {        // miseg_gemm_fuses_scatter held: st_ok, K in {48, 96}
-        const int mtiles = cdiv(p->M, 32);
-        int blocks = cdiv(mtiles, 4);
-        const int cap = lds > 80 * 1024 ? 256 : 512;
-        if (blocks > cap) blocks = cap;
-#define SC_CASE(k16)                                                                                                                         \
-  (void)hipFuncSetAttribute((const void*)gemm_nt_stream_kernel<k16, false, 12, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-  gemm_nt_stream_kernel<k16, false, 12, false, true><<<blocks, 256, lds, s>>>((const bf16*)p->A, p->lda, (const bf16*)p->B, p->ldb, (bf16*)p->C, p->ldc, p->M, p->N, epi, p->N)
-        if (p->K == 48) { SC_CASE(3); } else { SC_CASE(6); }
-#undef SC_CASE
-        MISEG_LAUNCH_CHECK("gemm_nt_stream(scatter)");
-        return MISEG_OK;
-      }
-      if (st_ok && p->stat) {
-        const int mtiles = cdiv(p->M, 32);
-        int blocks = cdiv(mtiles, 4);
-        if (blocks > 512) blocks = 512;
-        const int ns = nt_stream_groups(blocks, p->N), nper = p->N / ns;
-        size_t lds2 = (size_t)2 * nper * 65 * sizeof(float);
-        const size_t ldsg = (size_t)nper * (p->K * 2 + 16) + (size_t)nper * 4;
-        if (lds2 < ldsg) lds2 = ldsg;
-#define STS_CASE(k16)                                                                                                                        \
-  (void)hipFuncSetAttribute((const void*)gemm_nt_stream_kernel<k16, false, 6, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2); \
-  gemm_nt_stream_kernel<k16, false, 6, true><<<dim3(blocks, ns), 256, lds2, s>>>((const bf16*)p->A, p->lda, (const bf16*)p->B, p->ldb, (bf16*)p->C, p->ldc, p->M, p->N, epi, nper)
-        if (p->K == 48) { STS_CASE(3); } else if (p->K == 96) { STS_CASE(6); } else { STS_CASE(12); }
-#undef STS_CASE
-        MISEG_LAUNCH_CHECK("gemm_nt_stream(stat)");
-        return MISEG_OK;
-      }
-      if (st_ok) {
-        const int mtiles = cdiv(p->M, 32);
-        int blocks = cdiv(mtiles, 4);
-        const int cap = lds > 80 * 1024 ? 256 : 512;
-        if (blocks > cap) blocks = cap;
-        const int ns = nt_stream_groups(blocks, p->N), nper = p->N / ns;
-        const size_t ldsg = (size_t)nper * (p->K * 2 + 16) + (size_t)nper * 4;
-#define ST_CASE(k16, g, nch)                                                                                                                  \
-  (void)hipFuncSetAttribute((const void*)gemm_nt_stream_kernel<k16, g, nch>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsg);         \
-  gemm_nt_stream_kernel<k16, g, nch><<<dim3(blocks, ns), 256, ldsg, s>>>((const bf16*)p->A, p->lda, (const bf16*)p->B, p->ldb, (bf16*)p->C, p->ldc, p->M, p->N, epi, nper)
-        const bool ge = p->act == MISEG_ACT_GELU;
-        if (p->K == 48) { if (ge) { ST_CASE(3, true, 12); } else { ST_CASE(3, false, 12); } }
-        else if (p->K == 96) { if (ge) { ST_CASE(6, true, 12); } else { ST_CASE(6, false, 12); } }
-        else if (p->K == 192) { if (ge) { ST_CASE(12, true, 12); } else { ST_CASE(12, false, 12); } }
-        else if (p->K == 144) { if (ge) { ST_CASE(9, true, 12); } else { ST_CASE(9, false, 12); } }
-        else if (p->K == 288) { if (ge) { ST_CASE(18, true, 6); } else { ST_CASE(18, false, 6); } }
-        else { if (ge) { ST_CASE(24, true, 3); } else { ST_CASE(24, false, 3); } }
-#undef ST_CASE
-        MISEG_LAUNCH_CHECK("gemm_nt_stream");
-        return MISEG_OK;
-      }
-    }
-    if (p->stat) return set_error(MISEG_E_UNSUPPORTED, "gemm: fused statistics on this shape / path (ask miseg_gemm_fuses_stat first)");
-    const int nt = (p->N % 64 == 0) ? 4 : (p->N % 48 == 0) ? 3 : (p->N <= 16) ? 1 : (p->N <= 32) ? 2 : (p->N <= 48) ? 3 : 4;
-    dim3 grid(cdiv(p->M, 128), cdiv(p->N, 16 * nt), split);
+  }
+  if (pl.kernel == MISEG_GEMM_TN_GENERIC) {
+    gemm_tn_kernel<T, TO><<<grid, 256, 0, s>>>((const T*)p->A, p->lda, (const T*)p->B, p->ldb, (TO*)p->C, p->ldc, p->M, p->N, p->K, pl.out_mode, pl.al_a, pl.al_b, pl.k_per_split);
+    return MISEG_OK;
+  }
 #define NT_CASE(n)                                                                                                                          \
   case n:                                                                                                                                   \
     gemm_nt_kernel<T, TO, n><<<grid, 256, 0, s>>>((const T*)p->A, p->lda, (const T*)p->B, p->ldb, (TO*)p->C, p->ldc, p->M, p->N, p->K, epi, \
-                                                  mode, al_a, al_b, kps);                                                          \
-    break;
-    switch (nt) { NT_CASE(1) NT_CASE(2) NT_CASE(3) NT_CASE(4) }
+                                                  pl.out_mode, pl.al_a, pl.al_b, pl.k_per_split);                                            \
+    return MISEG_OK;
+  switch (pl.kernel == MISEG_GEMM_NT_GENERIC ? pl.nt : 0) { NT_CASE(1) NT_CASE(2) NT_CASE(3) NT_CASE(4) }
 #undef NT_CASE
-  } else if (p->ta == 1 && p->tb == 1) {
-    if (p->bias || p->act != MISEG_ACT_NONE) return set_error(MISEG_E_UNSUPPORTED, "gemm TN: no bias/act epilogue");
-    if constexpr (std::is_same<T, bf16>::value && std::is_same<TO, float>::value) {
-      // streaming path for tall token streams (see gemm_tn_stream_kernel); K is the token count here
-      TnStreamPlan pl;
-      if (tn_stream_plan(p, &pl)) {
-        float* partial = nullptr;
-        if (pl.splits > 1) {
-          MISEG_REQUIRE(p->workspace, MISEG_E_BADARG, "gemm: workspace required (miseg_gemm_workspace_bytes)");
-          partial = (float*)p->workspace;
-        }
-        const int BM = pl.wm * 48, BN = pl.wn * 48;
-        const size_t lds = (size_t)2 * 64 * (BM * 2 + BN * 2 + 32);
-        hipFuncSetAttribute((const void*)gemm_tn_stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        gemm_tn_stream_kernel<<<dim3(pl.gx, pl.gy, pl.splits), 256, lds, s>>>((const bf16*)p->A, p->lda, (const bf16*)p->B, p->ldb, (float*)p->C, p->ldc, p->M, p->N,
-                                                                             p->K, pl.wm, pl.wn, pl.tps, p->accumulate ? 1 : 0, partial, p->tn_colsum);
-        if (partial && !p->defer_reduce) {
-          const int groups = cdiv(pl.splits, TN_RG);
-          if (groups > 1 && !p->accumulate) {   // the groups meet in atomics
-            if (p->ldc == p->N) { if (fill_words_async(p->C, 0, (size_t)p->M * p->N, s) != hipSuccess) return set_error(MISEG_E_LAUNCH, "gemm: memset"); }
-            else if (fill_words_2d_async(p->C, (size_t)p->ldc, 0, (size_t)p->N, (size_t)p->M, s) != hipSuccess) return set_error(MISEG_E_LAUNCH, "gemm: memset2d");
-          }
-          gemm_tn_partial_reduce_kernel<<<dim3(cdiv(p->M * (p->N / 4), 256), groups), 256, 0, s>>>(partial, (float*)p->C, p->ldc, p->M, p->N, pl.splits, p->accumulate);
-        }
-        MISEG_LAUNCH_CHECK("gemm_tn_stream");
-        return MISEG_OK;
-      }
-    }
-    if (p->tn_colsum) return set_error(MISEG_E_UNSUPPORTED, "gemm TN: column sums ride on the streaming path only (ask miseg_gemm_tn_fuses_colsum first)");
-    constexpr int TN_BK = std::is_same<T, bf16>::value ? 128 : 64;
-    if (p->split_k == 0) {   // auto: enough workgroups for the chip, >= 512 reduction rows each
-      const int tiles = cdiv(p->M, 64) * cdiv(p->N, 64);
-      split = cdiv(p->K, 512);
-      if (split > 1024 / tiles) split = 1024 / tiles;
-      if (split < 1) split = 1;
-    }
-    int kps = cdiv(cdiv(p->K, split), TN_BK) * TN_BK;
-    split = cdiv(p->K, kps);
-    mode = split > 1 ? 2 : (p->accumulate ? 1 : 0);
-    if (split > 1 && !p->accumulate) {
-      if (p->ldc == p->N) { if (fill_words_async(p->C, 0, (size_t)p->M * p->N, s) != hipSuccess) return set_error(MISEG_E_LAUNCH, "gemm: memset"); }
-      else if (fill_words_2d_async(p->C, (size_t)p->ldc, 0, (size_t)p->N, (size_t)p->M, s) != hipSuccess) return set_error(MISEG_E_LAUNCH, "gemm: memset2d");
-    }
-    dim3 grid(cdiv(p->M, 64), cdiv(p->N, 64), split);
-    gemm_tn_kernel<T, TO><<<grid, 256, 0, s>>>((const T*)p->A, p->lda, (const T*)p->B, p->ldb, (TO*)p->C, p->ldc, p->M, p->N, p->K, mode, al_a, al_b, kps);
-  } else {
-    return set_error(MISEG_E_UNSUPPORTED, "gemm: only NT (ta=tb=0) and TN (ta=tb=1) are implemented");
-  }
-  MISEG_LAUNCH_CHECK("gemm");
-  return MISEG_OK;
+  return set_error(MISEG_E_UNSUPPORTED, "gemm: no kernel %d for dtype %d -> %d", pl.kernel, p->dtype, p->out_dtype);
 }
 
 extern "C" int miseg_gemm(const miseg_gemm_params* p, miseg_stream_t s_) {
   hipStream_t s = (hipStream_t)s_;
-  MISEG_REQUIRE(p && p->A && p->B && p->C, MISEG_E_BADARG, "gemm: null pointer");
-  MISEG_REQUIRE(p->M > 0 && p->N > 0 && p->K > 0, MISEG_E_BADARG, "gemm: bad shape M=%d N=%d K=%d", p->M, p->N, p->K);
-  MISEG_REQUIRE(p->act == MISEG_ACT_NONE || p->act == MISEG_ACT_GELU, MISEG_E_UNSUPPORTED, "gemm: act %d", p->act);
-  if (p->dtype == MISEG_F32 && p->out_dtype == MISEG_F32) return launch_gemm<float, float>(p, s);
-  if (p->dtype == MISEG_BF16 && p->out_dtype == MISEG_BF16) return launch_gemm<bf16, bf16>(p, s);
-  if (p->dtype == MISEG_BF16 && p->out_dtype == MISEG_F32) return launch_gemm<bf16, float>(p, s);
-  return set_error(MISEG_E_BADARG, "gemm: dtype %d -> %d", p->dtype, p->out_dtype);
-}
-
-extern "C" int miseg_gemm_tn_fuses_colsum(const miseg_gemm_params* p) {
-  TnStreamPlan pl;
-  return (p && p->ta == 1 && p->tb == 1 && p->dtype == MISEG_BF16 && p->out_dtype == MISEG_F32 && tn_stream_plan(p, &pl)) ? 1 : 0;
-}
-
-extern "C" int miseg_gemm_tn_splits(const miseg_gemm_params* p) {
-  TnStreamPlan pl;
-  return (p && tn_stream_plan(p, &pl)) ? pl.splits : 0;
+  miseg_gemm_plan_info pl;
+  int rc = gemm_plan(p, &pl, true);
+  if (rc != MISEG_OK) return rc;
+  Epi epi{p->bias, p->act, p->res, p->ldres, p->aux, p->ldaux, p->epi_mode, (double*)p->stat, p->scat_d, p->scat_h, p->scat_w, p->scat_cout};
+  epi.bx = p->bs_x; epi.ldbx = p->ld_bs_x; epi.bstat_in = (const double*)p->bs_stat; epi.beps = p->bs_eps;
+  epi.an_stat = (const double*)p->an.stat; epi.an_styles = p->an.styles; epi.an_eps = p->an.eps; epi.an_out = p->an_out; epi.ld_an_out = p->ld_an_out;
+  for (int i = 0; i < MISEG_MAX_STYLES; ++i) { epi.an_gamma[i] = i < p->an.num_styles ? p->an.gamma[i] : nullptr; epi.an_beta[i] = i < p->an.num_styles ? p->an.beta[i] : nullptr; }
+  const char* name = pl.kernel == MISEG_GEMM_NT_RANK1 ? "gemm_nt_k1" : pl.kernel == MISEG_GEMM_NT_RANK1_STAT ? "gemm_nt_k1(stat)" : "gemm";
+  switch (pl.kernel) {
+    case MISEG_GEMM_NT_SMALL: rc = launch_nt_small(p, pl, epi, s); name = "gemm_nt_small"; break;
+    case MISEG_GEMM_NT_STREAM:
+      rc = launch_nt_stream(p, pl, epi, s);
+      name = pl.anorm ? "gemm_nt_stream(anorm)" : pl.stat == 2 ? "gemm_nt_stream(bstat)" : pl.scat ? "gemm_nt_stream(scatter)" : pl.stat ? "gemm_nt_stream(stat)" : "gemm_nt_stream";
+      break;
+    case MISEG_GEMM_TN_STREAM: rc = launch_tn_stream(p, pl, s); name = "gemm_tn_stream"; break;
+    default:      // the dtype pair is one of these three (gemm_plan)
+      if (p->out_dtype == MISEG_BF16) rc = launch_gemm_typed<bf16, bf16>(p, pl, epi, s);
+      else if (p->dtype == MISEG_BF16) rc = launch_gemm_typed<bf16, float>(p, pl, epi, s);
+      else rc = launch_gemm_typed<float, float>(p, pl, epi, s);
+  }
+  if (rc != MISEG_OK) return rc;
+  MISEG_LAUNCH_CHECK(name);
+  return MISEG_OK;
 }
 
 // the workgroup target of a whole group: what a lone product aims at by itself (tn_stream_plan).  Step A/B on one box, parent 166.9 / 166.6

@@ -69,6 +69,12 @@ GemmTnStreamDesc = _struct("GemmTnStreamDesc", cname="miseg_gemm_tn_stream_desc"
 GemmTnStreamPlan = _struct("GemmTnStreamPlan", cname="miseg_gemm_tn_stream_plan", fields=[("wm", i32), ("wn", i32), ("gx", i32), ("gy", i32), ("splits", i32), ("tps", i32), ("block0", i32),
                                                                                   ("pad_", i32), ("workspace_bytes", i64)])
 TN_STREAM_GROUP_CAP = 8      # MISEG_TN_STREAM_GROUP
+GEMM_NONE, GEMM_NT_RANK1, GEMM_NT_RANK1_STAT, GEMM_NT_SMALL, GEMM_NT_STREAM, GEMM_NT_GENERIC, GEMM_TN_STREAM, GEMM_TN_GENERIC = range(8)      # miseg_gemm_plan_info.kernel
+GEMM_OUT_STORE, GEMM_OUT_ACCUMULATE, GEMM_OUT_ATOMIC = 0, 1, 2      # miseg_gemm_plan_info.out_mode
+GemmPlan = _struct("GemmPlan", cname="miseg_gemm_plan_info", fields=[(f, i32) for f in (
+    "kernel", "mtw", "ntw", "k16", "nch", "gelu", "stat", "scat", "anorm", "nt", "wm", "wn", "grid_x", "grid_y", "grid_z", "row_tiles", "col_groups", "cols_per_group",
+    "splits", "k_per_split", "out_mode", "zero_fill", "reduce_groups", "reduce_blocks", "al_a", "al_b", "fuses_stat", "fuses_anorm", "fuses_bstat", "fuses_scatter",
+    "tn_fuses_colsum")] + [("lds_bytes", C.c_size_t), ("workspace_bytes", C.c_size_t)])
 Colsum = _struct("Colsum", cname="miseg_colsum_params", fields=[("x", vp), ("ldx", i64), ("rows", i64), ("C", i32), ("dtype", i32), ("out", vp), ("accumulate", i32)])
 Conv3 = _struct("Conv3", cname="miseg_conv3_params", fields=[("x", vp), ("ldx", i64), ("y", vp), ("ldy", i64), ("wpk", vp), ("B", i32), ("D", i32), ("H", i32),
                           ("W", i32), ("Cin", i32), ("Cout", i32), ("dtype", i32), ("workspace", vp), ("res", vp), ("ldres", i64), ("stat", vp), ("background", i32), ("defer_slabs", i32),
@@ -259,6 +265,7 @@ PROTOS = {
     "miseg_mlp_bwd": (i32, [C.POINTER(Mlp), vp]),
     "miseg_gemm_workspace_bytes": (C.c_size_t, [C.POINTER(Gemm)]),
     "miseg_gemm": (i32, [C.POINTER(Gemm), vp]),
+    "miseg_gemm_plan": (i32, [C.POINTER(Gemm), C.POINTER(GemmPlan)]),
     "miseg_permute3": (i32, [vp, vp, i32, i32, i32, i64, i64, i64, i32, vp]),
     "miseg_colsum": (i32, [C.POINTER(Colsum), vp]),
     "miseg_gemm_tn_splits": (i32, [C.POINTER(Gemm)]),

@@ -23,7 +23,9 @@ shapes = []
 orig_call = ops._call
 def rec(fn_name, params, prof=None, extra=()):
     if fn_name == "miseg_gemm" and prof is not None and prof[0] == "gemm_nt":
-        shapes.append((params.M, params.N, params.K, bool(params.res), bool(params.stat), params.act, getattr(params, "scat_d", 0)))
+        plan = ops.L.GemmPlan()
+        ops.L.load().miseg_gemm_plan(ops.C.byref(params), ops.C.byref(plan))
+        shapes.append((params.M, params.N, params.K, bool(params.res), bool(params.stat), params.act, getattr(params, "scat_d", 0), plan.kernel))
     return orig_call(fn_name, params, prof=prof, extra=extra)
 ops._call = rec
 prof = roofline.profile_step(step)
@@ -36,5 +38,5 @@ for (ms, fl, nb, allms), sh in zip(lst, shapes):
 tot = sum(r[0] for r in rows)
 for ms, sh, nb in rows:
     if ms * 1e3 >= 9.0:
-        print(f"M {sh[0]:7d} N {sh[1]:5d} K {sh[2]:5d} res {int(sh[3])} stat {int(sh[4])} act {sh[5]} : {ms*1e3:7.1f} us  {nb/1e6:7.1f} MB  {nb/ms/1e6:7.0f} GB/s")
+        print(f"M {sh[0]:7d} N {sh[1]:5d} K {sh[2]:5d} res {int(sh[3])} stat {int(sh[4])} act {sh[5]} kernel {sh[7]} : {ms*1e3:7.1f} us  {nb/1e6:7.1f} MB  {nb/ms/1e6:7.0f} GB/s")
 print(f"total {tot*1e3:.1f} us over {len(rows)} launches; launches below 9 us: {sum(1 for r in rows if r[0]*1e3 < 9.0)} = {sum(r[0] for r in rows if r[0]*1e3 < 9.0)*1e3:.1f} us")

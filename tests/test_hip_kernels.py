@@ -27,6 +27,15 @@ def _L():
     return lib
 
 
+def _gemm_plan(M, N, K, **fields):
+    """the plan miseg_gemm dispatches on for a contiguous, aligned problem of this shape (gemm_cases.params keywords)"""
+    import ctypes
+    import gemm_cases
+    plan = _L().GemmPlan()
+    assert _L().load().miseg_gemm_plan(ctypes.byref(gemm_cases.params(_L(), M, N, K, **fields)), ctypes.byref(plan)) == 0
+    return plan
+
+
 def rnd(*shape, dtype=torch.float32, seed=0, scale=1.0):
     g = torch.Generator().manual_seed(seed + sum(shape))
     return (torch.randn(*shape, generator=g) * scale).to(DEV).to(dtype)
@@ -257,6 +266,7 @@ def test_gemm_nt_streaming_path(M, N, K):
     half k-step of K = 48 / 144, N beyond one accumulator chunk, bias + GELU epilogue; exact on small integers."""
     ops, L = _ops(), _L()
     dtype = torch.bfloat16
+    assert {_gemm_plan(M, N, K, bias=1, act=act).kernel for act in (L.ACT_NONE, L.ACT_GELU)} == {L.GEMM_NT_STREAM}
     a, w, bias = rnd(M, K, dtype=dtype, seed=21), rnd(N, K, dtype=dtype, seed=22) / K ** 0.5, rnd(N, seed=23)
     yr = a.double() @ w.double().t() + bias
     y = ops.gemm_nt(a, w, bias)
@@ -283,6 +293,8 @@ def test_gemm_nt_streaming_statistics(M, N, K, with_res):
     dtype = torch.bfloat16
     a, w, bias = rnd(M, K, dtype=dtype, seed=21), rnd(N, K, dtype=dtype, seed=22) / K ** 0.5, rnd(N, seed=23)
     res = rnd(M, N, dtype=dtype, seed=24) if with_res else None
+    plan = _gemm_plan(M, N, K, bias=1, stat=1, res=1 << 12 if with_res else None)
+    assert (plan.kernel, plan.stat) == (L.GEMM_NT_STREAM if M > 2048 else L.GEMM_NT_SMALL, 1)
     ops.begin_step()
     y = ops.gemm_nt(a, w, bias, res=res, want_stat=True)
     st = ops.pop_gemm_stat(y)
@@ -318,6 +330,8 @@ def test_gemm_nt_scatter_is_the_transposed_conv_store(grid, Cin, Cout):
     assert done == (B * d * h * w >= 4096)
     if not done:
         return
+    plan = _gemm_plan(B * d * h * w, 8 * Cout, Cin, ldc=2 * Cout, scat=(d, h, w, Cout))
+    assert (plan.kernel, plan.scat) == (_L().GEMM_NT_STREAM, 1)
     ref = torch.full_like(cat, 7.0)
     ops.channel_to_space(ops.gemm_nt(x, wf), STD_OFFSETS, (B, 2 * d, 2 * h, 2 * w, Cout), out=ref[..., :Cout])
     assert torch.equal(cat, ref)                      # the right half (the skip's place) untouched
@@ -331,6 +345,8 @@ def test_gemm_nt_scatter_is_the_transposed_conv_store(grid, Cin, Cout):
 def test_gemm_nt_rank1(dtype):
     """K == 1 (the stem block's 1x1x1 shortcut on a one-channel image): the outer-product kernel"""
     ops = _ops()
+    dt = _L().BF16 if dtype == torch.bfloat16 else _L().F32
+    assert (_gemm_plan(5003, 48, 1, dt=dt, bias=1).kernel, _gemm_plan(5003, 48, 1, dt=dt, stat=1).kernel) == (_L().GEMM_NT_RANK1, _L().GEMM_NT_RANK1_STAT)
     a, w, bias = rnd(5003, 1, dtype=dtype, seed=31), rnd(48, 1, dtype=dtype, seed=32), rnd(48, seed=33)
     yr = a.double() @ w.double().t()
     assert_parity(ops.gemm_nt(a, w), yr, TOL[dtype], "rank-1 product")
@@ -353,6 +369,7 @@ def test_gemm_nt_small_path(M, N, K):
     """deep-stage linears (M <= 2048, K % 32 == 0) take the register-direct kernel with K split over the four waves."""
     ops, L = _ops(), _L()
     dtype = torch.bfloat16
+    assert {_gemm_plan(M, N, K, act=act).kernel for act in (L.ACT_NONE, L.ACT_GELU)} == {L.GEMM_NT_SMALL}
     a, w, bias = rnd(M, K, dtype=dtype, seed=21), rnd(N, K, dtype=dtype, seed=22) / K ** 0.5, rnd(N, seed=23)
     yr = a.double() @ w.double().t() + bias
     assert_parity(ops.gemm_nt(a, w, bias), yr, TOL[dtype], "bias")
@@ -368,6 +385,8 @@ def test_gemm_nt_small_path(M, N, K):
 def test_gemm_nt_epilogues(dtype, M, N, K):
     """residual add, pre-activation side output and GELU-derivative epilogues on every NT kernel (streaming, small, generic)."""
     ops, L = _ops(), _L()
+    family = {5000: L.GEMM_NT_STREAM, 13824: L.GEMM_NT_STREAM, 216: L.GEMM_NT_SMALL, 300: L.GEMM_NT_GENERIC}[M] if dtype == torch.bfloat16 else L.GEMM_NT_GENERIC
+    assert _gemm_plan(M, N, K, dt=L.BF16 if dtype == torch.bfloat16 else L.F32, bias=1, res=1 << 12, aux=1 << 12, epi_mode=1, act=L.ACT_GELU).kernel == family
     a, w, bias = rnd(M, K, dtype=dtype, seed=21), rnd(N, K, dtype=dtype, seed=22) / K ** 0.5, rnd(N, seed=23)
     res, h = rnd(M, N, dtype=dtype, seed=24), rnd(M, N, dtype=dtype, seed=25)
     z = a.double() @ w.double().t() + bias
@@ -426,6 +445,8 @@ def test_gemm_with_the_instance_norm_folded_into_its_operand_load(M, K, N, gelu,
     norm(x) and for the GELU pre-activation; the Swin shapes qkv @ 48^3 / 24^3, fc1 @ 24^3 and a ragged row count."""
     ops, L = _ops(), _L()
     dt = torch.bfloat16
+    plan = _gemm_plan(M, N, K, an=2 if styled else 1, act=L.ACT_GELU if gelu else L.ACT_NONE)
+    assert (plan.kernel, plan.anorm, plan.gelu) == (L.GEMM_NT_STREAM if M > 2048 else L.GEMM_NT_SMALL, 1, int(gelu))
     x = (rnd(1, M, K, dtype=torch.float32, seed=91) * 1.7 + 0.4).to(dt)
     w, b = (rnd(N, K, seed=92) / K ** 0.5).to(dt), rnd(N, seed=93) / 4
     gam = [rnd(K, seed=94) * 0.2 + 1.0, rnd(K, seed=95) * 0.2 + 1.0] if styled else None
@@ -462,6 +483,8 @@ def test_gemm_with_the_norm_backward_sums_in_its_epilogue(M, K, N):
     norm's backward bar."""
     ops = _ops()
     dt = torch.bfloat16
+    plan = _gemm_plan(M, N, K, stat=1, stat_mode=2, bs_x=1 << 12)
+    assert (plan.kernel, plan.stat) == (_L().GEMM_NT_STREAM if M > 2048 else _L().GEMM_NT_SMALL, 2)
     dy = rnd(1, M, K, dtype=dt, seed=101)
     wt = (rnd(N, K, seed=102) / K ** 0.5).to(dt)
     x = (rnd(1, M, N, dtype=torch.float32, seed=103) * 1.3 - 0.2).to(dt)
@@ -895,6 +918,7 @@ def test_gemm_tn_with_the_bias_gradient_in_its_launch(K, M, N):
         ops.gemm_tn(dy, x, out=dw, accumulate=True, colsum_out=db)
         p = ops.L.Gemm(ops._ptr(dy), M, ops._ptr(x), N, ops._ptr(dw), N, M, N, K, 1, 1, ops.L.BF16, ops.L.F32, None, ops.L.ACT_NONE, 1, 0, None, None, 0, None, 0, 0, 0)
         fused = bool(ops.L.load().miseg_gemm_tn_fuses_colsum(ops.C.byref(p)))
+        assert (_gemm_plan(M, N, K, tn=1, accumulate=1).kernel == ops.L.GEMM_TN_STREAM) == fused
         assert fused == (M % 48 == 0 and N % 48 == 0 and K >= 2048)
         assert len(ops.DEFAULT_QUEUES.colsum) == (0 if fused else 1)
         ops.DEFAULT_QUEUES.flush()

@@ -295,6 +295,11 @@ def test_swin_block_and_decoder_block_grouped_against_ungrouped():
     from mi_seg_amd.networks.norms.utils import parse_normalization
     from mi_seg_amd.runtime.arena import ParamArena
     from mi_seg_amd.utils.detfill import fill_module_
+    import gemm_cases
+    L = _L()
+    for M, N in ((144, 48), (48, 48), (192, 48), (48, 192)):      # dW of qkv, proj, fc1, fc2 over the 4096 tokens
+        plan = L.GemmPlan()
+        assert L.load().miseg_gemm_plan(C.byref(gemm_cases.params(L, M, N, 4096, tn=1, accumulate=1)), C.byref(plan)) == 0 and plan.kernel == L.GEMM_TN_STREAM
     cond, inst = parse_normalization("instance_cond", True, 4, 2), parse_normalization("instance", True, 4, 2)
     swin = SwinTransformerBlock(48, 3, (7, 7, 7), (3, 3, 3), norm_type=cond)
     up = UnetrUpBlock(3, 96, 48, 3, 2, inst, res_block=True)
