@@ -926,6 +926,33 @@ int miseg_opt_step_pack_conv3_clipped(const miseg_opt_step_params* p, const mise
                                       int total_tiles, int dtype, int64_t* pack_state, const miseg_grad_clip_record* rec_dev, int mode, float clip_value,
                                       miseg_stream_t stream);
 
+/* Gradient accumulation over the micro-batches of a window (the reference's --iters_to_accumulate, utils/trainer.py:33-78, and Lightning's
+ * --accumulate_grad_batches; a new symbol and struct: MISEG_ABI_VERSION stays 16).  Every micro-batch runs its forward and backward pass as a
+ * step of its own (zero fill, storing weight-gradient kernels); miseg_grad_fold then streams once over the gradient arena `grad` and a second
+ * flat fp32 buffer `acc` laid out like it, in miseg_opt_step's geometry (the same descriptor table over ALL parameters; `param` is not
+ * looked at).  ops[i] (device int32 [ndesc]) says what happens to parameter i:  u (bit 0) = it has a gradient in this micro-batch,
+ * a (bit 1) = it had one in an earlier micro-batch of this window, F (bit 2) = this micro-batch closes the window.  Per element, every
+ * operation rounded on its own in fp32 (no contraction):
+ *   0, 2, 4      nothing: neither buffer's slot is read or written (it may hold anything)
+ *   1 (u)        acc = g                          acc is not read
+ *   3 (u, a)     acc = fl(acc + g)
+ *   5 (F, u)     grad = fl(g * scale)             acc is not touched
+ *   6 (F, a)     grad = fl(acc * scale)           the arena slot is not read
+ *   7 (F, u, a)  grad = fl(fl(acc + g) * scale)
+ * After the closing call the ARENA holds scale x the window's sum in micro-batch order (scale = fl(1 / window length): the mean), and
+ * miseg_grad_norm / miseg_opt_step* run on it unchanged with used[] = the union of the window.  No atomics; equal bits every run.
+ * Refused before any launch: a wrong struct_size, a null pointer, ndesc / total_blocks / arena_elems < 1, a scale that is not finite or
+ * <= 0, grad / acc not 16-byte aligned, [grad, grad + arena_elems) and [acc, acc + arena_elems) overlapping. */
+typedef struct {
+  uint32_t struct_size;
+  const miseg_opt_desc* descs_dev; int ndesc, total_blocks;
+  float* grad; float* acc;
+  const int32_t* ops;
+  int64_t arena_elems;             /* elements of each of the two buffers (the overlap check) */
+  float scale;
+} miseg_grad_fold_params;
+int miseg_grad_fold(const miseg_grad_fold_params* p, miseg_stream_t stream);
+
 /* Sliding-window stitching (MONAI sliding_window_inference, mode="constant", as used at lightning_monai.py:86-93,187): every window's logits
  * stay resident (win: fp32 [nd*nh*nw][C][rd][rh][rw], window (id, ih, iw) at index (id*nh + ih)*nw + iw, origin (start_d[id], start_h[ih],
  * start_w[iw]); 700 windows x 6 x 96^3 = 14.9 GB of the 288), and ONE gather pass writes out[c][d][h][w] = (sum over the windows covering the

@@ -187,6 +187,10 @@ GradClipRecord = _struct("GradClipRecord", cname="miseg_grad_clip_record", field
 GradNorm = _struct("GradNorm", cname="miseg_grad_norm_params", fields=[
     ("struct_size", C.c_uint32), ("mode", i32), ("descs_dev", vp), ("ndesc", i32), ("total_blocks", i32), ("grad", vp), ("used", vp), ("max_norm", f32),
     ("skip_nonfinite", i32), ("workspace", vp), ("record", vp), ("per_param", vp)])
+GradFold = _struct("GradFold", cname="miseg_grad_fold_params", fields=[
+    ("struct_size", C.c_uint32), ("descs_dev", vp), ("ndesc", i32), ("total_blocks", i32), ("grad", vp), ("acc", vp), ("ops", vp), ("arena_elems", i64),
+    ("scale", f32)])
+FOLD_USED, FOLD_EARLIER, FOLD_CLOSE = 1, 2, 4                          # bits of miseg_grad_fold's per-parameter op code (u, a, F)
 CLIP_NONE, CLIP_NORM, CLIP_VALUE = 0, 1, 2                             # MISEG_CLIP_*
 CLIP_MODES = {"norm": CLIP_NORM, "value": CLIP_VALUE}
 Stitch = _struct("Stitch", cname="miseg_stitch_params", fields=[
@@ -342,6 +346,7 @@ PROTOS = {
     "miseg_opt_step_pack_conv3": (i32, [C.POINTER(OptStep), vp, vp, i32, i32, i32, vp, vp]),
     "miseg_grad_norm_workspace_bytes": (C.c_size_t, [i32, i32]),
     "miseg_grad_norm": (i32, [C.POINTER(GradNorm), vp]),
+    "miseg_grad_fold": (i32, [C.POINTER(GradFold), vp]),
     "miseg_opt_step_clipped": (i32, [C.POINTER(OptStep), vp, i32, f32, vp]),
     "miseg_opt_step_pack_conv3_clipped": (i32, [C.POINTER(OptStep), vp, vp, i32, i32, i32, vp, vp, i32, f32, vp]),
     "miseg_stitch_windows": (i32, [C.POINTER(Stitch), vp]),

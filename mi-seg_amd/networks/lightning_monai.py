@@ -151,6 +151,18 @@ class LitMonai(_Base):
                               gradient_clip_val=d.get("gradient_clip_val"), gradient_clip_algorithm=d.get("gradient_clip_algorithm") or "norm",
                               skip_nonfinite=bool(d.get("skip_nonfinite_steps")), track_grad_norm=d.get("track_grad_norm", -1))
 
+    @property
+    def accumulation_steps(self):
+        """micro-batches per optimisation step, from the --accumulate_grad_batches / --iters_to_accumulate that arrived through **kwargs"""
+        from ..utils.parser import accumulation_steps
+        return accumulation_steps(self.__dict__)
+
+    def configure_train_step(self, arena, optimizer, batch_shape, label_shape):
+        """the whole training step (forward, loss, backward, the fused optimiser of configure_fused_optimizer) as replayed hipGraphs
+        (runtime/graph.py::GraphedTrainStep), with this module's gradient accumulation: call it once per micro-batch"""
+        from ..runtime.graph import GraphedTrainStep
+        return GraphedTrainStep(self.model, self.criterion, optimizer, batch_shape, label_shape, arena, accumulate_grad_batches=self.accumulation_steps)
+
     def configure_optimizers(self):
         if self.optim_name == "adam":
             opt = torch.optim.Adam(self.parameters(), lr=self.learning_rate, weight_decay=self.reg_weight)

@@ -376,11 +376,19 @@ class GraphedTrainStep:
     The optimiser kernel bumps the arena's device-side parameter version, so the refresh launches at the head of the NEXT replay re-cast
     and re-pack every weight (runtime/arena.py: versioned refresh) - the cost a real training loop pays and the forward + backward
     benchmark does not.  The learning rate lives in a device scalar (`set_lr`), so schedulers work under replay.  One graph per set of
-    modalities present in the batch (which conditional-norm rows get a gradient, and are touched by the optimiser, is recorded work)."""
+    modalities present in the batch (which conditional-norm rows get a gradient, and are touched by the optimiser, is recorded work).
 
-    def __init__(self, model, criterion, optimizer, batch_shape, label_shape, arena, label_dtype=torch.int32, warmup=2):
+    accumulate_grad_batches = k > 1: a call is one MICRO-batch and every k-th call (or one with last=True) an optimisation
+    step on the mean gradient of its window.  Two graphs per modality set then: "fold" = forward + backward + miseg_grad_fold, and
+    "fold_step" = the same with the closing fold and the optimiser behind it (training/optim.py::GradAccumulator).  k == 1 captures and
+    replays exactly what it always did."""
+
+    def __init__(self, model, criterion, optimizer, batch_shape, label_shape, arena, label_dtype=torch.int32, warmup=2, accumulate_grad_batches=1):
         if arena is None or optimizer.arena is not arena:
             raise ValueError("GraphedTrainStep needs the model's ParamArena and an ArenaOptimizer built over it")
+        from ..training.optim import GradAccumulator
+        acc = GradAccumulator(optimizer, accumulate_grad_batches)
+        self.acc = acc if acc.active else None
         self.model, self.criterion, self.opt, self.arena = model, criterion, optimizer, arena
         dev = arena.flat.device
         self.x = torch.zeros(*batch_shape, dtype=torch.float32, device=dev)
@@ -393,8 +401,9 @@ class GraphedTrainStep:
         # opt-in (MISEG_EARLY_OPT=1): measured SLOWER on the headline net - 138.1 / 137.3 patches/s against 140.1 / 139.1 with the one-launch
         # step behind the pass (same box): 1.2 GB of optimiser traffic beside the end-of-pass grouped launches lengthens the tail by more than
         # the 0.28 ms it takes off the chain (the same finding as the tiny-volume weight gradients on the branch, hip/ops.py::conv3_wgrad)
-        # (ignored with gradient clipping / the non-finite guard on: the early launch would run before the step's gradient norm exists)
-        self.early_optimizer = bool(os.environ.get("MISEG_EARLY_OPT")) and not optimizer.clipping
+        # (ignored with gradient clipping / the non-finite guard on: the early launch would run before the step's gradient norm exists - and
+        # with accumulation: before the window's mean does)
+        self.early_optimizer = bool(os.environ.get("MISEG_EARLY_OPT")) and not optimizer.clipping and self.acc is None
         if optimizer.lr_dev is None:
             optimizer.lr_dev = torch.tensor([optimizer.lr], dtype=torch.float32, device=dev)
 
@@ -407,7 +416,7 @@ class GraphedTrainStep:
         """the optimiser's static device scalar: global L2 norm of the last replay's gradient before clipping (ArenaOptimizer.grad_norm)"""
         return self.opt.grad_norm
 
-    def _run(self, host, optimise):
+    def _run(self, host, optimise, fold=False):
         # round 5, opt-in (self.early_optimizer): the parameters whose gradients are final when the main chain of the backward pass ends (the
         # tiny-volume conv weights of encoder10 / decoder5: 70 % of the headline net's bytes) are updated on the branch stream beside the
         # end-of-pass grouped launches (ops.join_branch -> branch_end_hook), the rest behind the pass: two launches over disjoint tables
@@ -420,31 +429,57 @@ class GraphedTrainStep:
             self.arena.end_backward()
         finally:
             self.arena.branch_end_hook = None
+        if fold:
+            self.acc.fold()                        # (its op codes are static too: GradAccumulator.plan() uploads them before every replay)
         if optimise:
             self.opt.step(update_flags=False)      # the flags of this graph are static: copied to the device before every replay
         return loss.detach()
 
-    def _capture(self, host):
+    def _capture(self, host, optimise=True):
+        """optimise=False (accumulation only): the "fold" form, which ends in the fold and leaves the optimiser out"""
+        fold = self.acc is not None
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            for _ in range(max(self.warmup, 2)):      # step 1 registers the weight re-layouts; no optimiser step: weights and moments stay put
+            # step 1 registers the weight re-layouts; no optimiser step: weights and moments stay put (and no fold: a window may be open)
+            for _ in range(max(self.warmup, 2)):
                 self._run(host, False)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         if self.early_optimizer:      # which parameters the warm-up steps wrote inline (none: the one-launch optimiser step)
             self.opt.split_early(getattr(self.arena, "inline_final_params", []))
         self.opt.prepare()            # device tables of the fused conv-weight launch: uploaded here, not under capture
+        if fold:
+            self.acc.prepare()
         for p in self.arena.params:
             p.grad = None
         g = _Graph()
         with _graph_capture(g):
-            loss = self._run(host, True)
+            loss = self._run(host, optimise, fold)
         ops.STAT_POOL.pin()
         return g, [bool(p._miseg_used) for p in self.arena.params], loss
 
-    def __call__(self, x, label, modalities):
-        """one optimisation step on (x [B,C,D,H,W] fp32, label [B,1,D,H,W] class ids); returns the loss (0-dim device tensor, static buffer)"""
+    def _call_accumulating(self, host, last):
+        """a micro-batch of a window (accumulate_grad_batches > 1): the inputs are in the static buffers"""
+        closes = self.acc.closes(last)
+        key = tuple(sorted(set(host))) + (len(host), "fold_step" if closes else "fold")
+        if key not in self.graphs:
+            self.graphs[key] = self._capture(host, optimise=closes)
+        g, used, loss = self.graphs[key]
+        for p, u in zip(self.arena.params, used):
+            p._miseg_used = u
+            p.grad = None                      # (no gradient to look at inside a window: the arena holds one micro-batch's)
+        if self.acc.plan(last) != closes:
+            raise RuntimeError("GradAccumulator.plan() and closes() disagree")
+        g.replay()
+        if closes:      # plan() has published the window's union (flags, p.grad); a non-closing replay changed no parameter: neither the host
+            self.arena.epoch += 1      # epoch nor the device's parameter version moves, and the next replay's weight refresh is a no-op
+        return loss
+
+    def __call__(self, x, label, modalities, last=None):
+        """one optimisation step on (x [B,C,D,H,W] fp32, label [B,1,D,H,W] class ids); returns the loss (0-dim device tensor, static buffer).
+        With accumulate_grad_batches = k > 1: one micro-batch; the k-th call of a window - or one with last=True, which closes a short window
+        at the end of an epoch (the mean still divides by k) - also steps.  The loss returned is the micro-batch's own, unscaled."""
         host = _check_styles(self.model, modalities, self.x.shape[0])
         self.x.copy_(x, non_blocking=True)
         self.label.copy_(label, non_blocking=True)
@@ -452,6 +487,8 @@ class GraphedTrainStep:
             self.styles.copy_(torch.tensor(host, dtype=torch.int32), non_blocking=True)
             self._styles_host = tuple(host)
         self.arena.params_changed()
+        if self.acc is not None:
+            return self._call_accumulating(host, last)
         key = tuple(sorted(set(host))) + (len(host),)
         if key not in self.graphs:
             self.graphs[key] = self._capture(host)

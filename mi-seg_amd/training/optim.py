@@ -295,3 +295,97 @@ class ArenaOptimizer:
         if self.state2 is not None:
             self.state2.copy_(sd["state2"])
         self.steps.copy_(sd["steps"])
+
+
+def accumulation_scale(k):
+    """fl(1 / k) in float32: what miseg_grad_fold multiplies a window's sum by"""
+    return float(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(k), dtype=torch.float32))
+
+
+class GradAccumulator:
+    """Gradient accumulation over `accumulate_grad_batches` micro-batches on the device (the reference's --iters_to_accumulate,
+    utils/trainer.py:33-78; Lightning's --accumulate_grad_batches).  Every micro-batch is a step of its own for the arena
+    (zero fill, storing weight-gradient kernels); after its backward pass ONE launch (miseg_grad_fold) adds the arena into `acc`, a second flat
+    fp32 buffer laid out like it, and on the micro-batch that closes the window writes the window's mean back into the ARENA, where the
+    norm, the update kernels and `p.grad` find it.  Which parameters have a gradient in a micro-batch is the host's `_miseg_used`; the launch
+    gets one op code per parameter.  A parameter absent from the whole window keeps `grad is None`: no update, no step count.
+
+        arena.begin_step(); loss.backward(); arena.publish()
+        closes = acc.plan(); acc.fold()
+        if closes: opt.step()
+
+    The mean is sum-then-scale: fl(fl(g1 + g2 + ..) * fl(1/k)); the scale stays 1/k for a window closed early (`plan(last=True)`), like the
+    reference and Lightning.  accumulate_grad_batches == 1: inert - no buffer, no launch, plan() returns True."""
+
+    def __init__(self, optimizer, accumulate_grad_batches):
+        k = int(accumulate_grad_batches)
+        if k < 1 or k != accumulate_grad_batches:
+            raise ValueError("accumulate_grad_batches {!r} must be an integer >= 1".format(accumulate_grad_batches))
+        self.opt, self.k = optimizer, k
+        self.scale = accumulation_scale(k)
+        self.acc = self.ops = None
+        self._patterns = {}          # bytes of a micro-batch's op codes -> the same codes on the device (grow-only: see plan())
+        self._seen = None            # per parameter: it had a gradient in an earlier micro-batch of the open window
+        self._count = 0              # micro-batches of the open window planned so far
+
+    @property
+    def active(self):
+        return self.k > 1
+
+    def prepare(self):
+        """allocate `acc` and the static op-code tensor - ONCE: a captured hipGraph holds their addresses; call before capturing fold()"""
+        if self.active and self.acc is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("GradAccumulator.prepare() must run before fold() is captured (it allocates the accumulator)")
+            flat = self.opt.arena.flat
+            self.acc = torch.empty_like(flat)          # never read before its first write of a window (op 1)
+            self.ops = torch.zeros(len(self.opt.arena.params), dtype=torch.int32, device=flat.device)
+            self._seen = [False] * len(self.opt.arena.params)
+
+    def closes(self, last=None):
+        """whether the coming micro-batch closes the window: the k-th one, or any one with last=True (a short window at the end of an epoch)"""
+        return (not self.active) or bool(last) or self._count + 1 >= self.k
+
+    def plan(self, last=None):
+        """the host bookkeeping of the coming micro-batch, outside capture and before the launch (or replay) that folds it: reads the
+        parameters' `_miseg_used`, uploads the op codes and returns whether this micro-batch closes the window.  On close the window's union
+        becomes the parameters' `_miseg_used` / `grad` and the optimiser's device flags, so opt.step(update_flags=False) may follow."""
+        if not self.active:
+            return True
+        self.prepare()
+        params = self.opt.arena.params
+        closes = self.closes(last)
+        used = [bool(p._miseg_used) for p in params]
+        key = bytes((L.FOLD_USED if u else 0) | (L.FOLD_EARLIER if a else 0) | (L.FOLD_CLOSE if closes else 0) for u, a in zip(used, self._seen))
+        # each distinct pattern is uploaded ONCE from a host buffer of its own and then copied device-to-device on the stream, and no entry is
+        # ever dropped: the reasons written in ArenaOptimizer.set_used_from_arena
+        dev = self._patterns.get(key)
+        if dev is None:
+            dev = self._patterns[key] = torch.tensor(list(key), dtype=torch.int32, device=self.ops.device)
+        self.ops.copy_(dev, non_blocking=True)
+        self._seen = [a or u for u, a in zip(used, self._seen)]
+        self._count += 1
+        if closes:
+            for p, v, u in zip(params, self.opt.arena.views, self._seen):
+                p._miseg_used = u
+                p.grad = v if u else None
+            self.opt.set_used_from_arena()
+            self.reset()
+        return closes
+
+    def fold(self):
+        """enqueue miseg_grad_fold for the micro-batch plan() prepared: one launch and nothing else, so it can be captured"""
+        if not self.active:
+            return
+        if self.acc is None:
+            self.prepare()          # (raises under capture)
+        opt = self.opt
+        p = L.GradFold(C.sizeof(L.GradFold), opt._table.data_ptr(), len(opt.arena.params), opt._blocks, opt.arena.flat.data_ptr(), self.acc.data_ptr(),
+                       self.ops.data_ptr(), opt.arena.flat.numel(), self.scale)
+        ops._call("miseg_grad_fold", p)
+
+    def reset(self):
+        """drop an open window: the next micro-batch starts a new one (`acc` needs no clearing: a window's first use of a slot overwrites it)"""
+        if self._seen is not None:
+            self._seen = [False] * len(self._seen)
+        self._count = 0

@@ -5,6 +5,14 @@ from argparse import ArgumentParser
 
 _T = "store_true"
 
+
+def _positive_int(text):
+    """argparse type of a count that must be >= 1"""
+    v = int(text)
+    if v < 1:
+        raise ValueError("{} is not >= 1".format(text))          # (argparse turns a type's ValueError into its usage error)
+    return v
+
 MODEL_ARGS = {
     "monai.net": [
         ("--pretrained", dict(type=str, help="path to pre-trained model checkpoint")),
@@ -103,8 +111,27 @@ TRAINER_ARGS = {
         ("--gradient_clip_algorithm", dict(default="norm", type=str, choices=("norm", "value"))),
         ("--track_grad_norm", dict(default=-1, type=int, choices=(-1, 2), help="2: compute the gradients' L2 norm every step for logging; -1: off")),
         ("--skip_nonfinite_steps", dict(action=_T, help="an optimisation step whose gradient norm is inf or NaN changes nothing")),
+        ("--accumulate_grad_batches", dict(default=1, type=_positive_int, help="micro-batches per optimisation step: the step runs on their mean gradient")),
     ],
 }
+
+
+def accumulation_steps(args):
+    """micro-batches per optimisation step (training/optim.py::GradAccumulator): Lightning's --accumulate_grad_batches, else the reference's
+    own --iters_to_accumulate (utils/trainer.py:33-78).  `args`: a namespace or a dict; a missing (or None) flag counts as 1.  ValueError for
+    a count below 1 and for two counts above 1 that differ."""
+    get = args.get if isinstance(args, dict) else (lambda k, d=None: getattr(args, k, d))
+    vals = {}
+    for k in ("accumulate_grad_batches", "iters_to_accumulate"):
+        v = get(k, None)
+        v = 1 if v is None else v
+        if isinstance(v, bool) or int(v) != v or int(v) < 1:
+            raise ValueError("{} {!r} must be an integer >= 1".format(k, v))
+        vals[k] = int(v)
+    a, b = vals["accumulate_grad_batches"], vals["iters_to_accumulate"]
+    if a > 1 and b > 1 and a != b:
+        raise ValueError("--accumulate_grad_batches {} and --iters_to_accumulate {} disagree: give one of them".format(a, b))
+    return a if a > 1 else b
 
 
 def _add(parser: ArgumentParser, table):
