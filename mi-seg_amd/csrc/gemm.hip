@@ -1204,7 +1204,7 @@ static int gemm_plan(const miseg_gemm_params* p, miseg_gemm_plan_info* pl, bool 
       return MISEG_OK;
     }
     if (p->tn_colsum) GEMM_REFUSE(MISEG_E_UNSUPPORTED, "gemm TN: column sums ride on the streaming path only (ask miseg_gemm_tn_fuses_colsum first)");
-    if (p->split_k == 0) {      // auto: enough workgroups for the chip, >= 512 reduction rows each
+    if (p->split_k == 0 && f32out) {      // auto: enough workgroups for the chip, >= 512 reduction rows each (splits meet in fp32 atomics: bf16 output keeps one)
       const int tiles = cdiv(M, 64) * cdiv(N, 64);
       split = cdiv(K, 512);
       if (split > 1024 / tiles) split = 1024 / tiles;
@@ -1269,8 +1269,8 @@ static int gemm_plan(const miseg_gemm_params* p, miseg_gemm_plan_info* pl, bool 
   }
   pl->kernel = MISEG_GEMM_NT_GENERIC;
   pl->nt = (N % 64 == 0) ? 4 : (N % 48 == 0) ? 3 : (N <= 16) ? 1 : (N <= 32) ? 2 : (N <= 48) ? 3 : 4;
-  // (4) the mode is the requested split_k's, the fill the rounded split's: split_k > 1 over a K of one stage adds to an unfilled C
-  pl->out_mode = p->split_k > 1 ? MISEG_GEMM_OUT_ATOMIC : accumulate;
+  // (4) mode and fill both follow the rounded split: split_k > 1 over a K of one stage is ONE split, which stores (or accumulates if asked)
+  pl->out_mode = pl->splits > 1 ? MISEG_GEMM_OUT_ATOMIC : accumulate;
   pl->zero_fill = pl->splits > 1 && !p->accumulate;
   pl->grid_x = cdiv(M, 128); pl->grid_y = cdiv(N, 16 * pl->nt); pl->grid_z = pl->splits;
   return MISEG_OK;

@@ -1,6 +1,7 @@
 """The table of miseg_gemm launches (tests/test_gemm_plan_cpu.py; scripts/gemm_table.py launches the same rows on the card) and the sweep
 over the seven question entry points.  A row is (id, params keywords, expected plan fields); the expected fields were worked out by hand from
-the dispatcher's text as it stood before miseg_gemm_plan existed, not printed from the plan.  CPU only: the plan touches no device."""
+the dispatcher's text as it stood before miseg_gemm_plan existed, not printed from the plan.  FORM_ROWS (further down) are the card-sized
+rows of every form that tests/test_hip_gemm_forms.py launches and judges.  CPU only: the plan touches no device."""
 import hashlib
 import struct
 
@@ -174,7 +175,7 @@ ROWS = [
     _r("nt-f32-split4", 256, 64, 512, dict(kernel=NT_GENERIC, grid_z=4, splits=4, k_per_split=128, out_mode=ATOMIC, zero_fill=1), dt=0, split_k=4),
     _r("nt-f32-split4-acc", 256, 64, 512, dict(kernel=NT_GENERIC, splits=4, out_mode=ATOMIC, zero_fill=0), dt=0, split_k=4, accumulate=1),
     _r("nt-bf16-f32-split4", 256, 40, 512, dict(kernel=NT_GENERIC, nt=3, grid_y=1, splits=4, k_per_split=128, out_mode=ATOMIC, zero_fill=1), odt=0, split_k=4),
-    _r("nt-f32-split4-one-stage", 64, 64, 32, dict(kernel=NT_GENERIC, splits=1, k_per_split=32, out_mode=ATOMIC, zero_fill=0), dt=0, split_k=4),
+    _r("nt-f32-split4-one-stage", 64, 64, 32, dict(kernel=NT_GENERIC, splits=1, k_per_split=32, out_mode=STORE, zero_fill=0), dt=0, split_k=4),
     _r("nt-bf16-split4-refused", 256, 64, 512, dict(rc=BADARG), split_k=4),
     _r("nt-bf16-acc-refused", 256, 64, 512, dict(rc=BADARG), accumulate=1),
     _r("nt-split4-gelu-refused", 256, 64, 512, dict(rc=BADARG), dt=0, split_k=4, act=GELU),
@@ -333,3 +334,308 @@ def sweep(so, L, count, seed, each=None):
         for K in K_VALUES:
             ask(_build(L, kw["M"], kw["N"], K, base))
     return h.hexdigest(), asked, dict(zip(QUESTIONS, yes))
+
+
+# ================================================================================================ the rows launched on the card
+# FORM_ROWS: card-sized launches of every form (tests/test_hip_gemm_forms.py launches each; tests/test_gemm_plan_cpu.py pins the plans here).
+# A row is (id, keywords, expected plan fields); the id spells the form, the expected fields were worked out by hand from gemm_plan's text.
+# Keywords: M, N, K, tn, dt, odt as in params(); bias / res / stat / bstat / an_out / colsum / defer / ints = 1; act; epi = epi_mode (aux is
+# implied); an = number of styles of a folded norm; scat = (d, h, w, cout) with M = B d h w; split_k; accumulate; lay = {operand: layout of
+# tests/layouts.py} for the row views A, B, C, res, aux, bs_x, an_out ("left": the left half of rows twice as wide, the scattered store's C).
+ES = {0: 4, 1: 2}      # bytes per element of MISEG_F32 / MISEG_BF16
+
+
+def layout(c, es, lay):
+    """(element offset of the view's first column, row stride) of a row view of c columns: what tests/layouts.py::Slot builds"""
+    n = 16 // es
+    cp = -(-c // n) * n
+    return {"contig": (0, c), "slice": (n, cp + 3 * n), "off8": (n // 2, cp + 2 * n), "ldodd": (0, cp + n + 1), "off4": (n // 4, cp + 2 * n),
+            "off2": (n // 8, cp + 2 * n), "left": (0, 2 * c)}[lay]
+
+
+def dtypes(kw):
+    tn, dt = kw.get("tn", 0), kw.get("dt", 1)
+    return dt, kw.get("odt", 0 if tn else dt)
+
+
+def operand_cols(kw):
+    """name -> (columns, bytes per element) of every row view the row's launch passes"""
+    dt, odt = dtypes(kw)
+    M, N, K = kw["M"], kw["N"], kw["K"]
+    if kw.get("tn", 0):
+        return dict(A=(M, ES[dt]), B=(N, ES[dt]), C=(N, ES[odt]))
+    d = dict(A=(K, ES[dt]), B=(K, ES[dt]), C=(kw["scat"][3] if "scat" in kw else N, ES[odt]))
+    for name, on in (("res", kw.get("res")), ("aux", kw.get("epi")), ("bs_x", kw.get("bstat"))):
+        if on:
+            d[name] = (N, ES[odt])
+    if kw.get("an_out"):
+        d["an_out"] = (K, ES[dt])
+    return d
+
+
+def form_params(L, kw, at=None):
+    """the miseg_gemm_params of a FORM_ROWS row.  at: name -> (address, row stride) of the real row views and name -> address of the real
+    bias / stat / bs_stat / an_stat / workspace / tn_colsum buffers; None: stand-in addresses with each layout's alignment and stride"""
+    tn = kw.get("tn", 0)
+    dt, odt = dtypes(kw)
+    cols = operand_cols(kw)
+
+    def view(name):
+        if at is not None:
+            return at[name]
+        c, es = cols[name]
+        off, ld = layout(c, es, kw.get("lay", {}).get(name, "contig"))
+        return A + off * es, ld
+
+    def buf(name):
+        return at[name] if at is not None else A
+
+    p = L.Gemm()
+    (p.A, p.lda), (p.B, p.ldb), (p.C, p.ldc) = view("A"), view("B"), view("C")
+    p.M, p.N, p.K, p.ta, p.tb, p.dtype, p.out_dtype = kw["M"], kw["N"], kw["K"], tn, tn, dt, odt
+    p.split_k = kw.get("split_k", 0 if tn else 1)
+    p.accumulate, p.act, p.epi_mode, p.defer_reduce = kw.get("accumulate", 0), kw.get("act", 0), kw.get("epi", 0), kw.get("defer", 0)
+    if kw.get("bias"):
+        p.bias = buf("bias")
+    if kw.get("res"):
+        p.res, p.ldres = view("res")
+    if kw.get("epi"):
+        p.aux, p.ldaux = view("aux")
+    if kw.get("stat") or kw.get("bstat"):
+        p.stat = buf("stat")
+    if kw.get("bstat"):
+        p.stat_mode, p.bs_stat, p.bs_eps = 2, buf("bs_stat"), 1e-5
+        p.bs_x, p.ld_bs_x = view("bs_x")
+    if kw.get("an"):      # (on the card ops.NormRef.fill writes the styles, gamma and beta rows behind this)
+        p.an.stat, p.an.num_styles, p.an.eps = buf("an_stat"), kw["an"], 1e-5
+    if kw.get("an_out"):
+        p.an_out, p.ld_an_out = view("an_out")
+    if "scat" in kw:
+        p.scat_d, p.scat_h, p.scat_w, p.scat_cout = kw["scat"]
+    if kw.get("colsum"):
+        p.tn_colsum = buf("tn_colsum")
+    if at is None or "workspace" in at:
+        p.workspace = buf("workspace")
+    return p
+
+
+def _f(id_, M, N, K, expect, **kw):
+    return (id_, dict(M=M, N=N, K=K, **kw), expect)
+
+
+FORM_ROWS = []
+
+# ---- the small kernel: a ragged M per tile that keeps the tile (nt_small_tile: the candidate with the most workgroups in 140 .. 256, else
+# the first of (2, 4) .. (1, 1) with >= 140, else the last that fits).  Workgroups of the six candidates (4,3) (2,4) (2,2) (2,1) (1,2) (1,1):
+#   2041 x 384:  256*  384   768  1536  1536  3072          1727 x 192:  108   162*  324   648   648  1296
+#   2047 x  96:   64    -    192*  384   384   768           215 x 384:   32    42    84   168*  168   336      ((2, 1) before (1, 2): first wins a tie)
+#    330 x 384:   48    66   132   264   252*  504            27 x 384:    -     6    12    24    24    48*     (none >= 140: the last)
+# grid_x: 256 and 192 are multiples of 8, 162 and 252 are not, 48 and the M <= 16 rows' 4 are below the 8 XCDs (the remap at the kernel's top)
+SMALL_TILE_ROWS = {
+    (4, 3): (2041, 384, dict(grid_x=256, row_tiles=32, col_groups=8, cols_per_group=48)),
+    (2, 4): (1727, 192, dict(grid_x=162, row_tiles=54, col_groups=3, cols_per_group=64)),
+    (2, 2): (2047, 96, dict(grid_x=192, row_tiles=64, col_groups=3, cols_per_group=32)),
+    (2, 1): (215, 384, dict(grid_x=168, row_tiles=7, col_groups=24, cols_per_group=16)),
+    (1, 2): (330, 384, dict(grid_x=252, row_tiles=21, col_groups=12, cols_per_group=32)),
+    (1, 1): (27, 384, dict(grid_x=48, row_tiles=2, col_groups=24, cols_per_group=16)),
+}
+SMALL_EPILOGUES = {"plain": ((0, 0, 0), {}), "gelu": ((1, 0, 0), dict(act=GELU)), "anorm": ((0, 0, 1), {}), "anorm-gelu": ((1, 0, 1), dict(act=GELU)),
+                   "stat": ((0, 1, 0), dict(stat=1)), "bstat": ((0, 2, 0), dict(bstat=1))}
+# K: 32 (three of the four waves have no k-step), 96, 160 (uneven over the waves), 544 (a wave's share is more than one batch of SM_BS
+# k-steps), 384 (the folded norm's ncoef limit); every epilogue sees at least two of them
+_SMALL = [
+    ((4, 3), "plain", 32, "", {}), ((2, 4), "plain", 96, "-bias-a-slice", dict(bias=1, lay=dict(A="slice"))),
+    ((2, 2), "plain", 160, "-res-off8", dict(res=1, lay=dict(res="off8"))), ((2, 1), "plain", 544, "-ggrad", dict(epi=2)),
+    ((1, 2), "plain", 32, "-c-off8", dict(lay=dict(C="off8"))), ((1, 1), "plain", 544, "-bias-b-slice", dict(bias=1, lay=dict(B="slice"))),
+    ((4, 3), "gelu", 96, "-bias-preact-aux-slice", dict(bias=1, epi=1, lay=dict(aux="slice"))), ((2, 4), "gelu", 160, "", {}),
+    ((2, 2), "gelu", 544, "-bias-res", dict(bias=1, res=1)), ((2, 1), "gelu", 32, "-c-slice", dict(lay=dict(C="slice"))),
+    ((1, 2), "gelu", 96, "-bias-preact", dict(bias=1, epi=1)), ((1, 1), "gelu", 160, "-res-slice", dict(res=1, lay=dict(res="slice"))),
+    ((4, 3), "anorm", 160, "-an_out", dict(an=1, an_out=1)), ((2, 4), "anorm", 384, "-styles2-an_out-slice", dict(an=2, an_out=1, lay=dict(an_out="slice"))),
+    ((2, 2), "anorm", 32, "-bias", dict(an=1, bias=1)), ((2, 1), "anorm", 96, "-styles4-a-slice", dict(an=4, lay=dict(A="slice"))),
+    ((1, 2), "anorm", 384, "-an_out-c-slice", dict(an=1, an_out=1, lay=dict(C="slice"))), ((1, 1), "anorm", 32, "-styles2", dict(an=2)),
+    ((4, 3), "anorm-gelu", 32, "-bias-preact-an_out", dict(an=1, bias=1, epi=1, an_out=1)), ((2, 4), "anorm-gelu", 96, "", dict(an=1)),
+    ((2, 2), "anorm-gelu", 160, "-styles2-an_out", dict(an=2, an_out=1)), ((2, 1), "anorm-gelu", 384, "-bias", dict(an=1, bias=1)),
+    ((1, 2), "anorm-gelu", 160, "-styles4-preact", dict(an=4, epi=1)), ((1, 1), "anorm-gelu", 384, "-an_out-slice", dict(an=1, an_out=1, lay=dict(an_out="slice"))),
+    ((4, 3), "stat", 544, "-res", dict(res=1)), ((2, 4), "stat", 32, "-bias", dict(bias=1)), ((2, 2), "stat", 96, "-c-slice", dict(lay=dict(C="slice"))),
+    ((2, 1), "stat", 160, "-bias-res-off8", dict(bias=1, res=1, lay=dict(res="off8"))), ((1, 2), "stat", 544, "", {}),
+    ((1, 1), "stat", 96, "-a-slice-b-slice", dict(lay=dict(A="slice", B="slice"))),
+    ((4, 3), "bstat", 96, "", {}), ((2, 4), "bstat", 544, "-bsx-off8", dict(lay=dict(bs_x="off8"))), ((2, 2), "bstat", 160, "-bias", dict(bias=1)),
+    ((2, 1), "bstat", 32, "-bsx-slice", dict(lay=dict(bs_x="slice"))), ((1, 2), "bstat", 160, "-c-slice", dict(lay=dict(C="slice"))),
+    ((1, 1), "bstat", 544, "-a-slice", dict(lay=dict(A="slice"))),
+]
+for (_m, _n), _e, _k, _suffix, _kw in _SMALL:
+    _M, _N, _grid = SMALL_TILE_ROWS[(_m, _n)]
+    (_g, _s, _a), _req = SMALL_EPILOGUES[_e]
+    FORM_ROWS.append(_f("small-%dx%d-%s-m%d-k%d%s" % (_m, _n, _e, _M, _k, _suffix), _M, _N, _k,
+                        dict(kernel=SMALL, mtw=_m, ntw=_n, gelu=_g, stat=_s, anorm=_a, **_grid), **dict(_req, **_kw)))
+_G4 = dict(grid_x=4, row_tiles=1, col_groups=4, cols_per_group=16)      # M <= 16: no (2, *) tile; (1, 2) 2 and (1, 1) 4 workgroups, the last fits
+FORM_ROWS += [
+    _f("small-1x1-plain-m1-k32", 1, 64, 32, dict(kernel=SMALL, mtw=1, ntw=1, gelu=0, stat=0, anorm=0, fuses_stat=0, **_G4)),
+    _f("small-1x1-plain-m15-k96-bias", 15, 64, 96, dict(kernel=SMALL, mtw=1, ntw=1, fuses_stat=0, fuses_anorm=0, **_G4), bias=1),
+    _f("small-1x1-stat-m16-k32", 16, 64, 32, dict(kernel=SMALL, mtw=1, ntw=1, stat=1, fuses_stat=1, **_G4), stat=1),
+    _f("small-2x4-plain-ints-m1727-k96", 1727, 192, 96, dict(kernel=SMALL, mtw=2, ntw=4, grid_x=162), ints=1),
+]
+
+
+# ---- the streaming kernel.  grid_x = min(cap, ceil(ceil(M / 32) / 4)): 4101 rows are 129 tiles (the last of 5 rows: its second 16-row half
+# is empty) on 33 workgroups = 132 waves, one tile a wave; column groups: the smallest divisor d of N / 16 with 33 d >= 300, else N / 16 -
+# 16 columns a group at N = 48 .. 192.  38405 rows: 1201 tiles, 301 workgroups, ONE column group (several accumulator chunks where
+# N > 16 nch).  66553 rows: 2080 tiles on the 512-workgroup cap = 2048 waves, 32 of which walk a second tile; 67320 = 2 x 30 x 33 x 34: 2104.
+def _st(id_, M, N, K, form, grid, **kw):
+    k16, gelu, nch, stat, scat, anorm = form
+    gx, gy, cpg = grid
+    e = dict(kernel=STREAM, k16=k16, gelu=gelu, nch=nch, stat=stat, scat=scat, anorm=anorm, grid_x=gx, grid_y=gy, col_groups=gy, cols_per_group=cpg)
+    e.update(kw.pop("expect", {}))
+    return _f(id_, M, N, K, e, **kw)
+
+
+FORM_ROWS += [
+    _st("stream-k3-plain-m4101-n48", 4101, 48, 48, (3, 0, 12, 0, 0, 0), (33, 3, 16), expect=dict(lds_bytes=1856)),
+    _st("stream-k3-gelu-m4101-n144-bias-c-off8", 4101, 144, 48, (3, 1, 12, 0, 0, 0), (33, 9, 16), act=GELU, bias=1, lay=dict(C="off8")),
+    _st("stream-k6-plain-m4101-n96-a-slice-b-slice-res-off8", 4101, 96, 96, (6, 0, 12, 0, 0, 0), (33, 6, 16), res=1, lay=dict(A="slice", B="slice", res="off8")),
+    _st("stream-k6-gelu-m4101-n192-preact-aux-slice", 4101, 192, 96, (6, 1, 12, 0, 0, 0), (33, 12, 16), act=GELU, epi=1, lay=dict(aux="slice")),
+    _st("stream-k9-plain-m4101-n48-ggrad", 4101, 48, 144, (9, 0, 12, 0, 0, 0), (33, 3, 16), epi=2),
+    _st("stream-k9-gelu-m4101-n96", 4101, 96, 144, (9, 1, 12, 0, 0, 0), (33, 6, 16), act=GELU),
+    _st("stream-k12-plain-m4101-n192-c-slice", 4101, 192, 192, (12, 0, 12, 0, 0, 0), (33, 12, 16), lay=dict(C="slice")),
+    _st("stream-k12-gelu-m4101-n48-bias", 4101, 48, 192, (12, 1, 12, 0, 0, 0), (33, 3, 16), act=GELU, bias=1),
+    _st("stream-k18-plain-m4101-n96", 4101, 96, 288, (18, 0, 6, 0, 0, 0), (33, 6, 16)),
+    _st("stream-k18-gelu-m4101-n48-res", 4101, 48, 288, (18, 1, 6, 0, 0, 0), (33, 3, 16), act=GELU, res=1),
+    _st("stream-k24-plain-m38405-n96-two-chunks", 38405, 96, 384, (24, 0, 3, 0, 0, 0), (301, 1, 96), bias=1),      # nch 3: chunks of 48 columns
+    _st("stream-k24-gelu-m4101-n48", 4101, 48, 384, (24, 1, 3, 0, 0, 0), (33, 3, 16), act=GELU),
+    _st("stream-k3-plain-m38405-n384-two-chunks", 38405, 384, 48, (3, 0, 12, 0, 0, 0), (301, 1, 384), bias=1, expect=dict(lds_bytes=44544)),
+    _st("stream-k3-plain-ints-m4101-n48", 4101, 48, 48, (3, 0, 12, 0, 0, 0), (33, 3, 16), ints=1),
+    _st("stream-k3-anorm-m4101-n144-styles2-an_out-slice", 4101, 144, 48, (3, 0, 12, 0, 0, 1), (33, 9, 16), an=2, an_out=1, lay=dict(an_out="slice")),
+    _st("stream-k3-anorm-gelu-m66553-n48-walk-an_out", 66553, 48, 48, (3, 1, 12, 0, 0, 1), (512, 1, 48), an=1, act=GELU, an_out=1, bias=1),
+    _st("stream-k6-anorm-m4101-n96-styles4", 4101, 96, 96, (6, 0, 12, 0, 0, 1), (33, 6, 16), an=4),
+    _st("stream-k6-anorm-gelu-m4101-n192-preact-an_out", 4101, 192, 96, (6, 1, 12, 0, 0, 1), (33, 12, 16), an=1, act=GELU, epi=1, an_out=1),
+    _st("stream-k3-stat-m66553-n48-walk-res", 66553, 48, 48, (3, 0, 6, 1, 0, 0), (512, 1, 48), stat=1, res=1, expect=dict(lds_bytes=24960)),
+    _st("stream-k6-stat-m4101-n96-bias", 4101, 96, 96, (6, 0, 6, 1, 0, 0), (33, 6, 16), stat=1, bias=1),
+    _st("stream-k12-stat-m4101-n48-c-off8", 4101, 48, 192, (12, 0, 6, 1, 0, 0), (33, 3, 16), stat=1, lay=dict(C="off8")),
+    _st("stream-k3-bstat-m66553-n48-walk", 66553, 48, 48, (3, 0, 6, 2, 0, 0), (512, 1, 48), bstat=1),
+    _st("stream-k6-bstat-m4101-n96-bsx-off8", 4101, 96, 96, (6, 0, 6, 2, 0, 0), (33, 6, 16), bstat=1, lay=dict(bs_x="off8")),
+    _st("stream-k9-bstat-m4101-n48", 4101, 48, 144, (9, 0, 6, 2, 0, 0), (33, 3, 16), bstat=1),
+    _st("stream-k12-bstat-m4101-n96-bias", 4101, 96, 192, (12, 0, 6, 2, 0, 0), (33, 6, 16), bstat=1, bias=1),
+    # one chunk per column group with the sums: 96 columns over nch 3 = 48 a chunk make two groups
+    _st("stream-k18-bstat-m38405-n96-two-groups", 38405, 96, 288, (18, 0, 3, 2, 0, 0), (301, 2, 48), bstat=1, expect=dict(lds_bytes=28992)),
+    # 4368 = 2 x 12 x 14 x 13 voxels: 137 tiles on 35 workgroups; the scattered store keeps one column group
+    _st("stream-k6-scat-m4368-n384-left-half", 4368, 384, 96, (6, 0, 12, 0, 1, 0), (35, 1, 384), scat=(12, 14, 13, 48), lay=dict(C="left"), expect=dict(lds_bytes=81408)),
+    _st("stream-k3-scat-m67320-n64-walk-left-half", 67320, 64, 48, (3, 0, 12, 0, 1, 0), (512, 1, 64), scat=(30, 33, 34, 8), lay=dict(C="left")),
+]
+
+
+# ---- the generic NT kernel: 128 x 16 nt tiles; a stage is 8 chunks of 16 bytes = 64 bf16 / 32 fp32 of K; k_per_split is a multiple of it
+def _g(id_, M, N, K, nt, grid, al, kps, mode=STORE, zf=0, **kw):
+    e = dict(kernel=NT_GENERIC, nt=nt, grid_x=grid[0], grid_y=grid[1], grid_z=grid[2], splits=grid[2], k_per_split=kps, out_mode=mode, zero_fill=zf, al_a=al[0], al_b=al[1])
+    return _f(id_, M, N, K, e, **kw)
+
+
+F32, BF32 = dict(dt=0), dict(dt=1, odt=0)
+_EDGE = dict(M=4101, N=48, K=48, nt=3, grid=(33, 1, 1), kps=64)      # what a-off2 .. ldres-50 of ROWS send to the generic kernel, at 4101 rows
+FORM_ROWS += [
+    _g("nt1-f32-m129-n12-k22-bias", 129, 12, 22, 1, (2, 1, 1), (0, 0), 32, bias=1, **F32),      # K below one stage, K % 4 != 0: element loads
+    _g("nt2-f32-m257-n24-k100-gelu-res", 257, 24, 100, 2, (3, 1, 1), (1, 1), 128, act=GELU, res=1, **F32),
+    _g("nt3-f32-m300-n40-k70-gelu-preact", 300, 40, 70, 3, (3, 1, 1), (0, 0), 96, act=GELU, epi=1, bias=1, **F32),
+    _g("nt4-f32-m130-n72-k33-ggrad", 130, 72, 33, 4, (2, 2, 1), (0, 0), 64, epi=2, **F32),
+    _g("nt4-f32-m129-n64-k64-plain", 129, 64, 64, 4, (2, 1, 1), (1, 1), 64, **F32),      # the 16-byte store of four columns
+    _g("nt4-f32-m129-n70-k64-c-ldodd", 129, 70, 64, 4, (2, 2, 1), (1, 1), 64, lay=dict(C="ldodd"), **F32),
+    _g("nt1-f32-m129-n12-k36-a-off4", 129, 12, 36, 1, (2, 1, 1), (0, 1), 64, lay=dict(A="off4"), **F32),
+    _g("nt4-f32-split4-m200-n64-k300-bias", 200, 64, 300, 4, (2, 1, 4), (1, 1), 96, ATOMIC, 1, split_k=4, bias=1, **F32),
+    _g("nt3-f32-split4-acc-m200-n40-k300-bias", 200, 40, 300, 3, (2, 1, 4), (1, 1), 96, ATOMIC, 0, split_k=4, accumulate=1, bias=1, **F32),
+    _g("nt2-f32-acc-m129-n20-k100", 129, 20, 100, 2, (2, 1, 1), (1, 1), 128, ACCUMULATE, 0, accumulate=1, **F32),
+    # split_k > 1 over a K of one stage: ONE split, so it stores (or accumulates if asked) - DESIGN.md 3.3 (4)
+    _g("nt4-f32-split4-one-stage-m64-n64-k32", 64, 64, 32, 4, (1, 1, 1), (1, 1), 32, STORE, 0, split_k=4, **F32),
+    _g("nt3-f32-split4-one-stage-m70-n40-k20-bias-c-ldodd", 70, 40, 20, 3, (1, 1, 1), (1, 1), 32, STORE, 0, split_k=4, bias=1, lay=dict(C="ldodd"), **F32),
+    _g("nt1-f32-split4-acc-one-stage-m70-n16-k32", 70, 16, 32, 1, (1, 1, 1), (1, 1), 32, ACCUMULATE, 0, split_k=4, accumulate=1, **F32),
+    _g("nt3-f32-ints-m70-n33-k40", 70, 33, 40, 3, (1, 1, 1), (1, 1), 64, ints=1, **F32),
+    _g("nt1-bf16f32-m129-n12-k20", 129, 12, 20, 1, (2, 1, 1), (0, 0), 64, **BF32),      # K below one stage, K % 8 != 0
+    _g("nt2-bf16f32-m257-n24-k104-bias-gelu", 257, 24, 104, 2, (3, 1, 1), (1, 1), 128, bias=1, act=GELU, **BF32),
+    _g("nt3-bf16f32-split4-bias-m300-n40-k600-c-ldodd", 300, 40, 600, 3, (3, 1, 4), (1, 1), 192, ATOMIC, 1, split_k=4, bias=1, lay=dict(C="ldodd"), **BF32),
+    _g("nt4-bf16f32-split4-acc-m200-n72-k600", 200, 72, 600, 4, (2, 2, 4), (1, 1), 192, ATOMIC, 0, split_k=4, accumulate=1, **BF32),
+    _g("nt1-bf16f32-split4-m129-n16-k300", 129, 16, 300, 1, (2, 1, 3), (0, 0), 128, ATOMIC, 1, split_k=4, **BF32),      # 4 asked, 3 of 128 run
+    _g("nt2-bf16f32-acc-m129-n32-k72-a-ldodd", 129, 32, 72, 2, (2, 1, 1), (0, 1), 128, ACCUMULATE, 0, accumulate=1, lay=dict(A="ldodd"), **BF32),
+    _g("nt4-bf16f32-split4-one-stage-m70-n64-k64", 70, 64, 64, 4, (1, 1, 1), (1, 1), 64, STORE, 0, split_k=4, **BF32),
+    _g("nt4-bf16f32-ints-m70-n72-k40", 70, 72, 40, 4, (1, 2, 1), (1, 1), 64, ints=1, **BF32),
+    _g("nt1-bf16-m2100-n16-k40-bias", 2100, 16, 40, 1, (17, 1, 1), (1, 1), 64, bias=1),      # 2048 < M < 4096: neither bf16 kernel
+    _g("nt2-bf16-m300-n20-k72-gelu-res", 300, 20, 72, 2, (3, 1, 1), (1, 1), 128, act=GELU, res=1),
+    _g("nt3-bf16-m300-n40-k100-gelu-preact", 300, 40, 100, 3, (3, 1, 1), (0, 0), 128, act=GELU, epi=1),
+    _g("nt4-bf16-m300-n72-k20-ggrad", 300, 72, 20, 4, (3, 2, 1), (0, 0), 64, epi=2),
+    _g("nt3-bf16-ints-m70-n33-k40", 70, 33, 40, 3, (1, 1, 1), (1, 1), 64, ints=1),
+    _g("nt3-bf16-m4101-a-off2", al=(0, 1), lay=dict(A="off2"), **_EDGE),
+    _g("nt3-bf16-m4101-b-off8", al=(1, 0), lay=dict(B="off8"), **_EDGE),
+    _g("nt3-bf16-m4101-c-off4", al=(1, 1), lay=dict(C="off4"), **_EDGE),
+    _g("nt3-bf16-m4101-res-off4", al=(1, 1), res=1, lay=dict(res="off4"), **_EDGE),
+    _g("nt3-bf16-m4101-preact-aux-off4", al=(1, 1), epi=1, lay=dict(aux="off4"), **_EDGE),
+    _g("nt3-bf16-m4101-a-ldodd", al=(0, 1), lay=dict(A="ldodd"), **_EDGE),
+    _g("nt3-bf16-m4101-b-ldodd", al=(1, 0), lay=dict(B="ldodd"), **_EDGE),
+    _g("nt3-bf16-m4101-c-ldodd", al=(1, 1), lay=dict(C="ldodd"), **_EDGE),
+    _g("nt3-bf16-m4101-res-ldodd", al=(1, 1), res=1, lay=dict(res="ldodd"), **_EDGE),
+]
+
+# ---- rank-1 (K = 1).  Plain: ceil(M (N / n16) / 256) workgroups; with statistics ceil(M / rows) with rows = floor(256 / (N / n16)) a workgroup:
+# 42 at 48 bf16 columns (5003 = 119 x 42 + 5), 32 at 32 fp32 columns
+FORM_ROWS += [
+    _f("rank1-bf16-m5003-n48", 5003, 48, 1, dict(kernel=RANK1, grid_x=118, grid_y=1, grid_z=1, fuses_stat=1)),
+    _f("rank1-bf16-bias-m5003-n48-a-slice", 5003, 48, 1, dict(kernel=RANK1, grid_x=118), bias=1, lay=dict(A="slice")),
+    _f("rank1-bf16-stat-m5003-n48", 5003, 48, 1, dict(kernel=RANK1_STAT, grid_x=120), stat=1),
+    _f("rank1-bf16-stat-bias-m5003-n48-a-slice-c-slice", 5003, 48, 1, dict(kernel=RANK1_STAT, grid_x=120), stat=1, bias=1, lay=dict(A="slice", C="slice")),
+    _f("rank1-bf16-stat-m100-n48", 100, 48, 1, dict(kernel=RANK1_STAT, grid_x=3), stat=1),
+    _f("rank1-bf16-m1000-n136", 1000, 136, 1, dict(kernel=RANK1, grid_x=67, fuses_stat=0)),
+    _f("rank1-bf16-ints-m100-n48", 100, 48, 1, dict(kernel=RANK1, grid_x=3), ints=1),
+    _f("rank1-f32-m1000-n32", 1000, 32, 1, dict(kernel=RANK1, grid_x=32, fuses_stat=1), **F32),
+    _f("rank1-f32-bias-m1000-n32-a-slice-b-slice", 1000, 32, 1, dict(kernel=RANK1, grid_x=32), bias=1, lay=dict(A="slice", B="slice"), **F32),
+    _f("rank1-f32-stat-m1000-n32", 1000, 32, 1, dict(kernel=RANK1_STAT, grid_x=32), stat=1, **F32),
+    _f("rank1-f32-stat-bias-m1001-n32-c-slice", 1001, 32, 1, dict(kernel=RANK1_STAT, grid_x=32), stat=1, bias=1, lay=dict(C="slice"), **F32),
+    _f("rank1-f32-split4-m1000-n32", 1000, 32, 1, dict(kernel=RANK1, grid_x=32, fuses_stat=0), split_k=4, **F32),
+    _f("rank1-f32-stat-ints-m100-n32", 100, 32, 1, dict(kernel=RANK1_STAT, grid_x=4), stat=1, ints=1, **F32),
+]
+
+
+# ---- TN, generic: 64 x 64 tiles; stages of 128 (bf16) / 64 (fp32) reduction rows; the library's split: ceil(K / 512), at most 1024 / tiles
+def _t(id_, M, N, K, grid, al, kps, mode=STORE, zf=0, **kw):
+    e = dict(kernel=TN_GENERIC, grid_x=grid[0], grid_y=grid[1], grid_z=grid[2], splits=grid[2], k_per_split=kps, out_mode=mode, zero_fill=zf, al_a=al[0], al_b=al[1],
+             tn_fuses_colsum=0, workspace_bytes=0)
+    return _f(id_, M, N, K, e, tn=1, **kw)
+
+
+FORM_ROWS += [
+    _t("tn-f32-split1-k333-m12-n36", 12, 36, 333, (1, 1, 1), (1, 1), 384, split_k=1, dt=0),
+    _t("tn-bf16f32-auto-k1000-m144-n50", 144, 50, 1000, (3, 1, 2), (1, 0), 512, ATOMIC, 1),
+    _t("tn-bf16f32-split4-k700-m70-n100", 70, 100, 700, (2, 2, 3), (0, 0), 256, ATOMIC, 1, split_k=4),      # 4 asked, 3 of 256 run
+    _t("tn-bf16f32-split4-acc-k700-m72-n104-c-ldodd", 72, 104, 700, (2, 2, 3), (1, 1), 256, ATOMIC, 0, split_k=4, accumulate=1, lay=dict(C="ldodd")),
+    _t("tn-f32-acc-split1-k200-m70-n100", 70, 100, 200, (2, 2, 1), (0, 1), 256, ACCUMULATE, 0, split_k=1, accumulate=1, dt=0),
+    _t("tn-f32-auto-k1100-m70-n100-a-off4", 70, 100, 1100, (2, 2, 3), (0, 1), 384, ATOMIC, 1, dt=0, lay=dict(A="off4")),
+    _t("tn-bf16-split1-k300-m70-n100", 70, 100, 300, (2, 2, 1), (0, 0), 384, split_k=1, odt=1),
+    # bf16 output has no atomics: the library's own split stays at one
+    _t("tn-bf16-auto-k1000-m72-n104", 72, 104, 1000, (2, 2, 1), (1, 1), 1024, odt=1),
+    _t("tn-f32-ints-split1-k100-m50-n70", 50, 70, 100, (1, 2, 1), (0, 0), 128, split_k=1, dt=0, ints=1),
+    _t("tn-bf16f32-ints-auto-k1000-m72-n104", 72, 104, 1000, (2, 2, 2), (1, 1), 512, ATOMIC, 1, ints=1),
+    # the three refusals of the streaming path, onto this kernel
+    _t("tn-stream-k2047", 144, 48, 2047, (3, 1, 4), (1, 1), 512, ATOMIC, 1),
+    _t("tn-stream-m40", 40, 48, 2048, (1, 1, 4), (1, 1), 512, ATOMIC, 1),
+    _t("tn-stream-a-off8", 144, 48, 2048, (3, 1, 4), (0, 1), 512, ATOMIC, 1, lay=dict(A="off8")),
+]
+
+
+# ---- TN, streaming: 48 x 48 wave tiles as (wm, wn); splits = min(ceil(384 / workgroups), ceil(K / 256)) of whole 64-row stages; reduce groups
+# of 16 splits; the partial tiles are splits x M x N floats
+def _ts(id_, M, N, K, wave, grid, kps, ws, groups, blocks, mode=STORE, zf=0, **kw):
+    e = dict(kernel=TN_STREAM, wm=wave[0], wn=wave[1], grid_x=grid[0], grid_y=grid[1], grid_z=grid[2], splits=grid[2], k_per_split=kps, workspace_bytes=ws,
+             reduce_groups=groups, reduce_blocks=blocks, out_mode=mode, zero_fill=zf, tn_fuses_colsum=1, lds_bytes=128 * (96 * (wave[0] + wave[1]) + 32))
+    return _f(id_, M, N, K, e, tn=1, **kw)
+
+
+FORM_ROWS += [
+    _ts("tnstream-4x1-k2048-m48-n48-one-group", 48, 48, 2048, (4, 1), (1, 1, 8), 256, 73728, 1, 3),
+    _ts("tnstream-4x1-ints-k2048-m48-n48", 48, 48, 2048, (4, 1), (1, 1, 8), 256, 73728, 1, 3, ints=1),
+    _ts("tnstream-1x4-k2048-m48-n96-a-slice-b-slice", 48, 96, 2048, (1, 4), (1, 1, 8), 256, 147456, 1, 5, lay=dict(A="slice", B="slice")),
+    _ts("tnstream-2x2-k2048-m96-n96-colsum", 96, 96, 2048, (2, 2), (1, 1, 8), 256, 294912, 1, 9, colsum=1),
+    _ts("tnstream-2x2-k2048-m96-n96-defer", 96, 96, 2048, (2, 2), (1, 1, 8), 256, 294912, 0, 0, defer=1),
+    # 144 rows on two workgroups of 96: the second one's upper waves have no tile
+    _ts("tnstream-2x2-k2048-m144-n96-acc-c-slice", 144, 96, 2048, (2, 2), (2, 1, 8), 256, 442368, 1, 14, ACCUMULATE, 0, accumulate=1, lay=dict(C="slice")),
+    # 4400 = 17 x 256 + 48: 18 splits, the last one short, two reduce groups that meet in atomics on a filled (or accumulating) C
+    _ts("tnstream-4x1-k4400-m144-n48-two-groups-colsum-c-ldodd", 144, 48, 4400, (4, 1), (1, 1, 18), 256, 497664, 2, 7, STORE, 1, colsum=1, lay=dict(C="ldodd")),
+    _ts("tnstream-4x1-k4400-m144-n48-two-groups-acc", 144, 48, 4400, (4, 1), (1, 1, 18), 256, 497664, 2, 7, ACCUMULATE, 0, accumulate=1),
+    # 400 workgroups: one split, the product goes straight to C
+    _ts("tnstream-2x2-k2048-m1920-n1920-one-split", 1920, 1920, 2048, (2, 2), (20, 20, 1), 2048, 0, 0, 0),
+    _ts("tnstream-2x2-k2048-m1920-n1920-one-split-acc", 1920, 1920, 2048, (2, 2), (20, 20, 1), 2048, 0, 0, 0, ACCUMULATE, 0, accumulate=1),
+]

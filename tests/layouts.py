@@ -20,7 +20,8 @@ def _bits(t):
 class Slot:
     """a channels-last view of `shape` = (..., C) inside a larger buffer.  layout: "contig" (the buffer is the view), "slice" (16-byte aligned
     channel slice of wider rows, ld % N == 0), "off8" (slice that starts 8 bytes into a 16-byte unit, ld % N == 0), "ldodd" (aligned base,
-    ld % N != 0).  The non-contiguous layouts have 16 leading and one trailing slab of rows around the view (16 keeps the base aligned)."""
+    ld % N != 0), "off4" / "off2" (slice that starts 4 / 2 bytes into a 16-byte unit, ld % N == 0; "off2": two-byte types only).  The
+    non-contiguous layouts have 16 leading and one trailing slab of rows around the view (16 keeps the base aligned)."""
 
     def __init__(self, shape, dtype, layout, fill):
         n = _nvec(dtype)
@@ -32,14 +33,16 @@ class Slot:
             self.view = self.buf
             self.index = None
             return
-        off, ld = {"slice": (n, cp + 3 * n), "off8": (n // 2, cp + 2 * n), "ldodd": (0, cp + n + 1)}[layout]
+        off, ld = {"slice": (n, cp + 3 * n), "off8": (n // 2, cp + 2 * n), "ldodd": (0, cp + n + 1), "off4": (n // 4, cp + 2 * n),
+                   "off2": (n // 8, cp + 2 * n)}[layout]
+        assert off > 0 or layout == "ldodd", (layout, dtype)
         pre = 16
         self.buf = torch.full((pre + shape[0] + 1,) + tuple(shape[1:-1]) + (ld,), fill, dtype=dtype, device=DEV)
         self.index = (slice(pre, pre + shape[0]),) + (slice(None),) * (len(shape) - 2) + (slice(off, off + c),)
         self.view = self.buf[self.index]
         es = self.buf.element_size()
         assert self.buf.data_ptr() % 16 == 0
-        assert (self.view.data_ptr() % 16 == 0) == (layout != "off8") and (ld % n == 0) == (layout != "ldodd") and ld * es >= c * es
+        assert (self.view.data_ptr() % 16 == 0) == (layout not in ("off8", "off4", "off2")) and (ld % n == 0) == (layout != "ldodd") and ld * es >= c * es
 
 
 def place_in(values, layout):

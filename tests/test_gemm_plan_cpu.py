@@ -1,7 +1,8 @@
 """One host-side plan per miseg_gemm launch (miseg_gemm_plan): the table of tests/gemm_cases.py - the GEMM shapes of the bench nets and
 the edges of every predicate - against plan fields worked out by hand from the dispatcher as it was before the plan existed; every kernel
 family, every small and streaming instantiation, every output mode reached by some row; no divisor of a launch is zero; the seven question
-entry points equal the plan's fields on every row, and over a seeded sweep answer what the parent commit's library answered.  CPU only."""
+entry points equal the plan's fields on every row, and over a seeded sweep answer what the parent commit's library answered.  FORM_ROWS, the
+card-sized rows tests/test_hip_gemm_forms.py launches, are pinned the same way and reach every form without ROWS.  CPU only."""
 import ctypes as C
 
 import pytest
@@ -25,7 +26,30 @@ def _plan(kw):
 @pytest.mark.parametrize("row", G.ROWS, ids=lambda r: r[0])
 def test_plan_of_the_table_rows(row):
     _, kw, expect = row
-    rc, pl, p = _plan(kw)
+    _check_row(kw, expect, *_plan(kw))
+
+
+def _form_plan(kw):
+    L = _L()
+    p = G.form_params(L, kw)
+    pl = L.GemmPlan()
+    rc = L.load().miseg_gemm_plan(C.byref(p), C.byref(pl))
+    return rc, pl, p
+
+
+@pytest.mark.parametrize("row", G.FORM_ROWS, ids=lambda r: r[0])
+def test_plan_of_the_form_rows(row):
+    """the rows tests/test_hip_gemm_forms.py launches on the card: each one's plan, with its operands in the row's layouts, has the fields worked
+    out by hand, and the shape is as small as its family allows (every one of them is accepted)"""
+    _, kw, expect = row
+    rc, pl, p = _form_plan(kw)
+    assert "rc" not in expect and "kernel" in expect
+    _check_row(kw, expect, rc, pl, p)
+    assert pl.kernel != G.SMALL or kw["M"] <= 2048
+    assert _L().load().miseg_gemm_workspace_bytes(C.byref(p)) == pl.workspace_bytes
+
+
+def _check_row(kw, expect, rc, pl, p):
     assert rc == expect.get("rc", 0)
     if rc != 0:
         assert pl.kernel == G.NONE and _L().load().miseg_last_error()
@@ -75,6 +99,42 @@ def test_every_launch_form_is_reached_by_a_row():
     assert {(pl.mtw, pl.ntw, pl.gelu, pl.stat, pl.anorm) for pl in plans if pl.kernel == G.SMALL} <= G.SMALL_FORMS
     assert {(pl.k16, pl.gelu, pl.nch, pl.stat, pl.scat, pl.anorm) for pl in plans if pl.kernel == G.STREAM} <= G.STREAM_FORMS
     assert {_plan(dict(M=4095, N=n, K=40))[1].nt for n in (8, 16, 24, 32, 40, 48, 56, 64, 96)} == {1, 2, 3, 4}
+
+
+def test_the_form_rows_alone_reach_every_launch_form():
+    """without ROWS: the seven families, the 36 + 26 instantiations and no other, nt 1 .. 4 under each dtype pair, both al_a and both al_b on
+    each generic kernel, the three TN wave forms, every (output mode, zero fill) pair of the generic kernels, and the TN streaming path with
+    one split, one reduce group, several reduce groups, accumulate, tn_colsum and defer_reduce"""
+    rows = [(kw, _form_plan(kw)[1]) for _, kw, _ in G.FORM_ROWS]
+    plans = [pl for _, pl in rows]
+    assert {pl.kernel for pl in plans} == {G.RANK1, G.RANK1_STAT, G.SMALL, G.STREAM, G.NT_GENERIC, G.TN_STREAM, G.TN_GENERIC}
+    assert {(pl.mtw, pl.ntw, pl.gelu, pl.stat, pl.anorm) for pl in plans if pl.kernel == G.SMALL} == G.SMALL_FORMS
+    assert {(pl.k16, pl.gelu, pl.nch, pl.stat, pl.scat, pl.anorm) for pl in plans if pl.kernel == G.STREAM} == G.STREAM_FORMS
+    assert {G.dtypes(kw) + (pl.nt,) for kw, pl in rows if pl.kernel == G.NT_GENERIC} == {(d, o, n) for d, o in ((0, 0), (1, 0), (1, 1)) for n in (1, 2, 3, 4)}
+    assert {G.dtypes(kw) for kw, pl in rows if pl.kernel == G.TN_GENERIC} == {(0, 0), (1, 0), (1, 1)}
+    assert {G.dtypes(kw) for kw, pl in rows if pl.kernel in (G.RANK1, G.RANK1_STAT)} == {(0, 0), (1, 1)}
+    for k in (G.NT_GENERIC, G.TN_GENERIC):
+        assert {pl.al_a for pl in plans if pl.kernel == k} == {0, 1} and {pl.al_b for pl in plans if pl.kernel == k} == {0, 1}
+        assert {(pl.out_mode, pl.zero_fill) for pl in plans if pl.kernel == k} == {(G.STORE, 0), (G.ACCUMULATE, 0), (G.ATOMIC, 1), (G.ATOMIC, 0)}
+    tns = [(kw, pl) for kw, pl in rows if pl.kernel == G.TN_STREAM]
+    assert {(pl.wm, pl.wn) for _, pl in tns} == {(4, 1), (1, 4), (2, 2)}
+    assert {(pl.out_mode, pl.zero_fill, min(pl.reduce_groups, 2), pl.splits > 1) for _, pl in tns} == {
+        (G.STORE, 0, 0, False), (G.ACCUMULATE, 0, 0, False), (G.STORE, 0, 1, True), (G.ACCUMULATE, 0, 1, True), (G.STORE, 1, 2, True), (G.ACCUMULATE, 0, 2, True),
+        (G.STORE, 0, 0, True)}      # (the last: defer_reduce)
+    assert any(kw.get("colsum") for kw, _ in tns) and any(kw.get("defer") and pl.reduce_groups == 0 and pl.splits > 1 for kw, pl in tns)
+    assert any(pl.splits % 16 and pl.splits > 16 for _, pl in tns)
+    # the streaming NT kernel: a wave with more than one tile under every family whose sums or stores live across tiles, more than one chunk
+    walks = {(pl.stat, pl.scat, pl.anorm) for kw, pl in rows if pl.kernel == G.STREAM and -(-kw["M"] // 32) > 4 * pl.grid_x}
+    assert walks >= {(1, 0, 0), (2, 0, 0), (0, 1, 0), (0, 0, 1)}
+    assert {pl.nch for kw, pl in rows if pl.kernel == G.STREAM and pl.cols_per_group > 16 * pl.nch} >= {3, 12}
+    assert any(pl.kernel == G.STREAM and pl.stat == 2 and pl.col_groups == 2 and pl.k16 == 18 for pl in plans)
+    # the small kernel's grids: below the eight XCDs, a multiple of eight, not a multiple of eight
+    gx = {pl.grid_x for pl in plans if pl.kernel == G.SMALL}
+    assert any(g < 8 for g in gx) and any(g >= 8 and g % 8 == 0 for g in gx) and any(g > 8 and g % 8 for g in gx)
+    # one exact-integer row per family
+    assert {pl.kernel for kw, pl in rows if kw.get("ints")} == {G.RANK1, G.RANK1_STAT, G.SMALL, G.STREAM, G.NT_GENERIC, G.TN_STREAM, G.TN_GENERIC}
+    ids = [r[0] for r in G.FORM_ROWS]
+    assert len(ids) == len(set(ids))
 
 
 def _instantiated(pl, small, stream):
