@@ -498,13 +498,13 @@ typedef struct {
   /* ABI 3: dropout on the attention probabilities (attn_drop of WindowAttention, swin_transformer_block.py:56-58,91; the SABlock of the
    * ViT): drop_p in [0, 1), 0 = off.  The mask is the counter-based one of miseg_dropout over the matrix [B*nW*heads*n rows][n columns]
    * (row = ((window * heads + head) * n + query), column = key) with the same (seed, stream_id, step_dev) key, so the backward call
-   * re-creates it from the same three values; nothing is stored.  With drop_p > 0 the one-lane-per-query kernels run (any head_dim, both
-   * dtypes): the matrix-core kernels take no mask. */
+   * re-creates it from the same three values; nothing is stored.  Every kernel family takes it: the matrix-core kernels as a template
+   * argument (`drop` of miseg_winattn_plan_info), the one-lane-per-query kernels as a run-time branch. */
   float drop_p; uint64_t drop_seed, drop_stream; const uint64_t* drop_step_dev;
 } miseg_winattn_params;
 int miseg_winattn_fwd(const miseg_winattn_params* p, miseg_stream_t stream);
-/* 1 when the head_dim-16 bf16 matrix-core kernels take this forward call (window attention with a bias table, <= 352 tokens per window;
- * since round 3 with or without attention dropout), 0 when the one-lane-per-query kernels do.  No launch. */
+/* 1 when miseg_winattn_fwd_plan accepts the call and names a matrix-core kernel (window or global), 0 when it names the one-lane-per-query
+ * kernels or refuses the call.  No launch. */
 int miseg_winattn_on_matrix_cores(const miseg_winattn_params* p);
 
 typedef struct {
@@ -516,10 +516,33 @@ typedef struct {
 } miseg_winattn_bwd_params;
 /* dbias_table without f.bias_table is refused (MISEG_E_BADARG): there is no table to take the gradient of */
 int miseg_winattn_bwd(const miseg_winattn_bwd_params* p, miseg_stream_t stream);
-/* 1 when a matrix-core kernel takes this backward call (the head_dim-16 bf16 window kernel: as the forward's, and the table fits its LDS
- * slots, qkv / dqkv 8-byte aligned with row strides % 4 == 0; or the head_dim-64 global kernel), 0 when the one-lane-per-query kernels do
- * or the call would be refused.  No launch; the launcher decides by the same function.  (A new symbol: MISEG_ABI_VERSION stays 16.) */
+/* 1 when miseg_winattn_bwd_plan accepts the call and names a matrix-core kernel, 0 when it names the one-lane-per-query kernels or refuses
+ * the call.  No launch.  (A new symbol: MISEG_ABI_VERSION stays 16.) */
 int miseg_winattn_bwd_on_matrix_cores(const miseg_winattn_bwd_params* p);
+
+/* What miseg_winattn_fwd(p) / miseg_winattn_bwd(p) do with these params - the launches dispatch on exactly this plan and the two question
+ * entry points above read it.  Pointers are only tested for NULL and alignment, so a host may ask with stand-ins for buffers it has not
+ * allocated yet.  Host only: touches no device.  Returns what the launch would return for a refused call, with the same miseg_last_error
+ * text (kernel == MISEG_WINATTN_NONE and every field 0 then).  (New symbols and a new struct: MISEG_ABI_VERSION stays 16.) */
+#define MISEG_WINATTN_NONE 0
+#define MISEG_WINATTN_QUERY_LANE 1      /* either dtype, head_dim 4 .. 64: <T, hd4>, one lane per query, grid (windows, heads) */
+#define MISEG_WINATTN_WINDOW_MFMA 2     /* bf16, head_dim 16, a table, <= 352 tokens: forward <mask, waves, drop>, backward <mask, table_grad, waves, drop> */
+#define MISEG_WINATTN_GLOBAL_MFMA 3     /* bf16, head_dim 64, one unshifted window of <= 256 tokens, no table: <tiles, drop>, grid (tiles of 64, heads, B) */
+typedef struct {
+  int32_t kernel;                        /* MISEG_WINATTN_* */
+  int32_t mask, drop, table_grad;        /* a shift is set / drop_p quantises to > 0 / dbias_table is given: template arguments of the
+                                          * matrix-core kernels, run-time branches of the query-lane ones */
+  int32_t waves;                         /* window forward 8, or 11 below 256 units; window backward 8; global 4; query-lane ceil(tokens / 64) */
+  int32_t hd4;                           /* query-lane: head_dim / 4 (1, 2, 3, 4, 8, 16); else 0 */
+  int32_t tiles;                         /* global: padded tokens / 16 (2, 4 .. 16); else 0 */
+  int32_t vec;                           /* window matrix-core: operand rows are read as 16-byte vectors (a run-time flag); else 0 */
+  int32_t grid_x, grid_y, grid_z, threads;
+  int32_t tokens, table_size;            /* tokens per window; (2 tw - 1)^3 table entries per head, 0 without a table */
+  int32_t units;                         /* workgroups: grid_x * grid_y * grid_z */
+  size_t lds_bytes;                      /* dynamic LDS of the launch */
+} miseg_winattn_plan_info;
+int miseg_winattn_fwd_plan(const miseg_winattn_params* p, miseg_winattn_plan_info* plan);
+int miseg_winattn_bwd_plan(const miseg_winattn_bwd_params* p, miseg_winattn_plan_info* plan);
 
 /* ------------------------------------------------------------------------------------------------
  * Data-movement / small kernels (all channels-last rows)

@@ -1,8 +1,12 @@
-// Fused 3D (shifted-)window attention core, forward and backward (round-1 version: fp32 VALU, one workgroup per
-// (window, head), one lane per query row; K/V rows are LDS broadcasts, scores never leave registers).
-// pad / roll / window partition / reverse / crop are pure index arithmetic here; the relative-position bias is
-// gathered from a per-head LDS copy of the table with idx = code[i] - code[j] + centre, and the shift mask is
-// derived from 27 region labels of the rolled grid (reference: swin_utils.py:107-143, window_attention.py:99-119).
+// Fused 3D (shifted-)window attention core, forward and backward.  pad / roll / window partition / reverse / crop are pure index arithmetic
+// here; the relative-position bias is gathered from a per-head LDS copy of the table with idx = code[i] - code[j] + centre, and the shift
+// mask is derived from 27 region labels of the rolled grid (reference: swin_utils.py:107-143, window_attention.py:99-119).  Two kernel families:
+//   * query-lane (either dtype, head_dim 4 .. 64): fp32 VALU, one workgroup per (window, head), one lane per query row; K/V rows are LDS
+//     broadcasts, scores never leave registers;
+//   * window matrix-core (bf16, head_dim 16, a bias table, <= 352 tokens per window): the MFMA kernels further down, with or without
+//     attention dropout.
+// A third family, the head_dim-64 global kernels, lives in attention_global.hip.  Which of the three a call takes, and in which form, is one
+// host plan per launch (attn_plan below: miseg_winattn_fwd_plan / _bwd_plan); the launchers at the end of this file read it.
 #include "common.h"
 
 namespace miseg {
@@ -83,7 +87,7 @@ __device__ __forceinline__ AttnSmem carve(char* base, int n, int tsize, bool bwd
   return s;
 }
 
-static size_t attn_smem_bytes(int n, int hd, int tsize, bool bwd) {
+static size_t attn_smem_bytes(int n, int hd, int64_t tsize, bool bwd) {
   return ((size_t)2 * n * hd + (size_t)tsize * (bwd ? 2 : 1) + (size_t)5 * n + (size_t)3 * hd) * sizeof(float);
 }
 
@@ -359,7 +363,7 @@ __global__ void __launch_bounds__(384) winattn_bwd_kernel(const T* __restrict__ 
 // =====================================================================================================================
 // MFMA path (bf16, head_dim 16): S^T = K Q^T on v_mfma_f32_32x32x16_bf16 with the QUERY on the lane, so the softmax
 // statistics are lane-local (+ one exchange with lane^32) and the exponentiated tile is directly the B operand of
-// O^T += V^T P^T (accumulator-as-operand, no LDS round trip).  One workgroup = (window, head), 4 waves, each wave owns
+// O^T += V^T P^T (accumulator-as-operand, no LDS round trip).  One workgroup = (window, head), NW waves, each wave owns
 // query tiles of 32; keys are walked in tiles of 32.
 // =====================================================================================================================
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -423,7 +427,7 @@ __device__ __forceinline__ void att_unit(int heads, int& win, int& head) {
 // DROP: attn_drop on the probabilities (round 3: on the matrix-core path too).  The mask is miseg_dropout's over [windows * heads * n][n]:
 // one 64-bit hash per (query row, group of 4 consecutive keys) - a lane of the 32x32 accumulator holds exactly such groups (keys 8g + 4h ..
 // + 3 of its query), so the cost is 4 hashes per 16 probabilities, what the query-lane kernels pay.
-template <bool MASK, int NW = 4, bool DROP = false>
+template <bool MASK, int NW, bool DROP>
 __global__ void __launch_bounds__(NW * 64) winattn_fwd_mfma_kernel(const bf16* __restrict__ qkv, int64_t ldq, bf16* __restrict__ out, int64_t ldo,
                                                                const float* __restrict__ qkv_bias, const float* __restrict__ bias_table,
                                                                float* __restrict__ lse_out, WinGeom g, int tsize, bool vec, AttnDrop dr) {
@@ -564,20 +568,19 @@ __global__ void __launch_bounds__(NW * 64) winattn_fwd_mfma_kernel(const bf16* _
 
 // ---------------------------------------------------------------------------------------------------------------------
 // MFMA backward (bf16, head_dim 16), single pass over 16x16 (query x key) units on v_mfma_f32_16x16x16_bf16.
-//   * a wave owns key tiles kt = wave, wave+4, ... (<= 6 of 16 keys); their K/V operands and the dK^T/dV^T accumulators
+//   * a wave owns key tiles kt = wave, wave+NW, ... (24 / NW of 16 keys); their K/V operands and the dK^T/dV^T accumulators
 //     (4 registers each) stay in registers for the whole workgroup; all waves walk the query tiles together.
 //   * S' = Q'K^T - lse' and dP - delta leave the MFMA ready: -lse' and -delta are the initial accumulators
 //     (log2 domain: Q' = q*scale*log2e, table' = table*log2e, p = exp2(S' + table' [+ mask'])).
 //   * key on the lane: the P / dS accumulators are directly the B operands of dV^T += dO^T P and dK^T += Q'^T dS;
 //     dS crosses LDS once (wave-private 16x16 tile, read back transposed) for dQ^T += K^T dS^T, which is summed over a
-//     wave's key tiles in registers and over the 4 waves through a double-buffered LDS tile per query tile.
+//     wave's key tiles in registers and over the NW waves through a double-buffered LDS tile per query tile.
 //   * A operands that need the token on the k index come from the row-major images by ds_read_b64_tr_b16 (no
 //     dim-major copies); the images swap the 16-byte halves of rows with bit 3 set (conflict-free 8-byte reads).
 //   * rel-pos bias gradients are LDS atomics, flushed once per workgroup.
 // ---------------------------------------------------------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
-static constexpr int ATT_NI = 6;                        // key tiles per wave (22 tiles of 16 / 4 waves)
 static constexpr int ATT_DS_LD = 48;                    // byte stride of the wave-private dS tile rows (conflict-free)
 
 __device__ __forceinline__ int att_chunk(int t, int c) { return t * 32 + ((c ^ ((t >> 2) & 2)) << 3); }   // byte offset of dims 4c..4c+3
@@ -626,7 +629,7 @@ __device__ __forceinline__ unsigned att_pk_bf16(float a, float b) {
 // waves halve (+1.2 % on the step), the large grids gain another 0.7 %.
 // DROP: dS = P o (M s o dP - delta) with the forward's mask M (re-created from the key), dV += (P o M s)^T dO.  A lane of the 16x16 accumulator
 // holds ONE key of four queries, i.e. four mask rows: four hashes per tile where the forward needs one per four probabilities.
-template <bool MASK, bool DT /* rel-pos table gradient wanted: no per-element branch around its atomics */, int NW = 4, bool DROP = false>
+template <bool MASK, bool DT /* rel-pos table gradient wanted: no per-element branch around its atomics */, int NW, bool DROP>
 __global__ void __launch_bounds__(NW * 64, 2) winattn_bwd_mfma_kernel(const bf16* __restrict__ qkv, int64_t ldq, const bf16* __restrict__ out, int64_t ldo,
                                                                   const bf16* __restrict__ dout, int64_t lddo, bf16* __restrict__ dqkv, int64_t lddq,
                                                                   const float* __restrict__ qkv_bias, const float* __restrict__ bias_table,
@@ -913,54 +916,28 @@ __global__ void __launch_bounds__(NW * 64, 2) winattn_bwd_mfma_kernel(const bf16
   }
 }
 
-static size_t attn_mfma_bwd_smem(int tsize, int nw = 4) {
-  (void)tsize;
+static size_t attn_mfma_bwd_smem(int nw) {      // both table copies have fixed ATT_TMAX slots: the size does not depend on the table
   return (size_t)3 * ATT_NP * 32 + (size_t)5 * ATT_NP * 4 + (size_t)2 * nw * 256 * 4 + (size_t)nw * 16 * ATT_DS_LD + 64 * 4 + (size_t)2 * ATT_TMAX * 4;
 }
+static size_t attn_mfma_fwd_smem(int64_t tsize) { return (size_t)(2 * ATT_NP * 16 + 16 * ATT_VT_LD) * 2 + (size_t)3 * ATT_NP * 4 + (size_t)tsize * 4; }
 
-static size_t attn_mfma_fwd_smem(int tsize) {
-  return (size_t)(2 * ATT_NP * 16 + 16 * ATT_VT_LD) * 2 + (size_t)3 * ATT_NP * 4 + (size_t)tsize * 4;
-}
-
-// csrc/attention_global.hip: head_dim 64 global attention on the matrix cores; return 1 when they took the call (status in *rc)
-int global_attn_fwd(const miseg_winattn_params* p, const AttnDrop& dr, hipStream_t s, int* rc);
-int global_attn_bwd(const miseg_winattn_bwd_params* p, const AttnDrop& dr, hipStream_t s, int* rc);
-bool global_attn_takes(const miseg_winattn_params* p);
-bool global_attn_bwd_takes(const miseg_winattn_bwd_params* p);
+// csrc/attention_global.hip: head_dim 64 global attention on the matrix cores - the LDS of either kernel and the launcher of a plan that names them
+size_t global_attn_lds_bytes(int NP, bool bwd);
+int global_attn_launch(const miseg_winattn_params* p, const miseg_winattn_bwd_params* b, const miseg_winattn_plan_info& pl, const AttnDrop& dr, hipStream_t s);
 
 }  // namespace miseg
 
 using namespace miseg;
 
-static int make_geom(const miseg_winattn_params* p, WinGeom* g) {
-  MISEG_REQUIRE(p->qkv && p->out && p->lse, MISEG_E_BADARG, "winattn: null pointer");
-  MISEG_REQUIRE(p->B > 0 && p->D > 0 && p->H > 0 && p->W > 0 && p->C > 0 && p->heads > 0 && p->C % p->heads == 0, MISEG_E_BADARG, "winattn: bad shape");
-  MISEG_REQUIRE(p->wd > 0 && p->wh > 0 && p->ww > 0 && p->wd * p->wh * p->ww <= 384, MISEG_E_UNSUPPORTED, "winattn: window %dx%dx%d (max 384 tokens)", p->wd, p->wh,
-                p->ww);
-  MISEG_REQUIRE(p->sd >= 0 && p->sd < p->wd && p->sh >= 0 && p->sh < p->wh && p->sw >= 0 && p->sw < p->ww, MISEG_E_BADARG, "winattn: shift must be < window");
-  g->B = p->B; g->D = p->D; g->H = p->H; g->W = p->W; g->C = p->C; g->heads = p->heads; g->hd = p->C / p->heads;
-  g->wd = p->wd; g->wh = p->wh; g->ww = p->ww; g->sd = p->sd; g->sh = p->sh; g->sw = p->sw; g->tw = p->bias_table ? p->tw : 1;
-  g->nwd = cdiv(p->D, p->wd); g->nwh = cdiv(p->H, p->wh); g->nww = cdiv(p->W, p->ww);
-  g->Dp = g->nwd * p->wd; g->Hp = g->nwh * p->wh; g->Wp = g->nww * p->ww;
-  g->n = p->wd * p->wh * p->ww;
-  g->scale = p->scale;
-  if (p->bias_table) {
-    MISEG_REQUIRE(p->tw > 0 && p->tw * p->tw * p->tw >= g->n, MISEG_E_BADARG, "winattn: table window %d^3 smaller than the %d-token window", p->tw, g->n);
-  }
-  MISEG_REQUIRE(g->hd % 4 == 0 && g->hd <= 64, MISEG_E_UNSUPPORTED, "winattn: head_dim %d (need multiple of 4, <= 64)", g->hd);
-  return MISEG_OK;
+static WinGeom win_geom(const miseg_winattn_params* p) {      // of a call the plan accepted
+  WinGeom g;
+  g.B = p->B; g.D = p->D; g.H = p->H; g.W = p->W; g.C = p->C; g.heads = p->heads; g.hd = p->C / p->heads;
+  g.wd = p->wd; g.wh = p->wh; g.ww = p->ww; g.sd = p->sd; g.sh = p->sh; g.sw = p->sw; g.tw = p->bias_table ? p->tw : 1;
+  g.nwd = cdiv(p->D, p->wd); g.nwh = cdiv(p->H, p->wh); g.nww = cdiv(p->W, p->ww);
+  g.Dp = g.nwd * p->wd; g.Hp = g.nwh * p->wh; g.Wp = g.nww * p->ww;
+  g.n = p->wd * p->wh * p->ww; g.scale = p->scale;
+  return g;
 }
-
-#define HD_SWITCH(hd4, ...)                                     \
-  switch (hd4) {                                                \
-    case 1: { constexpr int HD4 = 1; __VA_ARGS__; } break;      \
-    case 2: { constexpr int HD4 = 2; __VA_ARGS__; } break;      \
-    case 3: { constexpr int HD4 = 3; __VA_ARGS__; } break;      \
-    case 4: { constexpr int HD4 = 4; __VA_ARGS__; } break;      \
-    case 8: { constexpr int HD4 = 8; __VA_ARGS__; } break;      \
-    case 16: { constexpr int HD4 = 16; __VA_ARGS__; } break;    \
-    default: return set_error(MISEG_E_UNSUPPORTED, "winattn: head_dim %d not instantiated (4,8,12,16,32,64)", 4 * (hd4)); \
-  }
 
 static AttnDrop attn_drop_args(const miseg_winattn_params* p) {
   AttnDrop dr;
@@ -971,117 +948,176 @@ static AttnDrop attn_drop_args(const miseg_winattn_params* p) {
   return dr;
 }
 
-static bool fwd_takes_mfma(const miseg_winattn_params* p, const WinGeom& g) {
-  return p->dtype == MISEG_BF16 && g.hd == 16 && g.n <= ATT_NP && p->bias_table && ((uintptr_t)p->out % 8 == 0) && p->ldo % 4 == 0;
+// ------------------------------------------------------------------------------------------------ the plan of one miseg_winattn_fwd / _bwd launch
+// Host only.  Every predicate, grid and LDS size of the attention launchers is written here, once; the launchers below read the plan and decide
+// nothing.  One function serves both directions (b: the backward's params, NULL for a forward plan).  The order of the checks is the order in
+// which a launch has always refused or routed a call; where it looks odd, the condition is numbered and listed in DESIGN.md 3.4.
+static constexpr size_t ATT_MAX_LDS = 160 * 1024;
+static bool vec_rows(const void* ptr, int64_t ld, unsigned bytes, int elems) { return (uintptr_t)ptr % bytes == 0 && ld % elems == 0; }
+
+// a refusal: the code, kernel = none, and (say) its text for miseg_last_error - the question entry points ask quietly
+#define ATTN_REQUIRE(cond, code, ...)                                  \
+  if (!(cond)) {                                                       \
+    const int rc__ = say ? set_error((code), __VA_ARGS__) : (code);    \
+    *pl = miseg_winattn_plan_info{};                                   \
+    return rc__;                                                       \
+  }
+
+static int attn_plan(const miseg_winattn_params* p, const miseg_winattn_bwd_params* b, miseg_winattn_plan_info* pl, bool say) {
+  *pl = miseg_winattn_plan_info{};
+  const bool bwd = b != nullptr;
+  const char* who = bwd ? "winattn_bwd" : "winattn_fwd";
+  ATTN_REQUIRE(p, MISEG_E_BADARG, "winattn_fwd: null params");
+  if (bwd) {
+    ATTN_REQUIRE(b->dout && b->dqkv, MISEG_E_BADARG, "winattn_bwd: null pointer");
+    // without a table the kernels reserve no LDS for its gradient bins: the query-lane kernel's bin updates would land in its own log-sum-exp rows
+    ATTN_REQUIRE(!b->dbias_table || p->bias_table, MISEG_E_BADARG, "winattn_bwd: dbias_table given without a bias_table");
+  }
+  // ---- geometry
+  ATTN_REQUIRE(p->qkv && p->out && p->lse, MISEG_E_BADARG, "winattn: null pointer");
+  ATTN_REQUIRE(p->B > 0 && p->D > 0 && p->H > 0 && p->W > 0 && p->C > 0 && p->heads > 0 && p->C % p->heads == 0, MISEG_E_BADARG, "winattn: bad shape");
+  ATTN_REQUIRE(p->wd > 0 && p->wh > 0 && p->ww > 0 && (int64_t)p->wd * p->wh * p->ww <= 384, MISEG_E_UNSUPPORTED, "winattn: window %dx%dx%d (max 384 tokens)", p->wd, p->wh, p->ww);
+  ATTN_REQUIRE(p->sd >= 0 && p->sd < p->wd && p->sh >= 0 && p->sh < p->wh && p->sw >= 0 && p->sw < p->ww, MISEG_E_BADARG, "winattn: shift must be < window");
+  const int n = p->wd * p->wh * p->ww, hd = p->C / p->heads;
+  ATTN_REQUIRE(!p->bias_table || (p->tw > 0 && (int64_t)p->tw * p->tw * p->tw >= n), MISEG_E_BADARG, "winattn: table window %d^3 smaller than the %d-token window", p->tw, n);
+  ATTN_REQUIRE(hd % 4 == 0 && hd <= 64, MISEG_E_UNSUPPORTED, "winattn: head_dim %d (need multiple of 4, <= 64)", hd);
+  // (5) drop_p is looked at after the geometry
+  ATTN_REQUIRE(p->drop_p >= 0.f && p->drop_p < 1.f, MISEG_E_BADARG, "%s: drop_p = %f must lie in [0, 1)", who, (double)p->drop_p);
+  const int64_t tb = p->bias_table ? 2 * (int64_t)p->tw - 1 : 1, tsize = p->bias_table ? tb * tb * tb : 0;
+  const int windows = p->B * cdiv(p->D, p->wd) * cdiv(p->H, p->wh) * cdiv(p->W, p->ww);
+  const bool bf = p->dtype == MISEG_BF16, masked = (p->sd | p->sh | p->sw) != 0;
+  pl->tokens = n; pl->mask = masked; pl->drop = attn_drop_args(p).thresh != 0; pl->table_grad = bwd && b->dbias_table;
+  pl->grid_y = pl->grid_z = 1;
+  // alignment, each written once: rows of 16-byte vectors (8 bf16) and rows of 8-byte pieces (4 bf16)
+  const bool qkv16 = vec_rows(p->qkv, p->ldq, 16, 8), qkv8 = vec_rows(p->qkv, p->ldq, 8, 4);
+  const bool out16 = vec_rows(p->out, p->ldo, 16, 8), out8 = vec_rows(p->out, p->ldo, 8, 4);
+  const bool dout16 = bwd && vec_rows(b->dout, b->lddo, 16, 8), dqkv8 = bwd && vec_rows(b->dqkv, b->lddq, 8, 4);
+  // ---- (2) the global kernels are tried first, before the query-lane LDS bound: one unshifted window = the whole token grid, head_dim 64, bf16, no
+  // table.  (3) With a shift or a window smaller than the grid such a call is a query-lane call.  The forward stages whole 16-byte rows of qkv and
+  // stores out in 8-byte pieces; the backward also stages dO and O in 16-byte rows and stores dqkv in 8-byte pieces - a backward that declines by
+  // layout alone falls to the query-lane kernels (every forward kernel stores the log-sum-exp in natural-log units).
+  const bool global_shape = bf && !p->bias_table && hd == GA_HD && p->wd == p->D && p->wh == p->H && p->ww == p->W && !masked && n <= GA_MAXN;
+  const bool global_fwd = global_shape && qkv16 && out8, global_bwd = global_fwd && dout16 && out16 && dqkv8;
+  if (bwd ? global_bwd : global_fwd) {
+    const int NP = (n + 31) / 32 * 32;      // padded tokens: NP / 16 is even, 2 .. 16
+    pl->kernel = MISEG_WINATTN_GLOBAL_MFMA; pl->tiles = NP / 16; pl->waves = 4;
+    pl->grid_x = cdiv(n, 64) * (bwd ? 2 : 1); pl->grid_y = p->heads; pl->grid_z = p->B;      // backward: 64-query tiles of role "dQ", then as many 64-key tiles of role "dK,dV"
+    pl->lds_bytes = global_attn_lds_bytes(NP, bwd);
+  } else {
+    // ---- (1) the query-lane LDS bound applies before the window matrix-core branch: it also refuses calls those kernels would otherwise take
+    const size_t ql_lds = attn_smem_bytes(n, hd, tsize, bwd);
+    ATTN_REQUIRE(ql_lds <= ATT_MAX_LDS, MISEG_E_UNSUPPORTED, "%s: %zu bytes of LDS needed", who, ql_lds);
+    pl->table_size = (int)tsize;
+    // ---- the window matrix-core kernels: bf16, head_dim 16, a table, <= 352 tokens; the forward stores out in 8-byte pieces; the backward reads V
+    // and stores dqkv in 8-byte pieces and keeps both table copies in fixed slots of ATT_TMAX words
+    const bool win_shape = bf && hd == 16 && n <= ATT_NP && p->bias_table;
+    if (bwd ? win_shape && tsize <= ATT_TMAX && dqkv8 && qkv8 : win_shape && out8) {
+      pl->kernel = MISEG_WINATTN_WINDOW_MFMA; pl->grid_x = windows * p->heads;
+      // forward: fewer workgroups than CUs -> one query tile per wave; 8 waves otherwise and in every backward
+      pl->waves = !bwd && (int64_t)windows * p->heads < 256 ? 11 : 8;
+      pl->lds_bytes = bwd ? attn_mfma_bwd_smem(pl->waves) : attn_mfma_fwd_smem(tsize);
+      pl->vec = qkv16 && (!bwd || (out16 && dout16));      // operand rows as two 16-byte loads, else element by element
+      // (6) the forward keeps the whole table behind its tiles: a 33^3 table passes the bound above and does not fit here
+      ATTN_REQUIRE(pl->lds_bytes <= ATT_MAX_LDS, MISEG_E_UNSUPPORTED, "%s: %zu bytes of LDS needed", who, pl->lds_bytes);
+    } else {
+      // ---- the query-lane kernels.  (4) An unknown dtype surfaces only here, after the LDS check
+      ATTN_REQUIRE(p->dtype == MISEG_F32 || bf, MISEG_E_BADARG, "unknown dtype %d", p->dtype);
+      ATTN_REQUIRE(hd == 4 || hd == 8 || hd == 12 || hd == 16 || hd == 32 || hd == 64, MISEG_E_UNSUPPORTED, "winattn: head_dim %d not instantiated (4,8,12,16,32,64)", hd);
+      pl->kernel = MISEG_WINATTN_QUERY_LANE; pl->hd4 = hd / 4; pl->waves = cdiv(n, 64);
+      pl->grid_x = windows; pl->grid_y = p->heads; pl->lds_bytes = ql_lds;
+    }
+  }
+  pl->threads = pl->waves * 64;
+  pl->units = pl->grid_x * pl->grid_y * pl->grid_z;
+  return MISEG_OK;
+}
+#undef ATTN_REQUIRE
+
+// the backward's entry points hand in b and its forward half; a NULL b reads as the forward's "null params", so it is refused here
+static int attn_bwd_plan(const miseg_winattn_bwd_params* b, miseg_winattn_plan_info* pl, bool say) {
+  if (b) return attn_plan(&b->f, b, pl, say);
+  *pl = miseg_winattn_plan_info{};
+  return say ? set_error(MISEG_E_BADARG, "winattn_bwd: null pointer") : MISEG_E_BADARG;
+}
+extern "C" int miseg_winattn_fwd_plan(const miseg_winattn_params* p, miseg_winattn_plan_info* plan) {
+  MISEG_REQUIRE(plan, MISEG_E_BADARG, "winattn_fwd_plan: null plan");
+  return attn_plan(p, nullptr, plan, true);
+}
+extern "C" int miseg_winattn_bwd_plan(const miseg_winattn_bwd_params* p, miseg_winattn_plan_info* plan) {
+  MISEG_REQUIRE(plan, MISEG_E_BADARG, "winattn_bwd_plan: null plan");
+  return attn_bwd_plan(p, plan, true);
+}
+static int names_matrix_cores(int rc, const miseg_winattn_plan_info& pl) { return rc == MISEG_OK && pl.kernel != MISEG_WINATTN_QUERY_LANE; }
+extern "C" int miseg_winattn_on_matrix_cores(const miseg_winattn_params* p) { miseg_winattn_plan_info pl; return names_matrix_cores(attn_plan(p, nullptr, &pl, false), pl); }
+extern "C" int miseg_winattn_bwd_on_matrix_cores(const miseg_winattn_bwd_params* p) { miseg_winattn_plan_info pl; return names_matrix_cores(attn_bwd_plan(p, &pl, false), pl); }
+
+// ------------------------------------------------------------------------------------------------ the launchers: they read the plan
+// every winattn_fwd_kernel / winattn_bwd_kernel <T, HD4> a plan reaches
+#define QUERY_LANE_FORMS(X) X(float, 1) X(float, 2) X(float, 3) X(float, 4) X(float, 8) X(float, 16) X(bf16, 1) X(bf16, 2) X(bf16, 3) X(bf16, 4) X(bf16, 8) X(bf16, 16)
+// every winattn_fwd_mfma_kernel<MASK, NW, DROP> a plan reaches
+#define WINDOW_FWD_FORMS(X) X(false, 8, false) X(false, 8, true) X(false, 11, false) X(false, 11, true) X(true, 8, false) X(true, 8, true) X(true, 11, false) X(true, 11, true)
+// every winattn_bwd_mfma_kernel<MASK, DT, NW, DROP> a plan reaches
+#define WINDOW_BWD_FORMS(X) \
+  X(false, false, 8, false) X(false, false, 8, true) X(false, true, 8, false) X(false, true, 8, true) X(true, false, 8, false) X(true, false, 8, true) X(true, true, 8, false) X(true, true, 8, true)
+template <class T> static constexpr int dtype_of() { return sizeof(T) == 4 ? MISEG_F32 : MISEG_BF16; }
+
+// the query-lane and window matrix-core kernels of either direction (b: the backward's params with p = &b->f, NULL for the forward)
+static int launch_attn(const miseg_winattn_params* p, const miseg_winattn_bwd_params* b, const miseg_winattn_plan_info& pl, const AttnDrop& dr, hipStream_t s) {
+  const WinGeom g = win_geom(p);
+  const dim3 grid(pl.grid_x, pl.grid_y);
+  const bool ql = pl.kernel == MISEG_WINATTN_QUERY_LANE, win = pl.kernel == MISEG_WINATTN_WINDOW_MFMA;
+#define FWD_ARGS(T) (const T*)p->qkv, p->ldq, (T*)p->out, p->ldo, p->qkv_bias, p->bias_table, p->lse, g, pl.table_size
+#define BWD_ARGS(T) \
+  (const T*)p->qkv, p->ldq, (const T*)p->out, p->ldo, (const T*)b->dout, b->lddo, (T*)b->dqkv, b->lddq, p->qkv_bias, p->bias_table, p->lse, b->dqkv_bias, b->dbias_table, g, pl.table_size
+#define QL_FORM(T, h_)                                                                                        \
+  if (ql && p->dtype == dtype_of<T>() && pl.hd4 == h_ && !b) {                                                \
+    MISEG_SET_SMEM((winattn_fwd_kernel<T, h_>), pl.lds_bytes);                                                \
+    winattn_fwd_kernel<T, h_><<<grid, pl.threads, pl.lds_bytes, s>>>(FWD_ARGS(T), dr);                        \
+    return MISEG_OK;                                                                                          \
+  }                                                                                                           \
+  if (ql && p->dtype == dtype_of<T>() && pl.hd4 == h_ && b) {                                                 \
+    MISEG_SET_SMEM((winattn_bwd_kernel<T, h_>), pl.lds_bytes);                                                \
+    winattn_bwd_kernel<T, h_><<<grid, pl.threads, pl.lds_bytes, s>>>(BWD_ARGS(T), dr);                        \
+    return MISEG_OK;                                                                                          \
+  }
+#define WIN_FWD_FORM(m_, nw_, d_)                                                                             \
+  if (win && !b && pl.mask == m_ && pl.waves == nw_ && pl.drop == d_) {                                       \
+    MISEG_SET_SMEM((winattn_fwd_mfma_kernel<m_, nw_, d_>), pl.lds_bytes);                                     \
+    winattn_fwd_mfma_kernel<m_, nw_, d_><<<grid, pl.threads, pl.lds_bytes, s>>>(FWD_ARGS(bf16), pl.vec, dr);  \
+    return MISEG_OK;                                                                                          \
+  }
+#define WIN_BWD_FORM(m_, dt_, nw_, d_)                                                                        \
+  if (win && b && pl.mask == m_ && pl.table_grad == dt_ && pl.waves == nw_ && pl.drop == d_) {                \
+    MISEG_SET_SMEM((winattn_bwd_mfma_kernel<m_, dt_, nw_, d_>), pl.lds_bytes);                                \
+    winattn_bwd_mfma_kernel<m_, dt_, nw_, d_><<<grid, pl.threads, pl.lds_bytes, s>>>(BWD_ARGS(bf16), pl.vec, dr); \
+    return MISEG_OK;                                                                                          \
+  }
+  QUERY_LANE_FORMS(QL_FORM) WINDOW_FWD_FORMS(WIN_FWD_FORM) WINDOW_BWD_FORMS(WIN_BWD_FORM)
+#undef QL_FORM
+#undef WIN_FWD_FORM
+#undef WIN_BWD_FORM
+#undef FWD_ARGS
+#undef BWD_ARGS
+  return set_error(MISEG_E_UNSUPPORTED, "%s: no kernel %d <mask %d, table_grad %d, waves %d, drop %d, hd4 %d> for dtype %d", b ? "winattn_bwd" : "winattn_fwd", pl.kernel, pl.mask,
+                   pl.table_grad, pl.waves, pl.drop, pl.hd4, p->dtype);
 }
 
-extern "C" int miseg_winattn_on_matrix_cores(const miseg_winattn_params* p) {
-  WinGeom g;
-  if (!p || make_geom(p, &g)) return 0;
-  return (fwd_takes_mfma(p, g) || global_attn_takes(p)) ? 1 : 0;
-}
-
-// the backward's own conditions: the table must fit the fixed LDS slots of both its copies, and dqkv / qkv take 8-byte accesses
-static bool bwd_takes_mfma(const miseg_winattn_bwd_params* p, const WinGeom& g) {
-  const int tb = 2 * g.tw - 1;
-  return p->f.dtype == MISEG_BF16 && g.hd == 16 && g.n <= ATT_NP && p->f.bias_table && tb * tb * tb <= ATT_TMAX && ((uintptr_t)p->dqkv % 8 == 0) && p->lddq % 4 == 0 &&
-         ((uintptr_t)p->f.qkv % 8 == 0) && p->f.ldq % 4 == 0;
-}
-
-extern "C" int miseg_winattn_bwd_on_matrix_cores(const miseg_winattn_bwd_params* p) {
-  WinGeom g;
-  if (!p || !p->dout || !p->dqkv || make_geom(&p->f, &g)) return 0;
-  return (bwd_takes_mfma(p, g) || global_attn_bwd_takes(p)) ? 1 : 0;
-}
-
-extern "C" int miseg_winattn_fwd(const miseg_winattn_params* p, miseg_stream_t s_) {
-  hipStream_t s = (hipStream_t)s_;
-  MISEG_REQUIRE(p, MISEG_E_BADARG, "winattn_fwd: null params");
-  WinGeom g;
-  int rc = make_geom(p, &g);
-  if (rc) return rc;
-  MISEG_REQUIRE(p->drop_p >= 0.f && p->drop_p < 1.f, MISEG_E_BADARG, "winattn_fwd: drop_p = %f must lie in [0, 1)", (double)p->drop_p);
+// plan, then exactly the launch it names (p = &b->f in the backward)
+static int attn_launch(const miseg_winattn_params* p, const miseg_winattn_bwd_params* b, const miseg_winattn_plan_info& pl, hipStream_t s) {
+  static const char* const names[2][4] = {{"", "winattn_fwd", "winattn_fwd_mfma", "gattn_fwd"}, {"", "winattn_bwd", "winattn_bwd_mfma", "gattn_bwd"}};
   const AttnDrop dr = attn_drop_args(p);
-  if (global_attn_fwd(p, dr, s, &rc)) return rc;       // one window = the whole token grid, head_dim 64, bf16 (the ViT of C-UNETR; round 4: with attention dropout too)
-  const int tb = 2 * g.tw - 1, tsize = p->bias_table ? tb * tb * tb : 0;
-  const size_t sh = attn_smem_bytes(g.n, g.hd, tsize, false);
-  MISEG_REQUIRE(sh <= 160 * 1024, MISEG_E_UNSUPPORTED, "winattn_fwd: %zu bytes of LDS needed", sh);
-  dim3 grid(g.B * g.nwd * g.nwh * g.nww, g.heads);
-  const int threads = cdiv(g.n, 64) * 64;
-  if (fwd_takes_mfma(p, g)) {
-    const size_t shm = attn_mfma_fwd_smem(tsize);
-    const bool vec = p->ldq % 8 == 0 && (uintptr_t)p->qkv % 16 == 0;
-    const bool wide = (int64_t)grid.x * grid.y < 256;       // fewer workgroups than CUs: one query tile per wave
-#define FWD_MFMA_D(M, NWV, D)                                                                                                                  \
-  MISEG_SET_SMEM((winattn_fwd_mfma_kernel<M, NWV, D>), shm);                    \
-  winattn_fwd_mfma_kernel<M, NWV, D><<<grid.x * grid.y, NWV * 64, shm, s>>>((const bf16*)p->qkv, p->ldq, (bf16*)p->out, p->ldo, p->qkv_bias, p->bias_table, \
-                                                                 p->lse, g, tsize, vec, dr)
-#define FWD_MFMA(M, NWV) do { if (dr.thresh) { FWD_MFMA_D(M, NWV, true); } else { FWD_MFMA_D(M, NWV, false); } } while (0)
-    if ((g.sd | g.sh | g.sw) != 0) { if (wide) { FWD_MFMA(true, 11); } else { FWD_MFMA(true, 8); } }
-    else { if (wide) { FWD_MFMA(false, 11); } else { FWD_MFMA(false, 8); } }
-#undef FWD_MFMA
-#undef FWD_MFMA_D
-    MISEG_LAUNCH_CHECK("winattn_fwd_mfma");
-    return MISEG_OK;
-  }
-  return dispatch_dtype(p->dtype, [&](auto* tag) -> int {
-    typedef typename std::remove_pointer<decltype(tag)>::type T;
-    HD_SWITCH(g.hd / 4, {
-      MISEG_SET_SMEM((winattn_fwd_kernel<T, HD4>), sh);
-      winattn_fwd_kernel<T, HD4><<<grid, threads, sh, s>>>((const T*)p->qkv, p->ldq, (T*)p->out, p->ldo, p->qkv_bias, p->bias_table, p->lse, g, tsize, dr);
-    });
-    MISEG_LAUNCH_CHECK("winattn_fwd");
-    return MISEG_OK;
-  });
+  const int rc = pl.kernel == MISEG_WINATTN_GLOBAL_MFMA ? global_attn_launch(p, b, pl, dr, s) : launch_attn(p, b, pl, dr, s);      // global: the ViT of C-UNETR
+  if (rc != MISEG_OK) return rc;
+  MISEG_LAUNCH_CHECK(names[b != nullptr][pl.kernel]);
+  return MISEG_OK;
 }
-
-extern "C" int miseg_winattn_bwd(const miseg_winattn_bwd_params* p, miseg_stream_t s_) {
-  hipStream_t s = (hipStream_t)s_;
-  MISEG_REQUIRE(p && p->dout && p->dqkv, MISEG_E_BADARG, "winattn_bwd: null pointer");
-  // without a table the kernels reserve no LDS for its gradient bins: the query-lane kernel's bin updates would land in its own log-sum-exp rows
-  MISEG_REQUIRE(!p->dbias_table || p->f.bias_table, MISEG_E_BADARG, "winattn_bwd: dbias_table given without a bias_table");
-  WinGeom g;
-  int rc = make_geom(&p->f, &g);
-  if (rc) return rc;
-  MISEG_REQUIRE(p->f.drop_p >= 0.f && p->f.drop_p < 1.f, MISEG_E_BADARG, "winattn_bwd: drop_p = %f must lie in [0, 1)", (double)p->f.drop_p);
-  const AttnDrop dr = attn_drop_args(&p->f);
-  if (global_attn_bwd(p, dr, s, &rc)) return rc;       // a call it declines (stricter alignment than the forward's) falls through: every forward kernel stores the log-sum-exp in natural-log units
-  const int tb = 2 * g.tw - 1, tsize = p->f.bias_table ? tb * tb * tb : 0;
-  const size_t sh = attn_smem_bytes(g.n, g.hd, tsize, true);
-  MISEG_REQUIRE(sh <= 160 * 1024, MISEG_E_UNSUPPORTED, "winattn_bwd: %zu bytes of LDS needed", sh);
-  dim3 grid(g.B * g.nwd * g.nwh * g.nww, g.heads);
-  const int threads = cdiv(g.n, 64) * 64;
-  if (bwd_takes_mfma(p, g)) {
-    const bool vec = p->f.ldq % 8 == 0 && p->f.ldo % 8 == 0 && p->lddo % 8 == 0 && (uintptr_t)p->f.qkv % 16 == 0 && (uintptr_t)p->f.out % 16 == 0 &&
-                     (uintptr_t)p->dout % 16 == 0;
-    // fewer workgroups than CUs (stages 3 and 4): the 8-wave form
-    const bool wide = true;       // 8 waves everywhere: two such workgroups still fit a CU (2 x 81 KB LDS, 118 VGPRs) and every stage gains
-    const size_t shm = attn_mfma_bwd_smem(tsize, wide ? 8 : 4);
-#define BWD_MFMA_X(M, D, NWV, X)                                                                                                                            \
-  MISEG_SET_SMEM((winattn_bwd_mfma_kernel<M, D, NWV, X>), shm);                              \
-  winattn_bwd_mfma_kernel<M, D, NWV, X><<<grid.x * grid.y, NWV * 64, shm, s>>>((const bf16*)p->f.qkv, p->f.ldq, (const bf16*)p->f.out, p->f.ldo, (const bf16*)p->dout,    \
-                                                                    p->lddo, (bf16*)p->dqkv, p->lddq, p->f.qkv_bias, p->f.bias_table, p->f.lse, p->dqkv_bias, \
-                                                                    p->dbias_table, g, tsize, vec, dr)
-#define BWD_MFMA(M, D, NWV) do { if (dr.thresh) { BWD_MFMA_X(M, D, NWV, true); } else { BWD_MFMA_X(M, D, NWV, false); } } while (0)
-#define BWD_MFMA_W(M, D) do { if (wide) { BWD_MFMA(M, D, 8); } else { BWD_MFMA(M, D, 4); } } while (0)
-    const bool masked = (g.sd | g.sh | g.sw) != 0;
-    if (p->dbias_table) { if (masked) BWD_MFMA_W(true, true); else BWD_MFMA_W(false, true); }
-    else { if (masked) BWD_MFMA_W(true, false); else BWD_MFMA_W(false, false); }
-#undef BWD_MFMA_W
-#undef BWD_MFMA
-#undef BWD_MFMA_X
-    MISEG_LAUNCH_CHECK("winattn_bwd_mfma");
-    return MISEG_OK;
-  }
-  return dispatch_dtype(p->f.dtype, [&](auto* tag) -> int {
-    typedef typename std::remove_pointer<decltype(tag)>::type T;
-    HD_SWITCH(g.hd / 4, {
-      MISEG_SET_SMEM((winattn_bwd_kernel<T, HD4>), sh);
-      winattn_bwd_kernel<T, HD4><<<grid, threads, sh, s>>>((const T*)p->f.qkv, p->f.ldq, (const T*)p->f.out, p->f.ldo, (const T*)p->dout, p->lddo, (T*)p->dqkv, p->lddq,
-                                                           p->f.qkv_bias, p->f.bias_table, p->f.lse, p->dqkv_bias, p->dbias_table, g,
-                                                           tsize, dr);
-    });
-    MISEG_LAUNCH_CHECK("winattn_bwd");
-    return MISEG_OK;
-  });
+extern "C" int miseg_winattn_fwd(const miseg_winattn_params* p, miseg_stream_t s) {
+  miseg_winattn_plan_info pl;
+  const int rc = attn_plan(p, nullptr, &pl, true);
+  return rc != MISEG_OK ? rc : attn_launch(p, nullptr, pl, (hipStream_t)s);
+}
+extern "C" int miseg_winattn_bwd(const miseg_winattn_bwd_params* p, miseg_stream_t s) {
+  miseg_winattn_plan_info pl;
+  const int rc = attn_bwd_plan(p, &pl, true);
+  return rc != MISEG_OK ? rc : attn_launch(&p->f, p, pl, (hipStream_t)s);
 }

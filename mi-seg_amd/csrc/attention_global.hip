@@ -13,9 +13,7 @@
 
 namespace miseg {
 
-static constexpr int GA_HD = 64;
-static constexpr int GA_RS = GA_HD + 8;              // row stride (elements) of the row-major LDS images: 144 B, conflict-free 16-byte reads
-static constexpr int GA_MAXN = 256;
+static constexpr int GA_RS = GA_HD + 8;              // row stride (elements) of the row-major LDS images: 144 B, conflict-free 16-byte reads (GA_HD, GA_MAXN: common.h)
 static constexpr float GA_LOG2E = 1.4426950408889634f;
 
 struct GaGeom {
@@ -346,75 +344,38 @@ __global__ void __launch_bounds__(256) gattn_bwd_kernel(const bf16* __restrict__
   }
 }
 
-static bool ga_geom(const miseg_winattn_params* p, GaGeom* g) {
-  const int n = p->D * p->H * p->W;
-  if (p->dtype != MISEG_BF16 || p->bias_table || p->heads <= 0 || p->C != p->heads * GA_HD) return false;
-  if (p->wd != p->D || p->wh != p->H || p->ww != p->W || (p->sd | p->sh | p->sw) != 0 || n > GA_MAXN || n < 1) return false;
-  if (p->ldq % 8 || p->ldo % 4 || ((uintptr_t)p->qkv & 15) || ((uintptr_t)p->out & 7)) return false;
-  g->B = p->B; g->n = n; g->NP = (n + 31) / 32 * 32; g->heads = p->heads; g->C = p->C; g->ldq = p->ldq; g->ldo = p->ldo; g->lddo = 0; g->lddq = 0; g->scale = p->scale;
-  return true;
+// ------------------------------------------------------------------------------------------------ launcher of a plan whose kernel is the global one
+// Host side of this file: the LDS size of either kernel (the plan of csrc/attention.hip asks for it) and the launcher.  Whether a call is this
+// kernel's - dtype, head_dim, one unshifted window, token count, the two alignment levels - is the plan's decision, written there.
+size_t global_attn_lds_bytes(int NP, bool bwd) {
+  if (!bwd) return (size_t)(NP * GA_RS + GA_HD * (NP + 8)) * 2;
+  const size_t sh_q = (size_t)(2 * NP * GA_RS + GA_HD * (NP + 8)) * 2;                               // role "dQ"
+  const size_t sh_k = (size_t)(2 * NP * GA_RS + 2 * GA_HD * (NP + 8)) * 2 + (size_t)2 * NP * 4;      // role "dK,dV"
+  return sh_q > sh_k ? sh_q : sh_k;
 }
 
-bool global_attn_takes(const miseg_winattn_params* p) {
-  GaGeom g;
-  return ga_geom(p, &g) && g.NP / 16 >= 2 && g.NP / 16 <= 16;
-}
+// every gattn_fwd_kernel / gattn_bwd_kernel <NT, DROP> a plan reaches: NT = NP / 16 is even and 16 * NT covers 1 .. GA_MAXN tokens
+#define GLOBAL_FORMS(X) \
+  X(2, false) X(2, true) X(4, false) X(4, true) X(6, false) X(6, true) X(8, false) X(8, true) X(10, false) X(10, true) X(12, false) X(12, true) X(14, false) X(14, true) X(16, false) X(16, true)
 
-// 1: handled (rc in *rc), 0: not this kernel's shape
-int global_attn_fwd(const miseg_winattn_params* p, const AttnDrop& dr, hipStream_t s, int* rc) {
-  GaGeom g;
-  if (!ga_geom(p, &g)) return 0;
-  const size_t sh = (size_t)(g.NP * GA_RS + GA_HD * (g.NP + 8)) * 2;
-  const dim3 grid(cdiv(g.n, 64), g.heads, g.B);
-#define GA_FWD_D(NT, D) do { MISEG_SET_SMEM((gattn_fwd_kernel<NT, D>), sh); \
-    gattn_fwd_kernel<NT, D><<<grid, 256, sh, s>>>((const bf16*)p->qkv, (bf16*)p->out, p->lse, g, dr); } while (0)
-#define GA_FWD(NT) do { if (dr.thresh) GA_FWD_D(NT, true); else GA_FWD_D(NT, false); } while (0)
-  switch (g.NP / 16) {
-    case 2: GA_FWD(2); break; case 4: GA_FWD(4); break; case 6: GA_FWD(6); break; case 8: GA_FWD(8); break;
-    case 10: GA_FWD(10); break; case 12: GA_FWD(12); break; case 14: GA_FWD(14); break; case 16: GA_FWD(16); break;
-    default: return 0;
+// b: the backward's params (p = &b->f), NULL for the forward
+int global_attn_launch(const miseg_winattn_params* p, const miseg_winattn_bwd_params* b, const miseg_winattn_plan_info& pl, const AttnDrop& dr, hipStream_t s) {
+  const GaGeom g{p->B, pl.tokens, pl.tiles * 16, p->heads, p->C, p->ldq, p->ldo, b ? b->lddo : 0, b ? b->lddq : 0, p->scale};
+  const dim3 grid(pl.grid_x, pl.grid_y, pl.grid_z);      // backward: grid_x / 2 query tiles of role "dQ", then as many key tiles of role "dK,dV"
+#define GA_FORM(nt_, d_)                                                                                                                                       \
+  if (pl.tiles == nt_ && pl.drop == d_ && !b) {                                                                                                                \
+    MISEG_SET_SMEM((gattn_fwd_kernel<nt_, d_>), pl.lds_bytes);                                                                                                 \
+    gattn_fwd_kernel<nt_, d_><<<grid, pl.threads, pl.lds_bytes, s>>>((const bf16*)p->qkv, (bf16*)p->out, p->lse, g, dr);                                       \
+    return MISEG_OK;                                                                                                                                           \
+  }                                                                                                                                                            \
+  if (pl.tiles == nt_ && pl.drop == d_ && b) {                                                                                                                 \
+    MISEG_SET_SMEM((gattn_bwd_kernel<nt_, d_>), pl.lds_bytes);                                                                                                 \
+    gattn_bwd_kernel<nt_, d_><<<grid, pl.threads, pl.lds_bytes, s>>>((const bf16*)p->qkv, (const bf16*)p->out, (const bf16*)b->dout, p->lse, (bf16*)b->dqkv, g, pl.grid_x / 2, dr); \
+    return MISEG_OK;                                                                                                                                           \
   }
-#undef GA_FWD
-#undef GA_FWD_D
-  hipError_t e = hipGetLastError();
-  *rc = e == hipSuccess ? MISEG_OK : set_error(MISEG_E_LAUNCH, "gattn_fwd: %s", hipGetErrorString(e));
-  return 1;
-}
-
-// the backward stages dO and O with 16-byte loads and stores dqkv in 8-byte pieces: stricter than the forward
-static bool ga_bwd_geom(const miseg_winattn_bwd_params* p, GaGeom* g) {
-  if (!ga_geom(&p->f, g)) return false;
-  if (p->lddo % 8 || p->lddq % 4 || p->f.ldo % 8 || ((uintptr_t)p->dout & 15) || ((uintptr_t)p->f.out & 15) || ((uintptr_t)p->dqkv & 7)) return false;
-  g->lddo = p->lddo; g->lddq = p->lddq;
-  return true;
-}
-
-bool global_attn_bwd_takes(const miseg_winattn_bwd_params* p) {
-  GaGeom g;
-  return ga_bwd_geom(p, &g) && g.NP / 16 >= 2 && g.NP / 16 <= 16;
-}
-
-int global_attn_bwd(const miseg_winattn_bwd_params* p, const AttnDrop& dr, hipStream_t s, int* rc) {
-  GaGeom g;
-  if (!ga_bwd_geom(p, &g)) return 0;
-  const int nqt = cdiv(g.n, 64);
-  const size_t sh_q = (size_t)(2 * g.NP * GA_RS + GA_HD * (g.NP + 8)) * 2;
-  const size_t sh_k = (size_t)(2 * g.NP * GA_RS + 2 * GA_HD * (g.NP + 8)) * 2 + (size_t)2 * g.NP * 4;
-  const size_t sh = sh_q > sh_k ? sh_q : sh_k;
-  const dim3 grid(2 * nqt, g.heads, g.B);
-#define GA_BWD_D(NT, D) do { MISEG_SET_SMEM((gattn_bwd_kernel<NT, D>), sh); \
-    gattn_bwd_kernel<NT, D><<<grid, 256, sh, s>>>((const bf16*)p->f.qkv, (const bf16*)p->f.out, (const bf16*)p->dout, p->f.lse, (bf16*)p->dqkv, g, nqt, dr); } while (0)
-#define GA_BWD(NT) do { if (dr.thresh) GA_BWD_D(NT, true); else GA_BWD_D(NT, false); } while (0)
-  switch (g.NP / 16) {
-    case 2: GA_BWD(2); break; case 4: GA_BWD(4); break; case 6: GA_BWD(6); break; case 8: GA_BWD(8); break;
-    case 10: GA_BWD(10); break; case 12: GA_BWD(12); break; case 14: GA_BWD(14); break; case 16: GA_BWD(16); break;
-    default: return 0;
-  }
-#undef GA_BWD
-#undef GA_BWD_D
-  hipError_t e = hipGetLastError();
-  *rc = e == hipSuccess ? MISEG_OK : set_error(MISEG_E_LAUNCH, "gattn_bwd: %s", hipGetErrorString(e));
-  return 1;
+  GLOBAL_FORMS(GA_FORM)
+#undef GA_FORM
+  return set_error(MISEG_E_UNSUPPORTED, "gattn: no kernel <%d tiles, drop %d>", pl.tiles, pl.drop);
 }
 
 }  // namespace miseg

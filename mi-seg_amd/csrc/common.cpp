@@ -29,7 +29,7 @@ extern "C" size_t miseg_abi_struct_size(const char* name) {
   MISEG_SZ(miseg_instnorm_stats_params) MISEG_SZ(miseg_instnorm_apply_params) MISEG_SZ(miseg_instnorm_bwd_params) MISEG_SZ(miseg_instnorm_pair_bwd_params)
   MISEG_SZ(miseg_layernorm_fwd_params) MISEG_SZ(miseg_layernorm_bwd_params) MISEG_SZ(miseg_gemm_params) MISEG_SZ(miseg_tn_reduce_desc) MISEG_SZ(miseg_gemm_tn_desc) MISEG_SZ(miseg_gemm_tn_stream_desc) MISEG_SZ(miseg_gemm_tn_stream_plan) MISEG_SZ(miseg_gemm_plan_info)
   MISEG_SZ(miseg_mlp_params) MISEG_SZ(miseg_colsum_params) MISEG_SZ(miseg_colsum_desc) MISEG_SZ(miseg_conv3_params) MISEG_SZ(miseg_pack_conv3_params) MISEG_SZ(miseg_pack_conv3_desc)
-  MISEG_SZ(miseg_conv3_wgrad_params) MISEG_SZ(miseg_conv3_plan_info) MISEG_SZ(miseg_conv3_wgrad_plan_info) MISEG_SZ(miseg_winattn_params) MISEG_SZ(miseg_winattn_bwd_params) MISEG_SZ(miseg_add_params) MISEG_SZ(miseg_copy2d_params)
+  MISEG_SZ(miseg_conv3_wgrad_params) MISEG_SZ(miseg_conv3_plan_info) MISEG_SZ(miseg_conv3_wgrad_plan_info) MISEG_SZ(miseg_winattn_params) MISEG_SZ(miseg_winattn_bwd_params) MISEG_SZ(miseg_winattn_plan_info) MISEG_SZ(miseg_add_params) MISEG_SZ(miseg_copy2d_params)
   MISEG_SZ(miseg_cast_params) MISEG_SZ(miseg_cast_desc) MISEG_SZ(miseg_gelu_fwd_params) MISEG_SZ(miseg_gelu_bwd_params) MISEG_SZ(miseg_s2c_params)
   MISEG_SZ(miseg_patch_embed_params) MISEG_SZ(miseg_patch_embed_bwd_params) MISEG_SZ(miseg_conv3_thin_params) MISEG_SZ(miseg_conv3_thin_wgrad_params)
   MISEG_SZ(miseg_resample2_params) MISEG_SZ(miseg_upsample_cat_params) MISEG_SZ(miseg_upsample_cat_bwd_params) MISEG_SZ(miseg_rowbias_params) MISEG_SZ(miseg_prelu_fwd_params) MISEG_SZ(miseg_prelu_bwd_params) MISEG_SZ(miseg_head_params)

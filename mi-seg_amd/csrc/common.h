@@ -177,6 +177,8 @@ __device__ __forceinline__ void aug_source(const S& a, int rd, int rh, int rw, i
 
 // dropout on attention probabilities (attn_drop): thresh == 0 = off.  The mask is miseg_dropout's over the [windows * heads * n][n] matrix
 struct AttnDrop { unsigned thresh; float scale; uint64_t key; const uint64_t* step_dev; };
+// attention_global.hip: head_dim and the most tokens of the global kernels (the plan of attention.hip routes by them)
+static constexpr int GA_HD = 64, GA_MAXN = 256;
 
 // norm.hip: second launch of a split convolution - y = round(sum of nslabs fp32 slabs [B * S][C] (+ res)), and the instance-norm statistics
 // of y into `stat` (replicated fp64 layout of miseg_instnorm_stats; may be null)

@@ -101,6 +101,10 @@ Winattn = _struct("Winattn", cname="miseg_winattn_params", fields=[("qkv", vp), 
                               ("tw", i32), ("scale", f32), ("drop_p", f32), ("drop_seed", C.c_uint64), ("drop_stream", C.c_uint64), ("drop_step_dev", vp)])
 WinattnBwd = _struct("WinattnBwd", cname="miseg_winattn_bwd_params", fields=[("f", Winattn), ("dout", vp), ("lddo", i64), ("dqkv", vp), ("lddq", i64),
                                     ("dqkv_bias", vp), ("dbias_table", vp)])
+WINATTN_NONE, WINATTN_QUERY_LANE, WINATTN_WINDOW_MFMA, WINATTN_GLOBAL_MFMA = range(4)      # miseg_winattn_plan_info.kernel
+WinattnPlan = _struct("WinattnPlan", cname="miseg_winattn_plan_info", fields=[(f, i32) for f in (
+    "kernel", "mask", "drop", "table_grad", "waves", "hd4", "tiles", "vec", "grid_x", "grid_y", "grid_z", "threads", "tokens", "table_size", "units")] + [
+    ("lds_bytes", C.c_size_t)])
 Add = _struct("Add", cname="miseg_add_params", fields=[("a", vp), ("lda", i64), ("b", vp), ("ldb", i64), ("y", vp), ("ldy", i64), ("rows", i64), ("C", i32), ("dtype", i32)])
 GraphSplitInfo = _struct("GraphSplitInfo", cname="miseg_graph_split_info", fields=[("nodes", i32), ("lanes", i32), ("segments", i32), ("crossing_edges", i32),
                                                                                   ("side_streams", i32), ("main_lane_nodes", i32), ("streams_concurrent", i32)])
@@ -296,6 +300,8 @@ PROTOS = {
     "miseg_winattn_on_matrix_cores": (i32, [vp]),
     "miseg_winattn_bwd": (i32, [C.POINTER(WinattnBwd), vp]),
     "miseg_winattn_bwd_on_matrix_cores": (i32, [vp]),
+    "miseg_winattn_fwd_plan": (i32, [C.POINTER(Winattn), C.POINTER(WinattnPlan)]),
+    "miseg_winattn_bwd_plan": (i32, [C.POINTER(WinattnBwd), C.POINTER(WinattnPlan)]),
     "miseg_add": (i32, [C.POINTER(Add), vp]),
     "miseg_affine2": (i32, [C.POINTER(Affine2), vp]),
     "miseg_instnorm_bwd_reduce": (i32, [C.POINTER(InstnormBwd), vp]),

@@ -1137,7 +1137,7 @@ def _rows_ptr(t):
 
 
 def _plan(fn, p, plan):
-    """the library's plan of a 3x3x3 launch (miseg_conv3_fwd_plan / miseg_conv3_wgrad_plan) from the launch's own params"""
+    """the library's plan of a launch (miseg_conv3_fwd_plan / miseg_conv3_wgrad_plan / miseg_winattn_fwd_plan / _bwd_plan) from the launch's own params"""
     L.check(getattr(L.load(), fn)(C.byref(p), C.byref(plan)), fn)
     return plan
 
@@ -1474,13 +1474,28 @@ def winattn_params(qkv, out, qkv_bias, table, lse, heads, window, shift, tw, sca
                      window[0], window[1], window[2], shift[0], shift[1], shift[2], tw, scale, float(dp), seed, sid, _ptr(step))
 
 
+def winattn_fwd_plan(p):
+    """the plan (L.WinattnPlan) of miseg_winattn_fwd on these winattn_params; raises what the launch would raise for a call it refuses"""
+    return _plan("miseg_winattn_fwd_plan", p, L.WinattnPlan())
+
+
+def winattn_bwd_plan(p):
+    """the plan (L.WinattnPlan) of miseg_winattn_bwd on this L.WinattnBwd (winattn_params in .f)"""
+    return _plan("miseg_winattn_bwd_plan", p, L.WinattnPlan())
+
+
+def _windows_tokens(qkv, window):
+    """(windows over the padded grid, tokens per window)"""
+    B, D, H, W = _vol(qkv)
+    return B * -(-D // window[0]) * -(-H // window[1]) * -(-W // window[2]), window[0] * window[1] * window[2]
+
+
 def winattn_fwd(qkv, qkv_bias, table, heads, window, shift, tw, scale, drop=None):
     B, D, H, W = _vol(qkv)
     Cc = qkv.shape[-1] // 3
     out = torch.empty(B, D, H, W, Cc, dtype=qkv.dtype, device=qkv.device)
-    nw = B * -(-D // window[0]) * -(-H // window[1]) * -(-W // window[2])
-    lse = torch.empty(nw, heads, window[0] * window[1] * window[2], dtype=torch.float32, device=qkv.device)
-    n = window[0] * window[1] * window[2]
+    nw, n = _windows_tokens(qkv, window)
+    lse = torch.empty(nw, heads, n, dtype=torch.float32, device=qkv.device)
     _call("miseg_winattn_fwd", winattn_params(qkv, out, qkv_bias, table, lse, heads, window, shift, tw, scale, drop),
           prof=("winattn", 4.0 * nw * heads * n * n * (Cc // heads), _nb(qkv, out, lse)))
     return out, lse
@@ -1490,9 +1505,7 @@ def winattn_bwd(qkv, out, lse, dout, qkv_bias, table, heads, window, shift, tw, 
     dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
     f = winattn_params(qkv, out, qkv_bias, table, lse, heads, window, shift, tw, scale, drop)
     p = L.WinattnBwd(f, _ptr(dout), rows(dout)[0], _ptr(dqkv), rows(dqkv)[0], _ptr(dqkv_bias), _ptr(dtable))
-    B, D, H, W = _vol(qkv)
-    n = window[0] * window[1] * window[2]
-    nw = B * -(-D // window[0]) * -(-H // window[1]) * -(-W // window[2])
+    nw, n = _windows_tokens(qkv, window)
     _call("miseg_winattn_bwd", p, prof=("winattn", 10.0 * nw * heads * n * n * (qkv.shape[-1] // 3 // heads), _nb(qkv, out, lse, dout, dqkv)))
     return dqkv
 

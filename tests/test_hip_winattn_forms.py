@@ -4,8 +4,10 @@ dropout; backward with or without mask, table gradient and dropout; vector or sc
 (eight tile counts).  Every case stands against the float64 reference of tests/winattn_ref.py on the same fp32 or bf16-rounded inputs
 (pinned on the CPU by tests/test_winattn_ref_cpu.py, which also shows that the inputs leave a model of the matrix-core rounding points
 below half of every bar on `out`), pooled and per element (parity.assert_parity); forward and backward run twice and `out`, `lse`, `dqkv`
-must repeat bit for bit (`dtable` and `dqkv_bias` end in float atomics across workgroups: parity only); the kernel choice is asserted with
-miseg_winattn_on_matrix_cores / miseg_winattn_bwd_on_matrix_cores; `out`, `lse`, `dqkv` start NaN-filled (a skipped row stays NaN) or, as
+must repeat bit for bit (`dtable` and `dqkv_bias` end in float atomics across workgroups: parity only); before each launch the library's plan
+(miseg_winattn_fwd_plan / _bwd_plan) must equal, field for field, the hand-derived row of tests/winattn_cases.py for that call - kernel
+family, template arguments, vec, grid, threads, LDS, units - and miseg_winattn_on_matrix_cores / miseg_winattn_bwd_on_matrix_cores must
+answer as that plan; `out`, `lse`, `dqkv` start NaN-filled (a skipped row stays NaN) or, as
 views, inside sentinel-filled buffers that must survive outside the view.
 
 form -> case (winattn_ref.GEOMETRY unless said)
@@ -52,6 +54,7 @@ import functools
 import pytest
 import torch
 
+import winattn_cases as G
 import winattn_ref as W
 from layouts import SENT, assert_untouched, place_in
 from parity import assert_parity
@@ -112,16 +115,24 @@ def _ref(spec, dtype, drop_p):
     return r
 
 
+_CODE = {F32: G.F32, BF: G.BF16}
+
+
+def _forms(spec, dtype, drop_p=0.0, lay=None, want_dtable=True, want_dqb=True):
+    """(forward, backward) launch forms of a call - G.ql(hd4, waves) / G.win(waves, vec) / G.glob(tiles, grid_x) - from the hand-derived table of
+    tests/winattn_cases.py (pinned on the CPU by tests/test_winattn_plan_cpu.py)"""
+    return G.find(spec, _CODE[dtype], drop_p, lay, want_dtable, want_dqb)
+
+
 def _expected(spec, dtype):
-    """(forward, backward) on the matrix cores for contiguous operands, from the launch conditions of csrc/attention.hip (fwd_takes_mfma,
-    bwd_takes_mfma: bf16, head_dim 16, a table, <= 352 tokens; the backward's table must fit 2200 LDS words) and of
-    csrc/attention_global.hip (ga_geom: bf16, head_dim 64, no table, one unshifted window = the grid of <= 256 tokens)"""
-    if dtype != BF:
-        return 0, 0
-    if not spec.table:
-        return (1, 1) if spec.hd == 64 and spec.ws == spec.dims and not any(spec.ss) and spec.n <= 256 else (0, 0)
-    fwd = spec.hd == 16 and spec.n <= 352
-    return int(fwd), int(fwd and (2 * spec.tw - 1) ** 3 <= 2200)
+    """(forward, backward) on the matrix cores for contiguous operands: the table's rows"""
+    return tuple(int(f[0] != "ql") for f in _forms(spec, dtype))
+
+
+def _assert_plan(pl, spec, dtype, form, bwd, drop_p, want_dtable, what):
+    want = G.expected(spec, _CODE[dtype], form, bwd, drop_p, want_dtable)
+    got = {k: getattr(pl, k) for k in want}
+    assert got == want, f"{what}: the {'backward' if bwd else 'forward'} plan {got} is not the table's {want}"
 
 
 def _in(t, lay):
@@ -140,7 +151,9 @@ def run(spec, dtype, drop_p=0.0, lay=None, expect=None, want_dtable=True, want_d
     lay = lay or {}
     c, ref = _case(spec, dtype), _ref(spec, dtype, drop_p)
     what = f"{spec} {_name(dtype)} p={drop_p} {lay or ''}"
-    exp_f, exp_b = expect if expect is not None else _expected(spec, dtype)
+    form_f, form_b = _forms(spec, dtype, drop_p, lay, want_dtable, want_dqb)
+    exp_f, exp_b = int(form_f[0] != "ql"), int(form_b[0] != "ql")
+    assert expect is None or tuple(expect) == (exp_f, exp_b), f"{what}: the test expects {expect} on the matrix cores, the table {form_f} / {form_b}"
     drop = (drop_p, _key()) if drop_p else None
     qkv, dout = _in(c.qkv, lay.get("qkv")), _in(c.dout, lay.get("dout"))
     tol = W.TOL[dtype]
@@ -150,19 +163,21 @@ def run(spec, dtype, drop_p=0.0, lay=None, expect=None, want_dtable=True, want_d
         out = W.new_output(c.dout.shape, dtype, lay.get("out", "contig"))
         lse = torch.full((spec.windows, spec.heads, spec.n), float("nan"), device=DEV)
         prm = W.fwd_params(ops, spec, qkv, out.view, c.qb, c.table, lse, drop)
-        assert lib.miseg_winattn_on_matrix_cores(C.byref(prm)) == exp_f, f"{what}: forward kernel choice"
+        pl = ops.winattn_fwd_plan(prm)
+        _assert_plan(pl, spec, dtype, form_f, 0, drop_p, want_dtable, what)
+        assert lib.miseg_winattn_on_matrix_cores(C.byref(prm)) == exp_f == int(pl.kernel != L.WINATTN_QUERY_LANE), f"{what}: forward kernel choice"
         L.check(lib.miseg_winattn_fwd(C.byref(prm), ops._stream()), "winattn_fwd")
-        return out, lse
+        return out, lse, pl
 
-    out, lse = forward()
+    out, lse, plan_f = forward()
     pooled, loc = assert_parity(out.view, ref["out"], tol, f"{what}: out against float64")
     _report(what, dtype, "out", pooled, loc)
     assert bool(torch.isfinite(lse).all()), f"{what}: {int((~torch.isfinite(lse)).sum())} lse rows were never written"
-    lerr, yard = float((lse.double() - ref["lse"]).abs().max()), ref["yard"][exp_f]
+    lerr, yard = float((lse.double() - ref["lse"]).abs().max()), ref["yard"][int(plan_f.kernel != L.WINATTN_QUERY_LANE)]      # of the kernel family the plan names
     print(f"WINATTN {_name(dtype)} lse{'-mc' if exp_f else '-ql'} err {lerr:.3e} yardstick {yard:.3e} | {what}")
     assert lerr <= 2 * yard, f"{what}: lse off by {lerr:.3e}, allowed 2 x {yard:.3e} (the {'rounding model' if exp_f else 'fp32 logsumexp'})"
     assert_untouched(out, f"{what}: out")
-    out2, lse2 = forward()
+    out2, lse2, _ = forward()
     assert torch.equal(out.view, out2.view) and torch.equal(lse, lse2), f"{what}: the forward does not repeat bit for bit"
 
     def backward():
@@ -170,7 +185,9 @@ def run(spec, dtype, drop_p=0.0, lay=None, expect=None, want_dtable=True, want_d
         dtab = torch.zeros_like(c.table) if (want_dtable and c.table is not None) else None
         dqb = torch.zeros_like(c.qb) if (want_dqb and c.qb is not None) else None
         prm = W.bwd_params(ops, L, spec, qkv, out.view, c.qb, c.table, lse, dout, dqkv.view, dqb, dtab, drop)
-        assert lib.miseg_winattn_bwd_on_matrix_cores(C.byref(prm)) == exp_b, f"{what}: backward kernel choice"
+        pl = ops.winattn_bwd_plan(prm)
+        _assert_plan(pl, spec, dtype, form_b, 1, drop_p, want_dtable, what)
+        assert lib.miseg_winattn_bwd_on_matrix_cores(C.byref(prm)) == exp_b == int(pl.kernel != L.WINATTN_QUERY_LANE), f"{what}: backward kernel choice"
         L.check(lib.miseg_winattn_bwd(C.byref(prm), ops._stream()), "winattn_bwd")
         return dqkv, dtab, dqb
 
@@ -209,18 +226,22 @@ def test_capacity_edges_pick_the_kernels_the_table_and_the_token_count_allow():
     assert _expected(by[(6, 8, 8)], BF) == (0, 0) and by[(6, 8, 8)].n == 384
     assert _expected(by[(6, 6, 10)], BF) == (0, 0) and by[(6, 6, 10)].n == 360
     assert _expected(W.PRODUCTION, BF) == (1, 1) and W.PRODUCTION.windows * W.PRODUCTION.heads == 270
+    assert _forms(by[(11, 8, 4)], BF) == (G.win(11), G.ql(4, 6)) and _forms(by[(6, 8, 8)], BF) == _forms(by[(6, 6, 10)], BF) == (G.ql(4, 6), G.ql(4, 6))
 
 
 def test_the_production_form_with_dropout():
     """270 units of 343 tokens (the 8-wave forward, a wave owning two query tiles; a remainder in the unit mapping), padded, masked, p = 0.25"""
-    run(W.PRODUCTION, BF, drop_p=0.25)
+    spec = W.PRODUCTION
+    assert _forms(spec, BF, 0.25) == (G.win(8), G.win(8)) and any(spec.ss) and spec.windows * spec.heads == 270      # forward <1, 8, 1>
+    run(spec, BF, drop_p=0.25)
 
 
 @pytest.mark.parametrize("drop_p", [0.0, 0.25])
 def test_unshifted_grids_at_the_wave_boundary(drop_p):
     """256 units without a shift mask: the 8-wave forward's unmasked instantiations"""
     spec = S((16, 16, 16), (4, 4, 4), (0, 0, 0), 4, 64, B=1)
-    assert spec.windows * spec.heads == 256
+    assert spec.windows * spec.heads == 256 and not any(spec.ss)
+    assert _forms(spec, BF, drop_p) == (G.win(8), G.win(8))      # forward <mask 0, waves 8, drop>
     run(spec, BF, drop_p=drop_p)
 
 
@@ -233,6 +254,8 @@ def test_options(spec, drop_p, dtype):
     not the parameter gradients are asked for (bf16: mask x DT x DROP are the eight backward instantiations of the matrix-core kernel)"""
     full = run(spec, dtype, drop_p=drop_p)
     for want_dtable, want_dqb in ((False, True), (True, False), (False, False)):
+        # bf16: <mask, table gradient, 8, dropout> - run() holds each launch's plan to it; fp32: the query lanes
+        assert _forms(spec, dtype, drop_p, None, want_dtable, want_dqb) == ((G.win(11), G.win(8)) if dtype == BF else (G.ql(4, G._w(spec.n)),) * 2)
         got = run(spec, dtype, drop_p=drop_p, want_dtable=want_dtable, want_dqb=want_dqb)
         assert torch.equal(full, got), f"dqkv differs with dtable {'given' if want_dtable else 'None'}, dqkv_bias {'given' if want_dqb else 'None'}"
 
@@ -240,7 +263,7 @@ def test_options(spec, drop_p, dtype):
 # ----------------------------------------------------------------------------------------------------------------- c. head dims
 @pytest.mark.parametrize("spec,dtype", [(s, dt) for s, dts in W.HEAD_DIMS for dt in dts], ids=_id)
 def test_head_dims_on_the_query_lane_kernels(spec, dtype):
-    assert _expected(spec, dtype) == (0, 0)
+    assert _expected(spec, dtype) == (0, 0) and _forms(spec, dtype)[0] == _forms(spec, dtype)[1] == G.ql(spec.hd // 4, G._w(spec.n))
     run(spec, dtype)
 
 
@@ -257,6 +280,9 @@ _LAYOUT_CHOICE = {("out", "ldodd"): (0, 1), ("qkv", "ldodd"): (1, 0), ("dqkv", "
 @pytest.mark.parametrize("operand", ["qkv", "out", "dout", "dqkv"])
 def test_layouts(operand, layout, dtype):
     expect = _LAYOUT_CHOICE.get((operand, layout), (1, 1)) if dtype == BF else (0, 0)
+    if dtype == BF and layout == "off8":      # the scalar-load forms: vec = 0 wherever the operand passes through the staging loads
+        assert _forms(W.LAYOUT_SPEC, BF, lay={operand: layout}) == {"qkv": (G.win(11, 0), G.win(8, 0)), "out": (G.win(11, 1), G.win(8, 0)),
+                                                                    "dout": (G.win(11, 1), G.win(8, 0)), "dqkv": (G.win(11, 1), G.win(8, 1))}[operand]
     run(W.LAYOUT_SPEC, dtype, lay={operand: layout}, expect=expect)
 
 
@@ -266,6 +292,8 @@ def test_cross_kernel_pairs_draw_the_same_dropout_mask(operand):
     re-create the mask of the same key"""
     expect = _LAYOUT_CHOICE[(operand, "ldodd")]
     assert sum(expect) == 1
+    forms = _forms(W.LAYOUT_SPEC, BF, 0.25, {operand: "ldodd"})
+    assert sorted(f[0] for f in forms) == ["ql", "win"] and (forms[0][0] == "win") == bool(expect[0])      # one direction query-lane, the other matrix-core
     run(W.LAYOUT_SPEC, BF, drop_p=0.25, lay={operand: "ldodd"}, expect=expect)
 
 
@@ -274,12 +302,15 @@ def test_cross_kernel_pairs_draw_the_same_dropout_mask(operand):
 @pytest.mark.parametrize("spec", W.GLOBAL, ids=str)
 def test_global_head_dim_64_tile_counts(spec, drop_p):
     assert _expected(spec, BF) == (1, 1) and (spec.n + 31) // 32 * 2 in (2, 6, 10, 12)
+    tiles, gx = (spec.n + 31) // 32 * 2, -(-spec.n // 64)
+    assert _forms(spec, BF, drop_p) == (G.glob(tiles, gx), G.glob(tiles, 2 * gx))
     run(spec, BF, drop_p=drop_p)
 
 
 @pytest.mark.parametrize("drop_p", [0.0, 0.1])
 def test_global_above_the_token_limit_falls_to_the_query_lanes(drop_p):
     assert W.GLOBAL_ABOVE.n == 288 and _expected(W.GLOBAL_ABOVE, BF) == (0, 0)      # GA_MAXN = 256
+    assert _forms(W.GLOBAL_ABOVE, BF, drop_p) == (G.ql(16, 5), G.ql(16, 5))
     run(W.GLOBAL_ABOVE, BF, drop_p=drop_p)
 
 
@@ -288,13 +319,16 @@ def test_global_above_the_token_limit_falls_to_the_query_lanes(drop_p):
 def test_global_declines_by_layout(operand, layout, expect, drop_p):
     """qkv must be 16-byte aligned with ld % 8 == 0 for either global kernel; dO (16-byte loads) and dqkv (8-byte stores) only bind the
     backward, which then runs on the query lanes behind a global forward"""
+    forms = _forms(W.GLOBAL_LAYOUT, BF, drop_p, {operand: layout})
+    assert forms == tuple(G.glob(6, 2 * (1 + i)) if e else G.ql(16, 2) for i, e in enumerate(expect))      # a decline: the head_dim-64 query-lane kernel
     run(W.GLOBAL_LAYOUT, BF, drop_p=drop_p, lay={operand: layout}, expect=expect)
 
 
 # ----------------------------------------------------------------------------------------------------------------- f. refusals
 def test_refusals_return_before_any_launch():
-    """every call returns MISEG_E_BADARG (-1) or MISEG_E_UNSUPPORTED (-2) from make_geom, the drop_p check, the dbias_table guard, the LDS
-    check or the head_dim switch - all in front of the launch - and the sentinel-filled outputs keep every element.  All buffers are valid
+    """every call returns MISEG_E_BADARG (-1) or MISEG_E_UNSUPPORTED (-2) from the plan - its geometry checks, the drop_p check, the
+    dbias_table guard, the LDS bound or the head_dim set - in front of the launch, and the sentinel-filled outputs keep every element; the
+    plan entry point returns the same code and message and names no kernel, and the question entry point answers 0.  All buffers are valid
     and sized for the call."""
     ops, L = _ops(), _L()
     lib = L.load()
@@ -314,10 +348,16 @@ def test_refusals_return_before_any_launch():
         out, lse, dqkv, dqb, dtab = outs
         f = ops.winattn_params(qkv, out, qb, table, lse, spec.heads, spec.ws, spec.ss, tw, spec.scale, drop)
         b = L.WinattnBwd(f, ops._ptr(dout), Cc, ops._ptr(dqkv), 3 * Cc, ops._ptr(dqb), ops._ptr(dtab if (spec.table or dtable_without_table) else None))
-        calls = [("bwd", lib.miseg_winattn_bwd, b)] if bwd_only else [("fwd", lib.miseg_winattn_fwd, f), ("bwd", lib.miseg_winattn_bwd, b)]
-        for name, fn, prm in calls:
+        calls = [("fwd", lib.miseg_winattn_fwd, lib.miseg_winattn_fwd_plan, lib.miseg_winattn_on_matrix_cores, f),
+                 ("bwd", lib.miseg_winattn_bwd, lib.miseg_winattn_bwd_plan, lib.miseg_winattn_bwd_on_matrix_cores, b)][1 if bwd_only else 0:]
+        for name, fn, plan_fn, asks, prm in calls:
             assert fn(C.byref(prm), ops._stream()) == rc, f"{name} {spec}: {lib.miseg_last_error().decode()}"
-            assert match in lib.miseg_last_error().decode(), lib.miseg_last_error().decode()
+            said = lib.miseg_last_error().decode()
+            assert match in said, said
+            # the plan refuses with the launch's code and text and names no kernel; the question entry point answers 0
+            pl = L.WinattnPlan()
+            assert plan_fn(C.byref(prm), C.byref(pl)) == rc and lib.miseg_last_error().decode() == said and pl.kernel == L.WINATTN_NONE, f"{name} {spec}"
+            assert asks(C.byref(prm)) == 0, f"{name} {spec}: a refused call answered 1"
         torch.cuda.synchronize()
         for t in outs:
             assert bool((t == SENT).all()), f"{spec}: a refused call wrote something"
