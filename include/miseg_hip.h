@@ -239,7 +239,9 @@ int miseg_rank1_stats(const void* x, int64_t ldx, const void* w, int64_t ldw, in
  * first product is the operand of the second (v_mfma_f32_16x16x16_bf16).  Backward (miseg_mlp_bwd): recomputes the hidden pre-activation
  * from x, writes dz = (dy W2) * gelu'(z) and h = gelu(z) for the two weight-gradient products (miseg_gemm TN) and dx = dz W1.
  * bf16, C = 48, HID = 192, M >= 4096 (miseg_mlp_fused tells); weights in the compute dtype: w1 [HID][C], w2 [C][HID], w2t [HID][C] = w2
- * transposed, w1t [C][HID]; biases fp32 (may be NULL); stat: as miseg_gemm_params::stat (one sample, statistics of the rounded y). */
+ * transposed, w1t [C][HID]; biases fp32 (may be NULL); stat: as miseg_gemm_params::stat (one sample, statistics of the rounded y).
+ * Row operands: base 8-byte aligned, row stride a multiple of 4 elements and at least the row's width (C; HID for dz and h); weights
+ * 16-byte aligned.  Anything else is refused with MISEG_E_BADARG before a launch. */
 typedef struct {
   uint32_t struct_size;
   int32_t M, C, HID, dtype;

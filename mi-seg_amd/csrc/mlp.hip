@@ -359,7 +359,8 @@ static int mlp_check(const miseg_mlp_params* p, const char* what) {
 extern "C" int miseg_mlp_fwd(const miseg_mlp_params* p, miseg_stream_t s_) {
   if (int rc = mlp_check(p, "mlp_fwd")) return rc;
   MISEG_REQUIRE(p->w2 && p->y && ((uintptr_t)p->w2 % 16) == 0 && ((uintptr_t)p->y % 8) == 0 && p->ldy % 4 == 0 && p->ldy >= p->C, MISEG_E_BADARG, "mlp_fwd: w2 / y");
-  MISEG_REQUIRE(!p->res || (((uintptr_t)p->res % 8) == 0 && p->ldres % 4 == 0), MISEG_E_BADARG, "mlp_fwd: res alignment");
+  // (a row stride below the row's width: rows before the base pointer when negative, several producers per element of an output otherwise)
+  MISEG_REQUIRE(!p->res || (((uintptr_t)p->res % 8) == 0 && p->ldres % 4 == 0 && p->ldres >= p->C), MISEG_E_BADARG, "mlp_fwd: res alignment / ldres < C");
   const int Cc = p->C, Hh = 4 * Cc, ROW_C = Cc * 2 + 16, ROW_H = Hh * 2 + 16;
   size_t lds = (size_t)Hh * ROW_C + (size_t)Cc * ROW_H + (size_t)(Hh + Cc + 2 * Cc) * 4;
   const size_t red = (size_t)2 * Cc * (MLP_FWD_WAVES * 16 + 1) * sizeof(float);      // the statistics reduction re-uses the images
@@ -396,13 +397,18 @@ extern "C" int miseg_mlp_bwd(const miseg_mlp_params* p, miseg_stream_t s_) {
   MISEG_REQUIRE(((uintptr_t)p->dy % 8) == 0 && p->lddy % 4 == 0 && ((uintptr_t)p->dz % 8) == 0 && p->lddz % 4 == 0 && ((uintptr_t)p->h % 8) == 0 && p->ldh % 4 == 0 &&
                     (!p->dx || (((uintptr_t)p->dx % 8) == 0 && p->lddx % 4 == 0)) && ((uintptr_t)p->w2t % 16) == 0 && ((uintptr_t)p->w1t % 16) == 0,
                 MISEG_E_BADARG, "mlp_bwd: alignment");
+  // (as ldx / ldy: a row stride below the row's width names rows before the base pointer when negative, overlapping output rows otherwise)
+  MISEG_REQUIRE(p->lddy >= p->C && p->lddz >= p->HID && p->ldh >= p->HID && (!p->dx || p->lddx >= p->C), MISEG_E_BADARG,
+                "mlp_bwd: row stride below the row's width (lddy %lld lddx %lld < C %d, or lddz %lld ldh %lld < HID %d)", (long long)p->lddy, (long long)p->lddx, p->C,
+                (long long)p->lddz, (long long)p->ldh, p->HID);
   const int Cc = p->C, Hh = 4 * Cc, ROW_C = Cc * 2 + 16, ROW_H = Hh * 2 + 16;
   const size_t lds = (size_t)2 * Hh * ROW_C + (Cc == 48 ? (size_t)Cc * ROW_H : 0) + (size_t)(Hh + 2 * Cc) * 4;
   int blocks = cdiv(cdiv(p->M, 16), MLP_BWD_WAVES);
   if (blocks > (Cc == 48 ? 512 : 256)) blocks = Cc == 48 ? 512 : 256;
   MlpBstat bs{};
   if (p->bs_dstat) {
-    MISEG_REQUIRE(p->dx && p->bs_x && p->bs_stat && ((uintptr_t)p->bs_x % 8) == 0 && p->ld_bs_x % 4 == 0, MISEG_E_BADARG, "mlp_bwd: norm-backward sums need dx, bs_x (8-byte aligned rows), bs_stat");
+    MISEG_REQUIRE(p->dx && p->bs_x && p->bs_stat && ((uintptr_t)p->bs_x % 8) == 0 && p->ld_bs_x % 4 == 0 && p->ld_bs_x >= p->C, MISEG_E_BADARG,
+                  "mlp_bwd: norm-backward sums need dx, bs_x (8-byte aligned rows, ld_bs_x >= C), bs_stat");
     bs.x = (const bf16*)p->bs_x; bs.ldx = p->ld_bs_x; bs.stat_in = (const double*)p->bs_stat; bs.eps = p->bs_eps; bs.dstat = (double*)p->bs_dstat;
 #define MLP_BWD_LAUNCH(BS, CCV)                                                                                                                             \
   do {                                                                                                                                                      \
