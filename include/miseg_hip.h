@@ -146,6 +146,48 @@ typedef struct {
 } miseg_instnorm_pair_bwd_params;
 int miseg_instnorm_pair_bwd(const miseg_instnorm_pair_bwd_params* p, miseg_stream_t stream);
 
+/* ---- plans of the instance-norm family ----
+ * miseg_instnorm_<call>_plan takes the arguments of miseg_instnorm_<call> with a plan in place of the stream and tells what the call will
+ * launch: up to two kernels, each with its template lane width, thread geometry, grid and LDS bytes.  Every launcher dispatches on exactly
+ * this plan, and a call that is refused gets the same error code from the plan (n_launches == 0 then).  Pointers are only tested for NULL
+ * and alignment, so a host may ask with stand-ins for buffers it has not allocated.  Host only: touches no device.  (New symbols and
+ * structs: MISEG_ABI_VERSION stays 16.) */
+#define MISEG_IN_NONE 0
+#define MISEG_IN_STATS 1             /* streaming: (sum x, sum x^2) per channel, fp64 atomics into the replicas */
+#define MISEG_IN_APPLY 2             /* streaming: normalise (+ residual / shortcut norm / rank-1 shortcut) (+ activation) */
+#define MISEG_IN_BWD_REDUCE 3        /* streaming: (sum g, sum g * xhat) into dstat */
+#define MISEG_IN_BWD_APPLY 4         /* streaming: dx (+ dres, + gadd), dgamma / dbeta */
+#define MISEG_IN_PAIR_BWD_REDUCE 5   /* streaming, both norms of the residual pair */
+#define MISEG_IN_PAIR_BWD_APPLY 6
+#define MISEG_IN_FUSED_FWD 7         /* register-resident, S <= miseg_instnorm_fused_max_rows(): statistics + apply in one launch */
+#define MISEG_IN_FUSED_BWD 8
+#define MISEG_IN_PAIR_FUSED_BWD 9
+typedef struct {
+  int32_t kernel;                  /* MISEG_IN_* */
+  int32_t vec;                     /* the kernel's template lane width in elements: 16-byte lanes (8 bf16 / 4 fp32), 1, or - fused kernels only - a halving between */
+  int32_t from_slabs;              /* 1: the fused kernel's instantiation that sums fp32 partial slabs */
+  int32_t cv, tx, ty;              /* channel vectors per row (C / vec); thread grid of a workgroup: tx channel vectors x ty row lanes */
+  int32_t rpb, chunks, ctiles;     /* streaming: rows per workgroup, row chunks per sample, channel tiles; 0 for the fused kernels */
+  int32_t grid_x, grid_y, grid_z;  /* streaming: (chunks, B, ctiles); fused: (ceil(cv / tx), B, 1) */
+  int32_t threads;                 /* 256 */
+  int32_t rank1;                   /* 1: the launch forms the rank-1 shortcut from r1x / r1w */
+  int32_t lds_bytes;               /* dynamic LDS of the launch */
+} miseg_instnorm_launch;
+typedef struct {
+  int32_t n_launches;              /* 0 (refused), 1 or 2 */
+  int32_t aligned;                 /* 1: the 16-byte-lane predicate held for every launch of the call (a launch's own outcome is its vec) */
+  miseg_instnorm_launch launch[2];
+} miseg_instnorm_plan_info;
+int miseg_instnorm_stats_plan(const miseg_instnorm_stats_params* p, miseg_instnorm_plan_info* plan);
+int miseg_instnorm_apply_plan(const miseg_instnorm_apply_params* p, miseg_instnorm_plan_info* plan);
+int miseg_instnorm_fwd_plan(const miseg_instnorm_apply_params* p, miseg_instnorm_plan_info* plan);
+int miseg_instnorm_fwd_slabs_plan(const miseg_instnorm_apply_params* p, const float* slabs, int nslabs, int64_t slab_stride, miseg_instnorm_plan_info* plan);
+int miseg_instnorm_bwd_plan(const miseg_instnorm_bwd_params* p, miseg_instnorm_plan_info* plan);
+int miseg_instnorm_bwd_apply_plan(const miseg_instnorm_bwd_params* p, miseg_instnorm_plan_info* plan);
+int miseg_instnorm_bwd_slabs_plan(const miseg_instnorm_bwd_params* p, const float* slabs, int nslabs, int64_t slab_stride, miseg_instnorm_plan_info* plan);
+int miseg_instnorm_bwd_reduce_plan(const miseg_instnorm_bwd_params* p, miseg_instnorm_plan_info* plan);
+int miseg_instnorm_pair_bwd_plan(const miseg_instnorm_pair_bwd_params* p, miseg_instnorm_plan_info* plan);
+
 /* LayerNorm over the channel dim of channels-last rows (vit_norm_name="layer", the reference default:
  * networks/blocks/swin_transformer_block.py:104-105, transformer_block.py:82-83).  gamma/beta may be NULL. */
 typedef struct {

@@ -24,33 +24,6 @@ __device__ unsigned long long g_norm_stamps[16];
 static constexpr int NORM_THREADS = 256;
 static constexpr int NORM_TX_MAX = 32;   // channel vectors per block (wider rows are tiled over blockIdx.z)
 
-struct NormGeom {
-  int vec;      // elements per lane access (Vec16<T>::N or 1)
-  int cv;       // channel vectors per row
-  int tx, ty;   // thread grid inside a block
-  int rpb;      // rows per block
-  int chunks;   // row chunks per sample
-  int ctiles;   // channel tiles
-};
-
-static NormGeom norm_geom(int S, int C, bool vec_ok, int vecN, int target_blocks = 1024) {
-  NormGeom g;
-  g.vec = (vec_ok && C % vecN == 0) ? vecN : 1;
-  g.cv = C / g.vec;
-  g.tx = g.cv < NORM_TX_MAX ? g.cv : NORM_TX_MAX;
-  g.ty = NORM_THREADS / g.tx;
-  g.ctiles = cdiv(g.cv, g.tx);
-  // enough workgroups to fill 256 CUs even on the small grids of the deep stages, >= 4 rows per lane
-  // ~4 workgroups per CU for the streaming kernels (one per CU ran the 48^3 tensors at half the HBM rate); the statistics kernel
-  // asks for 256 (fewer fp64 atomics)
-  int rpb = cdiv(S, target_blocks);
-  if (rpb < 4 * g.ty) rpb = 4 * g.ty;
-  if (rpb > 1024) rpb = 1024;
-  g.rpb = rpb;
-  g.chunks = cdiv(S, rpb);
-  return g;
-}
-
 template <class T, int VEC> struct RowVec {
   float v[VEC];
   __device__ __forceinline__ void load(const T* p) {
@@ -1039,6 +1012,52 @@ __global__ void __launch_bounds__(NORM_THREADS) instnorm_pair_fused_bwd_kernel(c
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The three launch geometries of the family, side by side.  Host only, and called from norm_plan alone (below): a launcher reads the plan.
+// ---------------------------------------------------------------------------------------------------
+struct NormGeom {
+  int vec;      // elements per lane access (Vec16<T>::N or 1)
+  int cv;       // channel vectors per row
+  int tx, ty;   // thread grid inside a block
+  int rpb;      // rows per block
+  int chunks;   // row chunks per sample
+  int ctiles;   // channel tiles
+};
+
+// the streaming kernels
+static NormGeom norm_geom(int S, int C, bool vec_ok, int vecN, int target_blocks = 1024) {
+  NormGeom g;
+  g.vec = (vec_ok && C % vecN == 0) ? vecN : 1;
+  g.cv = C / g.vec;
+  g.tx = g.cv < NORM_TX_MAX ? g.cv : NORM_TX_MAX;
+  g.ty = NORM_THREADS / g.tx;
+  g.ctiles = cdiv(g.cv, g.tx);
+  // enough workgroups to fill 256 CUs even on the small grids of the deep stages, >= 4 rows per lane
+  // ~4 workgroups per CU for the streaming kernels (one per CU ran the 48^3 tensors at half the HBM rate); the statistics kernel
+  // asks for 256 (fewer fp64 atomics)
+  int rpb = cdiv(S, target_blocks);
+  if (rpb < 4 * g.ty) rpb = 4 * g.ty;
+  if (rpb > 1024) rpb = 1024;
+  g.rpb = rpb;
+  g.chunks = cdiv(S, rpb);
+  return g;
+}
+
+// slabs_to_out_stats_kernel: the tensors of a split convolution are tiny (27 .. 1728 rows): 8 vector columns x 32 rows per workgroup pass, so
+// that even the 3^3 volume is a dozen workgroups (norm_geom's >= 4 rows per lane made it three, 15 us for 16 slabs of 83 KB)
+static NormGeom slab_sum_geom(int S, int C, bool vec_ok, int vecN) {
+  NormGeom g;
+  g.vec = (vec_ok && C % vecN == 0) ? vecN : 1;
+  g.cv = C / g.vec;
+  g.tx = g.cv < 8 ? g.cv : 8;
+  g.ty = NORM_THREADS / g.tx;
+  g.ctiles = cdiv(g.cv, g.tx);
+  int per = cdiv(S, g.ty * 64);
+  g.rpb = g.ty * (per < 1 ? 1 : per > 8 ? 8 : per);
+  g.chunks = cdiv(S, g.rpb);
+  return g;
+}
+
 // thread geometry of the register-resident kernels: ty_n = the power of two >= S, between 16 and 256 - as FEW rows per lane as the tensor
 // allows, i.e. as many workgroups as it has channel vectors: these launches are bound by the instructions one wave issues (in-kernel stamps:
 // 8 rows x 8 channels per lane cost 3.2 us of arithmetic alone), not by bytes - and tx_n = 256 / ty_n <= 16 channel vectors
@@ -1187,32 +1206,280 @@ __global__ void __launch_bounds__(256) layernorm_bwd_param_kernel(const T* __res
 
 using namespace miseg;
 
-static bool aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
+// ---------------------------------------------------------------------------------------------------
+// The plan of an instance-norm call: validation, the 16-byte-lane predicate, the choice between the streaming and the
+// register-resident generation, geometry and LDS bytes of every launch - decided here, once, on the host.  The launchers below read it.
+// ---------------------------------------------------------------------------------------------------
+enum NormEntry { ENTRY_STATS, ENTRY_APPLY, ENTRY_FWD, ENTRY_FWD_SLABS, ENTRY_BWD, ENTRY_BWD_APPLY, ENTRY_BWD_SLABS, ENTRY_BWD_REDUCE, ENTRY_PAIR_BWD,
+                 ENTRY_SLAB_SUM };      // the last: slabs_to_out_stats (conv3d.hip), which has no public plan
+static constexpr int IN_SLAB_SUM = -1;      // miseg_instnorm_launch.kernel of that internal launch
+
+struct SlabSumParams { const void* y; int64_t ldy; const void* res; int64_t ldres; int B, S, C, dtype; };
+
+struct Operand { const void* p; int64_t ld; bool present; };
+
+// what the planner keeps of a validated call, whichever params struct it came in
+struct NormCall {
+  int B, S, C, V;         // V: elements of a 16-byte lane
+  Operand ops[7];         // the operands of the alignment predicate; an absent optional operand constrains nothing
+  int nops;
+  bool extra;             // the named terms of the entry's predicate that are no operand alignment (below)
+  bool rank1;
+};
+
+// THE alignment predicate: every present operand starts on a 16-byte boundary and its row stride is a whole number of 16-byte lanes
+static bool lanes16(const Operand* ops, int n, int V) {
+  for (int i = 0; i < n; ++i)
+    if (ops[i].present && (((uintptr_t)ops[i].p % 16) != 0 || ops[i].ld % V != 0)) return false;
+  return true;
+}
+// its named extra terms.  SLABS_AS_OPERAND: fp32 slabs stand in for dy / x - 16-byte aligned, slab_stride % 4 == 0, and their row stride is C
+static bool slabs_as_operand(const float* slabs, int64_t slab_stride, int C, int V) {
+  return !slabs || (((uintptr_t)slabs % 16) == 0 && slab_stride % 4 == 0 && C % V == 0);
+}
+// SLAB_SUM_LANES: slabs_to_out_stats reads the slabs in 16-byte fp32 lanes whatever the output's dtype (slab stride B S C: a multiple of 4 with C)
+static bool slab_sum_lanes(const float* slabs, int C) { return ((uintptr_t)slabs % 16) == 0 && C % 4 == 0; }
+// RANK1_WHOLE_LANES: the rank-1 pair reads r1w in the lanes of the tensors
+static bool rank1_whole_lanes(bool rank1, int C, int V) { return !rank1 || C % V == 0; }
+
+// THE generation choice: the register-resident one-launch kernels up to NORM_FUSED_MAX_ROWS rows per sample - for the entries that have one:
+// the single halves never (bwd_apply: the producer's sums stand in for the reduction at any size), the rank-1 pair never.  Slabs exist in
+// the register-resident kernels alone: a slab call this function sends to the streaming kernels is refused.
+static bool takes_fused(NormEntry e, int S, bool rank1) {
+  const bool has_fused = e == ENTRY_FWD || e == ENTRY_FWD_SLABS || e == ENTRY_BWD || e == ENTRY_BWD_SLABS || (e == ENTRY_PAIR_BWD && !rank1);
+  return has_fused && S <= NORM_FUSED_MAX_ROWS;
+}
+
+static int lane_elems(int dtype, int* V) {
+  return dispatch_dtype(dtype, [&](auto* tag) -> int {
+    *V = Vec16<typename std::remove_pointer<decltype(tag)>::type>::N;
+    return MISEG_OK;
+  });
+}
+
+// Every refusal of the nine entry points, in the parent launchers' order and with their codes and texts.  Kept disagreements:
+//   BWD_ACT_IS_BADARG            miseg_instnorm_bwd refuses a bad act with BADARG, miseg_instnorm_fwd / _apply with UNSUPPORTED
+//   STREAMING_FWD_SPEAKS_AS_ITS_HALVES   miseg_instnorm_fwd above NORM_FUSED_MAX_ROWS rows refuses with the checks and texts of miseg_instnorm_stats, then
+//                                of miseg_instnorm_apply (so: a shape check the fused path has not, and r1x without res_stat refused)
+static int apply_refusals(const miseg_instnorm_apply_params* p) {
+  MISEG_REQUIRE(p->num_styles >= 1 && p->num_styles <= MISEG_MAX_STYLES, MISEG_E_BADARG, "instnorm_apply: num_styles %d", p->num_styles);
+  MISEG_REQUIRE(p->act == MISEG_ACT_NONE || p->act == MISEG_ACT_LEAKY, MISEG_E_UNSUPPORTED, "instnorm_apply: act %d", p->act);
+  MISEG_REQUIRE(!p->res_stat || p->res || p->r1x, MISEG_E_BADARG, "instnorm_apply: res_stat without res");
+  MISEG_REQUIRE(!p->r1x || (p->res_stat && !p->res && p->r1w), MISEG_E_BADARG, "instnorm_apply: r1x needs res_stat and r1w, and excludes res");
+  return MISEG_OK;
+}
+static int stats_shape_refusal(int B, int S, int C, int64_t ldx) {
+  MISEG_REQUIRE(B > 0 && S > 0 && C > 0 && ldx >= C, MISEG_E_BADARG, "instnorm_stats: bad shape B=%d S=%d C=%d ld=%ld", B, S, C, (long)ldx);
+  return MISEG_OK;
+}
+static int slab_refusals(const char* who, NormEntry e, int B, int S, int C, int nslabs, int64_t slab_stride) {
+  MISEG_REQUIRE(takes_fused(e, S, false), MISEG_E_UNSUPPORTED, "%s: %d rows per sample (at most %d: miseg_instnorm_fused_max_rows)", who, S, NORM_FUSED_MAX_ROWS);
+  MISEG_REQUIRE(nslabs >= 1 && slab_stride >= (int64_t)B * S * C, MISEG_E_BADARG, "%s: nslabs / slab_stride", who);
+  return MISEG_OK;
+}
+
+static int norm_validate(NormEntry e, const void* params, const float* slabs, int nslabs, int64_t slab_stride, NormCall* c) {
+  int rc = MISEG_OK, dtype = -1;
+  c->nops = 0;
+  c->extra = true;
+  c->rank1 = false;
+  auto operand = [&](const void* p, int64_t ld, bool present = true) { c->ops[c->nops++] = Operand{p, ld, present}; };
+  auto shape = [&](int B, int S, int C, int dt) { c->B = B; c->S = S; c->C = C; dtype = dt; };
+  switch (e) {
+    case ENTRY_STATS: {
+      const auto* p = (const miseg_instnorm_stats_params*)params;
+      MISEG_REQUIRE(p && p->x && p->stat, MISEG_E_BADARG, "instnorm_stats: null pointer");
+      if ((rc = stats_shape_refusal(p->B, p->S, p->C, p->ldx))) return rc;
+      shape(p->B, p->S, p->C, p->dtype);
+      operand(p->x, p->ldx);
+      break;
+    }
+    case ENTRY_APPLY: case ENTRY_FWD: case ENTRY_FWD_SLABS: {
+      const auto* p = (const miseg_instnorm_apply_params*)params;
+      if (e == ENTRY_APPLY) {
+        MISEG_REQUIRE(p && p->x && p->y && p->stat, MISEG_E_BADARG, "instnorm_apply: null pointer");
+        if ((rc = apply_refusals(p))) return rc;
+      } else {
+        MISEG_REQUIRE(e == ENTRY_FWD || slabs, MISEG_E_BADARG, "instnorm_fwd_slabs: null slabs");
+        MISEG_REQUIRE(p && p->x && p->y && p->stat, MISEG_E_BADARG, "instnorm_fwd: null pointer");
+        MISEG_REQUIRE(!p->res_stat, MISEG_E_UNSUPPORTED, "instnorm_fwd: res_stat (shortcut norm on the fly) is a miseg_instnorm_apply feature");
+        if (slabs && (rc = slab_refusals("instnorm_fwd_slabs", e, p->B, p->S, p->C, nslabs, slab_stride))) return rc;
+        if (!takes_fused(e, p->S, false)) {      // STREAMING_FWD_SPEAKS_AS_ITS_HALVES
+          if ((rc = stats_shape_refusal(p->B, p->S, p->C, p->ldx)) || (rc = lane_elems(p->dtype, &c->V)) || (rc = apply_refusals(p))) return rc;
+        } else {
+          MISEG_REQUIRE(p->num_styles >= 1 && p->num_styles <= MISEG_MAX_STYLES, MISEG_E_BADARG, "instnorm_fwd: num_styles %d", p->num_styles);
+          MISEG_REQUIRE(p->act == MISEG_ACT_NONE || p->act == MISEG_ACT_LEAKY, MISEG_E_UNSUPPORTED, "instnorm_fwd: act %d", p->act);
+        }
+      }
+      shape(p->B, p->S, p->C, p->dtype);
+      operand(p->x, p->ldx);      // first: the statistics launch of the streaming forward reads this operand alone
+      operand(p->y, p->ldy);
+      operand(p->res, p->ldres, p->res != nullptr);
+      c->rank1 = e == ENTRY_APPLY && p->r1x;
+      break;
+    }
+    case ENTRY_BWD: case ENTRY_BWD_APPLY: case ENTRY_BWD_SLABS: {
+      const auto* p = (const miseg_instnorm_bwd_params*)params;
+      if (e == ENTRY_BWD_APPLY)
+        MISEG_REQUIRE(p && p->act == MISEG_ACT_NONE, MISEG_E_UNSUPPORTED, "instnorm_bwd_apply: no activation (the producer's sums know nothing of one)");
+      MISEG_REQUIRE(e != ENTRY_BWD_SLABS || slabs, MISEG_E_BADARG, "instnorm_bwd_slabs: null slabs");
+      MISEG_REQUIRE(p && (p->dy || slabs) && p->x && p->dx && p->stat && p->dstat, MISEG_E_BADARG, "instnorm_bwd: null pointer");
+      if (slabs && (rc = slab_refusals("instnorm_bwd_slabs", e, p->B, p->S, p->C, nslabs, slab_stride))) return rc;
+      MISEG_REQUIRE(p->act == MISEG_ACT_NONE || p->act == MISEG_ACT_LEAKY, MISEG_E_BADARG, "instnorm_bwd: act %d", p->act);      // BWD_ACT_IS_BADARG
+      MISEG_REQUIRE(p->num_styles >= 1 && p->num_styles <= MISEG_MAX_STYLES, MISEG_E_BADARG, "instnorm_bwd: num_styles %d", p->num_styles);
+      shape(p->B, p->S, p->C, p->dtype);
+      operand(p->dy, p->lddy, !slabs);
+      operand(p->x, p->ldx);
+      operand(p->dx, p->lddx);
+      operand(p->y, p->ldy, p->act != MISEG_ACT_NONE);      // y may be NULL with an activation (the sign is recomputed): NULL is aligned
+      operand(p->dres, p->lddres, p->dres != nullptr);
+      operand(p->gadd, p->ldgadd, p->gadd != nullptr);
+      break;
+    }
+    case ENTRY_BWD_REDUCE: {
+      const auto* p = (const miseg_instnorm_bwd_params*)params;
+      MISEG_REQUIRE(p && p->dy && p->x && p->stat && p->dstat, MISEG_E_BADARG, "instnorm_bwd_reduce: null pointer");
+      MISEG_REQUIRE(p->act == MISEG_ACT_NONE, MISEG_E_UNSUPPORTED, "instnorm_bwd_reduce: no activation (compose it outside)");
+      shape(p->B, p->S, p->C, p->dtype);
+      operand(p->dy, p->lddy);
+      operand(p->x, p->ldx);
+      break;
+    }
+    case ENTRY_PAIR_BWD: {
+      const auto* p = (const miseg_instnorm_pair_bwd_params*)params;
+      MISEG_REQUIRE(p && p->dy && p->xa && p->dxa && p->stat_a && p->stat_b && p->dstat_a && p->dstat_b, MISEG_E_BADARG, "instnorm_pair_bwd: null pointer");
+      MISEG_REQUIRE(p->r1x ? (p->r1w && p->r1dw && !p->xb && !p->dxb && !p->y) : (p->xb && p->dxb), MISEG_E_BADARG,
+                    "instnorm_pair_bwd: either xb / dxb, or the rank-1 shortcut (r1x, r1w, r1dw; no y)");
+      MISEG_REQUIRE(p->num_styles >= 1 && p->num_styles <= MISEG_MAX_STYLES, MISEG_E_BADARG, "instnorm_pair_bwd: num_styles %d", p->num_styles);
+      shape(p->B, p->S, p->C, p->dtype);
+      operand(p->dy, p->lddy);
+      operand(p->y, p->ldy, p->y != nullptr);
+      operand(p->xa, p->ldxa);
+      operand(p->xb, p->ldxb, p->xb != nullptr);
+      operand(p->dxb, p->lddxb, p->xb != nullptr);
+      operand(p->dxa, p->lddxa);
+      c->rank1 = p->r1x != nullptr;
+      break;
+    }
+    case ENTRY_SLAB_SUM: {
+      const auto* p = (const SlabSumParams*)params;
+      shape(p->B, p->S, p->C, p->dtype);
+      operand(p->y, p->ldy);
+      operand(p->res, p->ldres, p->res != nullptr);
+      break;
+    }
+  }
+  if ((rc = lane_elems(dtype, &c->V))) return rc;
+  // the one refusal the parent launchers did not have: they divided by C (or launched an empty grid) where an entry point checks no shape
+  MISEG_REQUIRE(c->B > 0 && c->S > 0 && c->C > 0, MISEG_E_BADARG, "instnorm: bad shape B=%d S=%d C=%d", c->B, c->S, c->C);
+  // the named extra terms.  The rank-1 PAIR asks C % V == 0 in its predicate; the apply entry with the same shortcut does not (kept: c->rank1
+  // of an apply call only marks its launch)
+  const bool pair_rank1 = e == ENTRY_PAIR_BWD && c->rank1;
+  if (e == ENTRY_SLAB_SUM) c->extra = slab_sum_lanes(slabs, c->C);
+  else c->extra = slabs_as_operand(slabs, slab_stride, c->C, c->V) && rank1_whole_lanes(pair_rank1, c->C, c->V);
+  return MISEG_OK;
+}
+
+static void plan_streaming(miseg_instnorm_plan_info* plan, int kernel, const NormGeom& g, const NormCall& c, size_t lds) {
+  miseg_instnorm_launch& l = plan->launch[plan->n_launches++];
+  l = miseg_instnorm_launch{kernel, g.vec, 0, g.cv, g.tx, g.ty, g.rpb, g.chunks, g.ctiles, g.chunks, c.B, g.ctiles, NORM_THREADS, c.rank1, (int32_t)lds};
+}
+static void plan_fused(miseg_instnorm_plan_info* plan, int kernel, const FusedGeom& g, const NormCall& c, bool from_slabs, size_t lds) {
+  miseg_instnorm_launch& l = plan->launch[plan->n_launches++];
+  l = miseg_instnorm_launch{kernel, g.vec, from_slabs, g.cv, g.tx, g.ty, 0, 0, 0, cdiv(g.cv, g.tx), c.B, 1, NORM_THREADS, 0, (int32_t)lds};
+}
+
+static int norm_plan(NormEntry e, const void* params, const float* slabs, int nslabs, int64_t slab_stride, miseg_instnorm_plan_info* plan) {
+  MISEG_REQUIRE(plan, MISEG_E_BADARG, "instnorm plan: null plan");
+  *plan = miseg_instnorm_plan_info{};
+  NormCall c;
+  if (int rc = norm_validate(e, params, slabs, nslabs, slab_stride, &c)) return rc;
+  const bool al = lanes16(c.ops, c.nops, c.V) && c.extra;
+  plan->aligned = al;
+  if (takes_fused(e, c.S, c.rank1)) {
+    const FusedGeom f = fused_geom(c.S, c.C, al, c.V);
+    if (e == ENTRY_PAIR_BWD) plan_fused(plan, MISEG_IN_PAIR_FUSED_BWD, f, c, false, fused_smem(f, 3, 2));
+    else if (e == ENTRY_BWD || e == ENTRY_BWD_SLABS) plan_fused(plan, MISEG_IN_FUSED_BWD, f, c, slabs != nullptr, fused_smem(f, 2, 1));
+    else plan_fused(plan, MISEG_IN_FUSED_FWD, f, c, slabs != nullptr, fused_smem(f, 2, 0));
+    return MISEG_OK;
+  }
+  if (e == ENTRY_SLAB_SUM) {
+    const NormGeom g = slab_sum_geom(c.S, c.C, al, c.V);
+    plan_streaming(plan, IN_SLAB_SUM, g, c, reduce_smem(g, 0));
+    return MISEG_OK;
+  }
+  if (e == ENTRY_STATS || e == ENTRY_FWD) {
+    // the statistics launch: a target of 256 workgroups (fewer fp64 atomics), and - in the streaming forward too - a predicate over x alone
+    // (ops[0]), so it keeps its 16-byte lanes where y or res send the apply launch of the same call to the scalar ones
+    const NormGeom g = norm_geom(c.S, c.C, lanes16(c.ops, 1, c.V), c.V, 256);
+    plan_streaming(plan, MISEG_IN_STATS, g, c, reduce_smem(g, 0));
+    if (e == ENTRY_STATS) return MISEG_OK;
+  }
+  const NormGeom g = norm_geom(c.S, c.C, al, c.V);
+  switch (e) {
+    case ENTRY_APPLY: case ENTRY_FWD: plan_streaming(plan, MISEG_IN_APPLY, g, c, apply_smem(g, 2)); break;
+    case ENTRY_BWD: case ENTRY_BWD_APPLY:
+      if (e == ENTRY_BWD) plan_streaming(plan, MISEG_IN_BWD_REDUCE, g, c, reduce_smem(g, 1));
+      plan_streaming(plan, MISEG_IN_BWD_APPLY, g, c, apply_smem(g, 2));
+      break;
+    case ENTRY_BWD_REDUCE: plan_streaming(plan, MISEG_IN_BWD_REDUCE, g, c, reduce_smem(g, 1)); break;
+    case ENTRY_PAIR_BWD:
+      plan_streaming(plan, MISEG_IN_PAIR_BWD_REDUCE, g, c, reduce_smem(g, 2));
+      plan_streaming(plan, MISEG_IN_PAIR_BWD_APPLY, g, c, apply_smem(g, 4, c.rank1));
+      break;
+    default: break;
+  }
+  return MISEG_OK;
+}
+
+extern "C" int miseg_instnorm_stats_plan(const miseg_instnorm_stats_params* p, miseg_instnorm_plan_info* plan) { return norm_plan(ENTRY_STATS, p, nullptr, 0, 0, plan); }
+extern "C" int miseg_instnorm_apply_plan(const miseg_instnorm_apply_params* p, miseg_instnorm_plan_info* plan) { return norm_plan(ENTRY_APPLY, p, nullptr, 0, 0, plan); }
+extern "C" int miseg_instnorm_fwd_plan(const miseg_instnorm_apply_params* p, miseg_instnorm_plan_info* plan) { return norm_plan(ENTRY_FWD, p, nullptr, 0, 0, plan); }
+extern "C" int miseg_instnorm_fwd_slabs_plan(const miseg_instnorm_apply_params* p, const float* slabs, int nslabs, int64_t slab_stride, miseg_instnorm_plan_info* plan) {
+  return norm_plan(ENTRY_FWD_SLABS, p, slabs, nslabs, slab_stride, plan);
+}
+extern "C" int miseg_instnorm_bwd_plan(const miseg_instnorm_bwd_params* p, miseg_instnorm_plan_info* plan) { return norm_plan(ENTRY_BWD, p, nullptr, 0, 0, plan); }
+extern "C" int miseg_instnorm_bwd_apply_plan(const miseg_instnorm_bwd_params* p, miseg_instnorm_plan_info* plan) { return norm_plan(ENTRY_BWD_APPLY, p, nullptr, 0, 0, plan); }
+extern "C" int miseg_instnorm_bwd_slabs_plan(const miseg_instnorm_bwd_params* p, const float* slabs, int nslabs, int64_t slab_stride, miseg_instnorm_plan_info* plan) {
+  return norm_plan(ENTRY_BWD_SLABS, p, slabs, nslabs, slab_stride, plan);
+}
+extern "C" int miseg_instnorm_bwd_reduce_plan(const miseg_instnorm_bwd_params* p, miseg_instnorm_plan_info* plan) { return norm_plan(ENTRY_BWD_REDUCE, p, nullptr, 0, 0, plan); }
+extern "C" int miseg_instnorm_pair_bwd_plan(const miseg_instnorm_pair_bwd_params* p, miseg_instnorm_plan_info* plan) { return norm_plan(ENTRY_PAIR_BWD, p, nullptr, 0, 0, plan); }
+
+// ---------------------------------------------------------------------------------------------------
+// The launchers: each reads its plan and issues the launches it names, with the plan's lane width, geometry, grid and LDS bytes
+// ---------------------------------------------------------------------------------------------------
+static dim3 grid_of(const miseg_instnorm_launch& l) { return dim3(l.grid_x, l.grid_y, l.grid_z); }
+
+template <class T> static void launch_stats(const miseg_instnorm_launch& l, const void* x, int64_t ldx, int S, int C, const void* stat, hipStream_t stream) {
+  for_lane_width<Vec16<T>::N, false>(l.vec, [&](auto w) {
+    instnorm_stats_kernel<T, decltype(w)::value><<<grid_of(l), l.threads, l.lds_bytes, stream>>>((const T*)x, ldx, S, C, l.cv, l.tx, l.ty, l.rpb, (double*)stat);
+  });
+}
+template <class T> static void launch_apply(const miseg_instnorm_launch& l, const miseg_instnorm_apply_params* p, hipStream_t stream) {
+  const StylePtrs sp = style_ptrs(p->gamma, p->beta, p->num_styles);
+  const StylePtrs rsp = style_ptrs(p->res_gamma, p->res_beta, p->res_stat ? p->num_styles : 0);
+  for_lane_width<Vec16<T>::N, false>(l.vec, [&](auto w) {
+    instnorm_apply_kernel<T, decltype(w)::value><<<grid_of(l), l.threads, l.lds_bytes, stream>>>(
+        (const T*)p->x, p->ldx, (const T*)p->res, p->ldres, (T*)p->y, p->ldy, p->S, p->C, l.cv, l.tx, l.ty, l.rpb, (const double*)p->stat, p->eps, p->styles, sp,
+        p->act, p->slope, (const double*)p->res_stat, rsp, (const T*)p->r1x, p->ldr1x, (const T*)p->r1w);
+  });
+}
 
 namespace miseg {
-// internal (conv3d.hip): enqueue the kernel above; stat may be null (plain sum + convert)
+// internal (conv3d.hip): y = round(sum of the slabs) (+ res) and its statistics; stat may be null (plain sum + convert)
 int slabs_to_out_stats(const float* slabs, int nslabs, void* y, int64_t ldy, const void* res, int64_t ldres, int B, int S, int C, int dtype, double* stat,
                        hipStream_t stream) {
+  const SlabSumParams sp{y, ldy, res, ldres, B, S, C, dtype};
+  miseg_instnorm_plan_info plan;
+  if (int rc = norm_plan(ENTRY_SLAB_SUM, &sp, slabs, nslabs, 0, &plan)) return rc;
   return dispatch_dtype(dtype, [&](auto* tag) -> int {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
-    constexpr int V = Vec16<T>::N;
-    const bool al = aligned16(y) && ldy % V == 0 && (!res || (aligned16(res) && ldres % V == 0)) && C % 4 == 0 && aligned16(slabs);
-    // the tensors of a split convolution are tiny (27 .. 1728 rows): 8 vector columns x 32 rows per workgroup pass, so that even the 3^3
-    // volume is a dozen workgroups (norm_geom's >= 4 rows per lane made it three, 15 us for 16 slabs of 83 KB)
-    NormGeom g;
-    g.vec = (al && C % V == 0) ? V : 1;
-    g.cv = C / g.vec;
-    g.tx = g.cv < 8 ? g.cv : 8;
-    g.ty = NORM_THREADS / g.tx;
-    g.ctiles = cdiv(g.cv, g.tx);
-    int per = cdiv(S, g.ty * 64);
-    g.rpb = g.ty * (per < 1 ? 1 : per > 8 ? 8 : per);
-    g.chunks = cdiv(S, g.rpb);
-    dim3 grid(g.chunks, B, g.ctiles);
+    const miseg_instnorm_launch& l = plan.launch[0];
     const int64_t stride = (int64_t)B * S * C;
-    for_lane_width<V, false>(g.vec, [&](auto w) {
-      slabs_to_out_stats_kernel<T, decltype(w)::value><<<grid, NORM_THREADS, reduce_smem(g, 0), stream>>>(slabs, nslabs, stride, (T*)y, ldy, (const T*)res, ldres, S, C,
-                                                                                                        g.cv, g.tx, g.ty, g.rpb, stat);
+    for_lane_width<Vec16<T>::N, false>(l.vec, [&](auto w) {
+      slabs_to_out_stats_kernel<T, decltype(w)::value><<<grid_of(l), l.threads, l.lds_bytes, stream>>>(slabs, nslabs, stride, (T*)y, ldy, (const T*)res, ldres, S, C, l.cv,
+                                                                                                      l.tx, l.ty, l.rpb, stat);
     });
     MISEG_LAUNCH_CHECK("slabs_to_out_stats");
     return MISEG_OK;
@@ -1225,83 +1492,48 @@ extern "C" int miseg_debug_norm_stamps(unsigned long long* out) { return (int)hi
 #endif
 
 extern "C" size_t miseg_instnorm_stat_bytes(int B, int C) { return (size_t)NORM_R * B * C * 2 * sizeof(double); }
+extern "C" int miseg_instnorm_fused_max_rows(void) { return NORM_FUSED_MAX_ROWS; }
 
-extern "C" int miseg_instnorm_stats(const miseg_instnorm_stats_params* p, miseg_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  MISEG_REQUIRE(p && p->x && p->stat, MISEG_E_BADARG, "instnorm_stats: null pointer");
-  MISEG_REQUIRE(p->B > 0 && p->S > 0 && p->C > 0 && p->ldx >= p->C, MISEG_E_BADARG, "instnorm_stats: bad shape B=%d S=%d C=%d ld=%ld", p->B, p->S, p->C,
-                (long)p->ldx);
+extern "C" int miseg_instnorm_stats(const miseg_instnorm_stats_params* p, miseg_stream_t stream) {
+  miseg_instnorm_plan_info plan;
+  if (int rc = norm_plan(ENTRY_STATS, p, nullptr, 0, 0, &plan)) return rc;
   return dispatch_dtype(p->dtype, [&](auto* tag) -> int {
-    typedef typename std::remove_pointer<decltype(tag)>::type T;
-    constexpr int V = Vec16<T>::N;
-    NormGeom g = norm_geom(p->S, p->C, aligned16(p->x) && p->ldx % V == 0, V, 256);
-    dim3 grid(g.chunks, p->B, g.ctiles);
-    for_lane_width<V, false>(g.vec, [&](auto w) {
-      instnorm_stats_kernel<T, decltype(w)::value><<<grid, NORM_THREADS, reduce_smem(g, 0), stream>>>((const T*)p->x, p->ldx, p->S, p->C, g.cv, g.tx, g.ty, g.rpb,
-                                                                                                    (double*)p->stat);
-    });
+    launch_stats<typename std::remove_pointer<decltype(tag)>::type>(plan.launch[0], p->x, p->ldx, p->S, p->C, p->stat, (hipStream_t)stream);
     MISEG_LAUNCH_CHECK("instnorm_stats");
     return MISEG_OK;
   });
 }
 
-extern "C" int miseg_instnorm_apply(const miseg_instnorm_apply_params* p, miseg_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  MISEG_REQUIRE(p && p->x && p->y && p->stat, MISEG_E_BADARG, "instnorm_apply: null pointer");
-  MISEG_REQUIRE(p->num_styles >= 1 && p->num_styles <= MISEG_MAX_STYLES, MISEG_E_BADARG, "instnorm_apply: num_styles %d", p->num_styles);
-  MISEG_REQUIRE(p->act == MISEG_ACT_NONE || p->act == MISEG_ACT_LEAKY, MISEG_E_UNSUPPORTED, "instnorm_apply: act %d", p->act);
-  MISEG_REQUIRE(!p->res_stat || p->res || p->r1x, MISEG_E_BADARG, "instnorm_apply: res_stat without res");
-  MISEG_REQUIRE(!p->r1x || (p->res_stat && !p->res && p->r1w), MISEG_E_BADARG, "instnorm_apply: r1x needs res_stat and r1w, and excludes res");
+extern "C" int miseg_instnorm_apply(const miseg_instnorm_apply_params* p, miseg_stream_t stream) {
+  miseg_instnorm_plan_info plan;
+  if (int rc = norm_plan(ENTRY_APPLY, p, nullptr, 0, 0, &plan)) return rc;
   return dispatch_dtype(p->dtype, [&](auto* tag) -> int {
-    typedef typename std::remove_pointer<decltype(tag)>::type T;
-    constexpr int V = Vec16<T>::N;
-    const int64_t ldor = p->ldx | p->ldy | (p->res ? p->ldres : 0);
-    const bool al = aligned16(p->x) && aligned16(p->y) && (!p->res || aligned16(p->res)) && ldor % V == 0;
-    NormGeom g = norm_geom(p->S, p->C, al, V);
-    const StylePtrs sp = style_ptrs(p->gamma, p->beta, p->num_styles);
-    const StylePtrs rsp = style_ptrs(p->res_gamma, p->res_beta, p->res_stat ? p->num_styles : 0);
-    dim3 grid(g.chunks, p->B, g.ctiles);
-    for_lane_width<V, false>(g.vec, [&](auto w) {
-      instnorm_apply_kernel<T, decltype(w)::value><<<grid, NORM_THREADS, apply_smem(g, 2), stream>>>(
-          (const T*)p->x, p->ldx, (const T*)p->res, p->ldres, (T*)p->y, p->ldy, p->S, p->C, g.cv, g.tx, g.ty, g.rpb, (const double*)p->stat, p->eps, p->styles, sp,
-          p->act, p->slope, (const double*)p->res_stat, rsp, (const T*)p->r1x, p->ldr1x, (const T*)p->r1w);
-    });
+    launch_apply<typename std::remove_pointer<decltype(tag)>::type>(plan.launch[0], p, (hipStream_t)stream);
     MISEG_LAUNCH_CHECK("instnorm_apply");
     return MISEG_OK;
   });
 }
 
-extern "C" int miseg_instnorm_fused_max_rows(void) { return NORM_FUSED_MAX_ROWS; }
-
-// statistics + normalisation: the two kernels above, or one fused launch for the small tensors of the deep stages
-static int instnorm_fwd_impl(const miseg_instnorm_apply_params* p, const float* slabs, int nslabs, int64_t slab_stride, miseg_stream_t stream_) {
+// statistics + normalisation: the two streaming kernels, or one fused launch for the small tensors of the deep stages
+static int instnorm_fwd_impl(NormEntry e, const miseg_instnorm_apply_params* p, const float* slabs, int nslabs, int64_t slab_stride, miseg_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  MISEG_REQUIRE(p && p->x && p->y && p->stat, MISEG_E_BADARG, "instnorm_fwd: null pointer");
-  MISEG_REQUIRE(!p->res_stat, MISEG_E_UNSUPPORTED, "instnorm_fwd: res_stat (shortcut norm on the fly) is a miseg_instnorm_apply feature");
-  if (slabs) {
-    MISEG_REQUIRE(p->S <= NORM_FUSED_MAX_ROWS, MISEG_E_UNSUPPORTED, "instnorm_fwd_slabs: %d rows per sample (at most %d: miseg_instnorm_fused_max_rows)", p->S,
-                  NORM_FUSED_MAX_ROWS);
-    MISEG_REQUIRE(nslabs >= 1 && slab_stride >= (int64_t)p->B * p->S * p->C, MISEG_E_BADARG, "instnorm_fwd_slabs: nslabs / slab_stride");
-  }
-  if (p->S > NORM_FUSED_MAX_ROWS) {
-    miseg_instnorm_stats_params sp_{p->x, p->ldx, p->B, p->S, p->C, p->dtype, const_cast<void*>(p->stat)};
-    const int rc = miseg_instnorm_stats(&sp_, stream_);
-    return rc ? rc : miseg_instnorm_apply(p, stream_);
-  }
-  MISEG_REQUIRE(p->num_styles >= 1 && p->num_styles <= MISEG_MAX_STYLES, MISEG_E_BADARG, "instnorm_fwd: num_styles %d", p->num_styles);
-  MISEG_REQUIRE(p->act == MISEG_ACT_NONE || p->act == MISEG_ACT_LEAKY, MISEG_E_UNSUPPORTED, "instnorm_fwd: act %d", p->act);
+  miseg_instnorm_plan_info plan;
+  if (int rc = norm_plan(e, p, slabs, nslabs, slab_stride, &plan)) return rc;
   return dispatch_dtype(p->dtype, [&](auto* tag) -> int {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
-    constexpr int V = Vec16<T>::N;
-    const int64_t ldor = p->ldx | p->ldy | (p->res ? p->ldres : 0) | (slabs ? p->C : 0);
-    const bool al = aligned16(p->x) && aligned16(p->y) && (!p->res || aligned16(p->res)) && ldor % V == 0 && (!slabs || (aligned16(slabs) && slab_stride % 4 == 0));
-    const FusedGeom g = fused_geom(p->S, p->C, al, V);
+    const miseg_instnorm_launch& l = plan.launch[0];
+    if (l.kernel == MISEG_IN_STATS) {
+      launch_stats<T>(l, p->x, p->ldx, p->S, p->C, p->stat, stream);
+      MISEG_LAUNCH_CHECK("instnorm_stats");
+      launch_apply<T>(plan.launch[1], p, stream);
+      MISEG_LAUNCH_CHECK("instnorm_apply");
+      return MISEG_OK;
+    }
     const StylePtrs sp = style_ptrs(p->gamma, p->beta, p->num_styles);
-    dim3 grid(cdiv(g.cv, g.tx), p->B);
-    for_lane_width<V, true>(g.vec, [&](auto w) {
-      for_flag(slabs != nullptr, [&](auto from_slabs) {
-        instnorm_fused_fwd_kernel<T, decltype(w)::value, decltype(from_slabs)::value><<<grid, NORM_THREADS, fused_smem(g, 2, 0), stream>>>(
-            (T*)p->x, p->ldx, (const T*)p->res, p->ldres, (T*)p->y, p->ldy, p->S, p->C, g.cv, g.tx, g.ty, (double*)p->stat, p->eps, p->styles, sp, p->act, p->slope,
+    for_lane_width<Vec16<T>::N, true>(l.vec, [&](auto w) {
+      for_flag(l.from_slabs, [&](auto from_slabs) {
+        instnorm_fused_fwd_kernel<T, decltype(w)::value, decltype(from_slabs)::value><<<grid_of(l), l.threads, l.lds_bytes, stream>>>(
+            (T*)p->x, p->ldx, (const T*)p->res, p->ldres, (T*)p->y, p->ldy, p->S, p->C, l.cv, l.tx, l.ty, (double*)p->stat, p->eps, p->styles, sp, p->act, p->slope,
             slabs, nslabs, slab_stride);
       });
     });
@@ -1310,91 +1542,67 @@ static int instnorm_fwd_impl(const miseg_instnorm_apply_params* p, const float* 
   });
 }
 
-extern "C" int miseg_instnorm_fwd(const miseg_instnorm_apply_params* p, miseg_stream_t stream) { return instnorm_fwd_impl(p, nullptr, 0, 0, stream); }
-
+extern "C" int miseg_instnorm_fwd(const miseg_instnorm_apply_params* p, miseg_stream_t stream) { return instnorm_fwd_impl(ENTRY_FWD, p, nullptr, 0, 0, stream); }
 extern "C" int miseg_instnorm_fwd_slabs(const miseg_instnorm_apply_params* p, const float* slabs, int nslabs, int64_t slab_stride, miseg_stream_t stream) {
-  MISEG_REQUIRE(slabs, MISEG_E_BADARG, "instnorm_fwd_slabs: null slabs");
-  return instnorm_fwd_impl(p, slabs, nslabs, slab_stride, stream);
+  return instnorm_fwd_impl(ENTRY_FWD_SLABS, p, slabs, nslabs, slab_stride, stream);
 }
 
-// apply_only: p->dstat already holds the backward sums (the epilogue of the GEMM that produced dy added them: miseg_gemm_params.stat_mode 2,
-// miseg_mlp_params.bs_dstat) - the reduction launch is skipped and tensors of any size take the streaming apply kernel
-static int instnorm_bwd_impl(const miseg_instnorm_bwd_params* p, const float* slabs, int nslabs, int64_t slab_stride, miseg_stream_t stream_, bool apply_only = false) {
+// ENTRY_BWD_APPLY: p->dstat already holds the backward sums (the epilogue of the GEMM that produced dy added them: miseg_gemm_params.stat_mode 2,
+// miseg_mlp_params.bs_dstat) - the plan names no reduction launch and tensors of any size take the streaming apply kernel
+static int instnorm_bwd_impl(NormEntry e, const miseg_instnorm_bwd_params* p, const float* slabs, int nslabs, int64_t slab_stride, miseg_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  MISEG_REQUIRE(p && (p->dy || slabs) && p->x && p->dx && p->stat && p->dstat, MISEG_E_BADARG, "instnorm_bwd: null pointer");
-  if (slabs) {
-    MISEG_REQUIRE(p->S <= NORM_FUSED_MAX_ROWS, MISEG_E_UNSUPPORTED, "instnorm_bwd_slabs: %d rows per sample (at most %d: miseg_instnorm_fused_max_rows)", p->S,
-                  NORM_FUSED_MAX_ROWS);
-    MISEG_REQUIRE(nslabs >= 1 && slab_stride >= (int64_t)p->B * p->S * p->C, MISEG_E_BADARG, "instnorm_bwd_slabs: nslabs / slab_stride");
-  }
-  MISEG_REQUIRE(p->act == MISEG_ACT_NONE || p->act == MISEG_ACT_LEAKY, MISEG_E_BADARG, "instnorm_bwd: act %d", p->act);
-  MISEG_REQUIRE(p->num_styles >= 1 && p->num_styles <= MISEG_MAX_STYLES, MISEG_E_BADARG, "instnorm_bwd: num_styles %d", p->num_styles);
+  miseg_instnorm_plan_info plan;
+  if (int rc = norm_plan(e, p, slabs, nslabs, slab_stride, &plan)) return rc;
   return dispatch_dtype(p->dtype, [&](auto* tag) -> int {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
     constexpr int V = Vec16<T>::N;
-    const int64_t ldor = (slabs ? p->C : p->lddy) | p->ldx | p->lddx | (p->act ? p->ldy : 0) | (p->dres ? p->lddres : 0) | (p->gadd ? p->ldgadd : 0);
-    const bool al = (slabs ? aligned16(slabs) && slab_stride % 4 == 0 : aligned16(p->dy)) && aligned16(p->x) && aligned16(p->dx) && (!p->act || aligned16(p->y)) &&
-                    (!p->dres || aligned16(p->dres)) && (!p->gadd || aligned16(p->gadd)) && ldor % V == 0;
-    NormGeom g = norm_geom(p->S, p->C, al, V);
     const StylePtrs sp = style_ptrs(p->gamma, p->beta, p->num_styles);
     const StyleGradPtrs gp = style_grad_ptrs(p->dgamma, p->dbeta, p->num_styles);
-    if (p->S <= NORM_FUSED_MAX_ROWS && !apply_only) {
-      const FusedGeom f = fused_geom(p->S, p->C, al, V);
-      dim3 fgrid(cdiv(f.cv, f.tx), p->B);
-      for_lane_width<V, true>(f.vec, [&](auto w) {
-        for_flag(slabs != nullptr, [&](auto from_slabs) {
-          instnorm_fused_bwd_kernel<T, decltype(w)::value, decltype(from_slabs)::value><<<fgrid, NORM_THREADS, fused_smem(f, 2, 1), stream>>>(
-              (const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->x, p->ldx, (T*)p->dx, p->lddx, (T*)p->dres, p->lddres, p->S, p->C, f.cv, f.tx, f.ty,
-              (const double*)p->stat, p->eps, p->styles, sp, gp, p->act, p->slope, (const T*)p->gadd, p->ldgadd, slabs, nslabs, slab_stride);
-        });
-      });
-      MISEG_LAUNCH_CHECK("instnorm_bwd");
-      return MISEG_OK;
-    }
-    dim3 grid(g.chunks, p->B, g.ctiles);
     const double* stat = (const double*)p->stat;
     double* dstat = (double*)p->dstat;
-    for_lane_width<V, false>(g.vec, [&](auto w) {
-      constexpr int W = decltype(w)::value;
-      if (!apply_only)
-        instnorm_bwd_reduce_kernel<T, W><<<grid, NORM_THREADS, reduce_smem(g, 1), stream>>>((const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->x, p->ldx, p->S,
-                                                                                           p->C, g.cv, g.tx, g.ty, g.rpb, stat, p->eps, p->act, p->slope, dstat, p->styles,
-                                                                                           sp);
-      instnorm_bwd_apply_kernel<T, W><<<grid, NORM_THREADS, apply_smem(g, 2), stream>>>((const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->x, p->ldx, (T*)p->dx,
-                                                                                       p->lddx, (T*)p->dres, p->lddres, p->S, p->C, g.cv, g.tx, g.ty, g.rpb, stat, p->eps,
-                                                                                       p->styles, sp, p->act, p->slope, dstat, gp, (const T*)p->gadd, p->ldgadd);
-    });
+    for (int i = 0; i < plan.n_launches; ++i) {
+      const miseg_instnorm_launch& l = plan.launch[i];
+      if (l.kernel == MISEG_IN_FUSED_BWD)
+        for_lane_width<V, true>(l.vec, [&](auto w) {
+          for_flag(l.from_slabs, [&](auto from_slabs) {
+            instnorm_fused_bwd_kernel<T, decltype(w)::value, decltype(from_slabs)::value><<<grid_of(l), l.threads, l.lds_bytes, stream>>>(
+                (const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->x, p->ldx, (T*)p->dx, p->lddx, (T*)p->dres, p->lddres, p->S, p->C, l.cv, l.tx, l.ty, stat,
+                p->eps, p->styles, sp, gp, p->act, p->slope, (const T*)p->gadd, p->ldgadd, slabs, nslabs, slab_stride);
+          });
+        });
+      else
+        for_lane_width<V, false>(l.vec, [&](auto w) {
+          constexpr int W = decltype(w)::value;
+          if (l.kernel == MISEG_IN_BWD_REDUCE)
+            instnorm_bwd_reduce_kernel<T, W><<<grid_of(l), l.threads, l.lds_bytes, stream>>>((const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->x, p->ldx, p->S,
+                                                                                           p->C, l.cv, l.tx, l.ty, l.rpb, stat, p->eps, p->act, p->slope, dstat, p->styles, sp);
+          else
+            instnorm_bwd_apply_kernel<T, W><<<grid_of(l), l.threads, l.lds_bytes, stream>>>((const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->x, p->ldx,
+                                                                                          (T*)p->dx, p->lddx, (T*)p->dres, p->lddres, p->S, p->C, l.cv, l.tx, l.ty, l.rpb, stat,
+                                                                                          p->eps, p->styles, sp, p->act, p->slope, dstat, gp, (const T*)p->gadd, p->ldgadd);
+        });
+    }
     MISEG_LAUNCH_CHECK("instnorm_bwd");
     return MISEG_OK;
   });
 }
 
-extern "C" int miseg_instnorm_bwd(const miseg_instnorm_bwd_params* p, miseg_stream_t stream) { return instnorm_bwd_impl(p, nullptr, 0, 0, stream); }
-
-extern "C" int miseg_instnorm_bwd_apply(const miseg_instnorm_bwd_params* p, miseg_stream_t stream) {
-  MISEG_REQUIRE(p && p->act == MISEG_ACT_NONE, MISEG_E_UNSUPPORTED, "instnorm_bwd_apply: no activation (the producer's sums know nothing of one)");
-  return instnorm_bwd_impl(p, nullptr, 0, 0, stream, true);
-}
-
+extern "C" int miseg_instnorm_bwd(const miseg_instnorm_bwd_params* p, miseg_stream_t stream) { return instnorm_bwd_impl(ENTRY_BWD, p, nullptr, 0, 0, stream); }
+extern "C" int miseg_instnorm_bwd_apply(const miseg_instnorm_bwd_params* p, miseg_stream_t stream) { return instnorm_bwd_impl(ENTRY_BWD_APPLY, p, nullptr, 0, 0, stream); }
 extern "C" int miseg_instnorm_bwd_slabs(const miseg_instnorm_bwd_params* p, const float* slabs, int nslabs, int64_t slab_stride, miseg_stream_t stream) {
-  MISEG_REQUIRE(slabs, MISEG_E_BADARG, "instnorm_bwd_slabs: null slabs");
-  return instnorm_bwd_impl(p, slabs, nslabs, slab_stride, stream);
+  return instnorm_bwd_impl(ENTRY_BWD_SLABS, p, slabs, nslabs, slab_stride, stream);
 }
 
-extern "C" int miseg_instnorm_bwd_reduce(const miseg_instnorm_bwd_params* p, miseg_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  MISEG_REQUIRE(p && p->dy && p->x && p->stat && p->dstat, MISEG_E_BADARG, "instnorm_bwd_reduce: null pointer");
-  MISEG_REQUIRE(p->act == MISEG_ACT_NONE, MISEG_E_UNSUPPORTED, "instnorm_bwd_reduce: no activation (compose it outside)");
+extern "C" int miseg_instnorm_bwd_reduce(const miseg_instnorm_bwd_params* p, miseg_stream_t stream) {
+  miseg_instnorm_plan_info plan;
+  if (int rc = norm_plan(ENTRY_BWD_REDUCE, p, nullptr, 0, 0, &plan)) return rc;
   return dispatch_dtype(p->dtype, [&](auto* tag) -> int {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
-    constexpr int V = Vec16<T>::N;
-    const bool al = aligned16(p->dy) && aligned16(p->x) && (p->lddy | p->ldx) % V == 0;
-    NormGeom g = norm_geom(p->S, p->C, al, V);
+    const miseg_instnorm_launch& l = plan.launch[0];
     const StylePtrs sp = style_ptrs(p->gamma, p->beta, 0);      // no activation: nothing reads the affine rows
-    dim3 grid(g.chunks, p->B, g.ctiles);
-    for_lane_width<V, false>(g.vec, [&](auto w) {
-      instnorm_bwd_reduce_kernel<T, decltype(w)::value><<<grid, NORM_THREADS, reduce_smem(g, 1), stream>>>(
-          (const T*)p->dy, p->lddy, nullptr, 0, (const T*)p->x, p->ldx, p->S, p->C, g.cv, g.tx, g.ty, g.rpb, (const double*)p->stat, p->eps, MISEG_ACT_NONE, 0.f,
+    for_lane_width<Vec16<T>::N, false>(l.vec, [&](auto w) {
+      instnorm_bwd_reduce_kernel<T, decltype(w)::value><<<grid_of(l), l.threads, l.lds_bytes, (hipStream_t)stream>>>(
+          (const T*)p->dy, p->lddy, nullptr, 0, (const T*)p->x, p->ldx, p->S, p->C, l.cv, l.tx, l.ty, l.rpb, (const double*)p->stat, p->eps, MISEG_ACT_NONE, 0.f,
           (double*)p->dstat, nullptr, sp);
     });
     MISEG_LAUNCH_CHECK("instnorm_bwd_reduce");
@@ -1404,42 +1612,36 @@ extern "C" int miseg_instnorm_bwd_reduce(const miseg_instnorm_bwd_params* p, mis
 
 extern "C" int miseg_instnorm_pair_bwd(const miseg_instnorm_pair_bwd_params* p, miseg_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  MISEG_REQUIRE(p && p->dy && p->xa && p->dxa && p->stat_a && p->stat_b && p->dstat_a && p->dstat_b, MISEG_E_BADARG, "instnorm_pair_bwd: null pointer");
-  MISEG_REQUIRE(p->r1x ? (p->r1w && p->r1dw && !p->xb && !p->dxb && !p->y) : (p->xb && p->dxb), MISEG_E_BADARG,
-                "instnorm_pair_bwd: either xb / dxb, or the rank-1 shortcut (r1x, r1w, r1dw; no y)");
-  MISEG_REQUIRE(p->num_styles >= 1 && p->num_styles <= MISEG_MAX_STYLES, MISEG_E_BADARG, "instnorm_pair_bwd: num_styles %d", p->num_styles);
+  miseg_instnorm_plan_info plan;
+  if (int rc = norm_plan(ENTRY_PAIR_BWD, p, nullptr, 0, 0, &plan)) return rc;
   return dispatch_dtype(p->dtype, [&](auto* tag) -> int {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
     constexpr int V = Vec16<T>::N;
-    const int64_t ldor = p->lddy | (p->y ? p->ldy : 0) | p->ldxa | (p->xb ? p->ldxb | p->lddxb : 0) | p->lddxa;
-    const bool al = aligned16(p->dy) && (!p->y || aligned16(p->y)) && aligned16(p->xa) && (!p->xb || (aligned16(p->xb) && aligned16(p->dxb))) && aligned16(p->dxa) &&
-                    ldor % V == 0 && (!p->r1x || p->C % V == 0);
-    NormGeom g = norm_geom(p->S, p->C, al, V);
     const StylePtrs spa = style_ptrs(p->gamma_a, p->beta_a, p->num_styles), spb = style_ptrs(p->gamma_b, p->beta_b, p->num_styles);      // betas: only read when y is absent
     const StyleGradPtrs gpa = style_grad_ptrs(p->dgamma_a, p->dbeta_a, p->num_styles), gpb = style_grad_ptrs(p->dgamma_b, p->dbeta_b, p->num_styles);
-    if (!p->r1x && p->S <= NORM_FUSED_MAX_ROWS) {      // small tensors: one register-resident launch
-      const FusedGeom f = fused_geom(p->S, p->C, al, V);
-      dim3 fgrid(cdiv(f.cv, f.tx), p->B);
-      for_lane_width<V, true>(f.vec, [&](auto w) {
-        instnorm_pair_fused_bwd_kernel<T, decltype(w)::value><<<fgrid, NORM_THREADS, fused_smem(f, 3, 2), stream>>>(
-            (const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->xa, p->ldxa, (const T*)p->xb, p->ldxb, (T*)p->dxa, p->lddxa, (T*)p->dxb, p->lddxb, p->S, p->C,
-            f.cv, f.tx, f.ty, (const double*)p->stat_a, (const double*)p->stat_b, p->eps, p->styles, spa, spb, p->slope, gpa, gpb);
-      });
-      MISEG_LAUNCH_CHECK("instnorm_pair_bwd");
-      return MISEG_OK;
+    for (int i = 0; i < plan.n_launches; ++i) {
+      const miseg_instnorm_launch& l = plan.launch[i];
+      if (l.kernel == MISEG_IN_PAIR_FUSED_BWD)      // small tensors: one register-resident launch
+        for_lane_width<V, true>(l.vec, [&](auto w) {
+          instnorm_pair_fused_bwd_kernel<T, decltype(w)::value><<<grid_of(l), l.threads, l.lds_bytes, stream>>>(
+              (const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->xa, p->ldxa, (const T*)p->xb, p->ldxb, (T*)p->dxa, p->lddxa, (T*)p->dxb, p->lddxb, p->S, p->C,
+              l.cv, l.tx, l.ty, (const double*)p->stat_a, (const double*)p->stat_b, p->eps, p->styles, spa, spb, p->slope, gpa, gpb);
+        });
+      else
+        for_lane_width<V, false>(l.vec, [&](auto w) {
+          constexpr int W = decltype(w)::value;
+          if (l.kernel == MISEG_IN_PAIR_BWD_REDUCE)
+            instnorm_pair_bwd_reduce_kernel<T, W><<<grid_of(l), l.threads, l.lds_bytes, stream>>>(
+                (const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->xa, p->ldxa, (const T*)p->xb, p->ldxb, p->S, p->C, l.cv, l.tx, l.ty, l.rpb,
+                (const double*)p->stat_a, (const double*)p->stat_b, p->eps, p->slope, (double*)p->dstat_a, (double*)p->dstat_b, p->styles, spa, spb, (const T*)p->r1x,
+                p->ldr1x, (const T*)p->r1w);
+          else
+            instnorm_pair_bwd_apply_kernel<T, W><<<grid_of(l), l.threads, l.lds_bytes, stream>>>(
+                (const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->xa, p->ldxa, (const T*)p->xb, p->ldxb, (T*)p->dxa, p->lddxa, (T*)p->dxb, p->lddxb, p->S, p->C,
+                l.cv, l.tx, l.ty, l.rpb, (const double*)p->stat_a, (const double*)p->stat_b, p->eps, p->styles, spa, spb, p->slope, (const double*)p->dstat_a,
+                (const double*)p->dstat_b, gpa, gpb, (const T*)p->r1x, p->ldr1x, (const T*)p->r1w, p->r1dw);
+        });
     }
-    dim3 grid(g.chunks, p->B, g.ctiles);
-    for_lane_width<V, false>(g.vec, [&](auto w) {
-      constexpr int W = decltype(w)::value;
-      instnorm_pair_bwd_reduce_kernel<T, W><<<grid, NORM_THREADS, reduce_smem(g, 2), stream>>>(
-          (const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->xa, p->ldxa, (const T*)p->xb, p->ldxb, p->S, p->C, g.cv, g.tx, g.ty, g.rpb,
-          (const double*)p->stat_a, (const double*)p->stat_b, p->eps, p->slope, (double*)p->dstat_a, (double*)p->dstat_b, p->styles, spa, spb, (const T*)p->r1x,
-          p->ldr1x, (const T*)p->r1w);
-      instnorm_pair_bwd_apply_kernel<T, W><<<grid, NORM_THREADS, apply_smem(g, 4, p->r1x != nullptr), stream>>>(
-          (const T*)p->dy, p->lddy, (const T*)p->y, p->ldy, (const T*)p->xa, p->ldxa, (const T*)p->xb, p->ldxb, (T*)p->dxa, p->lddxa, (T*)p->dxb, p->lddxb, p->S, p->C,
-          g.cv, g.tx, g.ty, g.rpb, (const double*)p->stat_a, (const double*)p->stat_b, p->eps, p->styles, spa, spb, p->slope, (const double*)p->dstat_a,
-          (const double*)p->dstat_b, gpa, gpb, (const T*)p->r1x, p->ldr1x, (const T*)p->r1w, p->r1dw);
-    });
     MISEG_LAUNCH_CHECK("instnorm_pair_bwd");
     return MISEG_OK;
   });

@@ -47,6 +47,23 @@ InstnormPairBwd = _struct("InstnormPairBwd", cname="miseg_instnorm_pair_bwd_para
                                               ("num_styles", i32), ("gamma_a", fp4), ("gamma_b", fp4), ("dgamma_a", fp4), ("dbeta_a", fp4),
                                               ("dgamma_b", fp4), ("dbeta_b", fp4), ("slope", f32), ("beta_a", fp4), ("beta_b", fp4),
                                               ("r1x", vp), ("ldr1x", i64), ("r1w", vp), ("r1dw", vp)])
+# miseg_instnorm_launch.kernel (MISEG_IN_*): what the instance-norm launchers run, as their plans report it
+IN_NONE, IN_STATS, IN_APPLY, IN_BWD_REDUCE, IN_BWD_APPLY, IN_PAIR_BWD_REDUCE, IN_PAIR_BWD_APPLY, IN_FUSED_FWD, IN_FUSED_BWD, IN_PAIR_FUSED_BWD = range(10)
+IN_KERNELS = {      # entry point -> the kernels its plan can name
+    "miseg_instnorm_stats": (IN_STATS,),
+    "miseg_instnorm_apply": (IN_APPLY,),
+    "miseg_instnorm_fwd": (IN_STATS, IN_APPLY, IN_FUSED_FWD),
+    "miseg_instnorm_fwd_slabs": (IN_FUSED_FWD,),
+    "miseg_instnorm_bwd": (IN_BWD_REDUCE, IN_BWD_APPLY, IN_FUSED_BWD),
+    "miseg_instnorm_bwd_apply": (IN_BWD_APPLY,),
+    "miseg_instnorm_bwd_slabs": (IN_FUSED_BWD,),
+    "miseg_instnorm_bwd_reduce": (IN_BWD_REDUCE,),
+    "miseg_instnorm_pair_bwd": (IN_PAIR_BWD_REDUCE, IN_PAIR_BWD_APPLY, IN_PAIR_FUSED_BWD),
+}
+InstnormLaunch = _struct("InstnormLaunch", cname="miseg_instnorm_launch", fields=[("kernel", i32), ("vec", i32), ("from_slabs", i32), ("cv", i32), ("tx", i32), ("ty", i32),
+                                                                                 ("rpb", i32), ("chunks", i32), ("ctiles", i32), ("grid_x", i32), ("grid_y", i32),
+                                                                                 ("grid_z", i32), ("threads", i32), ("rank1", i32), ("lds_bytes", i32)])
+InstnormPlan = _struct("InstnormPlan", cname="miseg_instnorm_plan_info", fields=[("n_launches", i32), ("aligned", i32), ("launch", InstnormLaunch * 2)])
 LayernormFwd = _struct("LayernormFwd", cname="miseg_layernorm_fwd_params", fields=[("x", vp), ("ldx", i64), ("y", vp), ("ldy", i64), ("rows", i64), ("C", i32),
                                         ("dtype", i32), ("eps", f32), ("gamma", vp), ("beta", vp), ("mean", vp), ("rstd", vp)])
 LayernormBwd = _struct("LayernormBwd", cname="miseg_layernorm_bwd_params", fields=[("dy", vp), ("lddy", i64), ("x", vp), ("ldx", i64), ("dx", vp), ("lddx", i64),
@@ -260,6 +277,15 @@ PROTOS = {
     "miseg_instnorm_fwd": (i32, [C.POINTER(InstnormApply), vp]),
     "miseg_instnorm_bwd": (i32, [C.POINTER(InstnormBwd), vp]),
     "miseg_instnorm_pair_bwd": (i32, [C.POINTER(InstnormPairBwd), vp]),
+    "miseg_instnorm_stats_plan": (i32, [C.POINTER(InstnormStats), C.POINTER(InstnormPlan)]),
+    "miseg_instnorm_apply_plan": (i32, [C.POINTER(InstnormApply), C.POINTER(InstnormPlan)]),
+    "miseg_instnorm_fwd_plan": (i32, [C.POINTER(InstnormApply), C.POINTER(InstnormPlan)]),
+    "miseg_instnorm_fwd_slabs_plan": (i32, [C.POINTER(InstnormApply), vp, i32, i64, C.POINTER(InstnormPlan)]),
+    "miseg_instnorm_bwd_plan": (i32, [C.POINTER(InstnormBwd), C.POINTER(InstnormPlan)]),
+    "miseg_instnorm_bwd_apply_plan": (i32, [C.POINTER(InstnormBwd), C.POINTER(InstnormPlan)]),
+    "miseg_instnorm_bwd_slabs_plan": (i32, [C.POINTER(InstnormBwd), vp, i32, i64, C.POINTER(InstnormPlan)]),
+    "miseg_instnorm_bwd_reduce_plan": (i32, [C.POINTER(InstnormBwd), C.POINTER(InstnormPlan)]),
+    "miseg_instnorm_pair_bwd_plan": (i32, [C.POINTER(InstnormPairBwd), C.POINTER(InstnormPlan)]),
     "miseg_layernorm_fwd": (i32, [C.POINTER(LayernormFwd), vp]),
     "miseg_layernorm_bwd": (i32, [C.POINTER(LayernormBwd), vp]),
     "miseg_gemm_fuses_stat": (i32, [C.POINTER(Gemm)]),

@@ -38,21 +38,24 @@ def bwd_tol(dtype, S):
 
 
 # ----------------------------------------------------------------------------------------------------------------- the case matrix
-STREAM_S = FUSED_MAX_ROWS + 1      # 2049: 65 chunks of 32 rows with 32 columns (more than the 16 replicas), 3 chunks with one column (the last: one row)
+STREAM_S = FUSED_MAX_ROWS + 1      # 2049: 65 chunks of 32 rows with 32 columns (more than the 16 replicas), 3 chunks with one column (the last: one
+#                                    row) - the rows `*-S2049-C*-onetile` / `-scalar1` of tests/instnorm_cases.py hold these figures
 FUSED_ROWS = (2, 8, 16, 17, 27, 256, 257, 512, 513, 1024, 1025, 2047, 2048)
-LONG_S = 1024 * 1024 + 1029        # the 1024-row cap of rows per workgroup with more chunks than any launcher's target grid
+LONG_S = 1024 * 1024 + 1029        # the 1024-row cap of rows per workgroup with more chunks than any launcher's target grid (rows `*-rowcap`: 1026 chunks)
 
 
 def stream_channels(dtype):
     """(id, C): tx = 3 (ty = 85, one idle thread); one full tile; two tiles with 8 of 32 columns live in the second; the scalar instantiation with
-    one column; scalar, two tiles, 18 live"""
+    one column; scalar, two tiles, 18 live.  Each id is the tag of the rows of tests/instnorm_cases.py (section a) that hold these figures as
+    literal numbers, asserted on the calls' plans (tests/test_instnorm_plan_cpu.py, and beside the launches of the GPU cases)."""
     V = nvec(dtype)
     return [("tx3", 3 * V), ("onetile", 32 * V), ("twotiles", 40 * V), ("scalar1", 1), ("scalar50", 50)]
 
 
 def fused_shapes(dtype):
     """(S, C): one vector and three scalar columns at every row count; dead channel columns in the last workgroup: tx = 8 with 5 columns, two
-    workgroups with one live column in the second, scalar 8 + 5"""
+    workgroups with one live column in the second, scalar 8 + 5.  Held by the rows `-tyfloor` / `-ty32` / `-ty256` / `-lane4` / `-lane2` /
+    `-dead3of8` / `-dead15of16` of tests/instnorm_cases.py (section b)."""
     V = nvec(dtype)
     return [(S, C) for S in FUSED_ROWS for C in (V, 3)] + [(27, 5 * V), (16, 17 * V), (27, 13)]
 
@@ -202,17 +205,63 @@ def backward(dy, x, styles, gammas, betas, res=None, act=True, gadd=None, slope=
     return {"y": y.detach(), "dx": _mask(dx, unsure), "dres": _mask(rl.grad, unsure) if rl is not None else None, "dgamma": _grads(gl, ns), "dbeta": _grads(bl, ns)}
 
 
-def pair_backward(dy, xa, xb, styles, gammas_a, betas_a, gammas_b, betas_b, slope=SLOPE, eps=EPS, work=torch.float64):
-    """y = LeakyReLU(norm_a(xa) + norm_b(xb)): dict(y, dxa, dxb, dgamma_a, dbeta_a, dgamma_b, dbeta_b)"""
+def pair_backward(dy, xa, xb, styles, gammas_a, betas_a, gammas_b, betas_b, slope=SLOPE, eps=EPS, work=torch.float64, mark=True):
+    """y = LeakyReLU(norm_a(xa) + norm_b(xb)): dict(y, dxa, dxb, dgamma_a, dbeta_a, dgamma_b, dbeta_b).  mark = False: no element is marked
+    NaN - for inputs whose dy is zero wherever the sign is undeterminable (rank1_case), so that either sign gives the same gradients"""
     al = xa.detach().to(work).requires_grad_(True)
     bl = xb.detach().to(work).requires_grad_(True)
     ga, ba, gb, bb = _leaves(gammas_a, work), _leaves(betas_a, work), _leaves(gammas_b, work), _leaves(betas_b, work)
-    unsure = [] if work == torch.float64 else None
+    unsure = [] if (work == torch.float64 and mark) else None
     y = forward(al, styles, ga, ba, res=bl, res_norm=(gb, bb), act=True, slope=slope, eps=eps, work=work, unsure=unsure)
     y.backward(dy.to(work))
     n = lambda ts: len(ts) if ts is not None else 0      # noqa: E731
     return {"y": y.detach(), "dxa": _mask(al.grad, unsure), "dxb": _mask(bl.grad, unsure), "dgamma_a": _grads(ga, n(gammas_a)), "dbeta_a": _grads(ba, n(betas_a)),
             "dgamma_b": _grads(gb, n(gammas_b)), "dbeta_b": _grads(bb, n(betas_b))}
+
+
+# ----------------------------------------------------------------------------------------------------------------- the rank-1 pair
+def rank1_channels(dtype):
+    """C of the rank-1 pair cases at STREAM_S rows: two channel tiles with one live column in the second; scalar lanes, 18 live in the second"""
+    return [33 * nvec(dtype), 50]
+
+
+class Rank1Case:
+    """the pair backward whose second input is the unstored product xb[row][c] = round(r1x[row] * r1w[c]) (the stem block's one-channel 1x1x1
+    shortcut), B = 2, S = STREAM_S.  xa, gradient and affine rows are those of Case; three things are shaped for the weight gradient
+    dW[c] = sum over rows of round(dxb[row][c]) * r1x[row] (the rounding is the kernels' definition: csrc/norm.hip, instnorm_pair_bwd_apply_kernel):
+
+    * r1x and r1w have amplitude 0.03, so the product's variance (1e-6) lies below eps: a norm in front of which the convolution's scale
+      survives.  At amplitude 1 the norm removes that scale and dW is what is left of terms that cancel 20 000-fold (measured: |dW| 0.06 of
+      summed |terms| 1256), which no fp32 run resolves to the bar;
+    * dy carries the sign of r1x, so the terms of dW add up (measured: |dW| 7600 of summed |terms| 8200) instead of cancelling like a random
+      walk (1 / 64 at 4098 rows) - one bf16 ulp of one term, where fp32 and float64 round dxb to different neighbours, is then 1e-6 of dW
+      and not 6e-5, 3 of which in one channel would stand above the bar;
+    * dy is zero wherever float64 cannot sign the pre-activation (SIGN_EPS; 4 to 25 elements): either sign gives the same gradients, so no
+      element has to be left out of sums that no test can take apart again.
+
+    What the cases are for - the rank-1 epilogue with a ragged last channel tile and with scalar lanes - depends on none of it."""
+
+    def __init__(self, dtype, C, device="cpu"):
+        c = Case(2, STREAM_S, C, dtype, device=device)
+        g = torch.Generator().manual_seed(99 + C)
+        self.B, self.S, self.C, self.dtype = 2, STREAM_S, C, dtype
+        self.styles = [1, 0]
+        self.xa, self.gam, self.bet, self.gam_b, self.bet_b = c.x, c.gam, c.bet, c.gam_b, c.bet_b
+        self.r1x = (torch.randn(2, STREAM_S, 1, generator=g) * 0.03).to(device).to(dtype)
+        self.r1w = ((torch.randn(C, generator=g) * 0.3 + 1) * 0.03).to(device).to(dtype)
+        self.xb = (self.r1x.float() * self.r1w.float()).to(dtype)      # one rounding of the fp32 product, as the kernels form it
+        unsure = []
+        forward(self.xa, self.styles, self.gam, self.bet, res=self.xb, res_norm=(self.gam_b, self.bet_b), unsure=unsure)
+        sign = torch.where(self.r1x < 0, -1.0, 1.0).to(dtype)
+        self.dy = torch.where(unsure[0], torch.zeros_like(c.dy), c.dy.abs() * sign)
+        self.n_unsure = int(unsure[0].sum())
+
+    def backward(self, work=torch.float64):
+        """pair_backward on the materialised product plus dw: the row sum of dxb, rounded once to the compute dtype, times r1x, in float64"""
+        r = pair_backward(self.dy, self.xa, self.xb, self.styles, self.gam, self.bet, self.gam_b, self.bet_b, work=work, mark=False)
+        r["dw_terms"] = r["dxb"].to(self.dtype).double() * self.r1x.double()
+        r["dw"] = r["dw_terms"].sum((0, 1))
+        return r
 
 
 # ----------------------------------------------------------------------------------------------------------------- the yardstick

@@ -11,7 +11,12 @@ tests/test_instnorm_ref_cpu.py, which also shows that honest fp32 arithmetic sta
 * every option alone and in the network's combination; y = NULL against y given; reduce + apply against the joint backward;
 * every operand of every entry point alone as an aligned slice, an 8-byte-offset slice and an odd-ld view (inputs in NaN-filled buffers,
   outputs in sentinel-filled ones that must survive outside the view); the lanes narrowed by divisibility, which only views reach;
-* the slab forms directly, with a gap between the slabs and with one slab; the refusals, which return before any launch.
+* the slab forms directly, with a gap between the slabs and with one slab; the refusals, which return before any launch;
+* the rank-1 pair with a ragged last channel tile and with scalar lanes.
+
+Which kernel instantiation, lane width, thread grid, chunk and tile count a case reaches is no prose here: where a case names one, the plan
+of that very call (miseg_instnorm_<call>_plan on the real operands) is asserted beside the launch against the hand-derived row of
+tests/instnorm_cases.py (the card serves unaligned 16-byte accesses, so the results alone could not tell).
 
 Tolerances are those of the existing tests of the same calls (instnorm_ref.fwd_tol / bwd_tol), pooled and per element (parity.assert_parity).
 Elements of dx / dres behind a LeakyReLU whose pre-activation no fp32 run can sign (instnorm_ref.SIGN_EPS) are left out.  No bound had to
@@ -23,9 +28,10 @@ import functools
 import pytest
 import torch
 
+import instnorm_cases as IC
 import instnorm_ref as R
 from layouts import P, SENT, assert_untouched, place_in, place_out
-from parity import assert_parity
+from parity import assert_parity, local_err
 
 pytestmark = pytest.mark.gpu
 
@@ -64,6 +70,26 @@ def _ref(dtype, B, S, Cc, opt):
 def _pair_ref(dtype, B, S, Cc):
     c = _case(dtype, B, S, Cc)
     return R.pair_backward(c.dy, c.x, c.xb, c.config()["styles"], c.gam, c.bet, c.gam_b, c.bet_b)
+
+
+# ----------------------------------------------------------------------------------------------------------------- the plan beside the launch
+def _tag(lay, family, names, plan):
+    """the table row's tag of one call: `operand-layout` where the case lays out one (present) operand of this call, else the case's own tag"""
+    mine = [(k.split(".")[1], v) for k, v in (lay or {}).items() if k.split(".")[0] == family and k.split(".")[1] in names]
+    assert len(mine) <= 1
+    return f"{mine[0][0]}-{mine[0][1]}" if mine else (None if plan is True else plan)
+
+
+def _plan(entry, dtype, S, Cc, tag, p, extra=()):
+    """the plan of this very call - the real operands - is what the hand-derived row of tests/instnorm_cases.py says"""
+    IC.assert_plan(_L(), IC.find(entry, _name(dtype), S, Cc, tag), p, extra)
+
+
+def _fwd_params(ops, L, x, res, y, B, S, stat):
+    """what the plan of a forward call looks at: the operands' addresses and row strides, the shape, non-NULL statistics"""
+    A = ops._style_arrays
+    return L.InstnormApply(P(x), _ld(ops, x), P(res), _ld(ops, res), P(y), _ld(ops, y), B, S, x.shape[-1], ops._dt(x), P(stat), R.EPS, None, 1, A(None, 1), A(None, 1),
+                           L.ACT_LEAKY, R.SLOPE)
 
 
 def _in(t, lay):
@@ -111,11 +137,14 @@ def _bwd_params(ops, L, dy, y, x, dx, dres, B, S, stat, dstat, styles, ns, gam, 
 
 
 # ----------------------------------------------------------------------------------------------------------------- one norm
-def run_single(dtype, B, S, Cc, opt="network", lay=None, default_lay="contig", y_given=True, one_call=False, case=None, ref=None):
+def run_single(dtype, B, S, Cc, opt="network", lay=None, default_lay="contig", y_given=True, one_call=False, case=None, ref=None, plan=None,
+               plan_calls=("stats", "fwd", "bwd")):
     """statistics, forward and backward of one (conditional) instance norm with the option combination `opt` (instnorm_ref.OPTIONS), every
     output against float64.  lay: {"stats.x" | "fwd.x" | "fwd.res" | "fwd.y" | "bwd.dy" | "bwd.y" | "bwd.x" | "bwd.dx" | "bwd.dres" | "bwd.gadd":
     layout}, the other operands take default_lay.  Above 2048 rows the forward is miseg_instnorm_stats + miseg_instnorm_apply (one_call:
-    miseg_instnorm_fwd, which launches the same two), up to there the one-launch miseg_instnorm_fwd; the backward is miseg_instnorm_bwd."""
+    miseg_instnorm_fwd, which launches the same two), up to there the one-launch miseg_instnorm_fwd; the backward is miseg_instnorm_bwd.
+    plan: the tag of the case's rows in tests/instnorm_cases.py (True: the one row of each call's shape) - the plan of each call in plan_calls
+    is asserted beside its launch."""
     ops, L = _ops(), _L()
     c = case or _case(dtype, B, S, Cc)
     cfg = c.config(**R.OPTIONS[opt])
@@ -130,11 +159,17 @@ def run_single(dtype, B, S, Cc, opt="network", lay=None, default_lay="contig", y
     gam, bet = cfg["gam"], cfg["bet"]
     act = L.ACT_LEAKY if cfg["act"] else L.ACT_NONE
     # statistics: the streaming kernel at every size
-    stat = ops.instnorm_stats(_in(c.x, lo("stats.x")), B, S)
+    xs = _in(c.x, lo("stats.x"))
+    stat = ops.instnorm_stats(xs, B, S)
+    if plan and "stats" in plan_calls:
+        _plan("stats", dtype, S, Cc, _tag(lay, "stats", ("x",), plan), L.InstnormStats(P(xs), _ld(ops, xs), B, S, Cc, ops._dt(xs), P(stat)))
     _check_stat(stat, c.x, what)
     # forward
     y = place_out((B, S, Cc), dtype, lo("fwd.y"))
     xv, rv = _in(c.x, lo("fwd.x")), _in(cfg["res"], lo("fwd.res")) if cfg["res"] is not None else None
+    if plan and "fwd" in plan_calls:
+        _plan("apply" if S > R.FUSED_MAX_ROWS and not one_call else "fwd", dtype, S, Cc, _tag(lay, "fwd", ("x", "y") + (("res",) if rv is not None else ()), plan),
+              _fwd_params(ops, L, xv, rv, y.view, B, S, stat))
     if S > R.FUSED_MAX_ROWS and not one_call:
         assert ops.instnorm_apply(xv, B, S, stat, styles, gam, bet, res=rv, act=act, slope=R.SLOPE, out=y.view) is y.view
     else:
@@ -154,6 +189,9 @@ def run_single(dtype, B, S, Cc, opt="network", lay=None, default_lay="contig", y
     dg = _zeros(ns, Cc, cfg["null_style"]) if gam is not None else None
     db = _zeros(ns, Cc, cfg["null_style"]) if bet is not None else None
     p = _bwd_params(ops, L, dyv, y_in, xv, dx.view, dres.view if dres else None, B, S, stat, _dstat(ops, L, B, Cc), styles, ns, gam, bet, dg, db, act, gv)
+    if plan and "bwd" in plan_calls:
+        present = ("dy", "x", "dx") + (("y",) if y_in is not None else ()) + (("dres",) if dres else ()) + (("gadd",) if gv is not None else ())
+        _plan("bwd", dtype, S, Cc, _tag(lay, "bwd", present, plan), p)
     ops._call("miseg_instnorm_bwd", p)
     assert_untouched(dx, what + ": dx")
     _close(dx.view, ref["dx"], bt, what + ": dx")
@@ -167,7 +205,7 @@ def run_single(dtype, B, S, Cc, opt="network", lay=None, default_lay="contig", y
     return {"y": y.view, "stat": stat, "dx": dx.view, "dres": dres.view if dres else None, "dgamma": dg, "dbeta": db}
 
 
-def run_split(dtype, B, S, Cc, lay=None, gadd=True):
+def run_split(dtype, B, S, Cc, lay=None, gadd=True, plan=None):
     """miseg_instnorm_bwd_reduce followed by miseg_instnorm_bwd_apply (the streaming kernels at every size; no activation) against
     miseg_instnorm_bwd on the same operands: dx to 1e-6 (fp64 atomics arrive in another order), both against float64.
     lay: {"reduce.dy" | "reduce.x": layout}"""
@@ -182,7 +220,13 @@ def run_split(dtype, B, S, Cc, lay=None, gadd=True):
     _fresh_stats(ops)
     styles = torch.tensor(cfg["styles"], dtype=torch.int32, device=DEV)
     stat = ops.instnorm_stats(c.x, B, S)
-    dstat = ops.instnorm_bwd_reduce(_in(c.dy, lay.get("reduce.dy", "contig")), _in(c.x, lay.get("reduce.x", "contig")), B, S, stat)
+    dyr, xr = _in(c.dy, lay.get("reduce.dy", "contig")), _in(c.x, lay.get("reduce.x", "contig"))
+    dstat = ops.instnorm_bwd_reduce(dyr, xr, B, S, stat)
+    if plan:      # the halves read dy, x (and dx): stand-ins for what the wrappers allocate
+        _plan("bwd_reduce", dtype, S, Cc, _tag(lay, "reduce", ("dy", "x"), plan),
+              _bwd_params(ops, L, dyr, None, xr, None, None, B, S, stat, dstat, None, 1, None, None, None, None, L.ACT_NONE, None))
+        _plan("bwd_apply", dtype, S, Cc, plan, _bwd_params(ops, L, c.dy, None, c.x, c.dy, None, B, S, stat, dstat, styles, 2, cfg["gam"], None, None, None, L.ACT_NONE,
+                                                           cfg["gadd"]))
     xh = (c.x.double() - c.x.double().mean(1, keepdim=True)) / torch.sqrt(c.x.double().var(1, unbiased=False, keepdim=True) + R.EPS)
     want = torch.stack([c.dy.double().sum(1), (c.dy.double() * xh).sum(1)], -1)
     assert_parity(dstat.sum(0), want, bt, what + ": dstat (sum dy, sum dy * xhat)")
@@ -191,6 +235,8 @@ def run_split(dtype, B, S, Cc, lay=None, gadd=True):
     dx1 = torch.full((B, S, Cc), SENT, dtype=dtype, device=DEV)
     dg1, db1 = _zeros(2, Cc), _zeros(2, Cc)
     p = _bwd_params(ops, L, c.dy, None, c.x, dx1, None, B, S, stat, _dstat(ops, L, B, Cc), styles, 2, cfg["gam"], cfg["bet"], dg1, db1, L.ACT_NONE, cfg["gadd"])
+    if plan:
+        _plan("bwd", dtype, S, Cc, plan, p)
     ops._call("miseg_instnorm_bwd", p)
     for tag, dx, g, b in (("reduce + apply", dx2, dg, db), ("joint", dx1, dg1, db1)):
         _close(dx, ref["dx"], bt, what + f": dx, {tag}")
@@ -201,7 +247,7 @@ def run_split(dtype, B, S, Cc, lay=None, gadd=True):
 
 
 # ----------------------------------------------------------------------------------------------------------------- the residual pair
-def run_pair(dtype, B, S, Cc, lay=None, default_lay="contig"):
+def run_pair(dtype, B, S, Cc, lay=None, default_lay="contig", plan=None):
     """y = LeakyReLU(norm_a(xa) + norm_b(xb)) (miseg_instnorm_apply with res_stat) and miseg_instnorm_pair_bwd without the rank-1 shortcut, with
     y given and with y = NULL (the same dx bits).  lay: {"pair.dy" | "pair.y" | "pair.xa" | "pair.xb" | "pair.dxa" | "pair.dxb": layout}"""
     ops, L = _ops(), _L()
@@ -227,6 +273,8 @@ def run_pair(dtype, B, S, Cc, lay=None, default_lay="contig"):
                               P(dxb.view), _ld(ops, dxb.view), B, S, Cc, ops._dt(av), P(sa), P(sb), R.EPS, P(ops.STAT_POOL.take(nb, sa.device)),
                               P(ops.STAT_POOL.take(nb, sa.device)), P(styles), 2, A(c.gam, 2), A(c.gam_b, 2), A(g[0], 2), A(g[1], 2), A(g[2], 2), A(g[3], 2), R.SLOPE,
                               A(c.bet, 2), A(c.bet_b, 2))
+        if plan:
+            _plan("pair", dtype, S, Cc, _tag(lay, "pair", ("dy", "xa", "xb", "dxa", "dxb") + (("y",) if y_in is not None else ()), plan), p)
         ops._call("miseg_instnorm_pair_bwd", p)
         tag = ", y given" if y_in is not None else ", y = NULL"
         assert_untouched(dxa, what + ": dxa" + tag)
@@ -256,13 +304,14 @@ def _stream_cases():
 def test_streaming_geometry(dtype, Cc):
     """miseg_instnorm_stats, _apply, _bwd (reduce + apply), _bwd_reduce, _bwd_apply at 2049 rows: 65 chunks of 32 rows with 32 columns (every
     replica several times), three chunks with one column, the last of them one row"""
-    run_single(dtype, 2, R.STREAM_S, Cc)
-    run_split(dtype, 2, R.STREAM_S, Cc)
+    cid = {C_: i for i, C_ in R.stream_channels(dtype)}[Cc]
+    run_single(dtype, 2, R.STREAM_S, Cc, plan=cid)
+    run_split(dtype, 2, R.STREAM_S, Cc, plan=cid)
 
 
 @pytest.mark.parametrize("dtype,Cc", _stream_cases())
 def test_streaming_geometry_pair(dtype, Cc):
-    run_pair(dtype, 2, R.STREAM_S, Cc)
+    run_pair(dtype, 2, R.STREAM_S, Cc, plan={C_: i for i, C_ in R.stream_channels(dtype)}[Cc])
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=_name)
@@ -274,7 +323,7 @@ def test_streaming_rows_per_workgroup_cap(dtype):
     assert -(-S // 1024) > 1024
     cfg = c.config()
     ref = R.backward(c.dy, c.x, cfg["styles"], cfg["gam"], cfg["bet"], res=cfg["res"])
-    run_single(dtype, 1, S, V, case=c, ref=ref)
+    run_single(dtype, 1, S, V, case=c, ref=ref, plan="rowcap")
 
 
 # ----------------------------------------------------------------------------------------------------------------- b. fused geometry
@@ -287,12 +336,12 @@ def test_fused_geometry(dtype, S, Cc):
     """miseg_instnorm_fwd / _bwd in one register-resident launch: S = 2 .. 16 sit on the ty floor (16 row lanes, 16 channel columns), 17 / 27 /
     256 / 257 step ty, 512 -> 513 and 1024 -> 1025 narrow a lane (rows per lane 2 -> 3, 4 -> 5), 2048 is the last fused size; C = 5 V at 27
     rows (tx = 8), 17 V at 16 rows (two workgroups) and 13 at 27 rows leave dead channel columns in the last workgroup"""
-    run_single(dtype, 2, S, Cc)
+    run_single(dtype, 2, S, Cc, plan=True, plan_calls=("fwd", "bwd"))
 
 
 @pytest.mark.parametrize("dtype,S,Cc", _fused_cases())
 def test_fused_geometry_pair(dtype, S, Cc):
-    run_pair(dtype, 2, S, Cc)
+    run_pair(dtype, 2, S, Cc, plan=True)
 
 
 def _head(c, S):
@@ -313,7 +362,8 @@ def test_the_boundary_between_the_generations_is_no_cliff(dtype, Cc):
     for S, cs in ((R.FUSED_MAX_ROWS, _head(c, R.FUSED_MAX_ROWS)), (R.STREAM_S, c)):
         cfg = cs.config()
         ref = R.backward(cs.dy, cs.x, cfg["styles"], cfg["gam"], cfg["bet"], res=cfg["res"])
-        run_single(dtype, 2, S, Cc, one_call=True, case=cs, ref=ref)
+        tag = {(2048, 48): "lastfused", (2048, 50): "lastfused-contig", (2049, 48): "contig", (2049, 50): "scalar50"}[(S, Cc)]
+        run_single(dtype, 2, S, Cc, one_call=True, case=cs, ref=ref, plan=tag, plan_calls=("fwd", "bwd"))
 
 
 # ----------------------------------------------------------------------------------------------------------------- c. options
@@ -356,14 +406,14 @@ LAYOUT_OPERANDS = ["stats.x", "fwd.x", "fwd.res", "fwd.y", "bwd.dy", "bwd.y", "b
                    "pair.dy", "pair.y", "pair.xa", "pair.xb", "pair.dxa", "pair.dxb"]
 
 
-def _run_layout(dtype, S, Cc, lay, default_lay="contig"):
+def _run_layout(dtype, S, Cc, lay, default_lay="contig", plan=None):
     kinds = {k.split(".")[0] for k in lay} if lay else {"stats", "pair"}
     if kinds & {"stats", "fwd", "bwd"}:
-        run_single(dtype, 2, S, Cc, opt="gadd", lay=lay, default_lay=default_lay)      # residual, dres and gadd: every operand exists
+        run_single(dtype, 2, S, Cc, opt="gadd", lay=lay, default_lay=default_lay, plan=plan)      # residual, dres and gadd: every operand exists
     if "reduce" in kinds:
-        run_split(dtype, 2, S, Cc, lay=lay)
+        run_split(dtype, 2, S, Cc, lay=lay, plan=plan)
     if "pair" in kinds:
-        run_pair(dtype, 2, S, Cc, lay=lay, default_lay=default_lay)
+        run_pair(dtype, 2, S, Cc, lay=lay, default_lay=default_lay, plan=plan)
 
 
 @pytest.mark.parametrize("layout", ["slice", "off8", "ldodd"])
@@ -373,8 +423,10 @@ def _run_layout(dtype, S, Cc, lay, default_lay="contig"):
 def test_one_operand_strided(dtype, S, operand, layout):
     """each operand of each entry point ALONE as an aligned channel slice (the vector instantiation with ld != C), a slice 8 bytes into a
     16-byte unit and an odd-ld view (either breaks the vector predicate for the whole launch); 48 channels.  As in test_hip_row_op_edges.py the
-    card serves unaligned vector accesses, so these cases show right results and untouched neighbours, not which instantiation ran."""
-    _run_layout(dtype, S, 48, {operand: layout})
+    card serves unaligned vector accesses, so the launches show right results and untouched neighbours; WHICH instantiation each call takes -
+    16-byte lanes for the slice, scalar ones for the other two, and in the streaming forward 16-byte statistics beside a scalar apply - is
+    asserted on the call's plan (tests/instnorm_cases.py, section c)."""
+    _run_layout(dtype, S, 48, {operand: layout}, plan="contig")
 
 
 @pytest.mark.parametrize("S", [27, 1000])
@@ -383,8 +435,8 @@ def test_lanes_narrowed_by_divisibility(dtype, Cc, S):
     """C = 12 / 10 bf16 and C = 6 fp32 inside 16-byte-aligned rows with ld % V == 0: the fused geometry halves the lane until it divides C (8-
     and 4-byte lanes).  Contiguous rows of these widths have ld % V != 0 and take the scalar lane, so only views get here: every operand of
     every fused kernel is an aligned slice."""
-    run_single(dtype, 2, S, Cc, opt="gadd", default_lay="slice")
-    run_pair(dtype, 2, S, Cc, default_lay="slice")
+    run_single(dtype, 2, S, Cc, opt="gadd", default_lay="slice", plan="slices", plan_calls=("fwd", "bwd"))
+    run_pair(dtype, 2, S, Cc, default_lay="slice", plan="slices")
 
 
 # ----------------------------------------------------------------------------------------------------------------- e. slabs, direct
@@ -429,6 +481,7 @@ def test_slab_forms_directly(dtype, S, Cc, nslabs, gap):
     nb = L.load().miseg_instnorm_stat_bytes(B, Cc) // 8
     stat = ops.STAT_POOL.take(nb, x.device).view(-1, B, Cc, 2)
     p = L.InstnormApply(P(x), Cc, P(c.res), Cc, P(y), Cc, B, S, Cc, ops._dt(x), P(stat), R.EPS, P(styles), 2, A(c.gam, 2), A(c.bet, 2), L.ACT_LEAKY, R.SLOPE)
+    _plan("fwd_slabs", dtype, S, Cc, f"{nslabs}slabs-gap{gap}", p, (P(ws), nslabs, stride))
     ops._call("miseg_instnorm_fwd_slabs", p, extra=(P(ws), nslabs, stride))
     assert torch.equal(x, want_x), what + ": x is not round(sum of the slabs)"
     y0, stat0 = ops.instnorm_fwd(want_x, B, S, styles, c.gam, c.bet, res=c.res, act=L.ACT_LEAKY, slope=R.SLOPE)
@@ -443,6 +496,7 @@ def test_slab_forms_directly(dtype, S, Cc, nslabs, gap):
         dg, db = _zeros(2, Cc), _zeros(2, Cc)
         p = _bwd_params(ops, L, None if slabs else want_x, None, c.x, dx, None, B, S, stat_x, _dstat(ops, L, B, Cc), styles, 2, c.gam, c.bet, dg, db, L.ACT_LEAKY, None)
         if slabs:
+            _plan("bwd_slabs", dtype, S, Cc, f"{nslabs}slabs-gap{gap}", p, (P(ws), nslabs, stride))
             ops._call("miseg_instnorm_bwd_slabs", p, extra=(P(ws), nslabs, stride))
         else:
             ops._call("miseg_instnorm_bwd", p)
@@ -479,9 +533,15 @@ def test_refusals_return_before_any_launch():
     x, out, stat, dstat = tensors(S)
     ws = torch.zeros(B * S * Cc, device=DEV)
     p = L.InstnormApply(P(out), Cc, None, 0, P(out), Cc, B, S, Cc, ops._dt(x), P(stat), R.EPS, None, 1, A(None, 1), A(None, 1), L.ACT_NONE, 0.0)
+    def refused(entry, prm, code, extra=()):
+        rc, pl = IC.ask(L, entry, prm, extra)
+        assert rc == code and pl.n_launches == 0, f"{entry}: the plan returns {rc}, the launch {code}"
+
+    refused("fwd_slabs", p, IC.UNSUPPORTED, (P(ws), 1, B * S * Cc))
     with pytest.raises(L.MisegHipError, match="rows per sample"):
         ops._call("miseg_instnorm_fwd_slabs", p, extra=(P(ws), 1, B * S * Cc))
     pb = _bwd_params(ops, L, None, None, x, out, None, B, S, stat, dstat, None, 1, None, None, None, None, L.ACT_NONE, None)
+    refused("bwd_slabs", pb, IC.UNSUPPORTED, (P(ws), 1, B * S * Cc))
     with pytest.raises(L.MisegHipError, match="rows per sample"):
         ops._call("miseg_instnorm_bwd_slabs", pb, extra=(P(ws), 1, B * S * Cc))
     untouched(out, stat, dstat)
@@ -489,12 +549,14 @@ def test_refusals_return_before_any_launch():
     S = 27
     x, out, stat, dstat = tensors(S)
     p = L.InstnormApply(P(x), Cc, P(x), Cc, P(out), Cc, B, S, Cc, ops._dt(x), P(stat), R.EPS, None, 1, A(None, 1), A(None, 1), L.ACT_NONE, 0.0, P(dstat))
+    refused("fwd", p, IC.UNSUPPORTED)
     with pytest.raises(L.MisegHipError, match="res_stat"):
         ops._call("miseg_instnorm_fwd", p)
     untouched(out, stat, dstat)
     # the halves of the backward know no activation
     pb = _bwd_params(ops, L, x, x, x, out, None, B, S, stat, dstat, None, 1, None, None, None, None, L.ACT_LEAKY, None)
     for fn in ("miseg_instnorm_bwd_apply", "miseg_instnorm_bwd_reduce"):
+        refused(fn[len("miseg_instnorm_"):], pb, IC.UNSUPPORTED)
         with pytest.raises(L.MisegHipError, match="activation"):
             ops._call(fn, pb)
     untouched(out, stat, dstat)
@@ -504,11 +566,53 @@ def test_refusals_return_before_any_launch():
     with pytest.raises(ValueError, match="r1x"):
         p = L.InstnormApply(P(x), Cc, P(x), Cc, P(out), Cc, B, S, Cc, ops._dt(x), P(stat), R.EPS, None, 1, A(None, 1), A(None, 1), L.ACT_NONE, 0.0, P(dstat),
                             A(None, 1), A(None, 1), P(x1), 1, P(w))
+        refused("apply", p, IC.BADARG)
         ops._call("miseg_instnorm_apply", p)
     dw = torch.zeros(Cc, device=DEV)
     with pytest.raises(ValueError, match="rank-1"):
         p = L.InstnormPairBwd(P(x), Cc, None, 0, P(x), Cc, P(x), Cc, P(out), Cc, P(out), Cc, B, S, Cc, ops._dt(x), P(stat), P(stat), R.EPS, P(dstat), P(dstat), None, 1,
                               A(None, 1), A(None, 1), A(None, 1), A(None, 1), A(None, 1), A(None, 1), R.SLOPE, A(None, 1), A(None, 1), P(x1), 1, P(w), P(dw))
+        refused("pair", p, IC.BADARG)
         ops._call("miseg_instnorm_pair_bwd", p)
     untouched(out, stat, dstat)
     assert not bool(dw.any())
+
+
+# ----------------------------------------------------------------------------------------------------------------- g. the rank-1 pair
+@functools.lru_cache(maxsize=4)
+def _rank1_case(dtype, Cc):
+    c = R.Rank1Case(dtype, Cc, device=DEV)
+    return c, c.backward()
+
+
+@pytest.mark.parametrize("dtype,Cc", [pytest.param(dt, Cc, id=f"{_name(dt)}-C{Cc}") for dt in DTYPES for Cc in R.rank1_channels(dt)])
+def test_rank1_pair_ragged_channel_tile_and_scalar_lanes(dtype, Cc):
+    """miseg_instnorm_pair_bwd with the rank-1 shortcut (r1x / r1w / r1dw; xb, dxb, y NULL) at 2 x 2049 rows: 33 vectors - two channel tiles,
+    one live column in the second, whose 31 dead columns still take part in the weight gradient's workgroup reduction - and 50 scalar channels,
+    18 live in the second tile.  The shortcut's statistics come from miseg_instnorm_stats of the materialised product; dxa and the affine
+    gradients stand against float64 at bwd_tol, dW (the row sum of round(dxb) * r1x) at the bar of test_instnorm_residual_pair_rank1_shortcut.
+    Inputs: instnorm_ref.Rank1Case."""
+    ops, L = _ops(), _L()
+    c, ref = _rank1_case(dtype, Cc)
+    B, S = c.B, c.S
+    what = f"rank-1 pair {_name(dtype)} S={S} C={Cc}"
+    bt = R.bwd_tol(dtype, S)
+    _fresh_stats(ops)
+    styles = torch.tensor(c.styles, dtype=torch.int32, device=DEV)
+    sa, sb = ops.instnorm_stats(c.xa, B, S), ops.instnorm_stats(c.xb, B, S)
+    dxa = torch.full((B, S, Cc), SENT, dtype=dtype, device=DEV)
+    g = [_zeros(2, Cc) for _ in range(4)]      # dgamma_a, dbeta_a, dgamma_b, dbeta_b
+    dw = torch.zeros(Cc, device=DEV)
+    A = ops._style_arrays
+    p = L.InstnormPairBwd(P(c.dy), Cc, None, 0, P(c.xa), Cc, None, 0, P(dxa), Cc, None, 0, B, S, Cc, ops._dt(c.xa), P(sa), P(sb), R.EPS, P(_dstat(ops, L, B, Cc)),
+                          P(_dstat(ops, L, B, Cc)), P(styles), 2, A(c.gam, 2), A(c.gam_b, 2), A(g[0], 2), A(g[1], 2), A(g[2], 2), A(g[3], 2), R.SLOPE, A(c.bet, 2),
+                          A(c.bet_b, 2), P(c.r1x), 1, P(c.r1w), P(dw))
+    _plan("pair", dtype, S, Cc, "rank1", p)
+    ops._call("miseg_instnorm_pair_bwd", p)
+    assert_parity(dxa, ref["dxa"], bt, what + ": dxa")
+    for k, name in enumerate(("dgamma_a", "dbeta_a", "dgamma_b", "dbeta_b")):
+        for s in range(2):
+            assert_parity(g[k][s], ref[name][s], bt, what + f": {name}[{s}]")
+    yard = local_err(ref["dw_terms"].float().sum((0, 1)), ref["dw"])[0]      # torch's own fp32 sum of the same terms
+    print(what, "dW yardstick", yard)
+    assert_parity(dw, ref["dw"], 1e-4, what + ": dW against float64", local_tol=max(1e-4, 2 * yard))

@@ -152,6 +152,30 @@ def test_fp32_compute_yardstick_stays_below_half_the_kernel_bars(dtype, S, Cc, o
     print("yardstick", _name(dtype), S, Cc, opt, {k: f"{p:.1e}/{l:.1e}" for k, (p, l) in worst.items()})
 
 
+def _rank1_matrix():
+    return [pytest.param(dt, Cc, id=f"{_name(dt)}-C{Cc}") for dt in DTYPES for Cc in R.rank1_channels(dt)]
+
+
+@pytest.mark.parametrize("dtype,Cc", _rank1_matrix())
+def test_fp32_compute_yardstick_of_the_rank1_pair_stays_below_half_the_kernel_bars(dtype, Cc):
+    """the inputs of the rank-1 pair cases of tests/test_hip_instnorm_forms.py (instnorm_ref.Rank1Case): dxa and the affine gradients below
+    half of bwd_tol, the weight gradient below half of the 1e-4 test_instnorm_residual_pair_rank1_shortcut holds it to.  Measured here:
+    dxa 6.5e-8 / 1.7e-3 pooled (fp32 / bf16), dW 3e-8 .. 6e-7 pooled, 5e-8 .. 3e-6 local"""
+    c = R.Rank1Case(dtype, Cc)
+    ref, yard = c.backward(), c.backward(work=torch.float32)
+    assert 0 < c.n_unsure < 64 and not torch.isnan(ref["dxa"]).any() and not torch.isnan(ref["dxb"]).any()
+    bt = R.bwd_tol(dtype, c.S)
+    worst = {}
+    _below_half(yard["dxa"].to(dtype), ref["dxa"], bt, "dxa", worst)
+    for k in ("dgamma_a", "dbeta_a", "dgamma_b", "dbeta_b"):
+        for s in range(2):
+            _below_half(yard[k][s], ref[k][s], bt, f"{k}[{s}]", worst)
+    _below_half(yard["dw"].float(), ref["dw"], 1e-4, "dw", worst)
+    # the terms add up instead of cancelling: what makes one bf16 ulp of one term small against the sum
+    assert float((ref["dw"].abs() / ref["dw_terms"].abs().sum((0, 1))).min()) > 0.5
+    print("yardstick rank-1", _name(dtype), Cc, {k: f"{p:.1e}/{l:.1e}" for k, (p, l) in worst.items()})
+
+
 # ----------------------------------------------------------------------------------------------------------------- mutations
 def _caught(got, ref, tol, what):
     got, ref = R.determined(got, ref)
