@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import rel_err
+from parity import assert_parity
 from mi_seg_amd.training.losses import DiceCELoss, DiceFocalLoss, GeneralizedDiceFocalLoss, GeneralizedDiceLoss
 from mi_seg_amd.training.metrics import GeneralizedDiceScore, compute_generalized_dice, generalized_dice_from_logits
 from test_generalized_dice_cpu import W_TYPES, gdice_focal_by_hand, tiny_case
@@ -37,7 +38,7 @@ def test_fused_generalized_dice_focal_matches_torch(w_type, include_background, 
     print(f"gdice_focal {w_type} bg={include_background} {shape}: loss {float(loss):.9g} ref {float(ref):.9g} rel {abs(float(loss) - float(ref)) / abs(float(ref)):.3g}"
           f" dlogits rel_err {rel_err(logits.grad, ref_in.grad):.3g}")
     assert abs(float(loss) - float(ref)) <= 1e-5 * abs(float(ref)), (float(loss), float(ref))
-    assert rel_err(logits.grad, ref_in.grad) < 1e-4
+    assert_parity(logits.grad, ref_in.grad, 1e-4, "d loss / d logits against float64")
     l2 = crit(logits.detach(), labels)
     assert torch.equal(l2, loss.detach())
     # the generalized Dice term alone takes the same kernels with lambda_focal = 0
@@ -58,7 +59,7 @@ def test_fused_generalized_dice_focal_wide(C):
     ref = crit.forward_torch(ref_in, labels.cpu())
     (ref * 1.7).backward()
     assert abs(float(loss) - float(ref)) <= 1e-5 * abs(float(ref)), (float(loss), float(ref))
-    assert rel_err(logits.grad, ref_in.grad) < 1e-4
+    assert_parity(logits.grad, ref_in.grad, 1e-4, "d loss / d logits against float64")
 
 
 @pytest.mark.parametrize("w_type", W_TYPES)
@@ -89,7 +90,7 @@ def test_existing_kinds_did_not_move(kind, shape):
     ref = crit.forward_torch(ref_in, labels.cpu())
     (ref * 1.7).backward()
     assert abs(float(loss) - float(ref)) <= 1e-5 * abs(float(ref)), (float(loss), float(ref))
-    assert rel_err(logits.grad, ref_in.grad) < 1e-4
+    assert_parity(logits.grad, ref_in.grad, 1e-4, "d loss / d logits against float64")
     again = logits.detach().clone().requires_grad_(True)
     l2 = crit(again, labels)
     (l2 * 1.7).backward()
