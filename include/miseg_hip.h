@@ -1020,6 +1020,58 @@ typedef struct {
 } miseg_grad_fold_params;
 int miseg_grad_fold(const miseg_grad_fold_params* p, miseg_stream_t stream);
 
+/* An average of the weights over the optimisation steps, kept on the device (EMA of the weights as nnU-Net-style / MONAI bundles ship it;
+ * Lightning's StochasticWeightAveraging / torch.optim.swa_utils.AveragedModel, which the reference's train.py takes through
+ * Trainer.add_argparse_args; new symbols and structs: MISEG_ABI_VERSION stays 16).  `avg` is a flat fp32 buffer laid out like the gradient
+ * arena (parameter i at element offset descs[i].off), walked in miseg_opt_step's geometry (the same descriptor table over ALL parameters).
+ *
+ * miseg_weight_average: one averaging call, in two launches.
+ *   1. the tick, one thread, reads and writes `record` (the caller zeroes it once; its counters run on).  If clip_record (optional: the
+ *      record miseg_grad_norm filled for this step) has skip set, the step wrote no weight and the call changes NOTHING - no counter, no
+ *      element of avg.  Otherwise, with t = calls before this call (calls then counts this one) and n = n_averaged before it:
+ *        apply = t >= start && (t - start) % every == 0;  first = n == 0;  n_averaged = n + apply;  and, when apply, coef = c:
+ *        MISEG_AVG_MEAN              c = 1.0f / (float)(n + 1)                                   (SWA: the running mean; correctly rounded)
+ *        MISEG_AVG_EMA               c = 1.0f - decay
+ *        MISEG_AVG_EMA, warmup != 0  c = 1.0f - fminf(decay, (1.0f + (float)n) / (10.0f + (float)n))   (the timm / TF warm-up: without it an
+ *                                    EMA stays biased towards the initial weights for about 1 / (1 - decay) steps)
+ *      every operation rounded on its own in fp32.  A call that does not apply leaves coef as it was.
+ *   2. the stream, one workgroup per 4096-element block, only READS the two records (no workgroup reads a word another workgroup of its
+ *      launch writes: that is why the tick is a launch of its own):  skip or apply == 0: every workgroup returns before its first load;
+ *      first: avg = w (avg is NOT read and may hold anything);  otherwise avg = fl(avg + fl(c * fl(w - avg))), no contraction.
+ *      ALL parameters, whatever their `used` flags (as AveragedModel: a parameter without a gradient simply did not move).  The
+ *      parameters are never written; the padding between the slots of avg keeps its bits.  No atomics, no LDS: equal bits every run.
+ * Refused before any launch: a wrong struct_size, a null descs_dev / avg / record, ndesc / total_blocks < 1, an unknown mode, a decay that
+ * is not finite or outside [0, 1) (whatever the mode), every < 1, start < 0, an avg that is not 16-byte aligned.
+ *
+ * miseg_weight_swap: ONE launch that exchanges param[i][e] <-> avg[off_i + e] for every descriptor (validation / export on the averaged
+ * weights): a pure exchange - a second call restores every bit of both sides; padding is not touched.  params_version (optional DEVICE
+ * int64, miseg_opt_step's field) is incremented once per launch: the refresh launches of the next step re-cast and re-pack every weight.
+ * Refused before any launch: a wrong struct_size, a null descs_dev / avg, ndesc / total_blocks < 1, an avg that is not 16-byte aligned. */
+enum { MISEG_AVG_EMA = 0, MISEG_AVG_MEAN = 1 };
+typedef struct {
+  int32_t apply, first;            /* of the last call that was not skipped */
+  float coef;                      /* of the last applying call */
+  uint32_t calls, n_averaged, reserved[3];
+} miseg_weight_average_record;
+typedef struct {
+  uint32_t struct_size;
+  int mode;                        /* MISEG_AVG_* */
+  const miseg_opt_desc* descs_dev; int ndesc, total_blocks;
+  float* avg;
+  miseg_weight_average_record* record;
+  const miseg_grad_clip_record* clip_record;      /* optional */
+  float decay;
+  int warmup, start, every;
+} miseg_weight_average_params;
+typedef struct {
+  uint32_t struct_size;
+  const miseg_opt_desc* descs_dev; int ndesc, total_blocks;
+  float* avg;
+  int64_t* params_version;         /* optional */
+} miseg_weight_swap_params;
+int miseg_weight_average(const miseg_weight_average_params* p, miseg_stream_t stream);
+int miseg_weight_swap(const miseg_weight_swap_params* p, miseg_stream_t stream);
+
 /* Sliding-window stitching (MONAI sliding_window_inference, mode="constant", as used at lightning_monai.py:86-93,187): every window's logits
  * stay resident (win: fp32 [nd*nh*nw][C][rd][rh][rw], window (id, ih, iw) at index (id*nh + ih)*nw + iw, origin (start_d[id], start_h[ih],
  * start_w[iw]); 700 windows x 6 x 96^3 = 14.9 GB of the 288), and ONE gather pass writes out[c][d][h][w] = (sum over the windows covering the

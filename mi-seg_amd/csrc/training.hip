@@ -661,6 +661,145 @@ static __global__ void __launch_bounds__(256) grad_fold_kernel(const miseg_opt_d
   }
 }
 
+// ------------------------------------------------------------------------------------------------ weight averaging (miseg_weight_average, miseg_weight_swap)
+// The tick: ONE thread turns the record's counters into this call's decision (apply, first, coef - the rules are written out in miseg_hip.h).
+// A launch of its own, so that no workgroup of the streaming launch behind it reads a word another workgroup of its launch writes.
+static __global__ void weight_average_tick_kernel(miseg_weight_average_record* __restrict__ rec, const miseg_grad_clip_record* __restrict__ clip, int mode,
+                                                  float decay, int warmup, int start, int every) {
+#pragma clang fp contract(off)
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  if (clip && clip->skip) return;      // the step wrote no weight: not a call
+  const uint32_t t = rec->calls, n = rec->n_averaged;
+  const int64_t since = (int64_t)t - (int64_t)start;
+  const int apply = (since >= 0 && since % (int64_t)every == 0) ? 1 : 0;
+  rec->calls = t + 1u;
+  rec->apply = apply;
+  rec->first = n == 0u ? 1 : 0;
+  if (apply) {
+    const float fn = (float)n;
+    float c;
+    if (mode == MISEG_AVG_MEAN) {
+      c = __fdiv_rn(1.0f, (float)(n + 1u));
+    } else {
+      const float dn = warmup ? fminf(decay, __fdiv_rn(__fadd_rn(1.0f, fn), __fadd_rn(10.0f, fn))) : decay;
+      c = __fsub_rn(1.0f, dn);
+    }
+    rec->coef = c;
+    rec->n_averaged = n + 1u;
+  }
+}
+
+// The stream: opt_step_kernel's geometry over the parameters (read) and `avg` (read unless first, written).  All of a thread's loads are in
+// flight before its first subtract; no LDS, no atomics; the difference, the product and the sum are rounded on their own.
+// Both sides are loaded non-temporally (fold_ld: `global_load_dwordx4 .. nt`), the stores are plain.
+// Measured on the headline arena (3 x 249 MB per launch; miseg_grad_fold op 3 in the same process: 117 us), kernel alone / what averaging
+// every step adds to the captured train step:  nt both 118.7 us / +179 us;  nt weights only 113.5 us / +207 us;  nt average only
+// 135.7 us / +213 us;  plain both 145.8 us / +201 us.  The weights were written by the launch just before, but 249 MB of them and as much of
+// their moments passed through a 256 MiB Infinity Cache since: neither side is found there, and both are read once.  Kept: nt on both - the
+// smallest median inside the step, where it counts, and level with the fold alone; nt on the weights only is 5 us faster alone, but its step
+// median is 17 us slower, over a range (6.486 .. 6.554 ms) that contains the other's (6.491 .. 6.518 ms): not a difference to build on.
+static __global__ void __launch_bounds__(256) weight_average_kernel(const miseg_opt_desc* __restrict__ descs, int ndesc, float* __restrict__ avg,
+                                                                  const miseg_weight_average_record* __restrict__ rec,
+                                                                  const miseg_grad_clip_record* __restrict__ clip) {
+#pragma clang fp contract(off)
+  if (clip && clip->skip) return;      // (the tick left the record alone: it still holds the call before)
+  if (!rec->apply) return;
+  const bool first = rec->first != 0;
+  const float c = rec->coef;
+  int lo = 0, hi = ndesc - 1;
+  while (lo < hi) {      // the last descriptor with block0 <= blockIdx.x
+    const int mid = (lo + hi + 1) >> 1;
+    if (descs[mid].block0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+  }
+  const miseg_opt_desc d = descs[lo];
+  const float* wp = d.param;
+  float* ap = avg + d.off;
+  const int e0 = ((int)blockIdx.x - d.block0) * OPT_BLOCK;
+  const bool vec = ((((uintptr_t)wp) | ((uintptr_t)ap)) & 15) == 0;      // arena slots are 16-byte aligned; a parameter view may not be
+  f32x4 w[4], a[4];
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int e = e0 + (it * 256 + threadIdx.x) * 4;
+    const int cnt = d.n - e;
+    if (vec && cnt >= 4) {
+      w[it] = fold_ld(wp + e);
+      a[it] = first ? f32x4{0.f, 0.f, 0.f, 0.f} : fold_ld(ap + e);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        w[it][k] = k < cnt ? wp[e + k] : 0.f;
+        a[it][k] = (!first && k < cnt) ? ap[e + k] : 0.f;
+      }
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int e = e0 + (it * 256 + threadIdx.x) * 4;
+    const int cnt = d.n - e;
+    f32x4 v;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float diff = w[it][k] - a[it][k];
+      const float step = c * diff;
+      v[k] = first ? w[it][k] : a[it][k] + step;
+    }
+    if (vec && cnt >= 4) {
+      *reinterpret_cast<f32x4*>(ap + e) = v;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < cnt) ap[e + k] = v[k];
+    }
+  }
+}
+
+// The exchange param <-> avg in the same geometry: every element is read from both sides and stored to the other (loads non-temporal: each
+// word is read once; stores plain).  Thread 0 of workgroup 0 bumps the parameter version - a word no other workgroup of the launch looks at.
+static __global__ void __launch_bounds__(256) weight_swap_kernel(const miseg_opt_desc* __restrict__ descs, int ndesc, float* __restrict__ avg,
+                                                               int64_t* __restrict__ params_version) {
+#pragma clang fp contract(off)
+  if (params_version && blockIdx.x == 0 && threadIdx.x == 0) *params_version += 1;      // the parameters change: the versioned refresh re-lays-out its copies
+  int lo = 0, hi = ndesc - 1;
+  while (lo < hi) {      // the last descriptor with block0 <= blockIdx.x
+    const int mid = (lo + hi + 1) >> 1;
+    if (descs[mid].block0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+  }
+  const miseg_opt_desc d = descs[lo];
+  float* wp = d.param;
+  float* ap = avg + d.off;
+  const int e0 = ((int)blockIdx.x - d.block0) * OPT_BLOCK;
+  const bool vec = ((((uintptr_t)wp) | ((uintptr_t)ap)) & 15) == 0;
+  f32x4 w[4], a[4];
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int e = e0 + (it * 256 + threadIdx.x) * 4;
+    const int cnt = d.n - e;
+    if (vec && cnt >= 4) {
+      w[it] = fold_ld(wp + e);
+      a[it] = fold_ld(ap + e);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        w[it][k] = k < cnt ? wp[e + k] : 0.f;
+        a[it][k] = k < cnt ? ap[e + k] : 0.f;
+      }
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int e = e0 + (it * 256 + threadIdx.x) * 4;
+    const int cnt = d.n - e;
+    if (vec && cnt >= 4) {
+      *reinterpret_cast<f32x4*>(wp + e) = a[it];
+      *reinterpret_cast<f32x4*>(ap + e) = w[it];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < cnt) { wp[e + k] = a[it][k]; ap[e + k] = w[it][k]; }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ stitching
 struct StitchArgs {
   int C, D, H, W, rd, rh, rw, nd, nh, nw, d0;
@@ -1114,6 +1253,37 @@ extern "C" int miseg_grad_fold(const miseg_grad_fold_params* p, miseg_stream_t s
   MISEG_REQUIRE(g0 + bytes <= a0 || a0 + bytes <= g0, MISEG_E_BADARG, "grad_fold: grad and acc overlap");
   grad_fold_kernel<<<p->total_blocks, 256, 0, s>>>(p->descs_dev, p->ndesc, p->grad, p->acc, p->ops, p->scale);
   MISEG_LAUNCH_CHECK("grad_fold");
+  return MISEG_OK;
+}
+
+extern "C" int miseg_weight_average(const miseg_weight_average_params* p, miseg_stream_t s_) {
+  hipStream_t s = (hipStream_t)s_;
+  MISEG_REQUIRE(p && p->struct_size == sizeof(miseg_weight_average_params), MISEG_E_BADARG, "weight_average: struct_size %u != %zu", p ? p->struct_size : 0u,
+                sizeof(miseg_weight_average_params));
+  MISEG_REQUIRE(p->descs_dev && p->avg && p->record, MISEG_E_BADARG, "weight_average: null pointer (descs_dev / avg / record)");
+  MISEG_REQUIRE(p->ndesc > 0 && p->total_blocks > 0, MISEG_E_BADARG, "weight_average: empty table (ndesc %d, total_blocks %d)", p->ndesc, p->total_blocks);
+  MISEG_REQUIRE(p->mode == MISEG_AVG_EMA || p->mode == MISEG_AVG_MEAN, MISEG_E_BADARG, "weight_average: mode %d", p->mode);
+  MISEG_REQUIRE(isfinite(p->decay) && p->decay >= 0.f && p->decay < 1.f, MISEG_E_BADARG, "weight_average: decay %g must be finite and in [0, 1)", (double)p->decay);
+  MISEG_REQUIRE(p->every >= 1, MISEG_E_BADARG, "weight_average: every %d must be >= 1", p->every);
+  MISEG_REQUIRE(p->start >= 0, MISEG_E_BADARG, "weight_average: start %d must be >= 0", p->start);
+  MISEG_REQUIRE((((uintptr_t)p->avg) & 15) == 0 && (((uintptr_t)p->record) & 3) == 0, MISEG_E_BADARG,
+                "weight_average: avg must be 16-byte aligned (record: 4-byte)");
+  weight_average_tick_kernel<<<1, 1, 0, s>>>(p->record, p->clip_record, p->mode, p->decay, p->warmup ? 1 : 0, p->start, p->every);
+  MISEG_LAUNCH_CHECK("weight_average_tick");
+  weight_average_kernel<<<p->total_blocks, 256, 0, s>>>(p->descs_dev, p->ndesc, p->avg, p->record, p->clip_record);
+  MISEG_LAUNCH_CHECK("weight_average");
+  return MISEG_OK;
+}
+
+extern "C" int miseg_weight_swap(const miseg_weight_swap_params* p, miseg_stream_t s_) {
+  hipStream_t s = (hipStream_t)s_;
+  MISEG_REQUIRE(p && p->struct_size == sizeof(miseg_weight_swap_params), MISEG_E_BADARG, "weight_swap: struct_size %u != %zu", p ? p->struct_size : 0u,
+                sizeof(miseg_weight_swap_params));
+  MISEG_REQUIRE(p->descs_dev && p->avg, MISEG_E_BADARG, "weight_swap: null pointer (descs_dev / avg)");
+  MISEG_REQUIRE(p->ndesc > 0 && p->total_blocks > 0, MISEG_E_BADARG, "weight_swap: empty table (ndesc %d, total_blocks %d)", p->ndesc, p->total_blocks);
+  MISEG_REQUIRE((((uintptr_t)p->avg) & 15) == 0, MISEG_E_BADARG, "weight_swap: avg must be 16-byte aligned");
+  weight_swap_kernel<<<p->total_blocks, 256, 0, s>>>(p->descs_dev, p->ndesc, p->avg, p->params_version);
+  MISEG_LAUNCH_CHECK("weight_swap");
   return MISEG_OK;
 }
 

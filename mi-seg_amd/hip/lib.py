@@ -211,6 +211,15 @@ GradNorm = _struct("GradNorm", cname="miseg_grad_norm_params", fields=[
 GradFold = _struct("GradFold", cname="miseg_grad_fold_params", fields=[
     ("struct_size", C.c_uint32), ("descs_dev", vp), ("ndesc", i32), ("total_blocks", i32), ("grad", vp), ("acc", vp), ("ops", vp), ("arena_elems", i64),
     ("scale", f32)])
+WeightAverageRecord = _struct("WeightAverageRecord", cname="miseg_weight_average_record", fields=[
+    ("apply", C.c_int32), ("first", C.c_int32), ("coef", f32), ("calls", C.c_uint32), ("n_averaged", C.c_uint32), ("reserved", C.c_uint32 * 3)])
+WeightAverage = _struct("WeightAverage", cname="miseg_weight_average_params", fields=[
+    ("struct_size", C.c_uint32), ("mode", i32), ("descs_dev", vp), ("ndesc", i32), ("total_blocks", i32), ("avg", vp), ("record", vp), ("clip_record", vp),
+    ("decay", f32), ("warmup", i32), ("start", i32), ("every", i32)])
+WeightSwap = _struct("WeightSwap", cname="miseg_weight_swap_params", fields=[
+    ("struct_size", C.c_uint32), ("descs_dev", vp), ("ndesc", i32), ("total_blocks", i32), ("avg", vp), ("params_version", vp)])
+AVG_EMA, AVG_MEAN = 0, 1                                               # MISEG_AVG_*
+AVG_MODES = {"ema": AVG_EMA, "swa": AVG_MEAN}
 FOLD_USED, FOLD_EARLIER, FOLD_CLOSE = 1, 2, 4                          # bits of miseg_grad_fold's per-parameter op code (u, a, F)
 CLIP_NONE, CLIP_NORM, CLIP_VALUE = 0, 1, 2                             # MISEG_CLIP_*
 CLIP_MODES = {"norm": CLIP_NORM, "value": CLIP_VALUE}
@@ -379,6 +388,8 @@ PROTOS = {
     "miseg_grad_norm_workspace_bytes": (C.c_size_t, [i32, i32]),
     "miseg_grad_norm": (i32, [C.POINTER(GradNorm), vp]),
     "miseg_grad_fold": (i32, [C.POINTER(GradFold), vp]),
+    "miseg_weight_average": (i32, [C.POINTER(WeightAverage), vp]),
+    "miseg_weight_swap": (i32, [C.POINTER(WeightSwap), vp]),
     "miseg_opt_step_clipped": (i32, [C.POINTER(OptStep), vp, i32, f32, vp]),
     "miseg_opt_step_pack_conv3_clipped": (i32, [C.POINTER(OptStep), vp, vp, i32, i32, i32, vp, vp, i32, f32, vp]),
     "miseg_stitch_windows": (i32, [C.POINTER(Stitch), vp]),

@@ -119,7 +119,14 @@ class LitMonai(_Base):
         arena = next((getattr(p, "_miseg_arena", None) for p in self.model.parameters()), None)
         if arena is not None:              # validation between optimiser steps: the arena's weight copies must be current
             arena.refresh_weights()
-        logits = self.model_inferer(image, modalities=modality)
+        # --weight_averaging: the metrics are those of the averaged weights (what is evaluated and shipped) once the average exists, unless
+        # --no_validate_averaged; applied() swaps them in with their casts and conv packs and puts the training weights back bit for bit
+        averager = self.__dict__.get("weight_averager")
+        if averager is not None and self.__dict__.get("validate_averaged", True) and averager.n_averaged > 0:
+            with averager.applied():
+                logits = self.model_inferer(image, modalities=modality)
+        else:
+            logits = self.model_inferer(image, modalities=modality)
         if self.infer_cpu:
             label = label.cpu()
         loss = self.criterion(logits, label.to(logits.device))
@@ -151,6 +158,20 @@ class LitMonai(_Base):
                               gradient_clip_val=d.get("gradient_clip_val"), gradient_clip_algorithm=d.get("gradient_clip_algorithm") or "norm",
                               skip_nonfinite=bool(d.get("skip_nonfinite_steps")), track_grad_norm=d.get("track_grad_norm", -1))
 
+    def configure_weight_averager(self, optimizer):
+        """the device-side average of the weights (training/optim.py::WeightAverager) that --weight_averaging {ema,swa} and its options ask for
+        (they arrive as attributes through **kwargs), kept as `self.weight_averager`; None - and nothing changes - when it is off or absent"""
+        from ..training.optim import WeightAverager
+        d = self.__dict__
+        mode = d.get("weight_averaging") or "none"
+        if mode == "none":
+            self.weight_averager = None
+            return None
+        self.validate_averaged = bool(d.get("validate_averaged", not d.get("no_validate_averaged", False)))
+        self.weight_averager = WeightAverager(optimizer, mode=mode, decay=d.get("ema_decay", 0.999), warmup=bool(d.get("ema_warmup", False)),
+                                              start_step=d.get("weight_averaging_start", 0), every=d.get("weight_averaging_every", 1))
+        return self.weight_averager
+
     @property
     def accumulation_steps(self):
         """micro-batches per optimisation step, from the --accumulate_grad_batches / --iters_to_accumulate that arrived through **kwargs"""
@@ -159,9 +180,14 @@ class LitMonai(_Base):
 
     def configure_train_step(self, arena, optimizer, batch_shape, label_shape):
         """the whole training step (forward, loss, backward, the fused optimiser of configure_fused_optimizer) as replayed hipGraphs
-        (runtime/graph.py::GraphedTrainStep), with this module's gradient accumulation: call it once per micro-batch"""
+        (runtime/graph.py::GraphedTrainStep), with this module's gradient accumulation: call it once per micro-batch - and with the
+        weight averaging the command line asks for (configure_weight_averager) recorded behind the optimiser"""
         from ..runtime.graph import GraphedTrainStep
-        return GraphedTrainStep(self.model, self.criterion, optimizer, batch_shape, label_shape, arena, accumulate_grad_batches=self.accumulation_steps)
+        averager = self.__dict__.get("weight_averager")
+        if averager is None or averager.opt is not optimizer:
+            averager = self.configure_weight_averager(optimizer)
+        return GraphedTrainStep(self.model, self.criterion, optimizer, batch_shape, label_shape, arena, accumulate_grad_batches=self.accumulation_steps,
+                                weight_averager=averager)
 
     def configure_optimizers(self):
         if self.optim_name == "adam":

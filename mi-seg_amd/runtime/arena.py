@@ -10,6 +10,7 @@ when the device-side parameter version moved since they last ran.  It moves when
     `refresh_weights()`, `GraphedStep` / `GraphedForward` / `GraphedTrainStep` before every replay, notices both and bumps it;
   * the caller says so: `arena.invalidate()` - REQUIRED after any other write: in-place ops on the `p.data` / `p.detach()` alias (it has a
     version counter of its own: an EMA swap-in or a weight clamp written that way is invisible), raw-pointer writes of custom kernels.
+    (training/optim.py::WeightAverager.swap() needs no such call: miseg_weight_swap bumps the device-side version itself, like the optimiser.)
 
 Without an arena the autograd Functions in hip/functional.py allocate and return each gradient (torch semantics,
 ``grad is None`` for parameters that were not used); with one they add into ``p._miseg_grad`` and return None, and

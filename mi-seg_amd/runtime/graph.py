@@ -381,11 +381,19 @@ class GraphedTrainStep:
     accumulate_grad_batches = k > 1: a call is one MICRO-batch and every k-th call (or one with last=True) an optimisation
     step on the mean gradient of its window.  Two graphs per modality set then: "fold" = forward + backward + miseg_grad_fold, and
     "fold_step" = the same with the closing fold and the optimiser behind it (training/optim.py::GradAccumulator).  k == 1 captures and
-    replays exactly what it always did."""
+    replays exactly what it always did.
 
-    def __init__(self, model, criterion, optimizer, batch_shape, label_shape, arena, label_dtype=torch.int32, warmup=2, accumulate_grad_batches=1):
+    weight_averager (training/optim.py::WeightAverager, DESIGN.md 7.14): its update - two launches - is recorded directly behind the
+    optimiser's, so the average of the weights moves inside the same replay (with accumulation: in the "fold_step" graph only; a step the
+    non-finite guard skipped is not averaged).  None: the class captures and replays exactly what it does without the argument."""
+
+    def __init__(self, model, criterion, optimizer, batch_shape, label_shape, arena, label_dtype=torch.int32, warmup=2, accumulate_grad_batches=1,
+                 weight_averager=None):
         if arena is None or optimizer.arena is not arena:
             raise ValueError("GraphedTrainStep needs the model's ParamArena and an ArenaOptimizer built over it")
+        if weight_averager is not None and weight_averager.opt is not optimizer:
+            raise ValueError("the WeightAverager must be built over this step's ArenaOptimizer")
+        self.averager = weight_averager
         from ..training.optim import GradAccumulator
         acc = GradAccumulator(optimizer, accumulate_grad_batches)
         self.acc = acc if acc.active else None
@@ -433,6 +441,8 @@ class GraphedTrainStep:
             self.acc.fold()                        # (its op codes are static too: GradAccumulator.plan() uploads them before every replay)
         if optimise:
             self.opt.step(update_flags=False)      # the flags of this graph are static: copied to the device before every replay
+            if self.averager is not None:
+                self.averager.update()
         return loss.detach()
 
     def _capture(self, host, optimise=True):
@@ -449,6 +459,8 @@ class GraphedTrainStep:
         if self.early_optimizer:      # which parameters the warm-up steps wrote inline (none: the one-launch optimiser step)
             self.opt.split_early(getattr(self.arena, "inline_final_params", []))
         self.opt.prepare()            # device tables of the fused conv-weight launch: uploaded here, not under capture
+        if self.averager is not None:
+            self.averager.prepare()
         if fold:
             self.acc.prepare()
         for p in self.arena.params:

@@ -389,3 +389,161 @@ class GradAccumulator:
         if self._seen is not None:
             self._seen = [False] * len(self._seen)
         self._count = 0
+
+
+def averaging_options(mode="ema", decay=0.999, warmup=False, start_step=0, every=1):
+    """(MISEG_AVG_* mode, decay, warm-up on, start, every) of WeightAverager's arguments; ValueError for what miseg_weight_average would refuse"""
+    if mode not in L.AVG_MODES:
+        raise ValueError("weight averaging mode {!r}: 'ema' or 'swa'".format(mode))
+    try:
+        d = float(decay)
+    except (TypeError, ValueError):
+        raise ValueError("decay {!r} must be a number in [0, 1)".format(decay))
+    if not (0.0 <= d < 1.0) or not (0.0 <= float(torch.tensor(d, dtype=torch.float32)) < 1.0):          # (what the kernel sees is the float32 of it)
+        raise ValueError("decay {!r} must be finite and in [0, 1)".format(decay))
+    for name, v, low in (("start_step", start_step, 0), ("every", every, 1)):
+        if isinstance(v, bool) or int(v) != v or int(v) < low or int(v) >= 2 ** 31:
+            raise ValueError("{} {!r} must be an integer >= {}".format(name, v, low))
+    return L.AVG_MODES[mode], d, bool(warmup), int(start_step), int(every)
+
+
+class WeightAverager:
+    """An average of the weights over the optimisation steps, kept on the device beside the arena:
+
+      mode="ema"   avg += (1 - decay) (w - avg) after every `every`-th step from step `start_step` on - the exponential moving average that
+                   nnU-Net-style and MONAI bundles evaluate and ship; warmup=True uses min(decay, (1 + n) / (10 + n)) for the n-th update (the
+                   timm / TF warm-up), without which the average stays biased towards the initial weights for about 1 / (1 - decay) steps
+      mode="swa"   the running mean of the weights seen: torch.optim.swa_utils.AveragedModel / Lightning's StochasticWeightAveraging
+
+    `avg` is a flat fp32 buffer laid out like the gradient arena; the first update copies the weights into it.  update() is two launches
+    (miseg_weight_average) and nothing else, so it sits inside a captured step (GraphedTrainStep(weight_averager=)); with gradient clipping or the
+    non-finite guard on it reads the optimiser's clip record on the device, and a skipped step is not averaged.  ALL trainable parameters are
+    averaged whatever their "used" flags, like AveragedModel: a parameter without a gradient simply did not move.
+
+        avg = WeightAverager(opt, "ema", decay=0.999); avg.prepare()
+        ... opt.step(); avg.update() ...
+        with avg.applied():            # the model computes on the averaged weights (conv packs and bf16 copies follow)
+            validate(model)
+        torch.save(avg.averaged_state_dict(model), path)
+
+    Under data parallelism nothing is exchanged: the optimiser leaves the same weights on every rank, so every rank forms the same average
+    from the same bytes."""
+
+    def __init__(self, optimizer, mode="ema", decay=0.999, warmup=False, start_step=0, every=1):
+        self._mode, self.decay, self.warmup, self.start_step, self.every = averaging_options(mode, decay, warmup, start_step, every)
+        self.mode = mode
+        self.opt = optimizer
+        self.avg = self._rec = None
+        self._swapped = False
+
+    @property
+    def arena(self):
+        return self.opt.arena
+
+    def prepare(self):
+        """allocate `avg` and the zeroed record (miseg_weight_average_record: its counters run on) - ONCE: a captured hipGraph holds their
+        addresses; call before capturing update()"""
+        if self.avg is None:
+            flat = self.arena.flat
+            if flat.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("WeightAverager.prepare() must run before update() is captured (it allocates the average and its record)")
+            self.avg = torch.empty_like(flat)          # never read before the first applying update writes it
+            self._rec = torch.zeros(C.sizeof(L.WeightAverageRecord) // 4, dtype=torch.int32, device=flat.device)
+
+    def update(self):
+        """enqueue miseg_weight_average behind the optimiser step just issued: the tick and the streaming launch, nothing else (capturable)"""
+        if self.avg is None:
+            self.prepare()          # (raises under capture)
+        if self._swapped:
+            raise RuntimeError("WeightAverager.update() inside applied(): the parameters hold the average")
+        opt = self.opt
+        clip = opt._clip_buffers().data_ptr() if opt.clipping else None          # the guard's `skip` lives there: a skipped step is not averaged
+        p = L.WeightAverage(C.sizeof(L.WeightAverage), self._mode, opt._table.data_ptr(), len(opt.arena.params), opt._blocks, self.avg.data_ptr(),
+                            self._rec.data_ptr(), clip, self.decay, int(self.warmup), self.start_step, self.every)
+        ops._call("miseg_weight_average", p)
+
+    def stats(self):
+        """the record read back once (one device-to-host copy): calls, n_averaged, and apply / first / coef of the last call"""
+        if self._rec is None:
+            return {"calls": 0, "n_averaged": 0, "apply": 0, "first": 0, "coef": 0.0}
+        r = self._rec.cpu()
+        return {"calls": int(r[3]) & 0xFFFFFFFF, "n_averaged": int(r[4]) & 0xFFFFFFFF, "apply": int(r[0]), "first": int(r[1]),
+                "coef": float(r[2:3].view(torch.float32)[0])}
+
+    @property
+    def n_averaged(self):
+        """how many updates the average holds (one device-to-host read)"""
+        return self.stats()["n_averaged"]
+
+    def swap(self):
+        """exchange the parameters and the average in ONE launch (miseg_weight_swap); the launch bumps the arena's device-side parameter
+        version, so the next refresh re-casts and re-packs every weight.  A second call restores every bit."""
+        if self.avg is None:
+            raise RuntimeError("WeightAverager.swap() before prepare(): there is no average")
+        opt, a = self.opt, self.arena
+        if [p.data_ptr() for p in a.params] != opt._ptrs:
+            raise RuntimeError("a parameter was re-allocated after the optimiser was built (e.g. model.to(...)): rebuild the ArenaOptimizer")
+        p = L.WeightSwap(C.sizeof(L.WeightSwap), opt._table.data_ptr(), len(a.params), opt._blocks, self.avg.data_ptr(), a.params_version_ptr())
+        ops._call("miseg_weight_swap", p)
+        a.epoch += 1
+        self._swapped = not self._swapped
+
+    def applied(self):
+        """context manager: inside it the model's parameters ARE the averaged weights (swap(), then arena.refresh_weights(): bf16 copies and
+        conv packs follow); on exit the training weights are back with their exact bits.  Raises while nothing has been averaged."""
+        avg = self
+
+        class _Applied:
+            def __enter__(self_):
+                if avg.n_averaged == 0:
+                    raise RuntimeError("WeightAverager.applied(): nothing has been averaged yet (n_averaged == 0)")
+                avg.swap()
+                avg.arena.refresh_weights()
+                return avg
+
+            def __exit__(self_, *exc):
+                avg.swap()
+                avg.arena.refresh_weights()
+                return False
+        return _Applied()
+
+    def _averaged_views(self):
+        if self._swapped:          # inside applied() the average sits in the parameters (and the training weights in `avg`)
+            return {id(p): p.detach() for p in self.arena.params}
+        return {id(p): self.avg[o:o + p.numel()].view(p.shape) for p, o in zip(self.arena.params, self.arena._offs)}
+
+    def averaged_state_dict(self, model):
+        """model.state_dict() - its keys, shapes and order - with every trainable arena parameter replaced by (a copy of) its averaged value;
+        frozen parameters and buffers pass through as they are.  A published-layout checkpoint loader takes it strictly."""
+        if self.n_averaged == 0:
+            raise RuntimeError("WeightAverager.averaged_state_dict(): nothing has been averaged yet (n_averaged == 0)")
+        views = self._averaged_views()
+        out = type(model.state_dict())()
+        for k, v in model.state_dict(keep_vars=True).items():
+            a = views.get(id(v))
+            out[k] = a.clone() if a is not None else v.detach()
+        return out
+
+    def state_dict(self):
+        st = self.stats()
+        return {"mode": self.mode, "decay": self.decay, "warmup": self.warmup, "start_step": self.start_step, "every": self.every,
+                "avg": None if self.avg is None else self.avg.clone(), "calls": st["calls"], "n_averaged": st["n_averaged"], "coef": st["coef"],
+                "numel": self.arena.flat.numel()}
+
+    def load_state_dict(self, sd):
+        """continue the average of a checkpoint: `avg`, the counters and the options (which replace this object's); a mode or a size that does
+        not match raises"""
+        if sd["mode"] != self.mode:
+            raise ValueError("weight averager state is {!r}, this one is {!r}".format(sd["mode"], self.mode))
+        if sd["numel"] != self.arena.flat.numel() or (sd["avg"] is not None and sd["avg"].numel() != self.arena.flat.numel()):
+            raise ValueError("weight averager state does not match this model (arena of {} elements, state of {})".format(self.arena.flat.numel(), sd["numel"]))
+        self._mode, self.decay, self.warmup, self.start_step, self.every = averaging_options(sd["mode"], sd["decay"], sd["warmup"], sd["start_step"], sd["every"])
+        self.prepare()
+        if sd["avg"] is not None:
+            self.avg.copy_(sd["avg"])
+        rec = torch.zeros(self._rec.numel(), dtype=torch.int32)
+        rec[2:3].view(torch.float32)[0] = float(sd.get("coef", 0.0))
+        for i, key in ((3, "calls"), (4, "n_averaged")):
+            v = int(sd[key])
+            rec[i] = v - (1 << 32) if v >= (1 << 31) else v
+        self._rec.copy_(rec)

@@ -154,10 +154,12 @@ def predict(model, datalist, args):
 def build_parser():
     """the reference's command line (predict_whs.py:117-127): the model options plus its own, with its defaults (the model options carry
     --infer_mode / --infer_sigma_scale / --infer_padding_mode, the window blend of predict_volume, and --infer_tta_flips / --ensemble_mode;
-    --ensemble_checkpoints names the further members of a model ensemble)"""
+    --ensemble_checkpoints names the further members of a model ensemble; --use_averaged_weights loads the averaged weights of a checkpoint
+    that data/checkpoint.py::export_state wrote with a weight averager)"""
     parser = add_model_argparse_args(ArgumentParser())
     parser.add_argument("--checkpoint", default="", type=str, help="Checkpoint")
     parser.add_argument("--ensemble_checkpoints", default=[], type=str, nargs="*", help="further checkpoints of the same architecture, ensembled with --checkpoint (--ensemble_mode)")
+    parser.add_argument("--use_averaged_weights", action="store_true", help="predict with the checkpoints' averaged weights (EMA / SWA: \"averaged_state_dict\")")
     parser.add_argument("--sample", default="", type=str, help="accepted for compatibility, unused")
     parser.add_argument("--space_x", default=1.0, type=float, help="spacing in x direction")
     parser.add_argument("--space_y", default=1.0, type=float, help="spacing in y direction")
@@ -188,7 +190,7 @@ def main(argv=None):
     models = []
     for checkpoint in [args.checkpoint] + list(args.ensemble_checkpoints or []):
         model = model_from_argparse_args(args)
-        load_model_state(model, checkpoint)
+        load_model_state(model, checkpoint, averaged=args.use_averaged_weights)
         models.append(model.to(args.device).eval())
     datalist = load_decathlon_datalist_with_modality(os.path.join(args.data_dir, args.json_list), True, "test", base_dir=args.data_dir)
     return predict(models[0] if len(models) == 1 else models, datalist, args)

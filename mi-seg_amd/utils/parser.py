@@ -112,6 +112,14 @@ TRAINER_ARGS = {
         ("--track_grad_norm", dict(default=-1, type=int, choices=(-1, 2), help="2: compute the gradients' L2 norm every step for logging; -1: off")),
         ("--skip_nonfinite_steps", dict(action=_T, help="an optimisation step whose gradient norm is inf or NaN changes nothing")),
         ("--accumulate_grad_batches", dict(default=1, type=_positive_int, help="micro-batches per optimisation step: the step runs on their mean gradient")),
+        # an average of the weights over the optimisation steps, kept on the device (training/optim.py::WeightAverager): Lightning's
+        # StochasticWeightAveraging ("swa") and the EMA of the weights that nnU-Net-style and MONAI bundles evaluate and ship; off by default
+        ("--weight_averaging", dict(default="none", type=str, choices=("none", "ema", "swa"), help="keep an average of the weights: ema | swa (default: none)")),
+        ("--ema_decay", dict(default=0.999, type=float, help="ema: avg += (1 - decay) (w - avg) per averaged step; in [0, 1)")),
+        ("--ema_warmup", dict(action=_T, help="ema: the n-th update uses min(decay, (1 + n) / (10 + n))")),
+        ("--weight_averaging_start", dict(default=0, type=int, help="the first optimisation step (counted from 0) that is averaged")),
+        ("--weight_averaging_every", dict(default=1, type=_positive_int, help="average every this many optimisation steps")),
+        ("--no_validate_averaged", dict(action=_T, help="validate on the training weights although an average is kept")),
     ],
 }
 
