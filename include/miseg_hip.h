@@ -1231,6 +1231,47 @@ typedef struct {
 size_t miseg_label_export_workspace_bytes(int box_nd, int box_nh, int box_nw);
 int miseg_label_export(const miseg_label_export_params* p, miseg_stream_t stream);
 
+/* The soft prediction export: class scores are resampled to the file's grid BEFORE the argmax (nnU-Net's resample-the-softmax rule, MONAI's
+ * Invertd(nearest_interp=False) + AsDiscreted(argmax=True)), and the resampled scores can be written beside the labels (DESIGN.md section
+ * 7.15).  The reference's own way back (predict_whs.py:92-114) is miseg_label_export above; this call replaces its nearest gather by a
+ * trilinear blend.  For each output axis a of X, Y, Z, three device tables of the file side's length give the two taps lo[a][i] <= hi[a][i]
+ * <= lo[a][i] + 1 along logits axis axis[a] (0 = D, 1 = H, 2 = W) and the weight t[a][i] of the hi tap.  The host builds them (flips, pad
+ * crop and the centre-aligned rule of miseg_resample3d folded in); the kernel computes no coordinate of its own.  lo_host / hi_host are the
+ * host's copies of lo / hi: every limit below, the table contents included, is checked on them before any launch (the kernel still clamps the
+ * device values into the box, so every gathered address lies inside the scores whatever the device tables hold).
+ *   Arithmetic, every operation rounded to fp32 on its own (no FMA contraction), so that a numpy restatement gives the same bits:
+ *   1. softmax != 0: every voxel of the box first becomes e_c = expf(x_c - max_c x), p_c = e_c / sum_c e_c, the maximum by a strict `>` scan
+ *      from channel 0 and the sum taken in channel order; one pass into the workspace.
+ *   2. per channel the 8 taps (lo | hi) of the three logits axes are blended along W first, then H, then D:
+ *      lerp(a, b, t) = t == 0 ? a : fl(fl(a * fl(1 - t)) + fl(b * t)).  Where t == 0 the hi tap is not used, so an inf or NaN there does not
+ *      leak in; with all three t zero the call is the nearest gather, bit for bit.
+ *   3. the first-maximum argmax of the blended values under miseg_label_export's strict `>` rule (a NaN in channel 0 gives class 0, a NaN in
+ *      a later channel never wins), through lut, truncated to out_bytes.
+ * Outputs, either may be NULL but not both: out, labels [nz][ny][nx] of out_bytes = 1, 2 or 4; prob, the blended scores [C][nz][ny][nx] (the
+ * Fortran order of an [X, Y, Z, C] NIfTI) of prob_bytes = 4 (fp32) or 1: q = min(255, (int)floorf(p * 255.f + 0.5f)), a NaN gives 0.  The
+ * 1-byte form needs softmax != 0 or unit_range != 0 (the caller declares the scores to lie in [0, 1]).
+ *   One workgroup blends a 64 (X) x 64 output tile channel after channel from an LDS image of the source voxels under the tile (read with the
+ * lanes along logits W whichever output axis maps to it, shared by the neighbouring outputs of an upsampling); a tile whose source span does
+ * not fit the image reads its taps from memory.  Stores are whole lines along X.  C 1..64, every side 1..65535, the box below 2^31 voxels.
+ * The call only enqueues, allocates nothing and reads nothing back: it can be captured into a graph. */
+typedef struct {
+  uint32_t struct_size;
+  const float* scores;             /* fp32 [C][D][H][W] */
+  int C, D, H, W;
+  int box_d0, box_h0, box_w0, box_nd, box_nh, box_nw;   /* the box of the scores the tables index */
+  int nx, ny, nz;
+  int axis_x, axis_y, axis_z;      /* logits axis indexed by output axis X / Y / Z: a permutation of 0, 1, 2 */
+  const int32_t* lo[3]; const int32_t* hi[3]; const float* t[3];   /* device [nx] / [ny] / [nz], per output axis X, Y, Z */
+  const int32_t* lo_host[3]; const int32_t* hi_host[3];            /* host copies of lo / hi, read during the call only */
+  const int32_t* lut;              /* device int32 [C]; may be NULL when out is */
+  int softmax, unit_range;
+  void* workspace;                 /* miseg_soft_export_workspace_bytes(C, box_nd, box_nh, box_nw, softmax) bytes, uninitialised; NULL when 0 */
+  void* out; int out_bytes;
+  void* prob; int prob_bytes;
+} miseg_soft_export_params;
+size_t miseg_soft_export_workspace_bytes(int C, int box_nd, int box_nh, int box_nw, int softmax);
+int miseg_soft_export(const miseg_soft_export_params* p, miseg_stream_t stream);
+
 /* Keep-largest-connected-component post-processing (MONAI 1.1.0 transforms/post/array.py::KeepLargestConnectedComponent with
  * num_components = 1, restated; parity unpinned - DESIGN.md section 7.7).  The class map is `cls` (cls_bytes 1: uint8, 4: int32), or the
  * first-maximum argmax of fp32 `logits` under miseg_label_export's strict `>` rule; exactly one of the two.  `applied`: bit c set = class c is

@@ -65,9 +65,10 @@ def read_nifti(path):
     return np.ascontiguousarray(arr.astype(dt.newbyteorder("=")) if arr.dtype.byteorder not in ("=", "|") else arr), A
 
 
-def write_nifti(path, array, affine=None, compresslevel=9, mtime=None):
+def write_nifti(path, array, affine=None, compresslevel=9, mtime=None, scl_slope=1.0, scl_inter=0.0):
     """single-file NIfTI-1 with an sform (used by tests and by the prediction export).  A .gz path is compressed at `compresslevel`; `mtime`
-    is the time stamp of the gzip header (None: now; 0 makes the file's bytes a function of its content alone)."""
+    is the time stamp of the gzip header (None: now; 0 makes the file's bytes a function of its content alone).  scl_slope / scl_inter: the
+    header's value scaling (a reader returns stored * slope + inter; the uint8 probability file carries 1 / 255)."""
     array = np.asarray(array)
     if array.dtype.name not in CODES:
         raise ValueError(f"dtype {array.dtype} has no NIfTI code")
@@ -80,7 +81,7 @@ def write_nifti(path, array, affine=None, compresslevel=9, mtime=None):
     struct.pack_into("<h", hdr, 72, array.dtype.itemsize * 8)
     vox = np.sqrt((affine[:3, :3] ** 2).sum(0))
     struct.pack_into("<8f", hdr, 76, 1.0, *[float(v) for v in vox], 0, 0, 0, 0)
-    struct.pack_into("<3f", hdr, 108, 352.0, 1.0, 0.0)
+    struct.pack_into("<3f", hdr, 108, 352.0, float(scl_slope), float(scl_inter))
     struct.pack_into("<2h", hdr, 252, 0, 1)
     struct.pack_into("<12f", hdr, 280, *[float(v) for v in affine[:3].reshape(-1)])
     hdr[344:348] = b"n+1\0"

@@ -110,6 +110,36 @@ class PredictionGeometry:
             tables[a], axes[a] = t.to(torch.int32), k
         return tables, axes
 
+    def lerp_tables(self, mode="trilinear"):
+        """(tables, axes) for hip/ops.py::soft_export: for each file axis a = X, Y, Z the triple (lo, hi, t) - the two padded-grid taps
+        (int32) along the logits axis axes[a] and the fp32 weight of the hi tap, one per file voxel along a.  Built in numpy fp32 on the host.
+        "trilinear": the centre-aligned rule of miseg_resample3d from the RAS size n back to the resampled size m, rounded step by step:
+        f = clip((r + 0.5) * (m / n) - 0.5, 0, m - 1) with r the RAS index of the file voxel (n - 1 - i under a flip), lo = floor(f),
+        hi = min(lo + 1, m - 1), t = f - lo; m == n gives lo = r and t = 0 exactly.  "nearest": lo = hi = the table of index_tables()
+        (nearest_index) and t = 0, with which soft_export is the nearest gather."""
+        if mode not in ("trilinear", "nearest"):
+            raise ValueError(f"lerp_tables: mode {mode!r} is not one of ('trilinear', 'nearest')")
+        tables, axes = [None] * 3, [None] * 3
+        for k, a in enumerate(self.order):
+            m, n = self.resampled_shape[k], self.ras_shape[k]
+            i = np.arange(n, dtype=np.int64)
+            r = n - 1 - i if self.flips[k] else i
+            if mode == "nearest":
+                lo = hi = nearest_index(m, n)[r]
+                t = np.zeros(n, dtype=np.float32)
+            else:
+                scale = np.float32(m) / np.float32(n)
+                f = (r.astype(np.float32) + np.float32(0.5)) * scale - np.float32(0.5)
+                f = np.clip(f, np.float32(0), np.float32(m - 1))
+                lo = np.floor(f).astype(np.int64)
+                hi = np.minimum(lo + 1, m - 1)
+                t = f - lo.astype(np.float32)
+            off = self.pad_before[k]
+            tables[a] = (torch.from_numpy((lo + off).astype(np.int32)), torch.from_numpy((hi + off).astype(np.int32)),
+                         torch.from_numpy(np.ascontiguousarray(t, dtype=np.float32)))
+            axes[a] = k
+        return tables, axes
+
 
 def load_image_for_prediction(path, pixdim=(1.0, 1.0, 1.0), roi=(96, 96, 96), device="cuda"):
     """the reference's prediction transforms (predict_whs.py:46-63: Orientationd RAS, Spacingd bilinear, ScaleIntensityd, SpatialPadd) on one

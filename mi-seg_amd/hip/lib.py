@@ -246,6 +246,11 @@ LabelExport = _struct("LabelExport", cname="miseg_label_export_params", fields=[
     ("box_nd", i32), ("box_nh", i32), ("box_nw", i32), ("nx", i32), ("ny", i32), ("nz", i32), ("axis_x", i32), ("axis_y", i32), ("axis_z", i32),
     ("table_x", vp), ("table_y", vp), ("table_z", vp), ("lut", vp), ("workspace", vp), ("out", vp), ("out_bytes", i32),
     ("cls", vp), ("cls_bytes", i32)])
+SoftExport = _struct("SoftExport", cname="miseg_soft_export_params", fields=[
+    ("struct_size", u32), ("scores", vp), ("C", i32), ("D", i32), ("H", i32), ("W", i32), ("box_d0", i32), ("box_h0", i32), ("box_w0", i32),
+    ("box_nd", i32), ("box_nh", i32), ("box_nw", i32), ("nx", i32), ("ny", i32), ("nz", i32), ("axis_x", i32), ("axis_y", i32), ("axis_z", i32),
+    ("lo", vp * 3), ("hi", vp * 3), ("t", vp * 3), ("lo_host", vp * 3), ("hi_host", vp * 3), ("lut", vp), ("softmax", i32), ("unit_range", i32),
+    ("workspace", vp), ("out", vp), ("out_bytes", i32), ("prob", vp), ("prob_bytes", i32)])
 KeepLargest = _struct("KeepLargest", cname="miseg_keep_largest_params", fields=[
     ("struct_size", u32), ("logits", vp), ("cls", vp), ("cls_bytes", i32), ("B", i32), ("C", i32), ("D", i32), ("H", i32), ("W", i32),
     ("applied", C.c_uint64), ("independent", i32), ("connectivity", i32), ("workspace", vp), ("out", vp), ("out_bytes", i32), ("stats", vp)])
@@ -398,6 +403,8 @@ PROTOS = {
     "miseg_resample3d": (i32, [C.POINTER(Resample3d), vp]),
     "miseg_label_export_workspace_bytes": (C.c_size_t, [i32, i32, i32]),
     "miseg_label_export": (i32, [C.POINTER(LabelExport), vp]),
+    "miseg_soft_export_workspace_bytes": (C.c_size_t, [i32, i32, i32, i32, i32]),
+    "miseg_soft_export": (i32, [C.POINTER(SoftExport), vp]),
     "miseg_keep_largest_workspace_bytes": (C.c_size_t, [i32, i32, i32, i32]),
     "miseg_keep_largest": (i32, [C.POINTER(KeepLargest), vp]),
     "miseg_fill_holes_workspace_bytes": (C.c_size_t, [i32, i32, i32, i32]),

@@ -1998,6 +1998,105 @@ def _label_export_map(pred, tables, axes, lut, dtype):
     return out
 
 
+_PROB_DTYPES = {torch.float32: 4, torch.uint8: 1}
+
+
+def _lerp(a, b, t):
+    """the export's blend of one level, every operation rounded to fp32 on its own: where t == 0 it is `a` itself (b is not looked at)"""
+    return torch.where(t == 0, a, a * (1 - t) + b * t)
+
+
+def softmax_in_channel_order(x):
+    """softmax over dim 0 as miseg_soft_export states it: the maximum by a strict `>` scan from channel 0, e = exp(x - max), the sum taken
+    in channel order, e / sum"""
+    mx = x[0]
+    for c in range(1, x.shape[0]):
+        mx = torch.where(x[c] > mx, x[c], mx)
+    e = torch.exp(x - mx[None])
+    total = torch.zeros_like(mx)
+    for c in range(x.shape[0]):
+        total = total + e[c]
+    return e / total[None]
+
+
+def quantize_unit(p):
+    """fp32 in [0, 1] -> uint8 as the kernel writes it: min(255, floor(p * 255 + 0.5)), a NaN gives 0"""
+    q = torch.floor(p * 255.0 + 0.5).clamp(0, 255)
+    return torch.where(p == p, q, torch.zeros_like(q)).to(torch.uint8)
+
+
+def soft_export(scores, tables, axes, lut, dtype=torch.uint16, softmax=True, want_labels=True, probabilities=None, unit_range=False):
+    """(labels or None, prob or None): the class scores blended trilinearly onto the file's grid, then the first-maximum argmax through lut
+    (miseg_soft_export).  scores fp32 [(1,) C, D, H, W]; tables[a] = (lo, hi, t) for the output axes a = X, Y, Z: the
+    two taps along scores axis axes[a] (int32, lo <= hi <= lo + 1) and the weight of the hi tap (fp32), as
+    data/preprocess.py::PredictionGeometry.lerp_tables builds them; lut int [C]; dtype uint8 / uint16 / uint32 of the labels [nz, ny, nx].
+    softmax: the scores are logits and their softmax is what is blended.  probabilities: None | torch.float32 | torch.uint8, the element type of
+    the blended scores [C, nz, ny, nx] (an [X, Y, Z, C] NIfTI's Fortran order); uint8 (floor(p * 255 + 0.5)) needs softmax, or unit_range=True:
+    the caller declares the scores to lie in [0, 1].  Device tensors take the kernel; CPU tensors take the same arithmetic in torch fp32,
+    operation by operation."""
+    if scores.dim() == 5 and scores.shape[0] == 1:
+        scores = scores[0]
+    if scores.dim() != 4 or scores.dtype != torch.float32:
+        raise ValueError("soft_export: scores must be float32 [C, D, H, W]")
+    if dtype not in _EXPORT_DTYPES:
+        raise ValueError(f"soft_export: dtype {dtype} (uint8 / uint16 / uint32)")
+    if probabilities is not None and probabilities not in _PROB_DTYPES:
+        raise ValueError(f"soft_export: probabilities {probabilities} (None / float32 / uint8)")
+    if not want_labels and probabilities is None:
+        raise ValueError("soft_export: nothing to return (want_labels=False and probabilities=None)")
+    if probabilities == torch.uint8 and not (softmax or unit_range):
+        raise ValueError("soft_export: uint8 probabilities need scores in [0, 1]: softmax=True, or unit_range=True for scores that already are")
+    if len(tables) != 3 or any(len(t) != 3 for t in tables):
+        raise ValueError("soft_export: tables must be three (lo, hi, t) triples, one per output axis X, Y, Z")
+    Cc, dims, dev = scores.shape[0], scores.shape[1:], scores.device
+    # the checks read the tables on the host, where lerp_tables built them (device tables are copied back once)
+    host = [[torch.as_tensor(v).detach().cpu().contiguous() for v in t] for t in tables]
+    host = [(lo.to(torch.int32), hi.to(torch.int32), t.to(torch.float32)) for lo, hi, t in host]
+    for a, (lo, hi, t) in enumerate(host):
+        if lo.dim() != 1 or lo.numel() == 0 or hi.shape != lo.shape or t.shape != lo.shape:
+            raise ValueError(f"soft_export: table {'XYZ'[a]} must be three non-empty vectors of one length")
+        if bool(((hi < lo) | (hi > lo + 1)).any()):
+            raise ValueError(f"soft_export: table {'XYZ'[a]} has a hi outside [lo, lo + 1]")
+    lut, _, box = _export_tables(Cc, dims, dev, [torch.cat([lo, hi]) for lo, hi, _ in host], axes, lut)
+    axes = [int(a) for a in axes]
+    n = [t[0].numel() for t in host]
+    mask = (1 << (8 * _EXPORT_DTYPES[dtype])) - 1
+    if not scores.is_cuda:
+        x = softmax_in_channel_order(scores) if softmax else scores
+        role = [axes.index(k) for k in range(3)]                  # the output axis that indexes scores axis k
+
+        def taps(k, which):
+            shape = [1, 1, 1, 1]
+            shape[1 + k] = -1
+            return host[role[k]][which].view(shape)
+
+        def at(bd, bh, bw):
+            v = x.index_select(1, host[role[0]][bd].long()).index_select(2, host[role[1]][bh].long())
+            return v.index_select(3, host[role[2]][bw].long())
+
+        tD, tH, tW = taps(0, 2), taps(1, 2), taps(2, 2)
+        c = [[_lerp(at(bd, bh, 0), at(bd, bh, 1), tW) for bh in (0, 1)] for bd in (0, 1)]
+        v = _lerp(_lerp(c[0][0], c[0][1], tH), _lerp(c[1][0], c[1][1], tH), tD)
+        v = v.permute(0, 1 + axes[2], 1 + axes[1], 1 + axes[0]).contiguous()             # [C, nz, ny, nx]
+        labels = (lut & mask)[first_max_argmax(v)].to(dtype).contiguous() if want_labels else None
+        prob = None if probabilities is None else (v if probabilities == torch.float32 else quantize_unit(v))
+        return labels, prob
+    scores = scores.contiguous()
+    devt = [tuple(v.to(dev) for v in t) for t in host]
+    labels = torch.empty(n[2], n[1], n[0], dtype=dtype, device=dev) if want_labels else None
+    prob = torch.empty(Cc, n[2], n[1], n[0], dtype=probabilities, device=dev) if probabilities is not None else None
+    lut32 = (lut & mask).to(torch.int32)             # the kernel truncates lut[c] to the element width
+    nbytes = int(L.load().miseg_soft_export_workspace_bytes(Cc, box[0][1], box[1][1], box[2][1], int(bool(softmax))))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    vp3 = C.c_void_p * 3
+    _call("miseg_soft_export", L.SoftExport(
+        C.sizeof(L.SoftExport), _ptr(scores), Cc, *dims, box[0][0], box[1][0], box[2][0], box[0][1], box[1][1], box[2][1], *n, *axes,
+        vp3(*(_ptr(t[0]) for t in devt)), vp3(*(_ptr(t[1]) for t in devt)), vp3(*(_ptr(t[2]) for t in devt)),
+        vp3(*(t[0].data_ptr() for t in host)), vp3(*(t[1].data_ptr() for t in host)), _ptr(lut32), int(bool(softmax)), int(bool(unit_range)),
+        _ptr(ws), _ptr(labels), _EXPORT_DTYPES[dtype] if want_labels else 0, _ptr(prob), _PROB_DTYPES[probabilities] if prob is not None else 0))
+    return labels, prob
+
+
 def stitch_windows(win, out, starts, roi, count=None, slab=None, weight=None, wsum=None):
     """win fp32 [nd*nh*nw, C, rd, rh, rw] (the windows of the nd depth layers `starts[0]`, all resident), out fp32 [C, D, H, W];
     starts = (list_d, list_h, list_w).  slab = (d_begin, d_count): write only these depths of `out` from the resident layers (which then

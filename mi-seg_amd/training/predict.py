@@ -3,11 +3,14 @@
 of the pad, the spacing and the orientation, the MM-WHS label codes - as one miseg_label_export call on the device, into a uint16 NIfTI
 label map in the image's own grid and affine.  --keep_largest puts MONAI's KeepLargestConnectedComponent between the
 argmax and the way back, on the device (hip/ops.py::keep_largest_component, DESIGN.md section 7.7); --fill_holes puts MONAI's FillHoles
-there too, after the keep-largest filter when both are given (hip/ops.py::fill_holes, DESIGN.md section 7.8)."""
+there too, after the keep-largest filter when both are given (hip/ops.py::fill_holes, DESIGN.md section 7.8).  --invert_mode trilinear
+blends the class scores onto the image grid before the argmax and --save_probabilities writes them beside the label map
+(hip/ops.py::soft_export, DESIGN.md section 7.15); both are off by default."""
 import os
 import time
 from argparse import ArgumentParser
 
+import numpy as np
 import torch
 
 from ..data.checkpoint import load_model_state
@@ -38,17 +41,66 @@ def label_lut(C, mapping=LABEL_MAP):
     return torch.tensor(lut, dtype=torch.int32)
 
 
-def invert_prediction(logits, geometry, lut, dtype=torch.uint16, pred=None):
+INVERT_MODES = ("nearest", "trilinear")
+INVERT_QUANTITIES = ("probabilities", "logits")
+PROBABILITY_DTYPES = {"float32": torch.float32, "uint8": torch.uint8}
+VOTE_UINT8_MESSAGE = ("predict_whs: --probability_dtype uint8 needs values in [0, 1]; --ensemble_mode vote leaves vote counts, which are not "
+                      "normalised: use --probability_dtype float32, or --ensemble_mode mean_prob")
+
+
+def invert_prediction(logits, geometry, lut, dtype=torch.uint16, pred=None, mode="nearest", softmax=True):
     """logits [(1,) C, D, H, W] on the padded, resampled RAS grid -> label map in the file's grid: an [X, Y, Z] view of a C-contiguous [Z, Y, X]
     buffer (the file's Fortran order), lut[first-maximum argmax] per voxel.  Device logits take miseg_label_export, CPU logits the same
     arithmetic in torch (hip/ops.py::label_export).  pred= (logits None): a uint8 / int32 class map [(1,) D, H, W] of len(lut) classes on that
-    grid instead of the logits' argmax."""
+    grid instead of the logits' argmax.  mode "trilinear": the scores - the softmax of the logits, or the values as given with softmax=False -
+    are blended onto the file's grid before the argmax (hip/ops.py::soft_export, DESIGN.md section 7.15); logits only."""
+    if mode not in INVERT_MODES:
+        raise ValueError(f"invert_prediction: mode {mode!r} is not one of {INVERT_MODES}")
     src = logits if pred is None else pred
     shape = tuple(src.shape[-3:])
     if shape != geometry.padded_shape:
         raise ValueError(f"invert_prediction: logits grid {shape} is not the geometry's padded grid {geometry.padded_shape}")
+    if mode == "trilinear":
+        if pred is not None:
+            raise ValueError("invert_prediction: mode 'trilinear' blends scores, a class map has none")
+        tables, axes = geometry.lerp_tables("trilinear")
+        return ops.soft_export(logits, tables, axes, lut, dtype, softmax=softmax)[0].permute(2, 1, 0)
     tables, axes = geometry.index_tables(src.device if src.is_cuda else None)
     return ops.label_export(logits, tables, axes, lut, dtype, pred=pred).permute(2, 1, 0)
+
+
+def score_kind(args):
+    """what the inferer's output holds: "logits" (one member, or the mean of logits), "mean_prob" (probabilities) or "vote" (vote counts)"""
+    members = (1 + len(getattr(args, "ensemble_checkpoints", None) or [])) * len(tta_flip_sets(getattr(args, "infer_tta_flips", None) or ()))
+    mode = getattr(args, "ensemble_mode", "mean_logits")
+    return "logits" if members == 1 or mode == "mean_logits" else mode
+
+
+def export_options(args):
+    """the checked export options of the command line: dict(mode, quantity, save, dtype (torch), kind); the default is the reference's way back
+    (nearest, no probability file).  Refuses uint8 probabilities of vote counts."""
+    opt = dict(mode=getattr(args, "invert_mode", "nearest"), quantity=getattr(args, "invert_quantity", "probabilities"),
+               save=bool(getattr(args, "save_probabilities", False)), kind=score_kind(args))
+    name = getattr(args, "probability_dtype", "float32")
+    if opt["mode"] not in INVERT_MODES or opt["quantity"] not in INVERT_QUANTITIES or name not in PROBABILITY_DTYPES:
+        raise SystemExit(f"predict_whs: --invert_mode {opt['mode']} / --invert_quantity {opt['quantity']} / --probability_dtype {name}")
+    opt["dtype"] = PROBABILITY_DTYPES[name]
+    if opt["save"] and opt["dtype"] == torch.uint8 and opt["kind"] == "vote":
+        raise SystemExit(VOTE_UINT8_MESSAGE)
+    return opt
+
+
+def probability_path(label_path):
+    """<label name minus extension>_prob.nii.gz beside the label map"""
+    for ext in (".nii.gz", ".nii"):
+        if label_path.endswith(ext):
+            return label_path[:-len(ext)] + "_prob.nii.gz"
+    return label_path + "_prob.nii.gz"
+
+
+def _identity_tables(shape_zyx):
+    """tables / axes with which label_export maps a class map [Z, Y, X] on the file's grid onto itself through the lut"""
+    return [torch.arange(n, dtype=torch.int32) for n in reversed(shape_zyx)], (2, 1, 0)
 
 
 def keep_largest_options(args):
@@ -111,8 +163,11 @@ def predict_volume(model, item, args):
     del image
     t2 = _sync(device)
     keep, fill = keep_largest_options(args), fill_holes_options(args)
-    filtered, tk = "", t2
-    if keep is None and fill is None:
+    opt = export_options(args)
+    filtered, tk, prob = "", t2, None
+    if opt["mode"] == "trilinear":
+        label, prob, filtered, tk = _soft_inverse(logits, geom, opt, keep, fill, device, t2)
+    elif keep is None and fill is None:
         label = invert_prediction(logits, geom, label_lut(logits.shape[1]))
     else:
         cls = None
@@ -128,6 +183,10 @@ def predict_volume(model, item, args):
             filtered += f"fill-holes {1e3 * (tk - tf):.2f} ms (voxels filled per class: {filled[0].tolist()}), "
         label = invert_prediction(None, geom, label_lut(logits.shape[1]), pred=cls[0])
         del cls
+    if opt["mode"] == "nearest" and opt["save"]:  # the scores under the nearest gather: the same tables with t = 0
+        tables, axes = geom.lerp_tables("nearest")
+        prob = ops.soft_export(logits, tables, axes, label_lut(logits.shape[1]), softmax=opt["kind"] == "logits", want_labels=False,
+                               probabilities=opt["dtype"], unit_range=opt["kind"] == "mean_prob")[1]
     del logits                                    # the next volume's inference starts without this one's logits
     t3 = _sync(device)
     host = to_host(label)
@@ -136,10 +195,54 @@ def predict_volume(model, item, args):
     path = output_path(item["image"], args.result_dir)
     write_nifti(path, host, geom.affine, compresslevel=COMPRESSLEVEL, mtime=0)
     t5 = time.perf_counter()
+    saved = ""
+    if prob is not None:
+        scores = prob.cpu().numpy().transpose(3, 2, 1, 0)                 # [C, Z, Y, X] buffer -> [X, Y, Z, C] in Fortran order, as it lies
+        del prob
+        write_nifti(probability_path(path), scores, geom.affine, compresslevel=COMPRESSLEVEL, mtime=0,
+                    scl_slope=1.0 / 255.0 if scores.dtype == np.uint8 else 1.0)
+        saved = f", probabilities ({scores.dtype.name}) device-to-host + write {time.perf_counter() - t5:.3f} s"
     print(f"{os.path.basename(path)}: {'x'.join(str(s) for s in host.shape)} read+preprocess {t1 - t0:.3f} s, inference {t2 - t1:.3f} s "
           f"({members} member{'s' if members > 1 else ''}: models {len(models)} x flips {len(flips)}), "
-          f"{filtered}inverse {1e3 * (t3 - tk):.2f} ms, device-to-host {1e3 * (t4 - t3):.2f} ms, write {t5 - t4:.3f} s", flush=True)
+          f"{filtered}inverse ({opt['mode']}) {1e3 * (t3 - tk):.2f} ms, device-to-host {1e3 * (t4 - t3):.2f} ms, write {t5 - t4:.3f} s{saved}", flush=True)
     return path
+
+
+def _soft_inverse(logits, geom, opt, keep, fill, device, t2):
+    """the trilinear way back of predict_volume: (label [X, Y, Z] view, prob [C, Z, Y, X] or None, the filters' part of the timing line, the
+    time the last filter ended).  The blended quantity is the softmax of the logits (--invert_quantity probabilities) or the inferer's values
+    as given (logits, or an ensemble's probabilities / votes).  The post-filters run on the file's grid: soft_export writes a uint8 class-index
+    map [Z, Y, X], the filters take it as pred=, and label_export with identity tables applies the label codes."""
+    Cc = logits.shape[1]
+    lut, ident = label_lut(Cc), torch.arange(Cc, dtype=torch.int32)
+    tables, axes = geom.lerp_tables("trilinear")
+    from_logits, unit = opt["kind"] == "logits", opt["kind"] == "mean_prob"
+    softmax = from_logits and opt["quantity"] == "probabilities"
+    one_pass = opt["save"] and (softmax or not from_logits)       # what is blended for the labels is what the file holds
+    post = keep is not None or fill is not None
+    label, prob = ops.soft_export(logits, tables, axes, ident if post else lut, torch.uint8 if post else torch.uint16, softmax=softmax,
+                                  probabilities=opt["dtype"] if one_pass else None, unit_range=unit)
+    if opt["save"] and not one_pass:                              # labels from blended logits; the file holds the blended softmax
+        prob = ops.soft_export(logits, tables, axes, lut, softmax=True, want_labels=False, probabilities=opt["dtype"])[1]
+    filtered, tk = "", t2
+    if post:
+        tk = _sync(device)
+        filtered = f"soft export {1e3 * (tk - t2):.2f} ms, "
+        cls = label[None]
+        if keep is not None:
+            tf = tk
+            cls, stats = ops.keep_largest_component(pred=cls, num_classes=Cc, stats=True, **keep)
+            tk = _sync(device)
+            removed = (stats[0, :, 0] - stats[0, :, 1]).tolist()
+            filtered += f"keep-largest {1e3 * (tk - tf):.2f} ms (voxels removed per class: {removed}), "
+        if fill is not None:
+            tf = tk
+            cls, filled = ops.fill_holes(pred=cls, num_classes=Cc, stats=True, **fill)
+            tk = _sync(device)
+            filtered += f"fill-holes {1e3 * (tk - tf):.2f} ms (voxels filled per class: {filled[0].tolist()}), "
+        id_tables, id_axes = _identity_tables(tuple(cls.shape[1:]))
+        label = ops.label_export(None, id_tables, id_axes, lut, torch.uint16, pred=cls[0])
+    return label.permute(2, 1, 0), prob, filtered, tk
 
 
 def predict(model, datalist, args):
@@ -175,11 +278,21 @@ def build_parser():
     parser.add_argument("--fill_holes", action="store_true", help="fill the enclosed holes of each class before the export (after --keep_largest)")
     parser.add_argument("--fill_holes_labels", default=None, type=int, nargs="+", help="classes whose holes are filled (default: all foreground)")
     parser.add_argument("--fill_holes_connectivity", default=3, type=int, choices=(1, 2, 3), help="6 / 18 / 26 neighbourhood of a hole")
+    parser.add_argument("--invert_mode", default="nearest", type=str, choices=INVERT_MODES,
+                        help="how the scores go back to the image grid: nearest (argmax first, then a nearest gather) | trilinear (blend the scores, then argmax)")
+    parser.add_argument("--invert_quantity", default="probabilities", type=str, choices=INVERT_QUANTITIES,
+                        help="what --invert_mode trilinear interpolates: the softmax of the logits (nnU-Net's rule) | the logits; an ensemble's probabilities or votes are blended as given")
+    parser.add_argument("--save_probabilities", action="store_true",
+                        help="also write <label name>_prob.nii.gz: the class probabilities on the image grid, [X, Y, Z, C] (either invert mode)")
+    parser.add_argument("--probability_dtype", default="float32", type=str, choices=tuple(PROBABILITY_DTYPES),
+                        help="element type of the probability file; uint8 stores floor(p * 255 + 0.5) with scl_slope 1/255 and is refused for "
+                             "--ensemble_mode vote, whose vote counts are not normalised to [0, 1]")
     return parser
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    export_options(args)
     if args.no_gpu or not torch.cuda.is_available():
         raise SystemExit(NO_GPU_MESSAGE)
     if len(args.feature_size) == 1:
