@@ -1169,6 +1169,49 @@ typedef struct {
 } miseg_augment_affine_params;
 int miseg_augment_affine(const miseg_augment_affine_params* p, miseg_stream_t stream);
 
+/* Separable Gaussian filter on a batch of patches: the smoothing and sharpening end of the augmentation chain (MONAI RandGaussianSmoothd /
+ * RandGaussianSharpend and nnU-Net's GaussianBlurTransform, restated; parity unpinned - DESIGN.md section 7.16; csrc/gaussian.hip).  A new
+ * symbol and new structs: MISEG_ABI_VERSION stays 16.  One call is ONE filter application over n <= MISEG_AUG_MAX_SAMPLES samples of C
+ * channels: src, dst fp32 [n][C][D][H][W], contiguous, distinct and not overlapping; every channel volume is filtered on its own.
+ *   Taps (the host's, MONAI gaussian_1d(sigma, truncated = 4, approx = "erf"), not normalised; data/augment.py::gaussian_taps):
+ *     r = int(max(4 sigma, 0.5) + 0.5),  t = 0.70710678 / |sigma|,  w[k] = max(0.5 (erf(t (k + 0.5)) - erf(t (k - 0.5))), 0) for k = -r..r,
+ *     in float64, rounded once to fp32.  taps[a][k + r] is w[k] of axis a; a = 0, 1, 2 = D, H, W.  r <= MISEG_GAUSS_MAX_RADIUS.
+ *     radius[a] == 0 (sigma == 0) skips axis a: the exact identity, bit for bit - no tap is read.
+ *   The filter: three 1-D passes in the fixed order W, then H, then D; each reads the previous pass's fp32 result with ZEROS outside the
+ *     volume (MONAI filters the cropped patch with zero padding).  Per output element
+ *       acc = 0;  for k = -r..r:  acc = fl(acc + fl(w[k] * v[x + k]))
+ *     in fp32, every product and every sum rounded on its own (no FMA: contraction is off for the whole file).  A tap outside the volume
+ *     contributes exactly 0.  Inputs are finite; what an inf or a NaN gives is unspecified, except for the verbatim copy below.
+ *   sharpen != 0: the epilogue  dst = fl(src + fl(alpha * fl(src - filtered)))  in place of  dst = filtered  (three separate roundings).
+ *     Sharpening x is two calls: b1 = G(sigma1)(x), then G(sigma2) on b1 with the epilogue and alpha - out = b1 + alpha (b1 - G(sigma2)(b1)) -
+ *     and no third elementwise pass.
+ *   A sample whose radii are all 0 and whose sharpen is 0 is copied verbatim (NaN payloads and signed zeros included).
+ *   One workgroup per MISEG_GAUSS_TILE_D x _H x _W output tile of one channel volume: tile + halo staged into LDS a few planes at a time
+ *   (16-byte loads when src is 16-byte aligned and W % 4 == 0, 4-byte loads otherwise), W and H passes in LDS, the H results of all planes
+ *   kept for the D pass, stores with W fastest.  The passes are unrolled for even radii: an odd radius runs as the next even one with a
+ *   zero tap at either end, which adds fl(0 * v) = +-0 to an acc that is never -0 and so changes no bit (v is finite).  The descriptors
+ *   travel in the kernel arguments: one launch, no allocation, no host synchronisation, no atomics; only enqueues, can be captured.
+ * Refused before any launch (MISEG_E_BADARG): a wrong struct_size, a null src / dst / samples_host, src and dst that overlap, n outside
+ * 1..MISEG_AUG_MAX_SAMPLES, C, D, H or W below 1, a radius outside 0..MISEG_GAUSS_MAX_RADIUS, a non-finite tap among the 2 r + 1 of an axis,
+ * a non-finite alpha; MISEG_E_UNSUPPORTED: C above 65535 or more than 2^31 - 1 tiles in a channel volume. */
+#define MISEG_GAUSS_MAX_RADIUS 8
+#define MISEG_GAUSS_TILE_D 8
+#define MISEG_GAUSS_TILE_H 16
+#define MISEG_GAUSS_TILE_W 32
+typedef struct {
+  int32_t radius[3];                               /* D, H, W; 0: the axis is skipped */
+  float taps[3][2 * MISEG_GAUSS_MAX_RADIUS + 1];   /* taps[a][0 .. 2 radius[a]] */
+  float alpha;
+  int32_t sharpen;                                 /* != 0: the sharpen epilogue */
+} miseg_gaussian_filter_sample;
+typedef struct {
+  uint32_t struct_size;
+  const float* src; float* dst;
+  int n, C, D, H, W;
+  const miseg_gaussian_filter_sample* samples_host;
+} miseg_gaussian_filter_params;
+int miseg_gaussian_filter3d(const miseg_gaussian_filter_params* p, miseg_stream_t stream);
+
 /* Dropout / stochastic depth on channels-last rows (the `drop` / `dropout_path_rate` arguments of the reference's Swin stack:
  * networks/blocks/swin_transformer_block.py:90-97,205,247; MONAI Dropout / DropPath semantics): y = x * keep / (1 - p).
  *   rows_per_sample == 0: one Bernoulli(1 - p) draw per ELEMENT (nn.Dropout); > 0: one draw per SAMPLE (DropPath: rows r belong to

@@ -22,7 +22,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function", "-Wno-unused-value",
          "-I", os.path.join(ROOT, "include"), f'-DMISEG_COMPILED_ARCH="{ARCH}"']
-SOURCES = ["common.cpp", "graphsplit.cpp", "norm.hip", "elementwise.hip", "net_end.hip", "gemm.hip", "mlp.hip", "conv3d.hip", "attention.hip", "attention_global.hip", "training.hip", "surface.hip", "components.hip", "ensemble.hip", "augment.hip", "export_soft.hip"]
+SOURCES = ["common.cpp", "graphsplit.cpp", "norm.hip", "elementwise.hip", "net_end.hip", "gemm.hip", "mlp.hip", "conv3d.hip", "attention.hip", "attention_global.hip", "training.hip", "surface.hip", "components.hip", "ensemble.hip", "augment.hip", "gaussian.hip", "export_soft.hip"]
 
 
 def lib_path(prof=False):

@@ -36,6 +36,7 @@ extern "C" size_t miseg_abi_struct_size(const char* name) {
   MISEG_SZ(miseg_head_bwd_params) MISEG_SZ(miseg_im2col3_params) MISEG_SZ(miseg_seg_loss_params) MISEG_SZ(miseg_dice_metric_params) MISEG_SZ(miseg_surface_distance_params) MISEG_SZ(miseg_surface_metrics_params) MISEG_SZ(miseg_surface_dice_params) MISEG_SZ(miseg_opt_desc) MISEG_SZ(miseg_opt_pack_map)
   MISEG_SZ(miseg_opt_step_params) MISEG_SZ(miseg_stitch_params) MISEG_SZ(miseg_aug_sample) MISEG_SZ(miseg_augment_params) MISEG_SZ(miseg_resample3d_params) MISEG_SZ(miseg_label_export_params) MISEG_SZ(miseg_soft_export_params) MISEG_SZ(miseg_keep_largest_params) MISEG_SZ(miseg_fill_holes_params) MISEG_SZ(miseg_dropout_params)
   MISEG_SZ(miseg_affine2_params) MISEG_SZ(miseg_graph_split_info) MISEG_SZ(miseg_norm_ref) MISEG_SZ(miseg_ensemble_params) MISEG_SZ(miseg_aug_affine_sample) MISEG_SZ(miseg_augment_affine_params)
+  MISEG_SZ(miseg_gaussian_filter_sample) MISEG_SZ(miseg_gaussian_filter_params)
   MISEG_SZ(miseg_net_end_launch) MISEG_SZ(miseg_head_bwd_plan_info) MISEG_SZ(miseg_grad_clip_record) MISEG_SZ(miseg_grad_norm_params) MISEG_SZ(miseg_grad_fold_params)
   MISEG_SZ(miseg_weight_average_record) MISEG_SZ(miseg_weight_average_params) MISEG_SZ(miseg_weight_swap_params)
   MISEG_SZ(miseg_conv3_wgrad_form_info) MISEG_SZ(miseg_instnorm_launch) MISEG_SZ(miseg_instnorm_plan_info)

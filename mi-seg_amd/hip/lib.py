@@ -238,6 +238,12 @@ AugmentAffine = _struct("AugmentAffine", cname="miseg_augment_affine_params", fi
     ("struct_size", u32), ("image", vp), ("label", vp), ("label_bytes", i32), ("C", i32), ("D", i32), ("H", i32), ("W", i32), ("rd", i32), ("rh", i32),
     ("rw", i32), ("n", i32), ("out_image", vp), ("out_label", vp), ("samples_host", vp), ("padding_mode", i32), ("seed", C.c_uint64), ("draw", C.c_uint64),
     ("minmax", vp)])
+GAUSS_MAX_RADIUS = 8                                                   # MISEG_GAUSS_MAX_RADIUS
+GAUSS_TILE = (8, 16, 32)                                               # MISEG_GAUSS_TILE_D / _H / _W: the output tile of one workgroup
+GaussSample = _struct("GaussSample", cname="miseg_gaussian_filter_sample", fields=[
+    ("radius", i32 * 3), ("taps", (f32 * (2 * GAUSS_MAX_RADIUS + 1)) * 3), ("alpha", f32), ("sharpen", i32)])
+GaussianFilter = _struct("GaussianFilter", cname="miseg_gaussian_filter_params", fields=[
+    ("struct_size", u32), ("src", vp), ("dst", vp), ("n", i32), ("C", i32), ("D", i32), ("H", i32), ("W", i32), ("samples_host", vp)])
 Resample3d = _struct("Resample3d", cname="miseg_resample3d_params", fields=[
     ("struct_size", u32), ("in", vp), ("out", vp), ("C", i32), ("Di", i32), ("Hi", i32), ("Wi", i32), ("Do", i32), ("Ho", i32), ("Wo", i32),
     ("mode", i32), ("elem_bytes", i32)])
@@ -400,6 +406,7 @@ PROTOS = {
     "miseg_stitch_windows": (i32, [C.POINTER(Stitch), vp]),
     "miseg_augment_crop": (i32, [C.POINTER(Augment), vp]),
     "miseg_augment_affine": (i32, [C.POINTER(AugmentAffine), vp]),
+    "miseg_gaussian_filter3d": (i32, [C.POINTER(GaussianFilter), vp]),
     "miseg_resample3d": (i32, [C.POINTER(Resample3d), vp]),
     "miseg_label_export_workspace_bytes": (C.c_size_t, [i32, i32, i32]),
     "miseg_label_export": (i32, [C.POINTER(LabelExport), vp]),

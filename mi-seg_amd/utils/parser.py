@@ -87,6 +87,12 @@ DATA_ARGS = {
         ("--gamma_range", dict(default=[0.5, 4.5], type=float, nargs=2, help="gamma of RandAdjustContrastd: drawn U(low, high)")),
         ("--randGaussianNoised_prob", dict(default=0.0, type=float)),
         ("--noise_std", dict(default=0.1, type=float, help="RandGaussianNoised: the std of a sample is drawn U(0, noise_std)")),
+        ("--randGaussianSmoothd_prob", dict(default=0.0, type=float)),
+        ("--smooth_sigma_range", dict(default=[0.25, 1.5], type=float, nargs=2, help="RandGaussianSmoothd: sigma per axis drawn U(low, high), voxels")),
+        ("--randGaussianSharpend_prob", dict(default=0.0, type=float)),
+        ("--sharpen_sigma1_range", dict(default=[0.5, 1.0], type=float, nargs=2, help="RandGaussianSharpend: the first sigma per axis, U(low, high)")),
+        ("--sharpen_sigma2", dict(default=0.5, type=float, help="RandGaussianSharpend: the second sigma of an axis is drawn between this and the first")),
+        ("--sharpen_alpha_range", dict(default=[10.0, 30.0], type=float, nargs=2, help="RandGaussianSharpend: alpha drawn U(low, high)")),
         ("--use_normal_dataset", dict(action=_T)), ("--cache_num", dict(default=24, type=int)), ("--loader_workers", dict(default=8, type=int)),
         ("--batch_size", dict(default=1, type=int)), ("--num_workers", dict(default=8, type=int)),
     ],
