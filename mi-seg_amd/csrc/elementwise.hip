@@ -457,6 +457,7 @@ extern "C" int miseg_col2im3(const miseg_im2col3_params* p, miseg_stream_t s) { 
 extern "C" int miseg_colsum(const miseg_colsum_params* p, miseg_stream_t s_) {
   hipStream_t s = (hipStream_t)s_;
   MISEG_REQUIRE(p && p->x && p->out && p->rows > 0 && p->C > 0, MISEG_E_BADARG, "colsum: bad args");
+  MISEG_REQUIRE(p->dtype == MISEG_F32 || p->dtype == MISEG_BF16, MISEG_E_BADARG, "colsum: unknown dtype %d", p->dtype);      // before the fill
   if (!p->accumulate) {
     hipError_t e = miseg::fill_words_async(p->out, 0, (size_t)p->C, s);
     MISEG_REQUIRE(e == hipSuccess, MISEG_E_LAUNCH, "colsum: memset failed");

@@ -28,8 +28,9 @@ bit, atomic rows (split_k, several reduce groups) are judged by parity only.
 NOT launched (pinned on the host in tests/test_gemm_plan_cpu.py): the workload's own shapes (13 824 .. 884 736 rows: tests/test_hip_kernels.py and
 scripts/gemm_table.py launch them); the 256-workgroup cap of a weight above 80 KB with a walking wave (M above 32 768 at N = 400, K = 96: the cap
 is one `min` in the plan, the walk is the 512-cap rows').  The fused MLP has its rows in tests/test_hip_mlp_forms.py (tests/mlp_cases.py);
-miseg_gemm_tn_group / miseg_gemm_tn_stream_group and miseg_permute3 have no rows here.  Nothing here searches a kernel's assembly or runs under a
-sanitizer.
+miseg_gemm_tn_group, miseg_gemm_tn_reduce_batch and the column sums have theirs in tests/test_hip_step_end_forms.py (tests/step_end_cases.py),
+miseg_gemm_tn_stream_group in tests/test_hip_tn_stream_group.py and miseg_permute3 in tests/test_hip_row_op_edges.py: none of them has rows here.
+Nothing here searches a kernel's assembly or runs under a sanitizer.
 
 Measured on an MI355X, worst over the rows, pooled / per element (the last test of the file prints this table; no row needed the local_tol rule):
   small, stream, rank-1, generic NT and TN with bf16 output   1.7e-3 / 3.3e-3   (bar 2e-2: one rounding of the output to bf16, 2^-9 at the worst)

@@ -880,9 +880,10 @@ def test_conv3_wgrad_tiny_volumes(B, S, Cin, Cout):
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_gemm_tn_grouped_launch_with_both_tile_forms(dtype):
-    """the queued small weight-gradient GEMMs of a step in one grouped call: products with large outputs and a short reduction (the ViT shapes:
-    216 tokens, 768 .. 3072 channels a side) take 128 x 128 tiles (round 5, bf16), the others 64 x 64; accumulate modes 1 (add to what the slot
-    holds) and 2 (the slot is known to hold zeros)."""
+    """the queued small weight-gradient GEMMs of a step in one grouped call (miseg_gemm_tn_group): every problem runs in 64 x 64 tiles, the only
+    tile gemm_tn_group_kernel has, here from 2 x 2 (100 x 72) to 36 x 12 (2304 x 768) workgroups, none with a split reduction (K <= 2048);
+    accumulate modes 1 (add to what the slot holds) and 2 (the slot is known to hold zeros: the tiles are stored).  The launch forms, the
+    split path and the operand layouts have their rows in tests/test_hip_step_end_forms.py."""
     ops = _ops()
     shapes = [(216, 768, 3072), (216, 2304, 768), (1728, 192, 768), (216, 384, 1536), (27, 768, 3072), (216, 768, 768), (300, 640, 512), (216, 100, 72)]
     for mode in (1, 2):
