@@ -446,6 +446,27 @@ typedef struct {
 } miseg_conv3_plan_info;
 int miseg_conv3_fwd_plan(const miseg_conv3_params* p, miseg_conv3_plan_info* plan);
 int miseg_conv3_fwd(const miseg_conv3_params* p, miseg_stream_t stream);
+/* ABI 16 (new symbol): the whole FORM of the launch miseg_conv3_fwd(p) makes - a superset of the plan; the launcher dispatches on exactly this
+ * struct and computes nothing itself.  Host only, stand-in pointers as for miseg_conv3_fwd_plan.  A field means the same for every kernel:
+ * `nt` is the planned tile count for FWD_TINY too (that kernel does not use it); fields of a kernel that is not launched are 0, and none of
+ * those is a divisor of the launch that is made. */
+typedef struct {
+  miseg_conv3_plan_info plan;
+  int32_t gpt, nchunks, cps;       /* FWD96 / FWD_TINY: 16-byte channel groups per chunk (6 / 4 / 2), chunks of the K side, chunks per split */
+  int32_t nt;                      /* 16-channel output tiles per workgroup: FWD96 / FWD_TINY 1 .. 3 (as planned), GENERIC 1, 2, 3, 4, 6 */
+  int32_t wd, epi;                 /* FWD96: conv3_fwd96_kernel<T, nt, wd, epi, gpt> */
+  int32_t vec_x, vec_y;            /* 16-byte aligned base and whole vectors per row of x / y, for every kernel (only FWD96 and its second launch use vec_y) */
+  int32_t vec_r, vec_fs_y;         /* the same test on res / fs_y: what the epilogues of FWD96 find for their own operands (0 without the operand) */
+  int32_t ny;                      /* FWD96: output-channel groups per brick = ceil(Cout / (16 nt)); 0 for the other kernels */
+  int32_t nbricks;                 /* bricks over the batch: 4 x 4 x 16 voxels (FWD96; counted for FWD_TINY too), 4 x 8 x 8 (GENERIC) */
+  int32_t tiny_mt, tiny_mg;        /* FWD_TINY: conv3_fwd_tiny_kernel<MT, MG>: <2, 1> up to 32 voxels, else <4, 4>; else 0 */
+  int32_t chunk_bytes;             /* GENERIC: bytes of a staged channel chunk = the padded row (at most 48) */
+  int32_t grid_x, grid_y, grid_z;  /* the main launch */
+  int32_t second_launch;           /* 1: a second launch sums the slabs (+ res) into y and takes the statistics (splits > 1, not deferred) */
+  int32_t pad_;
+  size_t lds_bytes;                /* dynamic LDS of the main launch */
+} miseg_conv3_fwd_form_info;
+int miseg_conv3_fwd_form(const miseg_conv3_params* p, miseg_conv3_fwd_form_info* form);
 
 /* w: fp32 torch layout [Cout][Cin][3][3][3].  fwd_pack feeds miseg_conv3_fwd on x, bwd_pack (taps mirrored, channels swapped) feeds it
  * on dy; either may be NULL.  The layout is internal (row-major [Cout][27][CinP] or planar [27][CinP/k][CoutP16][k], by channel count);

@@ -39,7 +39,7 @@ extern "C" size_t miseg_abi_struct_size(const char* name) {
   MISEG_SZ(miseg_gaussian_filter_sample) MISEG_SZ(miseg_gaussian_filter_params)
   MISEG_SZ(miseg_net_end_launch) MISEG_SZ(miseg_head_bwd_plan_info) MISEG_SZ(miseg_grad_clip_record) MISEG_SZ(miseg_grad_norm_params) MISEG_SZ(miseg_grad_fold_params)
   MISEG_SZ(miseg_weight_average_record) MISEG_SZ(miseg_weight_average_params) MISEG_SZ(miseg_weight_swap_params)
-  MISEG_SZ(miseg_conv3_wgrad_form_info) MISEG_SZ(miseg_instnorm_launch) MISEG_SZ(miseg_instnorm_plan_info)
+  MISEG_SZ(miseg_conv3_wgrad_form_info) MISEG_SZ(miseg_conv3_fwd_form_info) MISEG_SZ(miseg_instnorm_launch) MISEG_SZ(miseg_instnorm_plan_info)
 #undef MISEG_SZ
   return 0;
 }

@@ -709,7 +709,7 @@ __global__ void __launch_bounds__(256) conv3_fwd_tiny_kernel(const bf16* __restr
     const int v = (mg * MT + mt) * 16 + fi, co = ct * 16 + fq * 4;
     if (v < nvox) {
       float* sl = scratch + ((int64_t)chunk * nvox_total + (int64_t)b * nvox + v) * Cout + co;
-      if (co + 3 < Cout) *reinterpret_cast<f32x4*>(sl) = acc[mt];
+      if (Cout % 4 == 0 && co + 3 < Cout) *reinterpret_cast<f32x4*>(sl) = acc[mt];      // (a row of Cout % 4 != 0 floats starts 8 bytes into a 16-byte unit at every other voxel)
       else {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
@@ -1964,40 +1964,85 @@ static void fwd96_plan(int nbricks, int Cout, int nchunks, int* nt, int* ksplit)
   *ksplit = ks;
 }
 
-// THE plan of a forward launch: conv3_fwd_launch dispatches on it and miseg_conv3_fwd_plan returns its public part (host only)
+// THE plan of a forward launch: conv3_fwd_launch dispatches on it, miseg_conv3_fwd_form returns its form and miseg_conv3_fwd_plan the public
+// part of that (host only).  Every divisor, grid extent, LDS size and template selector of the launch is a field here: the launcher computes
+// nothing.  A field means the same for every kernel (`nt` is the planned tile count for the tiny kernel too; no 0 stands for "not
+// applicable" in a field something divides by); `ny` belongs to the 96-byte kernel's launch alone.
 struct Conv3FwdPlan {
-  miseg_conv3_plan_info pub;
-  int k96, gpt, nchunks, nt, cps;      // fast path: K extent, groups per chunk, chunks, 16-channel tiles per block, chunks per split
+  miseg_conv3_fwd_form_info f;
+  int k96, CinP, CoP;        // K extent of the fast path (0: row-major kernel), padded channel counts
+  int chunk_elems, rowb;     // row-major kernel: elements per chunk (the whole row), LDS row bytes
+  int nbd, nbh, nbw;         // bricks per axis of the kernel's brick
+  int64_t voxels;            // B D H W
+  int nvox;                  // D H W: voxels of a sample
 };
 static void conv3_fwd_plan(const miseg_conv3_params* p, Conv3FwdPlan* q) {
   const int esz = p->dtype == MISEG_F32 ? 4 : 2, kpc = 16 / esz;
   const bool bf16 = p->dtype == MISEG_BF16;
   *q = Conv3FwdPlan{};
-  q->pub.splits = 1;
+  miseg_conv3_fwd_form_info& f = q->f;
+  miseg_conv3_plan_info& pub = f.plan;
+  pub.splits = 1;
+  q->voxels = (int64_t)p->B * p->D * p->H * p->W;
+  q->nvox = p->D * p->H * p->W;
+  q->CoP = round_up(p->Cout, 16);
+  f.vec_x = ((uintptr_t)p->x % 16 == 0) && (p->ldx % kpc == 0);
+  f.vec_y = ((uintptr_t)p->y % 16 == 0) && (p->ldy % kpc == 0);
+  f.vec_r = p->res && ((uintptr_t)p->res % 16 == 0) && (p->ldres % kpc == 0);      // (mirrors of the tests the epilogue makes on its own arguments)
+  f.vec_fs_y = p->fs_y && ((uintptr_t)p->fs_y % 16 == 0) && (p->ld_fs_y % kpc == 0);
   q->k96 = conv3_k96(p->Cin, esz, conv3_pad_min_bytes());
-  if (!q->k96) { q->pub.kernel = MISEG_CONV3_GENERIC; return; }      // (weights come from the row-major pack: same predicate in the pack)
-  q->gpt = conv3_gpt(p->Cin, esz, conv3_pad_min_bytes());
-  q->nchunks = q->k96 * esz / (16 * q->gpt);
+  if (!q->k96) {      // (weights come from the row-major pack: same predicate in the pack)
+    pub.kernel = MISEG_CONV3_GENERIC;
+    q->CinP = round_up(p->Cin, kpc);
+    f.chunk_bytes = q->CinP * esz;      // the chunk is the row: conv3_k96 leaves this kernel rows of at most 48 bytes (tests/test_conv3_fwd_forms_cpu.py)
+    q->chunk_elems = q->CinP;
+    q->rowb = f.chunk_bytes + 16;
+    f.lds_bytes = (size_t)(BD + 2) * HH * HW * q->rowb;
+    f.nt = p->Cout <= 16 ? 1 : p->Cout <= 32 ? 2 : p->Cout <= 48 ? 3 : p->Cout <= 64 ? 4 : (p->Cout % 96 == 0 || p->Cout > 128) ? 6 : 4;
+    q->nbd = cdiv(p->D, BD); q->nbh = cdiv(p->H, BH); q->nbw = cdiv(p->W, BW);
+    f.nbricks = p->B * q->nbd * q->nbh * q->nbw;
+    f.grid_x = f.nbricks; f.grid_y = cdiv(p->Cout, 16 * f.nt); f.grid_z = 1;
+    return;
+  }
+  q->CinP = q->k96;
+  f.gpt = conv3_gpt(p->Cin, esz, conv3_pad_min_bytes());
+  f.nchunks = q->k96 * esz / (16 * f.gpt);
+  q->nbd = cdiv(p->D, FBD); q->nbh = cdiv(p->H, FBH); q->nbw = cdiv(p->W, FBW);
+  f.nbricks = p->B * q->nbd * q->nbh * q->nbw;
   int ks;
-  fwd96_plan(p->B * cdiv(p->D, FBD) * cdiv(p->H, FBH) * cdiv(p->W, FBW), p->Cout, q->nchunks, &q->nt, &ks);
-  q->cps = cdiv(q->nchunks, ks);
-  const int splits = q->pub.splits = cdiv(q->nchunks, q->cps);
-  q->pub.workspace_bytes = splits > 1 ? (size_t)splits * p->B * p->D * p->H * p->W * p->Cout * sizeof(float) : 0;
-  const bool vec_x = ((uintptr_t)p->x % 16 == 0) && (p->ldx % kpc == 0);
+  fwd96_plan(f.nbricks, p->Cout, f.nchunks, &f.nt, &ks);
+  f.cps = cdiv(f.nchunks, ks);
+  const int splits = pub.splits = cdiv(f.nchunks, f.cps);
+  pub.workspace_bytes = splits > 1 ? (size_t)splits * p->B * p->D * p->H * p->W * p->Cout * sizeof(float) : 0;
   // tiny volumes whose every chunk is a split of its own: the weight-streaming kernel (same pack, same slabs)
-  const int nvox = p->D * p->H * p->W;
-  const bool tiny = bf16 && splits > 1 && q->gpt == 6 && splits == q->nchunks && nvox <= 256 && vec_x && !p->background && p->Cin % 8 == 0 &&
-                    (size_t)(p->D + 2) * (p->H + 2) * (p->W + 2) * TINY_ROWB <= 64 * 1024;
-  q->pub.kernel = tiny ? MISEG_CONV3_FWD_TINY : MISEG_CONV3_FWD96;
-  q->pub.defer_slabs = p->defer_slabs && splits > 1 && !p->res;
-  q->pub.res = p->res != nullptr;
-  q->pub.stat = p->stat && !q->pub.defer_slabs;
+  const int nvox = q->nvox;
+  const size_t lds_tiny = (size_t)(p->D + 2) * (p->H + 2) * (p->W + 2) * TINY_ROWB;
+  const bool tiny = bf16 && splits > 1 && f.gpt == 6 && splits == f.nchunks && nvox <= 256 && f.vec_x && !p->background && p->Cin % 8 == 0 &&
+                    lds_tiny <= 64 * 1024;
+  pub.kernel = tiny ? MISEG_CONV3_FWD_TINY : MISEG_CONV3_FWD96;
+  pub.defer_slabs = p->defer_slabs && splits > 1 && !p->res;
+  pub.res = p->res != nullptr;
+  pub.stat = p->stat && !pub.defer_slabs;
   // the three folds of round 5 ride in the unsplit fast-path launch only
-  q->pub.sc = p->sc_x && bf16 && q->gpt == 6 && splits == 1 && p->sc_w && p->sc_C > 0 && p->sc_C % (6 * kpc) == 0 && (uintptr_t)p->sc_x % 16 == 0 &&
-              p->ld_sc_x % kpc == 0 && (uintptr_t)p->sc_w % 16 == 0;
-  q->pub.fs = p->fs_w && bf16 && q->gpt == 6 && splits == 1 && p->fs_y && p->Cin % (6 * kpc) == 0 && vec_x && (uintptr_t)p->fs_w % 16 == 0;
-  q->pub.s2c = p->s2c_out && splits == 1 && p->s2c_C > 0 && p->s2c_C < p->Cout && p->s2c_C % (16 * q->nt) == 0 && p->s2c_C % kpc == 0 &&
-               p->D % 2 == 0 && p->H % 2 == 0 && p->W % 2 == 0 && (uintptr_t)p->s2c_out % 16 == 0;
+  pub.sc = p->sc_x && bf16 && f.gpt == 6 && splits == 1 && p->sc_w && p->sc_C > 0 && p->sc_C % (6 * kpc) == 0 && (uintptr_t)p->sc_x % 16 == 0 &&
+           p->ld_sc_x % kpc == 0 && (uintptr_t)p->sc_w % 16 == 0;
+  pub.fs = p->fs_w && bf16 && f.gpt == 6 && splits == 1 && p->fs_y && p->Cin % (6 * kpc) == 0 && f.vec_x && (uintptr_t)p->fs_w % 16 == 0;
+  pub.s2c = p->s2c_out && splits == 1 && p->s2c_C > 0 && p->s2c_C < p->Cout && p->s2c_C % (16 * f.nt) == 0 && p->s2c_C % kpc == 0 &&
+            p->D % 2 == 0 && p->H % 2 == 0 && p->W % 2 == 0 && (uintptr_t)p->s2c_out % 16 == 0;
+  f.second_launch = splits > 1 && !pub.defer_slabs;      // slabs_to_out_stats: sum of the slabs + residual -> y, with the statistics of y
+  if (tiny) {
+    const bool small = nvox <= 32;      // <2, 1>: a wave owns a 16-channel tile and all (at most 32) voxels; <4, 4>: four waves share a tile
+    f.tiny_mt = small ? 2 : 4; f.tiny_mg = small ? 1 : 4;
+    f.grid_x = small ? cdiv(q->CoP / 16, 4) : q->CoP / 16; f.grid_y = f.nchunks; f.grid_z = p->B;
+    f.lds_bytes = lds_tiny;
+    return;
+  }
+  f.wd = f.nt == 2 ? 2 : 3;
+  f.epi = splits == 1 && (pub.res || pub.stat || pub.sc || pub.s2c || pub.fs);
+  f.ny = cdiv(p->Cout, 16 * f.nt);
+  f.grid_x = f.nbricks * f.ny; f.grid_y = 1; f.grid_z = splits;
+  f.lds_bytes = (size_t)f.gpt * FPS * 16 + (size_t)2 * 12 * 16 * f.nt * 16;
+  if (p->background && f.lds_bytes < 83 * 1024) f.lds_bytes = 83 * 1024;      // more than half of the 160 KB: one workgroup per CU
 }
 
 static int conv3_fwd_check(const miseg_conv3_params* p) {
@@ -2012,96 +2057,81 @@ extern "C" int miseg_conv3_fwd_plan(const miseg_conv3_params* p, miseg_conv3_pla
   if (const int rc = conv3_fwd_check(p)) return rc;
   Conv3FwdPlan q;
   conv3_fwd_plan(p, &q);
-  *plan = q.pub;
+  *plan = q.f.plan;
+  return MISEG_OK;
+}
+
+extern "C" int miseg_conv3_fwd_form(const miseg_conv3_params* p, miseg_conv3_fwd_form_info* form) {
+  MISEG_REQUIRE(p && form, MISEG_E_BADARG, "conv3_fwd_form: null pointer");
+  if (const int rc = conv3_fwd_check(p)) return rc;
+  Conv3FwdPlan q;
+  conv3_fwd_plan(p, &q);
+  *form = q.f;
   return MISEG_OK;
 }
 
 template <class T>
 static int conv3_fwd_launch(const miseg_conv3_params* p, hipStream_t s) {
-  constexpr int KPC = Vec16<T>::N;
   Conv3FwdPlan q;
   conv3_fwd_plan(p, &q);
-  const miseg_conv3_plan_info& pl = q.pub;
-  const int CinP = q.k96 ? q.k96 : round_up(p->Cin, KPC);
-  const int rowbytes = CinP * (int)sizeof(T);
-  ConvGeom g{p->B, p->D, p->H, p->W, cdiv(p->D, BD), cdiv(p->H, BH), cdiv(p->W, BW)};
-  const int nbricks = g.B * g.nbd * g.nbh * g.nbw;
-  const bool vec_x = ((uintptr_t)p->x % 16 == 0) && (p->ldx % KPC == 0);
+  const miseg_conv3_fwd_form_info& f = q.f;
+  const miseg_conv3_plan_info& pl = f.plan;
   MISEG_REQUIRE(!p->res || pl.res, MISEG_E_UNSUPPORTED, "conv3_fwd: fused residual needs 96-byte channel chunks");
   MISEG_REQUIRE(!p->stat || pl.stat || pl.defer_slabs, MISEG_E_UNSUPPORTED, "conv3_fwd: fused statistics need 96-byte channel chunks");
   MISEG_REQUIRE(!p->sc_x || pl.sc, MISEG_E_UNSUPPORTED, "conv3_fwd: fused shortcut on these operands (ask miseg_conv3_fwd_plan first)");
   MISEG_REQUIRE(!p->fs_w || pl.fs, MISEG_E_UNSUPPORTED, "conv3_fwd: second (1x1x1) output on these operands (ask miseg_conv3_fwd_plan first)");
   MISEG_REQUIRE(!p->s2c_out || pl.s2c, MISEG_E_UNSUPPORTED, "conv3_fwd: space-to-channel store on these operands (ask miseg_conv3_fwd_plan first)");
   MISEG_REQUIRE(!pl.workspace_bytes || p->workspace, MISEG_E_BADARG, "conv3_fwd: workspace required (miseg_conv3_plan_info.workspace_bytes)");
+  const ConvGeom g{p->B, p->D, p->H, p->W, q.nbd, q.nbh, q.nbw};      // (bricks of the kernel the plan chose)
+  const dim3 grid(f.grid_x, f.grid_y, f.grid_z);
+  const size_t lds = f.lds_bytes;
+  const bool vec_x = f.vec_x, vec_y = f.vec_y;
   // ---- fast path: 96-byte channel chunks, planar LDS images (weights must come from the planar pack: same predicate
   // in miseg_pack_conv3_weight: conv3_k96)
   if (pl.kernel != MISEG_CONV3_GENERIC) {
-    ConvGeom gf{p->B, p->D, p->H, p->W, cdiv(p->D, FBD), cdiv(p->H, FBH), cdiv(p->W, FBW)};
-    const int nbr = gf.B * gf.nbd * gf.nbh * gf.nbw;
-    const int nt = q.nt, gpt = q.gpt, nchunks = q.nchunks, cps = q.cps, ksplit = pl.splits;
-    float* scratch = ksplit > 1 ? (float*)p->workspace : nullptr;
-    const bool vec_y = ((uintptr_t)p->y % 16 == 0) && (p->ldy % KPC == 0);
-    const int CoP = round_up(p->Cout, 16);
-    size_t lds = (size_t)gpt * FPS * 16 + (size_t)2 * 12 * 16 * nt * 16;
-    if (p->background && lds < 83 * 1024) lds = 83 * 1024;      // more than half of the 160 KB: one workgroup per CU
-    MISEG_REQUIRE((int64_t)p->B * p->D * p->H * p->W < (1LL << 31), MISEG_E_UNSUPPORTED, "conv3_fwd: more than 2^31 voxels");
-    const int ny = cdiv(p->Cout, 16 * nt);
+    float* scratch = pl.splits > 1 ? (float*)p->workspace : nullptr;
+    MISEG_REQUIRE(q.voxels < (1LL << 31), MISEG_E_UNSUPPORTED, "conv3_fwd: more than 2^31 voxels");
     if constexpr (std::is_same<T, bf16>::value) {
-      const int nvox = p->D * p->H * p->W;
       if (pl.kernel == MISEG_CONV3_FWD_TINY) {
-        const size_t lds_t = (size_t)(p->D + 2) * (p->H + 2) * (p->W + 2) * TINY_ROWB;
-        if (nvox <= 32) {
-          dim3 gt(cdiv(CoP / 16, 4), nchunks, p->B);
-          (void)hipFuncSetAttribute((const void*)conv3_fwd_tiny_kernel<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t);
-          conv3_fwd_tiny_kernel<2, 1><<<gt, 256, lds_t, s>>>((const bf16*)p->x, p->ldx, (const bf16*)p->wpk, p->D, p->H, p->W, p->Cin, p->Cout, CoP, scratch, p->B * nvox);
+        if (f.tiny_mg == 1) {
+          (void)hipFuncSetAttribute((const void*)conv3_fwd_tiny_kernel<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+          conv3_fwd_tiny_kernel<2, 1><<<grid, 256, lds, s>>>((const bf16*)p->x, p->ldx, (const bf16*)p->wpk, p->D, p->H, p->W, p->Cin, p->Cout, q.CoP, scratch, (int)q.voxels);
         } else {
-          dim3 gt(CoP / 16, nchunks, p->B);
-          (void)hipFuncSetAttribute((const void*)conv3_fwd_tiny_kernel<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t);
-          conv3_fwd_tiny_kernel<4, 4><<<gt, 256, lds_t, s>>>((const bf16*)p->x, p->ldx, (const bf16*)p->wpk, p->D, p->H, p->W, p->Cin, p->Cout, CoP, scratch, p->B * nvox);
+          (void)hipFuncSetAttribute((const void*)conv3_fwd_tiny_kernel<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+          conv3_fwd_tiny_kernel<4, 4><<<grid, 256, lds, s>>>((const bf16*)p->x, p->ldx, (const bf16*)p->wpk, p->D, p->H, p->W, p->Cin, p->Cout, q.CoP, scratch, (int)q.voxels);
         }
         MISEG_LAUNCH_CHECK("conv3_fwd_tiny");
-        if (pl.defer_slabs) return MISEG_OK;
-        return slabs_to_out_stats(scratch, ksplit, p->y, p->ldy, p->res, p->ldres, p->B, nvox, p->Cout, p->dtype, (double*)p->stat, s);
+        if (!f.second_launch) return MISEG_OK;
+        return slabs_to_out_stats(scratch, pl.splits, p->y, p->ldy, p->res, p->ldres, p->B, q.nvox, p->Cout, p->dtype, (double*)p->stat, s);
       }
     }
-    dim3 grid(nbr * ny, 1, ksplit);
 #define F96_LAUNCH(n, wd, epi, gp)                                                                                                           \
     (void)hipFuncSetAttribute((const void*)conv3_fwd96_kernel<T, n, wd, epi, gp>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);    \
-    conv3_fwd96_kernel<T, n, wd, epi, gp><<<grid, 256, lds, s>>>((const T*)p->x, p->ldx, (T*)p->y, p->ldy, (const T*)p->wpk, gf, p->Cin, CinP, \
-                                                                 p->Cout, CoP, vec_x, vec_y, scratch, cps, scratch ? nullptr : (const T*)p->res, \
-                                                                 p->ldres, (double*)p->stat, ny, (const T*)p->sc_x, p->ld_sc_x, (const T*)p->sc_w, p->sc_C, \
+    conv3_fwd96_kernel<T, n, wd, epi, gp><<<grid, 256, lds, s>>>((const T*)p->x, p->ldx, (T*)p->y, p->ldy, (const T*)p->wpk, g, p->Cin, q.CinP, \
+                                                                 p->Cout, q.CoP, vec_x, vec_y, scratch, f.cps, scratch ? nullptr : (const T*)p->res, \
+                                                                 p->ldres, (double*)p->stat, f.ny, (const T*)p->sc_x, p->ld_sc_x, (const T*)p->sc_w, p->sc_C, \
                                                                  (T*)p->s2c_out, p->s2c_C, (const T*)p->fs_w, (T*)p->fs_y, p->ld_fs_y, (double*)p->fs_stat)
 #define F96_CASE(n, wd, gp)                                                                                                                  \
   case n:                                                                                                                                   \
-    if (!scratch && (pl.res || pl.stat || pl.sc || pl.s2c || pl.fs)) { F96_LAUNCH(n, wd, true, gp); } else { F96_LAUNCH(n, wd, false, gp); }   \
+    if (f.epi) { F96_LAUNCH(n, wd, true, gp); } else { F96_LAUNCH(n, wd, false, gp); }                                                        \
     break;
-    if (gpt == 6) { switch (nt) { F96_CASE(1, 3, 6) F96_CASE(2, 2, 6) F96_CASE(3, 3, 6) } }
-    else if (gpt == 4) { switch (nt) { F96_CASE(1, 3, 4) F96_CASE(2, 2, 4) F96_CASE(3, 3, 4) } }
-    else { switch (nt) { F96_CASE(1, 3, 2) F96_CASE(2, 2, 2) F96_CASE(3, 3, 2) } }
+    if (f.gpt == 6) { switch (f.nt) { F96_CASE(1, 3, 6) F96_CASE(2, 2, 6) F96_CASE(3, 3, 6) } }
+    else if (f.gpt == 4) { switch (f.nt) { F96_CASE(1, 3, 4) F96_CASE(2, 2, 4) F96_CASE(3, 3, 4) } }
+    else { switch (f.nt) { F96_CASE(1, 3, 2) F96_CASE(2, 2, 2) F96_CASE(3, 3, 2) } }
 #undef F96_CASE
 #undef F96_LAUNCH
     MISEG_LAUNCH_CHECK("conv3_fwd96");
-    if (pl.defer_slabs) return MISEG_OK;      // the caller's next launch sums the slabs itself (miseg_instnorm_fwd_slabs)
-    if (scratch)      // sum of the slabs + residual -> y, with the statistics of y when asked for (one launch)
-      return slabs_to_out_stats(scratch, ksplit, p->y, p->ldy, p->res, p->ldres, p->B, p->D * p->H * p->W, p->Cout, p->dtype, (double*)p->stat, s);
-    return MISEG_OK;
+    if (!f.second_launch) return MISEG_OK;      // unsplit, or the caller's next launch sums the slabs itself (miseg_instnorm_fwd_slabs)
+    // sum of the slabs + residual -> y, with the statistics of y when asked for (one launch)
+    return slabs_to_out_stats(scratch, pl.splits, p->y, p->ldy, p->res, p->ldres, p->B, q.nvox, p->Cout, p->dtype, (double*)p->stat, s);
   }
-  int chunk_bytes;
-  if (rowbytes <= 128) chunk_bytes = rowbytes;
-  else if (rowbytes % 128 == 0) chunk_bytes = 128;
-  else chunk_bytes = 64;
-  const int chunk_elems = chunk_bytes / (int)sizeof(T);
-  const int rowb = chunk_bytes + 16;
-  const size_t lds = (size_t)(BD + 2) * HH * HW * rowb;
-  const int nt = p->Cout <= 16 ? 1 : p->Cout <= 32 ? 2 : p->Cout <= 48 ? 3 : p->Cout <= 64 ? 4 : (p->Cout % 96 == 0 || p->Cout > 128) ? 6 : 4;
-  dim3 grid(nbricks, cdiv(p->Cout, 16 * nt));
 #define FWD_CASE(n)                                                                                                                             \
   case n:                                                                                                                                       \
     hipFuncSetAttribute((const void*)conv3_fwd_kernel<T, n>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                              \
-    conv3_fwd_kernel<T, n><<<grid, 256, lds, s>>>((const T*)p->x, p->ldx, (T*)p->y, p->ldy, (const T*)p->wpk, g, p->Cin, CinP, p->Cout, chunk_elems, \
-                                                  rowb, vec_x);                                                                                 \
+    conv3_fwd_kernel<T, n><<<grid, 256, lds, s>>>((const T*)p->x, p->ldx, (T*)p->y, p->ldy, (const T*)p->wpk, g, p->Cin, q.CinP, p->Cout, q.chunk_elems, \
+                                                  q.rowb, vec_x);                                                                               \
     break;
-  switch (nt) { FWD_CASE(1) FWD_CASE(2) FWD_CASE(3) FWD_CASE(4) FWD_CASE(6) }
+  switch (f.nt) { FWD_CASE(1) FWD_CASE(2) FWD_CASE(3) FWD_CASE(4) FWD_CASE(6) }
 #undef FWD_CASE
   MISEG_LAUNCH_CHECK("conv3_fwd");
   return MISEG_OK;

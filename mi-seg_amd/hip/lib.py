@@ -105,6 +105,10 @@ Conv3Wgrad = _struct("Conv3Wgrad", cname="miseg_conv3_wgrad_params", fields=[("x
 CONV3_GENERIC, CONV3_FWD96, CONV3_FWD_TINY = 0, 1, 2      # miseg_conv3_plan_info.kernel
 Conv3Plan = _struct("Conv3Plan", cname="miseg_conv3_plan_info", fields=[("kernel", i32), ("splits", i32), ("workspace_bytes", C.c_size_t), ("res", i32), ("stat", i32),
                                   ("sc", i32), ("s2c", i32), ("fs", i32), ("defer_slabs", i32)])
+# the whole launch form of miseg_conv3_fwd (host only): what conv3_fwd_launch dispatches on, a superset of the plan
+Conv3FwdForm = _struct("Conv3FwdForm", cname="miseg_conv3_fwd_form_info", fields=[("plan", Conv3Plan)] + [(f, i32) for f in (
+    "gpt", "nchunks", "cps", "nt", "wd", "epi", "vec_x", "vec_y", "vec_r", "vec_fs_y", "ny", "nbricks", "tiny_mt", "tiny_mg", "chunk_bytes", "grid_x", "grid_y",
+    "grid_z", "second_launch", "pad_")] + [("lds_bytes", C.c_size_t)])
 CONV3_WGRAD_F32, CONV3_WGRAD_NARROW, CONV3_WGRAD_TINY, CONV3_WGRAD_BF16 = 0, 1, 2, 3      # miseg_conv3_wgrad_plan_info.kernel
 Conv3WgradPlan = _struct("Conv3WgradPlan", cname="miseg_conv3_wgrad_plan_info", fields=[("kernel", i32), ("pad_", i32), ("workspace_bytes", C.c_size_t)])
 # the whole launch form of a weight gradient (host only): what the launchers dispatch on, a superset of the plan
@@ -332,6 +336,7 @@ PROTOS = {
     "miseg_colsum_batch": (i32, [vp, i32, i32, vp]),
     "miseg_conv3_fwd_plan": (i32, [C.POINTER(Conv3), C.POINTER(Conv3Plan)]),
     "miseg_conv3_fwd": (i32, [C.POINTER(Conv3), vp]),
+    "miseg_conv3_fwd_form": (i32, [C.POINTER(Conv3), C.POINTER(Conv3FwdForm)]),
     "miseg_conv3_wgrad_form": (i32, [C.POINTER(Conv3Wgrad), C.POINTER(Conv3WgradForm)]),
     "miseg_conv3_wgrad_group_form": (i32, [C.POINTER(Conv3Wgrad), i32, C.POINTER(Conv3WgradForm)]),
     "miseg_pack_conv3_elems": (C.c_size_t, [i32, i32, i32, i32]),

@@ -27,7 +27,7 @@ repeat bit for bit; the atomic reduce is judged by parity only.
 
 NOT launched (pinned in tests/test_conv3_forms_cpu.py): the `span >= 2^31` exit from the pipelined loop (a halo slab of 2 GB); the reduce launch
 with ONE group per tile (plain read-modify-write instead of atomics), which needs Cout x ceil(Cin / 48) >= 2048.  The forward and data-gradient
-kernels (miseg_conv3_fwd) have no rows here: they stay on tests/test_hip_kernels.py.
+kernels (miseg_conv3_fwd) have no rows here: their table is tests/conv3_fwd_cases.py, launched by tests/test_hip_conv3_fwd_forms.py.
 
 Measured on an MI355X, worst over the rows, pooled / per element (the last test of the file prints this table; no row needed the local_tol rule):
   dw, slab kernels      fp32 3.4e-7 / 1.4e-6    bf16 1.7e-7 / 8.3e-7   (bars 2e-4 / 2e-2: bf16 products are exact in fp32, only the order of summation differs)
